@@ -23,9 +23,11 @@ kernel = traj_fast_kernel, MFMA-bound: algorithmic fp32 flops / launch duration 
 TFLOP/s fp32-MFMA peak) and `cpu_baseline` (the reference algorithm restated op by op on torch-CPU,
 all host cores, both directions computed like sampler.py:35-36; rank 0, N=1 only).
 
-Short runs: a K-step plan that would last less than `--min-timed-ms` (20 ms) is repeated R times
-inside the timed region (R in `config.repeats`; value / ms_per_step are means over the K x R steps),
-so `--steps 20` (0.5 ms of GPU time) measures the same rate as a long run.
+The timed region is exactly `--steps` proposals; `ms_per_step` is its wall time per proposal, so a caller can size
+`--steps` for a timed region of the length it wants.  `--dump-outputs DIR` writes what the timed path hands its caller
+after the last timed step -- the chain state `x` (chains x 50) and that proposal's accept probability `accept_prob` --
+as DIR/<name>.npy in float32.  All inputs are seeded, so with the same arguments two builds can be compared output for
+output.
 
 Multi-GPU: `--gpus N` alone is weak scaling (`--chains` per GPU; the bench line); `--total-chains C` makes the line
 strong scaling (C chains split over the N ranks).  At N > 1 two extra keys: `strong65536` = the north star's operating
@@ -87,6 +89,22 @@ def make_problem(seed, n_chains, device):
         prob["nets"][net] = w
     prob["x0"] = (rng.randn(n_chains, D) * np.sqrt(var)).astype(np.float32)
     return prob
+
+
+def dump_outputs(out_dir, arrays, suffix="", max_bytes=64 << 20):
+    """--dump-outputs: `arrays` (name -> per-chain array, chains on axis 0) as out_dir/<name><suffix>.npy in float32.  When
+    they would exceed `max_bytes`, the same fixed, seeded sample of chains is taken from every array and its chain indices
+    are written as chain_index<suffix>.npy (float64, exact)."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    n = len(next(iter(arrays.values())))
+    keep = max_bytes // (sum(a[:1].nbytes for a in arrays.values()) + 8)
+    if n > keep:
+        idx = np.sort(np.random.RandomState(0).choice(n, keep, replace=False))
+        arrays = {k: a[idx] for k, a in arrays.items()}
+        arrays["chain_index"] = idx.astype(np.float64)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + suffix + ".npy"), a)
 
 
 def usable_cores():
@@ -501,9 +519,13 @@ def main():
                          "keyed by global chain index); bank: pre-generated draws read from HBM")
     ap.add_argument("--preheat", type=int, default=1000,
                     help="untimed proposals run BEFORE the --warmup steps so that the GPU clocks have ramped "
-                         "whatever --warmup is; they also calibrate the repeat count; config.preheat_proposals")
+                         "whatever --warmup is; config.preheat_proposals")
     ap.add_argument("--min-timed-ms", type=float, default=20.0,
-                    help="repeat the --steps plan inside the timed region until it lasts at least this long")
+                    help="extra roofline points (sweep, strong65536): repeat their 100-step plan inside their timed region "
+                         "until it lasts at least this long (the main timed region is exactly --steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's chain state and accept probability as "
+                         "DIR/x.npy and DIR/accept_prob.npy (float32; suffix _rank<r> when N > 1)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-ess", action="store_true", help="skip the SCG-2D ESS/sec leg (N=1) / the dist leg (N>1)")
     ap.add_argument("--no-sweep", action="store_true", help="skip the 65 536-chain roofline point (N=1 only)")
@@ -526,6 +548,8 @@ def main():
                          "(1 = one launch per step); a shorter last launch covers any remainder")
     ap.add_argument("--cpu-baseline-only", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.cpu_baseline_only:
         print(json.dumps(cpu_baseline(make_problem(0, CHAINS, None))))
         return
@@ -620,7 +644,7 @@ def main():
             a = self.a
             src, dst = self.bufs[self.flip], self.bufs[self.flip ^ 1]
             self.flip ^= 1
-            a.n_proposals = count
+            a.n_proposals = self.last_count = count
             a.x, a.x_next = src.data_ptr(), dst.data_ptr()
             if args.rng == "philox":
                 a.rng_flags, a.rng_seed = _ffi.RNG_V | _ffi.RNG_DIR | _ffi.RNG_U, 20260926
@@ -675,22 +699,23 @@ def main():
 
     main_run = Runner(n, chain_off, 1234 + rank)     # chains differ per rank
     pre = max(0, args.preheat)
-    nxt, est_ms = calibrate(main_run, 0, pre) if pre > 0 else (0, 0.0)
+    nxt = calibrate(main_run, 0, pre)[0] if pre > 0 else 0
     nxt = main_run.run(nxt, args.warmup)
-    R = 1
-    if est_ms > 0 and args.steps * est_ms < args.min_timed_ms:
-        R = int(math.ceil(args.min_timed_ms / (args.steps * est_ms)))
-    elapsed, gpu_ms, nl, nxt = timed(main_run, nxt, args.steps, R)
+    elapsed, gpu_ms, nl, nxt = timed(main_run, nxt, args.steps, 1)
     main_kernel = _ffi.last_kernel()
     mean_p = float(main_run.p_out.mean())
     finite = bool(torch.isfinite(main_run.bufs[main_run.flip]).all())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"x": main_run.bufs[main_run.flip].cpu().numpy(),
+                                         "accept_prob": main_run.p_out[main_run.last_count - 1].cpu().numpy()},
+                     "" if world == 1 else "_rank%d" % rank, (64 << 20) // world)
     rank_values = None
     if world > 1:
         # every rank's own wall time of the timed region (-> per-rank `value`s in the line), then the MAX the contract asks for
         tg = torch.zeros(world, device=dev, dtype=torch.float64)
         tg[rank] = elapsed
         dist.all_reduce(tg)
-        rank_values = [float(n) * T * args.steps * R / float(t_) for t_ in tg.cpu()]
+        rank_values = [float(n) * T * args.steps / float(t_) for t_ in tg.cpu()]
         elapsed = float(tg.max())
 
     flops_cs = algorithmic_flops_per_chain_step(D, H, T, 3 * D)      # diagonal precision: 3d
@@ -745,7 +770,7 @@ def main():
         dist_out = dist_leg(dev, rank, world)
 
     if rank == 0:
-        k_timed = args.steps * R
+        k_timed = args.steps
         steps_total = float(n_total) * T * k_timed
         m_avg = k_timed / float(nl)                                      # proposals per launch (mean)
         per_launch_flops = flops_cs * n * T * m_avg
@@ -764,7 +789,7 @@ def main():
                        "chains_per_gpu": n, "chains_total": n_total, "x_dim": D, "hidden": H, "leapfrog_steps": T,
                        "proposals_per_launch": m_avg, "proposals_per_launch_max": M, "rng": args.rng,
                        "preheat_proposals": pre,
-                       "repeats": R, "timed_steps": k_timed,
+                       "timed_steps": k_timed,
                        "parallelism": "chains sharded, no data-path collective",
                        "mean_accept_prob": mean_p, "state_finite": finite},
             "roofline": {"bound": "mfma", "achieved": ach, "peak": PEAK_F32_MFMA_TFLOPS,

@@ -144,19 +144,23 @@ def test_separate_aux_branches_take_the_general_path():
     assert not Dynamics(d, energy, T=3, eps=0.1, net_factory=shared)._user_nets
 
 
-def test_bench_dist_leg_over_rccl_world_size_1():
+def test_bench_dist_leg_over_rccl_world_size_1(tmp_path):
     """bench.py --force-dist: process group on backend nccl (= RCCL), the sharded-ESS all-reduces and the
-    flat-gradient all-reduce of a training step run on the GPU box's one GPU; --steps 20 exercises the
-    short-run repeat logic."""
+    flat-gradient all-reduce of a training step run on the GPU box's one GPU; --steps 20 times exactly 20 steps, and
+    --dump-outputs writes the last timed step's chain state and accept probabilities."""
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29533", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--force-dist", "--steps", "20", "--warmup", "5",
-                        "--no-cpu-baseline", "--no-sweep"], capture_output=True, text=True, timeout=280, env=env)
+                        "--no-cpu-baseline", "--no-sweep", "--dump-outputs", str(tmp_path)],
+                       capture_output=True, text=True, timeout=280, env=env)
     assert r.returncode == 0, r.stderr[-800:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert out["dist"]["ranks"] == 1 and out["dist"]["backend"] == "nccl" and out["dist"]["sharded_training"]["parameters_identical_across_ranks"]
     assert 4e-3 < out["dist"]["sharded_ess"]["ess_per_mh_step"] < 8e-3         # notebook: 5.63e-3
-    assert out["config"]["repeats"] > 1 and out["config"]["timed_steps"] == 20 * out["config"]["repeats"]
+    assert out["steps"] == 20 and out["config"]["timed_steps"] == 20 and out["ms_per_step"] > 0
     assert out["value"] > 1e8 and out["config"]["state_finite"]
+    x, p = np.load(str(tmp_path / "x.npy")), np.load(str(tmp_path / "accept_prob.npy"))
+    assert x.dtype == np.float32 and x.shape == (4096, 50) and np.all(np.isfinite(x))
+    assert p.dtype == np.float32 and p.shape == (4096,) and np.all((p >= 0) & (p <= 1)) and 0.01 < p.mean() < 1.0
 
 
 def test_vae_sampler_loop_with_library_philox_matches_injected_draws_and_oracle():

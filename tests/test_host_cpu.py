@@ -134,6 +134,26 @@ def test_bench_host_helpers():
     assert a["mask"].shape == (bench.T, bench.D) and np.all(a["mask"].sum(axis=1) == bench.D // 2)
 
 
+def test_bench_dump_outputs_keeps_float32_and_samples_above_the_cap(tmp_path):
+    """bench.py --dump-outputs: every array as <name><suffix>.npy in float32; above the byte cap the same seeded sample of
+    chains from every array, the chain indices alongside, the whole within the cap."""
+    import bench
+    x, p = np.arange(1000 * 5, dtype=np.float64).reshape(1000, 5), np.arange(1000, dtype=np.float64) / 1000
+    bench.dump_outputs(str(tmp_path / "all"), {"x": x, "accept_prob": p})
+    assert sorted(os.listdir(str(tmp_path / "all"))) == ["accept_prob.npy", "x.npy"]
+    xa = np.load(str(tmp_path / "all" / "x.npy"))
+    assert xa.dtype == np.float32 and np.array_equal(xa, x.astype(np.float32))
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), {"x": x, "accept_prob": p}, "_rank1", max_bytes=4000)
+    f = {n: np.load(str(tmp_path / "s1" / n)) for n in ("x_rank1.npy", "accept_prob_rank1.npy", "chain_index_rank1.npy")}
+    idx = f["chain_index_rank1.npy"]
+    assert idx.dtype == np.float64 and len(idx) == 4000 // (6 * 4 + 8) and np.all(np.diff(idx) > 0)
+    assert np.array_equal(f["x_rank1.npy"], x[idx.astype(int)].astype(np.float32))
+    assert np.array_equal(f["accept_prob_rank1.npy"], p[idx.astype(int)].astype(np.float32))
+    assert sum(a.nbytes for a in f.values()) <= 4000
+    assert np.array_equal(np.load(str(tmp_path / "s2" / "chain_index_rank1.npy")), idx)
+
+
 def test_small_func_utils_and_losses_helpers():
     """utils/func_utils.py:59-109 and utils/losses.py:26-59 as values: closed forms on small inputs"""
     import torch

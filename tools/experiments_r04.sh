@@ -74,7 +74,6 @@ echo "== no MH block, no x_head"; timeout 300 python tools/pytest_with_lib.py $V
 echo "== phase timing, f32 heads"; L2HMC_PT_LIB=$R/$V/libl2hmc_hip_pt.so timeout 200 python tools/phase_timing.py 4096 4 2>&1 | grep -v amdgpu
 echo "== phase timing, bf16x3 pipelined heads"; L2HMC_PT_LIB=$R/$V/libl2hmc_hip_ptbfp.so timeout 200 python tools/phase_timing.py 4096 4 2>&1 | grep -v amdgpu
 } 2>&1 | tee $OUT/phase.txt
-ASAN_TIMEOUT=600 bash tools/collect_r04_asan.sh
 }
 
 exp_d() {
@@ -96,7 +95,6 @@ echo "== training / sharding tests (in-tree library)" | tee $OUT/tests.txt
 timeout 900 python -m pytest tests/test_gpu_parity.py tests/test_gpu_round2.py tests/test_gpu_round3.py tests/test_sharding_gloo.py tests/test_gpu_round4.py -q -x -m gpu \
    -k "training or checkpoint or adam or two_rank or round4 or bench_dist or user_energy or full_size or config4 or tempered" -p no:cacheprovider 2>&1 | tail -8 | tee -a $OUT/tests.txt
 timeout 300 python tools/bench_train.py --no-cpu 2>&1 | grep -v amdgpu | tee $OUT/train_timing.txt
-ASAN_TIMEOUT=700 bash tools/collect_r04_asan.sh
 }
 
 exp_e() {
