@@ -388,7 +388,10 @@ int l2hmc_p_accept_energies(const float* U0, const float* v0, const float* U1, c
  * Targets with analytic Hessian-vector products: Gaussian (diag / dense), GMM (prec = RAW (k,d,d)
  * precisions, logc, n_comp <= 8), Rough Well; any d, H whose 16-chain tile fits the 160 KiB LDS
  * (d = 50, H = 10 uses 122 KiB; larger shapes return L2HMC_ERR_UNSUPPORTED).  Every chain runs in
- * its own direction. */
+ * its own direction.
+ * energy.temperature is honoured: the dynamics, the accept probability and the gradient are those of
+ * U / temperature (a finite temperature > 0; else L2HMC_ERR_ARG).  energy.anneal_beta is not: training on the
+ * AIS bridge returns L2HMC_ERR_UNSUPPORTED. */
 typedef struct L2hmcTrainArgs {
   const L2hmcNet* xnet;
   const L2hmcNet* vnet;
@@ -483,7 +486,11 @@ typedef struct L2hmcTrainSplitArgs {
   const L2hmcMlp3* aux_encoder;  /* (n_pix -> H) or NULL                                                   */
   const L2hmcMlp3* decoder;      /* (d -> n_pix); NULL with `energy`                                       */
   const float* aux;              /* (N, n_pix)                                                             */
-  const L2hmcEnergy* energy;     /* NULL: the decoder posterior.  Else a built-in target (as l2hmc_energy takes it)  */
+  const L2hmcEnergy* energy;     /* NULL: the decoder posterior.  Else a built-in target (as l2hmc_energy takes it),
+                                  * its temperature honoured (anneal_beta is not).  An energy of kind 0 next to the decoder
+                                  * posterior or energy_cb carries only the temperature (anneal_beta = 0): the library
+                                  * tempers the decoder's U, grad U and Hessian-vector products itself, the callbacks
+                                  * return those of U / temperature; the energy_scale term uses the plain U either way */
   const float* hess;             /* GAUSS_DENSE / GMM: the RAW (n_comp, d, d) precisions (Hessian-vector products)   */
   const float* masks;            /* (T, d) */
   const float* trig;             /* (T, 2) */

@@ -64,6 +64,7 @@ struct TArgs {
   // l2hmc_train_step: chains [0, n_head) start from x_head (n_head = 0: all from x)
   const float* x_head;
   long long n_head;
+  float itemp;               // 1 / L2hmcEnergy.temperature: the kernels train on U / temperature (1: the plain energy)
 #ifdef L2HMC_DBG_EPILOGUE_SELECT     // round-4 experiment: the Metropolis select in the gradient kernel's epilogue
   const float* u;
   float* x_next;
@@ -415,7 +416,9 @@ __device__ __forceinline__ void t_net_bwd(const TCtx& X, const float* W, float* 
   TT_MARK(8);
 }
 
+template <bool TEMP>                             // TEMP: as train_fast_kernel (train_fast.hpp)
 __global__ __launch_bounds__(TTHREADS) void train_kernel(const TArgs A) {
+  const float itemp = TEMP ? A.itemp : 1.f;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   lds_poison(smem);
   const int tid = threadIdx.x;
@@ -466,12 +469,15 @@ __global__ __launch_bounds__(TTHREADS) void train_kernel(const TArgs A) {
     for (int i = tid; i < 2 * T; i += TTHREADS) Trg[i] = A.trig[i];
     if (ek != L2HMC_ENERGY_ROUGHWELL) {
       for (int i = tid; i < nc * d; i += TTHREADS) Mu[i] = A.mu[i];
+      // (temperature: a Gaussian's U, grad U and Hessian are linear in its precision -- the tempered target is the Gaussian
+      //  of precision P / temperature, so the precision is scaled here; the mixture scales its outputs instead)
       if (ek == L2HMC_ENERGY_GAUSS_DIAG) {
-        for (int i = tid; i < d; i += TTHREADS) Pr[i] = A.prec[i];
+        for (int i = tid; i < d; i += TTHREADS) Pr[i] = A.prec[i] * itemp;
       } else {                  // symmetric part G = (S + S^T) / 2 of each raw precision
+        const float ps = ek == L2HMC_ENERGY_GMM ? 1.f : itemp;
         for (int i = tid; i < nc * d * d; i += TTHREADS) {
           const int cc = i / (d * d), u = i - cc * d * d, k = u / d, j = u - k * d;
-          Pr[i] = 0.5f * (A.prec[cc * d * d + k * d + j] + A.prec[cc * d * d + j * d + k]);
+          Pr[i] = 0.5f * (A.prec[cc * d * d + k * d + j] + A.prec[cc * d * d + j * d + k]) * ps;
         }
       }
     }
@@ -490,6 +496,9 @@ __global__ __launch_bounds__(TTHREADS) void train_kernel(const TArgs A) {
   const float eps = A.alpha != nullptr ? expf(*A.alpha) : A.eps_host;
   const float heps = 0.5f * eps;
   const float rw_den = A.den;
+  // U / temperature: the Gaussians carry it in Pr (staging); Rough Well and the mixture multiply their finished outputs by
+  // the wave-uniform 1 / temperature (the constant 1 in the untempered instantiation: folded away, the plain energy's code)
+  const float rs = ek == L2HMC_ENERGY_ROUGHWELL || ek == L2HMC_ENERGY_GMM ? itemp : 1.f;
   const bool EL = ek == L2HMC_ENERGY_GAUSS_DIAG || ek == L2HMC_ENERGY_ROUGHWELL;   // elementwise grad / Hessian
   float deps = 0.f;           // this thread's share of d loss / d eps
   int s_me = 0;               // step index of this thread's chain at iteration X.it
@@ -506,10 +515,10 @@ __global__ __launch_bounds__(TTHREADS) void train_kernel(const TArgs A) {
     return isf ? m : 1.f - m;
   };
   auto g_elem = [&](float z, int k) {          // elementwise grad U
-    return ek == L2HMC_ENERGY_GAUSS_DIAG ? Pr[k] * (z - Mu[k]) : z - (A.eta / rw_den) * sinf(z / rw_den);
+    return ek == L2HMC_ENERGY_GAUSS_DIAG ? Pr[k] * (z - Mu[k]) : (z - (A.eta / rw_den) * sinf(z / rw_den)) * rs;
   };
   auto h_elem = [&](float z, int k) {          // elementwise Hessian diagonal
-    return ek == L2HMC_ENERGY_GAUSS_DIAG ? Pr[k] : 1.f - (A.eta / (rw_den * rw_den)) * cosf(z / rw_den);
+    return ek == L2HMC_ENERGY_GAUSS_DIAG ? Pr[k] : (1.f - (A.eta / (rw_den * rw_den)) * cosf(z / rw_den)) * rs;
   };
   // y_comp(k) = sum_j G_comp(k, j) (z_j - [center] mu_comp_j) for one chain row (dense / mixture kinds)
   auto matG = [&](int comp, const float* zrow, bool center, int k) {
@@ -549,11 +558,12 @@ __global__ __launch_bounds__(TTHREADS) void train_kernel(const TArgs A) {
       } else {
         out = matG(0, zrow, true, k);
       }
-      g[c * ldd + k] = out;
+      g[c * ldd + k] = out * rs;
     }
     __syncthreads();
   };
-  // U(z) of chain cc, given g = grad U(z) (and WV of the same z for the mixture); one thread per chain
+  // U(z) of chain cc, given g = grad U(z) (and WV of the same z for the mixture); one thread per chain.  (The Gaussians' g
+  // is already tempered -- U = (z - mu) . g / 2 is then too -- the other kinds scale the finished sum)
   auto energyU = [&](const float* z, const float* g, int cc) {
     const float* zrow = z + cc * ldd;
     float u = 0.f;
@@ -565,7 +575,7 @@ __global__ __launch_bounds__(TTHREADS) void train_kernel(const TArgs A) {
     } else {
       for (int k = 0; k < d; ++k) u += 0.5f * (zrow[k] - Mu[k]) * g[cc * ldd + k];
     }
-    return u;
+    return u * rs;
   };
   // out <- Hessian(z) vec for the dense / mixture kinds (needs WV of the same z); ends with a barrier
   auto hessvec_full = [&](const float* z, const float* vec, float* out) {
@@ -595,7 +605,7 @@ __global__ __launch_bounds__(TTHREADS) void train_kernel(const TArgs A) {
       } else {
         o = matG(0, vrow, false, k);
       }
-      out[c * ldd + k] = o;
+      out[c * ldd + k] = o * rs;
     }
     __syncthreads();
   };
@@ -978,8 +988,14 @@ inline bool train_small_ok(int ek, int d, int H) {
 }
 template <int EK>
 int launch_train_small(const TArgs& k, int KH, unsigned blocks, long long lds, hipStream_t s) {
-  if (KH <= 3) hipLaunchKernelGGL((train_small_kernel<EK, 3>), dim3(blocks), dim3(128), (size_t)lds, s, k);
-  else hipLaunchKernelGGL((train_small_kernel<EK, 4>), dim3(blocks), dim3(128), (size_t)lds, s, k);
+  const bool tp = k.itemp != 1.f;
+  if (KH <= 3) {
+    if (tp) hipLaunchKernelGGL((train_small_kernel<EK, 3, true>), dim3(blocks), dim3(128), (size_t)lds, s, k);
+    else hipLaunchKernelGGL((train_small_kernel<EK, 3, false>), dim3(blocks), dim3(128), (size_t)lds, s, k);
+  } else {
+    if (tp) hipLaunchKernelGGL((train_small_kernel<EK, 4, true>), dim3(blocks), dim3(128), (size_t)lds, s, k);
+    else hipLaunchKernelGGL((train_small_kernel<EK, 4, false>), dim3(blocks), dim3(128), (size_t)lds, s, k);
+  }
   return L2HMC_OK;
 }
 
@@ -1001,8 +1017,9 @@ int launch_train_fast(const TArgs& k, int KH, unsigned blocks, long long lds, hi
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(64 * NW), (size_t)lds, s, k);
     return L2HMC_OK;
   };
-  if (KH <= 3) return go(train_fast_kernel<EK, NW, 3>);
-  return go(train_fast_kernel<EK, NW, 4>);
+  const bool tp = k.itemp != 1.f;
+  if (KH <= 3) return tp ? go(train_fast_kernel<EK, NW, 3, true>) : go(train_fast_kernel<EK, NW, 3, false>);
+  return tp ? go(train_fast_kernel<EK, NW, 4, true>) : go(train_fast_kernel<EK, NW, 4, false>);
 }
 
 }  // namespace l2hmc
@@ -1097,7 +1114,8 @@ static int train_launch(const L2hmcTrainArgs* a, const L2hmcTrainStep* st, void*
   if (ek == L2HMC_ENERGY_GMM && (!a->energy.logc || a->energy.n_comp < 1 || a->energy.n_comp > KC))
     return fail(L2HMC_ERR_ARG, "GMM training needs logc and 1 <= n_comp <= 8%s");
   if (ek == L2HMC_ENERGY_ROUGHWELL && !(a->energy.eta > 0.f)) return fail(L2HMC_ERR_ARG, "roughwell needs eta > 0%s");
-  if (!(a->energy.temperature == 1.f)) return fail(L2HMC_ERR_UNSUPPORTED, "training kernel: temperature must be 1%s");
+  if (!(a->energy.temperature > 0.f && a->energy.temperature < INFINITY))
+    return fail(L2HMC_ERR_ARG, "training kernel: temperature must be finite and > 0%s");
   if (a->energy.anneal_beta != 0.f && a->energy.anneal_beta != 1.f)
     return fail(L2HMC_ERR_UNSUPPORTED, "training kernel: annealed energies are not supported%s");
   if (!a->alpha && !(a->eps_host > 0.f)) return fail(L2HMC_ERR_ARG, "eps must be > 0%s");
@@ -1110,6 +1128,7 @@ static int train_launch(const L2hmcTrainArgs* a, const L2hmcTrainStep* st, void*
   k.mu = a->energy.mu; k.prec = a->energy.prec; k.logc = a->energy.logc; k.eta = a->energy.eta;
   k.ncomp = ek == L2HMC_ENERGY_GMM ? a->energy.n_comp : 1; k.easy = a->energy.easy;
   k.den = roughwell_den(&a->energy);
+  k.itemp = 1.f / a->energy.temperature;
   k.scale = a->scale; k.inv_n = a->inv_n;
   k.Lx = a->Lx; k.p = a->p; k.v1 = a->v1; k.grad = a->grad; k.ws = a->workspace;
   k.x_head = st ? st->x_head : nullptr; k.n_head = st ? st->n_head : 0;
@@ -1152,11 +1171,13 @@ static int train_launch(const L2hmcTrainArgs* a, const L2hmcTrainStep* st, void*
     if (lds > 160 * 1024)
       return fail(L2HMC_ERR_UNSUPPORTED, "training kernel needs %s%lld bytes of LDS (> 160 KiB): d / H too large for the 16-chain tile", "", lds);
     if (lds > 48 * 1024) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(train_kernel),
+      hipError_t e = hipFuncSetAttribute(k.itemp != 1.f ? reinterpret_cast<const void*>(train_kernel<true>)
+                                                         : reinterpret_cast<const void*>(train_kernel<false>),
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
       if (e != hipSuccess) return fail(L2HMC_ERR_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(e));
     }
-    hipLaunchKernelGGL(train_kernel, dim3(blocks), dim3(TTHREADS), (size_t)lds, s, k);
+    if (k.itemp != 1.f) hipLaunchKernelGGL(train_kernel<true>, dim3(blocks), dim3(TTHREADS), (size_t)lds, s, k);
+    else hipLaunchKernelGGL(train_kernel<false>, dim3(blocks), dim3(TTHREADS), (size_t)lds, s, k);
     note_kernel("train_kernel");
     part = a->workspace + (long long)a->T * a->n_chains * CKPT * a->d;
   }

@@ -51,8 +51,11 @@ __host__ __device__ inline TFLayout tf_layout(int T, int NW) {
 // layer 2 in the re-evaluation (storing the head outputs too was measured: at 4096 chains its 1 GB of traffic eats the gain)
 constexpr int TF_CK = 13;
 
-template <int EK, int NW, int KH>
+// TEMP: the target is tempered (A.itemp != 1).  The untempered instantiation multiplies by the constant 1, which the compiler
+// folds away: its code -- every multiply-add it forms -- is the one of the plain energy, bit for bit.
+template <int EK, int NW, int KH, bool TEMP>
 __global__ __launch_bounds__(64 * NW, 1) void train_fast_kernel(const TArgs A) {
+  const float itemp = TEMP ? A.itemp : 1.f;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   lds_poison(smem);
   TS_DECL;
@@ -171,9 +174,11 @@ __global__ __launch_bounds__(64 * NW, 1) void train_fast_kernel(const TArgs A) {
       esx[r] = dok ? expf(s0) : 0.f; eqx[r] = dok ? expf(s1) : 0.f;
       esv[r] = dok ? expf(s2) : 0.f; eqv[r] = dok ? expf(s3) : 0.f;
       if (EK != L2HMC_ENERGY_ROUGHWELL && EK != L2HMC_ENERGY_FUNNEL) emu[r] = dok ? m0 : 0.f;
-      if (EK == L2HMC_ENERGY_GAUSS_DIAG) epr[r] = dok ? p0 : 0.f;
+      // (temperature: U / temperature of a Gaussian is the Gaussian of precision P / temperature -- grad U, the Hessian and
+      //  U = (z - mu) . g / 2 follow from the scaled precision; 1 / temperature is exactly 1.0f on untempered targets)
+      if (EK == L2HMC_ENERGY_GAUSS_DIAG) epr[r] = dok ? p0 * itemp : 0.f;
       if (EK == L2HMC_ENERGY_GAUSS_DENSE)       // NW == 1: A operand of y = G dx, rows = out dims c, k = 4 q + r
-        Gf[r] = (c < d && dok) ? 0.5f * (ga + gb) : 0.f;
+        Gf[r] = (c < d && dok) ? 0.5f * (ga + gb) * itemp : 0.f;
     }
   }
   const f4 live4 = f4{dim0 < d ? 1.f : 0.f, dim0 + 1 < d ? 1.f : 0.f, dim0 + 2 < d ? 1.f : 0.f, dim0 + 3 < d ? 1.f : 0.f};
@@ -224,6 +229,9 @@ __global__ __launch_bounds__(64 * NW, 1) void train_fast_kernel(const TArgs A) {
   };
 
   // ---- energies ------------------------------------------------------------------------------------------------
+  // U / temperature: the Gaussians carry 1 / temperature in their precision (above); Rough Well and the funnel multiply the
+  // finished grad U, Hessian-vector product and energy by the wave-uniform 1 / temperature (`itemp`: the constant 1 when the
+  // target is not tempered)
   // funnel (distributions.py:155-180; NW == 1): v = z_0 lives in lane (c, 0) component 0; the chain's 4 lanes share
   // v, q = sum_{k >= 1} z_k^2 and the branch (free / clipped at +- 4 sigma) through wave shuffles
   struct Fun { float v, qsum, inv, s; bool clipped; };
@@ -246,14 +254,14 @@ __global__ __launch_bounds__(64 * NW, 1) void train_fast_kernel(const TArgs A) {
       const Fun F = fun_parts(z);
       g = z * F.inv;
       if (q == 0) g[0] = F.v / (A.eta * A.eta) + (F.clipped ? 0.f : 0.5f * ((float)(d - 1) - F.qsum * F.inv));
-      return g;
+      return g * itemp;
     }
     if (EK == L2HMC_ENERGY_GAUSS_DIAG) g = epr * (z - emu);
     else if (EK == L2HMC_ENERGY_GAUSS_DENSE) g = chain4(Gf, z - emu, Z);
     else {
 #pragma unroll
       for (int r = 0; r < 4; ++r) g[r] = z[r] - (A.eta / rw_den) * sinf(z[r] / rw_den);
-      g = g * live4;
+      g = g * live4 * itemp;
     }
     return g;
   };
@@ -267,14 +275,14 @@ __global__ __launch_bounds__(64 * NW, 1) void train_fast_kernel(const TArgs A) {
       const float fr = F.clipped ? 0.f : 1.f;
       o = vec * F.inv - z * (fr * u0 * F.inv);
       if (q == 0) o[0] = u0 * (1.f / (A.eta * A.eta) + fr * 0.5f * F.qsum * F.inv) - fr * dot * F.inv;
-      return o;
+      return o * itemp;
     }
     if (EK == L2HMC_ENERGY_GAUSS_DIAG) o = epr * vec;
     else if (EK == L2HMC_ENERGY_GAUSS_DENSE) o = chain4(Gf, vec, Z);
     else {
 #pragma unroll
       for (int r = 0; r < 4; ++r) o[r] = (1.f - (A.eta / (rw_den * rw_den)) * cosf(z[r] / rw_den)) * vec[r];
-      o = o * live4;
+      o = o * live4 * itemp;
     }
     return o;
   };
@@ -283,11 +291,12 @@ __global__ __launch_bounds__(64 * NW, 1) void train_fast_kernel(const TArgs A) {
     if (EK == L2HMC_ENERGY_FUNNEL) {
       const Fun F = fun_parts(z);
       const float lp = (F.v / A.eta) * (F.v / A.eta);
-      return lane < 16 ? 0.5f * (lp + F.qsum * F.inv + (float)(d - 1) * logf(6.283185307179586f * F.s)) : 0.f;
+      return lane < 16 ? (0.5f * itemp) * (lp + F.qsum * F.inv + (float)(d - 1) * logf(6.283185307179586f * F.s)) : 0.f;
     }
     if (EK == L2HMC_ENERGY_ROUGHWELL) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) u += live4[r] * (0.5f * z[r] * z[r] + A.eta * cosf(z[r] / rw_den));
+      u = u * itemp;
     } else {
       u = 0.5f * hsum((z - emu) * g);
     }

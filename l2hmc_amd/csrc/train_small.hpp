@@ -42,8 +42,9 @@ __host__ __device__ inline TSLayout ts_layout(int T) {
 constexpr int TS_CK = 49;
 static_assert(TS_CK * 64 <= TF_CK * 256, "the d <= 4 trainer's checkpoints must fit the per-tile workspace stride");
 
-template <int EK, int KH>
+template <int EK, int KH, bool TEMP>          // TEMP: as train_fast_kernel
 __global__ __launch_bounds__(128, 1) void train_small_kernel(const TArgs A) {
+  const float itemp = TEMP ? A.itemp : 1.f;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   lds_poison(smem);
   TS_DECL;
@@ -147,9 +148,10 @@ __global__ __launch_bounds__(128, 1) void train_small_kernel(const TArgs A) {
     esx = livedim ? expf(s0) : 0.f; eqx = livedim ? expf(s1) : 0.f;
     esv = livedim ? expf(s2) : 0.f; eqv = livedim ? expf(s3) : 0.f;
     emu = livedim ? m0 : 0.f;
-    epr = livedim ? p0 : 0.f;
+    // (temperature: the Gaussians' precision carries 1 / temperature -- train_fast.hpp, "temperature")
+    epr = livedim ? p0 * itemp : 0.f;
     // dense Gaussian: A operand of y = G dx: row 4 j <- G[j][q] (symmetrised), else 0
-    if (EK == L2HMC_ENERGY_GAUSS_DENSE) Gf = (livedim && (c & 3) == 0 && j < d) ? 0.5f * (ga + gb) : 0.f;
+    if (EK == L2HMC_ENERGY_GAUSS_DENSE) Gf = (livedim && (c & 3) == 0 && j < d) ? 0.5f * (ga + gb) * itemp : 0.f;
   }
   // mixture of Gaussians (distributions.py:104-134): per component the mean of this lane's dimension, the A operand of
   // y_k = G_k (z - mu_k) (as Gf above) and the log-weight constant; KC = 8 components at most, all in registers
@@ -296,11 +298,13 @@ __global__ __launch_bounds__(128, 1) void train_small_kernel(const TArgs A) {
       if (k < A.ncomp) { GP.r[k] *= inv; GP.g += GP.r[k] * GP.y[k]; }
     GP.lse = logf(se) + mx;
   };
+  // U / temperature: the Gaussians carry it in epr / Gf (staging); the mixture and Rough Well scale their finished outputs by
+  // the wave-uniform itemp -- never GP's cached gradient, which hessvec's g g^T term reads again (it would square the factor)
   auto gradU = [&](float z) {
     if (EK == L2HMC_ENERGY_GAUSS_DIAG) return epr * (z - emu);
     if (EK == L2HMC_ENERGY_GAUSS_DENSE) { const f4 y = MFMA16(Gf, z - emu, Z); return y.x * live1; }
-    if (EK == L2HMC_ENERGY_GMM) { gmm_parts(z); return GP.g; }
-    return live1 * (z - (A.eta / rw_den) * sinf(z / rw_den));
+    if (EK == L2HMC_ENERGY_GMM) { gmm_parts(z); return GP.g * itemp; }
+    return (live1 * itemp) * (z - (A.eta / rw_den) * sinf(z / rw_den));
   };
   auto hessvec = [&](float z, float vec) {           // GMM: at the point of the last gradU call
     if (EK == L2HMC_ENERGY_GAUSS_DIAG) return epr * vec;
@@ -314,13 +318,13 @@ __global__ __launch_bounds__(128, 1) void train_small_kernel(const TArgs A) {
           const f4 Gu = MFMA16(gGf[k], u, Z);
           out += GP.r[k] * (Gu.x * live1 - GP.y[k] * qsum(GP.y[k] * u));
         }
-      return out;
+      return out * itemp;
     }
-    return live1 * (1.f - (A.eta / (rw_den * rw_den)) * cosf(z / rw_den)) * vec;
+    return (live1 * itemp) * (1.f - (A.eta / (rw_den * rw_den)) * cosf(z / rw_den)) * vec;
   };
   auto energy_part = [&](float z, float g) {        // this lane's share of U(z)  (GMM: of the last gradU point)
-    if (EK == L2HMC_ENERGY_ROUGHWELL) return live1 * (0.5f * z * z + A.eta * cosf(z / rw_den));
-    if (EK == L2HMC_ENERGY_GMM) return q == 0 ? -GP.lse : 0.f;
+    if (EK == L2HMC_ENERGY_ROUGHWELL) return (live1 * itemp) * (0.5f * z * z + A.eta * cosf(z / rw_den));
+    if (EK == L2HMC_ENERGY_GMM) return q == 0 ? -GP.lse * itemp : 0.f;
     return 0.5f * (z - emu) * g;
   };
 

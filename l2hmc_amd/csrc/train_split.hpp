@@ -172,8 +172,9 @@ __global__ void k_comb_v2(float* lx, const float* dAB, const float* hv, long lon
 
 // Hessian-vector products of the built-in targets (oracle/l2hmc_train_oracle.py *Target.hessvec): diagonal Gaussian
 // P u; Rough Well (1 - (eta / den^2) cos(x / den)) u; dense Gaussian G u with G = (S + S^T) / 2 of the RAW precision
+// (it = 1 / temperature: the products of U / temperature)
 __global__ void k_hvp_builtin(int kind, const float* x, int ldx, const float* u, float* hv, const float* prec,
-                              const float* hess, float eta, float den, long long N, int d) {
+                              const float* hess, float eta, float den, float it, long long N, int d) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= N * d) return;
   const long long n = i / d;
@@ -187,7 +188,7 @@ __global__ void k_hvp_builtin(int kind, const float* x, int ldx, const float* u,
     o = 0.f;
     for (int j = 0; j < d; ++j) o += 0.5f * (hess[k * d + j] + hess[j * d + k]) * u[n * d + j];
   }
-  hv[i] = o;
+  hv[i] = o * it;
 }
 
 // Hessian-vector products that couple the dimensions of a chain (oracle/l2hmc_train_oracle.py GMMTarget / FunnelTarget
@@ -197,8 +198,9 @@ __global__ void k_hvp_builtin(int kind, const float* x, int ldx, const float* u,
 //   funnel (distributions.py:155-180), s = e^{x_0} (constant on the clipped branches), q = sum_{k>=1} x_k^2:
 //     (H u)_k = u_k / s - [free] x_k u_0 / s,   (H u)_0 = u_0 (1 / sigma^2 + [free] q / (2 s)) - [free] sum_k x_k u_k / s
 constexpr int HVP_MAXC = 32;
+//   (it = 1 / temperature multiplies the finished product -- never the mixture's gradient g, which enters twice)
 __global__ void k_hvp_chain(int kind, const float* x, int ldx, const float* u, float* hv, float* gs, const float* mu,
-                            const float* hess, const float* logc, int ncomp, float sigma, long long N, int d) {
+                            const float* hess, const float* logc, int ncomp, float sigma, float it, long long N, int d) {
   const long long n = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (n >= N) return;
   const float* xr = x + n * ldx;
@@ -211,8 +213,8 @@ __global__ void k_hvp_chain(int kind, const float* x, int ldx, const float* u, f
     const float inv_s = 1.f / (hi ? expf(clip) : (lo ? expf(-clip) : expf(v)));
     float q = 0.f, dot = 0.f;
     for (int k = 1; k < d; ++k) { q += xr[k] * xr[k]; dot += xr[k] * ur[k]; }
-    for (int k = 1; k < d; ++k) o[k] = ur[k] * inv_s - fr * xr[k] * ur[0] * inv_s;
-    o[0] = ur[0] * (1.f / (sigma * sigma) + fr * 0.5f * q * inv_s) - fr * dot * inv_s;
+    for (int k = 1; k < d; ++k) o[k] = (ur[k] * inv_s - fr * xr[k] * ur[0] * inv_s) * it;
+    o[0] = (ur[0] * (1.f / (sigma * sigma) + fr * 0.5f * q * inv_s) - fr * dot * inv_s) * it;
     return;
   }
   // mixture: y(c, k) = sum_j G_c[k][j] (x_j - mu_c[j])
@@ -251,11 +253,27 @@ __global__ void k_hvp_chain(int kind, const float* x, int ldx, const float* u, f
       o[k] += w[c] * (Gu - ycomp(c, k) * yu);
     }
   }
+  if (it != 1.f)
+    for (int k = 0; k < d; ++k) o[k] *= it;
+}
+
+// U / temperature and grad U / temperature of a point whose energy was evaluated plain (the decoder posterior): rows of g
+// (stride ldg) and, when given, U (double); also the decoder's Hessian-vector products (U = NULL)
+__global__ void k_temper(float* g, int ldg, double* U, float it, double itd, long long N, int d) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N * d) return;
+  const long long n = i / d;
+  const int k = (int)(i % d);
+  g[n * ldg + k] *= it;
+  if (U != nullptr && k == 0) U[n] *= itd;
 }
 
 // accept probability (dynamics.py:302-309), the loss argument and the adjoint seeds of the reverse sweep
 // (train.hip "accept probability, loss term and the adjoint seeds"); one wave per chain.
 //   es > 0: + es inv_n sum_n (1 / ed_n - ed_n),  ed = (U(Lx) - U(x))^2 p + 1e-4   (mnist_vae.py:214-224, energy_scale)
+//     U0 / U1 / g1 are those of U / temperature (what the dynamics and the accept probability see); the energy term is built
+//     from the PLAIN U (mnist_vae.py:209 calls the untempered closure): dU = temperature (U1 - U0), and its cotangent on the
+//     tempered g1 carries the factor temperature
 //   no_accept: a link of chain_operator (sampler.py:57-85, propose(log_jac=True)): no accept probability and no loss
 //   term of its own -- the seeds are the caller's cotangents on Lx / Lv / the summed log-Jacobian.
 __global__ __launch_bounds__(256) void k_train_seed(const float* x0, const float* x1, int ldx1, const float* v1,
@@ -265,7 +283,7 @@ __global__ __launch_bounds__(256) void k_train_seed(const float* x0, const float
                                                     int no_accept, float scale, float inv_n, float es, float* Lx,
                                                     float* Lv_out, float* lj_out, float* p_out, float* v1_out,
                                                     float* ed_out, float* lam, float* lamU, float* dv1p_out, float* lx,
-                                                    float* lv, float* deps, long long N, int d) {
+                                                    float* lv, float* deps, float temp, long long N, int d) {
   const long long n = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
   if (n >= N) return;
@@ -300,11 +318,11 @@ __global__ __launch_bounds__(256) void k_train_seed(const float* x0, const float
   const bool pfin = (val == val) && p > 0.f;          // the finite branch of dynamics.py:309 actually taken
   const bool ok = sq < 3.0e38f;                       // a diverged chain contributes no gradient (train.hip)
   // energy term: ed = dU^2 p + 1e-4
-  const float dU = (float)(U1[n] - U0[n]);
+  const float dU = (float)((U1[n] - U0[n]) * (double)temp);
   const bool eok = es > 0.f && ok && fabsf(dU) < 1.0e18f;
   const float ed = eok ? dU * dU * p + 1e-4f : 1.f;
   const float de = eok ? es * inv_n * (-1.f / (ed * ed) - 1.f) : 0.f;
-  const float eu = de * 2.f * dU * p;                 // d term / d U(Lx) through dU  (= - d term / d U(x))
+  const float eu = de * 2.f * dU * (p * temp);        // d term / d (U(Lx) / temperature) through dU  (= - ... / d U(x))
   const float lm = (ok && pfin && val < 0.f) ? (dv1 * sq + de * dU * dU) * p : 0.f;
   const float dv1p = ok ? dv1 * p * 2.f : 0.f;
   if (lane == 0) {
@@ -749,7 +767,10 @@ int l2hmc_train_split_grad(const L2hmcTrainSplitArgs* a, void* stream) {
   t_gemm_bf3 = a ? a->gemm_mode != 0 : 0;
   t_plane_mode = 0;          // (the adjoint planes hold entries scaled by 1 / chains: they need bf16's exponent range)
   if (!a) return fail(L2HMC_ERR_ARG, "args is NULL%s");
-  const bool builtin = a->energy != nullptr;
+  // `energy` of kind 0 next to the decoder posterior or energy_cb: only its temperature is read (the target's own form is the
+  // decoder / the callbacks)
+  const bool tcarrier = a->energy != nullptr && a->energy->kind == 0;
+  const bool builtin = a->energy != nullptr && !tcarrier;
   const bool user = a->energy_cb != nullptr;       // the caller's energy: U / grad U and Hessian-vector products by callback
   const bool vae = !builtin && !user;              // the decoder posterior
   // (ABI 6) the caller's own S/T/Q nets (any callable, dynamics.py:69-79): forward by net_cb, reverse by net_vjp_cb
@@ -764,8 +785,11 @@ int l2hmc_train_split_grad(const L2hmcTrainSplitArgs* a, void* stream) {
   const int d = a->d, H = unets ? 4 : a->H, T = a->T;     // (caller-supplied nets: no hidden activations are planned for)
   if (N < 0 || d < 1 || H < 1 || T < 1) return fail(L2HMC_ERR_ARG, "bad n_chains / d / H / T%s");
   if (N == 0) return L2HMC_OK;
+  if (tcarrier && (a->energy->anneal_beta != 0.f || !(a->energy->temperature > 0.f && a->energy->temperature < INFINITY)))
+    return fail(L2HMC_ERR_ARG, "an energy of kind 0 (the temperature of the decoder posterior / energy_cb) needs a finite "
+                "temperature > 0 and anneal_beta = 0%s");
   if (user) {
-    if (builtin || a->decoder) return fail(L2HMC_ERR_ARG, "energy_cb excludes energy and decoder%s");
+    if (builtin || a->decoder) return fail(L2HMC_ERR_ARG, "energy_cb excludes a built-in energy and decoder%s");
     if (!a->hvp_cb) return fail(L2HMC_ERR_ARG, "training on a caller-supplied energy needs hvp_cb (the loss differentiates through grad U)%s");
     if (a->aux_encoder && !a->aux) return fail(L2HMC_ERR_ARG, "aux_encoder needs aux%s");
   } else if (builtin) {
@@ -777,8 +801,9 @@ int l2hmc_train_split_grad(const L2hmcTrainSplitArgs* a, void* stream) {
       return fail(L2HMC_ERR_ARG, "dense Gaussian / mixture: hess = the RAW (n_comp, d, d) precisions%s");
     if (ek == L2HMC_ENERGY_GMM && a->energy->n_comp > HVP_MAXC)
       return fail(L2HMC_ERR_UNSUPPORTED, "mixture training: at most %s%lld components", "", (long long)HVP_MAXC);
-    if (a->energy->temperature != 1.f || (a->energy->anneal_beta != 0.f && a->energy->anneal_beta != 1.f))
-      return fail(L2HMC_ERR_UNSUPPORTED, "training differentiates the plain energy (temperature 1, no annealing)%s");
+    if (!(a->energy->temperature < INFINITY)) return fail(L2HMC_ERR_ARG, "temperature must be finite and > 0%s");
+    if (a->energy->anneal_beta != 0.f && a->energy->anneal_beta != 1.f)
+      return fail(L2HMC_ERR_UNSUPPORTED, "training does not differentiate the annealed energy (anneal_beta)%s");
   } else {
     if ((rc = check_mlp(a->decoder, "decoder"))) return rc;
     if (!a->aux) return fail(L2HMC_ERR_ARG, "the decoder posterior needs aux%s");
@@ -827,6 +852,11 @@ int l2hmc_train_split_grad(const L2hmcTrainSplitArgs* a, void* stream) {
   float *tb = w + f.tb, *ld = w + f.ld;
   float* aux_h = a->aux_encoder ? w + f.aux_h : nullptr;
   double *U0d = reinterpret_cast<double*>(w + f.U0), *U1d = reinterpret_cast<double*>(w + f.U1);
+  // training on U / temperature: the built-in energies (l2hmc_energy) and the callbacks return it tempered; the decoder
+  // posterior is evaluated plain and tempered behind (k_temper), only when temperature != 1
+  const float temp = a->energy != nullptr ? a->energy->temperature : 1.f;
+  const float itemp = 1.f / temp;
+  const bool temper_dec = vae && temp != 1.f;
   const long long NL = N * L, NH = N * H, N3 = N * 3 * d, Nd = N * d;
   // stash slices of evaluation `ne` (= 2 it + which) of net `net` (0 = X, 1 = V)
   auto AB = [&](int net, int ne) { return w + p.AB[net] + ne * NL; };
@@ -936,6 +966,8 @@ int l2hmc_train_split_grad(const L2hmcTrainSplitArgs* a, void* stream) {
     }
     if (vae) {
       vae_energy_keep(s, dec, a->aux, ab, L, N, d, dws, w + f.lg, w + f.rowsum, Ud, ab + d, L, dec_point(j));
+      if (temper_dec)
+        hipLaunchKernelGGL(k_temper, dim3(nblk(Nd)), dim3(256), 0, s, ab + d, L, Ud, itemp, 1.0 / (double)temp, N, d);
       return L2HMC_OK;
     }
     (void)hipMemcpy2DAsync(w + f.xp, sizeof(float) * d, ab, sizeof(float) * L, sizeof(float) * d, (size_t)N, hipMemcpyDeviceToDevice, s);
@@ -1049,7 +1081,7 @@ int l2hmc_train_split_grad(const L2hmcTrainSplitArgs* a, void* stream) {
     hipLaunchKernelGGL(k_train_seed, dim3(nw4), dim3(256), 0, s, a->x, abe, L, VS(T), abe + d, L, U0d, U1d, w + f.K0, ld,
                        a->dist_weight, a->dLx_in, a->dLv_in, a->dlogjac_in, a->no_accept, a->scale, a->inv_n,
                        a->energy_scale, a->Lx, a->Lv_out, a->logjac_out, a->p, a->v1, a->ediff_out, lam, lamU, dv1p, lx, lv,
-                       deps, N, d);
+                       deps, temp, N, d);
   }
   // VNet evaluation at trajectory point j (inputs (x, grad U(x)) in `ab`):  lx += d a + Hessian(x) (dg + d b).
   // Every interior point is the input of TWO VNet evaluations (the end of one leapfrog step and the start of the next,
@@ -1072,12 +1104,14 @@ int l2hmc_train_split_grad(const L2hmcTrainSplitArgs* a, void* stream) {
       if (r) return fail(L2HMC_ERR_ARG, "the Hessian-vector callback failed (returned %s%lld)", "", (long long)r);
     } else if (vae) {
       vae_hvp(s, dec, N, d, dws, dec_point(j), p, w, uu, hv);
+      if (temper_dec) hipLaunchKernelGGL(k_temper, dim3(nblk(Nd)), dim3(256), 0, s, hv, d, (double*)nullptr, itemp, 1.0, N, d);
     } else if (a->energy->kind == L2HMC_ENERGY_GMM || a->energy->kind == L2HMC_ENERGY_FUNNEL) {
       hipLaunchKernelGGL(k_hvp_chain, dim3(nblk(N)), dim3(256), 0, s, a->energy->kind, ab, L, uu, hv, dg, a->energy->mu, a->hess,
-                         a->energy->logc, a->energy->n_comp, a->energy->eta, N, d);      // (dg is free: its sum went into uu)
+                         a->energy->logc, a->energy->n_comp, a->energy->eta, itemp, N, d);   // (dg is free: its sum went into uu)
     } else {
       hipLaunchKernelGGL(k_hvp_builtin, dim3(nblk(Nd)), dim3(256), 0, s, a->energy->kind, ab, L, uu, hv, a->energy->prec,
-                         a->hess, a->energy->eta, a->energy->kind == L2HMC_ENERGY_ROUGHWELL ? roughwell_den(a->energy) : 1.f, N, d);
+                         a->hess, a->energy->eta, a->energy->kind == L2HMC_ENERGY_ROUGHWELL ? roughwell_den(a->energy) : 1.f, itemp,
+                         N, d);
     }
     hipLaunchKernelGGL(k_comb_v2, dim3(nblk(Nd)), dim3(256), 0, s, lx, dAB, hv, N, d);
     return L2HMC_OK;

@@ -22,6 +22,7 @@ rank's Philox offset) is exchanged ONCE, on the first step of every rank, or dec
 the buffers and the collective.
 """
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -41,6 +42,23 @@ def _numel(code, d, H):
 
 
 RNG_STREAM = "philox4x32-10/hw-boxmuller"       # (l2hmc_kernels.hpp philox_normal4; "…/libm-normals" up to ABI 3)
+
+
+def train_temperature(dynamics):
+    """The temperature the training loss differentiates at: U / temperature inside the dynamics (leapfrog, net inputs,
+    accept probability), the reference's rule of dynamics.py:204-205 -- `dynamics.temperature` if `use_temperature`, else 1.
+    Read at every call (the reference feeds its placeholder on every sess.run): an annealing schedule sets
+    `dynamics.temperature` before each step.  A non-finite or non-positive temperature is an argument error."""
+    t = float(dynamics.temperature) if dynamics.use_temperature else 1.0
+    if not (math.isfinite(t) and t > 0.0):
+        raise ValueError("temperature must be finite and > 0, got %r" % (t,))
+    return t
+
+
+def _refuse_annealed(dynamics):
+    if float(dynamics.anneal_beta or 0.0) != 0.0:
+        raise NotImplementedError("the training kernels differentiate U / temperature, not the AIS bridge: an annealed "
+                                  "(anneal_beta) Dynamics is not supported")
 
 
 class Trainer(object):
@@ -69,9 +87,8 @@ class Trainer(object):
                  beta1=0.9, beta2=0.999, epsilon=1e-8, seed=0):
         if dynamics.hmc:
             raise ValueError("an HMC-mode Dynamics has nothing to train")
-        if (dynamics.use_temperature and float(dynamics.temperature) != 1.0) or float(dynamics.anneal_beta or 0.0) != 0.0:
-            raise NotImplementedError("the training kernel differentiates the plain energy U: a tempered "
-                                      "(temperature != 1) or annealed (anneal_beta) Dynamics is not supported")
+        _refuse_annealed(dynamics)
+        train_temperature(dynamics)
         self.dyn, self.scale = dynamics, float(scale)
         self.lr0, self.decay_steps, self.decay_rate = float(lr), int(decay_steps), float(decay_rate)
         self.beta1, self.beta2, self.epsilon = float(beta1), float(beta2), float(epsilon)
@@ -208,8 +225,9 @@ class Trainer(object):
             raise NotImplementedError("training supports the Gaussian, GMM, Rough-Well and funnel targets")
         a = _ffi.L2hmcTrainArgs()
         a.xnet, a.vnet = C.pointer(xs), C.pointer(vs)
+        _refuse_annealed(dyn)
         a.energy = _ffi.L2hmcEnergy(fn.kind, fn.n_comp, _ffi.ptr(buf["mu"]), _ffi.ptr(prec), _ffi.ptr(buf["logc"]),
-                                    fn.eta, int(fn.easy), 1.0, 0.0, fn.den, 0)
+                                    fn.eta, int(fn.easy), train_temperature(dyn), 0.0, fn.den, 0)
         a.masks, a.trig = dyn._mask.data_ptr(), dyn._trig.data_ptr()
         if dyn.eps_override is None:
             a.alpha, a.eps_host = dyn.alpha.data_ptr(), 0.0
@@ -445,9 +463,8 @@ class SplitTrainer(Trainer):
                  beta1=0.9, beta2=0.999, epsilon=1e-8, seed=0, clip_norm=None):
         if dynamics.hmc:
             raise ValueError("an HMC-mode Dynamics has nothing to train")
-        if (dynamics.use_temperature and float(dynamics.temperature) != 1.0) or float(dynamics.anneal_beta or 0.0) != 0.0:
-            raise NotImplementedError("training differentiates the plain energy U: a tempered or annealed Dynamics "
-                                      "is not supported")
+        _refuse_annealed(dynamics)
+        train_temperature(dynamics)
         from .vae import mlp3_struct
         self._mlp3_struct = mlp3_struct
         self.dyn = dynamics
@@ -578,6 +595,12 @@ class SplitTrainer(Trainer):
             a.xnet, a.vnet, a.H = C.pointer(xs), C.pointer(vs), dyn.H
         a.aux_encoder = C.pointer(enc_s) if enc_s is not None else None
         keep = None
+        _refuse_annealed(dyn)
+        tau = train_temperature(dyn)
+        # the decoder posterior and a caller-supplied energy name their temperature in an energy of kind 0 (include/l2hmc.h):
+        # the library tempers the decoder's U, grad U and Hessian-vector products itself, the callbacks below temper theirs,
+        # and the energy_scale term of the VAE objective is formed from the plain U (mnist_vae.py:209)
+        tcar = _ffi.L2hmcEnergy(0, 0, None, None, None, 0.0, 0, tau, 0.0, 0.0, 0) if tau != 1.0 else None
         if self.user:
             fn, ws = dyn._fn, self._ws
             base = ws.data_ptr()
@@ -592,7 +615,7 @@ class SplitTrainer(Trainer):
 
             def energy_cb(_user, xp, ldx, n, dd, Up, gp, ldg, _stream):
                 try:
-                    U, g = fn.evaluate(view(xp, n, dd, ldx), 1.0, want_U=bool(Up), want_grad=True, aux=aux)
+                    U, g = fn.evaluate(view(xp, n, dd, ldx), tau, want_U=bool(Up), want_grad=True, aux=aux)
                     if tuple(g.shape) != (n, dd):
                         raise ValueError("grad_energy must return shape (N, d), got %s" % (tuple(g.shape),))
                     view(gp, n, dd, ldg).copy_(g)
@@ -606,13 +629,15 @@ class SplitTrainer(Trainer):
 
             def hvp_cb(_user, xp, ldx, up, ldu, n, dd, hp, ldh, _stream):
                 try:
-                    view(hp, n, dd, ldh).copy_(fn.hvp(view(xp, n, dd, ldx), view(up, n, dd, ldu), aux=aux))
+                    hv = fn.hvp(view(xp, n, dd, ldx), view(up, n, dd, ldu), aux=aux)
+                    view(hp, n, dd, ldh).copy_(hv / tau if tau != 1.0 else hv)
                     return 0
                 except Exception as e:
                     cb_error.append(e)
                     return 1
             keep = (_ffi.ENERGY_CALLBACK(energy_cb), _ffi.HVP_CALLBACK(hvp_cb))     # alive for the duration of the call
             a.energy_cb, a.hvp_cb = C.cast(keep[0], C.c_void_p), C.cast(keep[1], C.c_void_p)
+            a.energy = C.pointer(tcar) if tcar is not None else None
         elif self.vae:
             if aux is None:
                 raise ValueError("the image-conditioned sampler needs aux=")
@@ -620,9 +645,10 @@ class SplitTrainer(Trainer):
             if aux.shape != (N, dyn._fn.n_pix):
                 raise ValueError("aux must be (N, %d)" % dyn._fn.n_pix)
             a.decoder, a.aux = C.pointer(dec_s), aux.data_ptr()
+            a.energy = C.pointer(tcar) if tcar is not None else None
         else:
             fn = dyn._fn
-            keep = fn.c_struct(dyn.device, 1.0, 0.0)
+            keep = fn.c_struct(dyn.device, tau, 0.0)
             a.energy = C.pointer(keep)
             if fn.kind in (_ffi.ENERGY_GAUSS_DENSE, _ffi.ENERGY_GMM):
                 a.hess = fn._buffers(dyn.device)["_raw"].data_ptr()
@@ -742,6 +768,11 @@ class SplitTrainer(Trainer):
         world = self._world()
         R = int(random_lf_composition)
         es = float(energy_scale)
+        tau = train_temperature(dyn)
+        if self.vae and tau != 1.0 and (MH > 1 or R > 0):
+            # the forward-only iterations run on the sampler, whose decoder posterior is not tempered
+            raise NotImplementedError("a tempered decoder posterior trains with MH = 1 and random_lf_composition = 0 (the "
+                                      "sampler does not temper the built-in decoder posterior)")
 
         def normal():
             return torch.randn((N, d), device=dev, generator=gen)
@@ -817,12 +848,12 @@ class SplitTrainer(Trainer):
             sq = (wgt * dx * dx).sum(1).double()
             v1 = sq * p64 + 1e-4
             dv1 = (-1.0 / (v1 * v1) - 1.0) * inv
-            dU = last["U1"] - last["U0"]
+            dU = (last["U1"] - last["U0"]) * tau          # U0 / U1 / g0 / g1 are of U / tau; the energy term of the plain U
             ed = dU * dU * p64 + 1e-4
             de = (-1.0 / (ed * ed) - 1.0) * inv * es
             live = ((val < 0) & torch.isfinite(val) & (p64 > 0)).double()
             lm = ((dv1 * sq + de * dU * dU) * p64 * live).float()
-            eu = (de * 2.0 * dU * p64).float()
+            eu = (de * 2.0 * dU * (p64 * tau)).float()
             dv1p = (dv1 * p64 * 2.0).float()
             dLx = dv1p[:, None] * wgt * dx + (eu - lm)[:, None] * g1
             dLv = (-lm)[:, None] * last["Lv"]

@@ -2,7 +2,10 @@
 """Training-step timing (GPU box): the notebook's training configuration (SCGExperiment.ipynb raw
 156-181, 254-271: SCG 2-d, 200 chains, T=10, H=10) and the 50-d ICG at 200 / 4096 chains.
 
-    python tools/bench_train.py [--no-cpu]
+    python tools/bench_train.py [--no-cpu] [--temperature TAU] [--cases icg50:4096,mog2d:200]
+
+--temperature trains every configuration on U / TAU (Dynamics(use_temperature=True), temperature = TAU); --cases keeps only the
+listed case:chains pairs.
 
 Prints, per configuration: the `l2hmc_train_propose_grad` call rate (HIP events around back-to-back calls, one x- plus one
 z-proposal = the device work of a training step; for the d <= 4 kernel this loop is HOST-bound -- the kernel itself is
@@ -69,11 +72,22 @@ def cpu_reference(dyn, x, cov, reps):
     return (time.perf_counter() - t0) / reps
 
 
+def _arg(name, default=None):
+    return sys.argv[sys.argv.index(name) + 1] if name in sys.argv else default
+
+
 def main():
     dev = torch.device("cuda", 0)
+    tau = float(_arg("--temperature", "1"))
+    keep = _arg("--cases")
+    keep = None if keep is None else set(keep.split(","))
     for case, n, steps in (("scg2d", 200, 200), ("mog2d", 200, 200), ("icg50", 200, 50), ("icg50", 4096, 20),
                            ("rough128", 4096, 10), ("rough512", 4096, 5)):
+        if keep is not None and "%s:%d" % (case, n) not in keep:
+            continue
         dyn, x, cov = make(case, n, dev)
+        if tau != 1.0:
+            dyn.use_temperature, dyn.temperature = True, tau
         tr = Trainer(dyn)
         tr.variant = int(os.environ.get("L2HMC_TRAIN_VARIANT", "0"))      # kernel-choice experiments (include/l2hmc.h)
         v = torch.randn_like(x)
@@ -98,7 +112,7 @@ def main():
             _, _, xs, _ = tr.step(xs)
         torch.cuda.synchronize()
         full = (time.perf_counter() - t0) / steps
-        line = "%s chains %5d: propose+grad kernel %9.1f us / training step, Trainer.step %9.1f us" % (case, n, kern * 1e6, full * 1e6)
+        line = "%s chains %5d tau %g: propose+grad kernel %9.1f us / training step, Trainer.step %9.1f us" % (case, n, tau, kern * 1e6, full * 1e6)
         if "--no-cpu" not in sys.argv and cov is not None:
             try:
                 cpu = cpu_reference(dyn, x, cov, 2 if n <= 200 else 1)
