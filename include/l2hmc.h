@@ -162,6 +162,40 @@ typedef struct L2hmcTrajectoryArgs {
 
 enum { L2HMC_RNG_V = 1, L2HMC_RNG_DIR = 2, L2HMC_RNG_U = 4 };
 
+/* Parallel tempering (replica exchange over a temperature ladder) on the persistent sampler loop: l2hmc_trajectory_ladder.
+ * Layout: N = n_ladders * K rows; row r belongs to ladder r / K and never moves.  Each row carries a rung label
+ * rung_of_row[r] (initially r % K, unless the caller passes others); its temperature is temperatures[rung_of_row[r]].
+ * Global round g = round0 + j (j = 0 .. n_rounds - 1) is proposals_per_round = M proposals -- each the proposal + MH step
+ * of l2hmc_trajectory with U / T of the row's current rung in the leapfrog, the nets' grad U input and the accept
+ * probability -- then one deterministic even-odd swap sweep: for every k = g mod 2, g mod 2 + 2, ... with k + 1 < K, in
+ * every ladder, the rows a (rung k) and b (rung k + 1) exchange labels iff
+ *     log u < (1 / T_k - 1 / T_{k+1}) (U_a - U_b),
+ * U the untempered energy of each row's current state; a NaN on either side rejects.  u is injected (swap_u) or drawn from
+ * the Philox stream keyed by (rng_seed, global ladder index, g) -- stream 2 of csrc/l2hmc_kernels.hpp (philox_swap_u):
+ * counter (chain_offset / K + ladder, 0xFFFFFFFF, g mod 2^32, (g >> 32) << 4 | (k >> 1) << 1 | 1), u = (word 0 >> 8) 2^-24.
+ * Proposal draws are keyed as in l2hmc_trajectory (global chain, proposal index rng_proposal0 + j M + m), so splitting the
+ * ladders over launches or ranks (chain_offset a multiple of K) gives the same bits.
+ * Round trips: a row that has reached rung K - 1 since it last left rung 0 completes one when it is back at rung 0
+ * (evaluated on the labels after every sweep; trip_state[r] = 1 while the row is on its way down). */
+typedef struct L2hmcLadderArgs {
+  int32_t n_rungs;              /* K: 2, 4, 8 or 16                                                                      */
+  int32_t n_rounds;             /* R >= 1                                                                                */
+  int32_t proposals_per_round;  /* M >= 1; the launch runs R * M proposals (L2hmcTrajectoryArgs.n_proposals is ignored:  */
+                                /* injected v / direction / u are (R M, N, ...), p_out / logjac_out (R M, N))            */
+  int32_t reserved_;            /* must be 0                                                                             */
+  float temperatures[16];       /* T_0 .. T_{K-1}: positive, finite, non-decreasing (equal rungs allowed); rest ignored  */
+  uint64_t round0;              /* global index of this launch's first round                                             */
+  int8_t* rung_of_row;          /* (N) labels, read and updated in place                                                 */
+  int8_t* trip_state;           /* (N) round-trip states, read and updated in place, or NULL (all 0, not kept)           */
+  const float* swap_u;          /* (R, n_ladders, K / 2) uniforms of the pairs (k, k + 1) at index k / 2, or NULL        */
+  float* cold_hist;             /* (R M, n_ladders, d) the rung-0 state of every ladder after every proposal (after the  */
+                                /* round's sweep at its last proposal), or NULL                                          */
+  int8_t* rung_hist;            /* (R, N) the labels after every sweep, or NULL                                          */
+  int64_t* swaps_accepted;      /* (K - 1) accepted swaps of the pair (k, k + 1), accumulated (+=), or NULL              */
+  int64_t* swaps_attempted;     /* (K - 1) attempted swaps, accumulated (+=), or NULL                                    */
+  int64_t* round_trips;         /* (n_ladders) completed round trips, accumulated (+=), or NULL                          */
+} L2hmcLadderArgs;
+
 int l2hmc_abi_version(void);
 const char* l2hmc_last_error(void);
 /* Name of the kernel the last l2hmc_trajectory / l2hmc_train_propose_grad / l2hmc_train_step call of THIS thread chose
@@ -193,6 +227,13 @@ int l2hmc_pack_gaussian(const float* i_sigma, int32_t d, float* packed, void* st
  *   propose + tf_accept                    sampler.py:28-55     (direction, u, x_next)
  * Each chain runs only in its drawn direction (the reference runs both and discards one). */
 int l2hmc_trajectory(const L2hmcTrajectoryArgs* args, void* stream);
+
+/* l2hmc_trajectory on a temperature ladder (parallel tempering, L2hmcLadderArgs above): the general trajectory kernel
+ * (variant 0 or 100 + v picks its geometry as for l2hmc_trajectory's 100 + v) with HMC or fused S/T/Q nets (H <= 15) and
+ * every built-in energy.  Needs u (or L2HMC_RNG_U).  L2HMC_ERR_ARG: K not in {2, 4, 8, 16}, N or chain_offset not a
+ * multiple of K, a bad ladder, energy.temperature != 1 (the ladder replaces it); L2HMC_ERR_UNSUPPORTED: AIS fields set,
+ * energy.anneal_beta != 0, any other variant. */
+int l2hmc_trajectory_ladder(const L2hmcTrajectoryArgs* args, const L2hmcLadderArgs* ladder, void* stream);
 
 /* ONE generalised leapfrog step straight from the reference-layout weights -- the per-step entry point
  * SURVEY.md 8(b) names: Dynamics._forward_step (dynamics.py:115-157; dir = 1) / ._backward_step (:159-201;
@@ -590,7 +631,8 @@ int l2hmc_autocov(const float* X, int64_t steps, int64_t n_chains, int32_t d, do
  * what the library was compiled with (l2hmc_amd/_ffi.py does both when it loads the library).
  * which: one of L2HMC_STRUCT_*; returns sizeof in bytes, or L2HMC_ERR_ARG. */
 enum { L2HMC_STRUCT_NET = 0, L2HMC_STRUCT_ENERGY = 1, L2HMC_STRUCT_TRAJECTORY_ARGS = 2, L2HMC_STRUCT_MLP3 = 3,
-       L2HMC_STRUCT_SPLIT_ARGS = 4, L2HMC_STRUCT_TRAIN_ARGS = 5, L2HMC_STRUCT_TRAIN_SPLIT_ARGS = 6, L2HMC_STRUCT_TRAIN_STEP = 7 };
+       L2HMC_STRUCT_SPLIT_ARGS = 4, L2HMC_STRUCT_TRAIN_ARGS = 5, L2HMC_STRUCT_TRAIN_SPLIT_ARGS = 6, L2HMC_STRUCT_TRAIN_STEP = 7,
+       L2HMC_STRUCT_LADDER_ARGS = 8 };
 int64_t l2hmc_struct_bytes(int32_t which);
 
 #ifdef __cplusplus

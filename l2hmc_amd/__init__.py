@@ -8,6 +8,8 @@ hand-written HIP kernels of `csrc/` behind the C ABI of `include/l2hmc.h`.
 from . import _ffi, distributions, func_utils, layers, losses  # noqa: F401
 from .dynamics import Dynamics  # noqa: F401
 from .sampler import chain_operator, propose, sample_chain, tf_accept  # noqa: F401
+from . import tempering  # noqa: F401
+from .tempering import ParallelTempering, geometric_ladder  # noqa: F401
 
-__all__ = ["Dynamics", "propose", "tf_accept", "chain_operator", "sample_chain", "layers", "distributions",
-           "func_utils", "losses"]
+__all__ = ["Dynamics", "propose", "tf_accept", "chain_operator", "sample_chain", "ParallelTempering", "geometric_ladder",
+           "layers", "distributions", "func_utils", "losses", "tempering"]

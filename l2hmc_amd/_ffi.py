@@ -113,8 +113,15 @@ class L2hmcTrainStep(C.Structure):
                 ("epsilon", C.c_float), ("step", C.c_int64), ("train_alpha", C.c_int32)]
 
 
+class L2hmcLadderArgs(C.Structure):
+    _fields_ = [("n_rungs", C.c_int32), ("n_rounds", C.c_int32), ("proposals_per_round", C.c_int32), ("reserved_", C.c_int32),
+                ("temperatures", C.c_float * 16), ("round0", C.c_uint64), ("rung_of_row", _fp), ("trip_state", _fp),
+                ("swap_u", _fp), ("cold_hist", _fp), ("rung_hist", _fp), ("swaps_accepted", _fp), ("swaps_attempted", _fp),
+                ("round_trips", _fp)]
+
+
 STRUCTS = (L2hmcNet, L2hmcEnergy, L2hmcTrajectoryArgs, L2hmcMlp3, L2hmcSplitArgs, L2hmcTrainArgs, L2hmcTrainSplitArgs,
-           L2hmcTrainStep)
+           L2hmcTrainStep, L2hmcLadderArgs)
 
 # every symbol include/l2hmc.h declares: name -> (restype, argtypes)
 SYMBOLS = {
@@ -129,6 +136,7 @@ SYMBOLS = {
     "l2hmc_packed_gaussian_floats": (C.c_int64, [C.c_int32]),
     "l2hmc_pack_gaussian": (C.c_int, [_fp, C.c_int32, _fp, _fp]),
     "l2hmc_trajectory": (C.c_int, [C.POINTER(L2hmcTrajectoryArgs), _fp]),
+    "l2hmc_trajectory_ladder": (C.c_int, [C.POINTER(L2hmcTrajectoryArgs), C.POINTER(L2hmcLadderArgs), _fp]),
     "l2hmc_energy": (C.c_int, [C.POINTER(L2hmcEnergy), _fp, C.c_int64, C.c_int32, _fp, _fp, _fp]),
     "l2hmc_p_accept": (C.c_int, [C.POINTER(L2hmcEnergy), _fp, _fp, _fp, _fp, _fp, C.c_int64,
                                  C.c_int32, _fp, _fp]),

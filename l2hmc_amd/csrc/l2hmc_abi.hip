@@ -504,6 +504,7 @@ int64_t l2hmc_struct_bytes(int32_t which) {
     case L2HMC_STRUCT_TRAIN_ARGS: return sizeof(L2hmcTrainArgs);
     case L2HMC_STRUCT_TRAIN_SPLIT_ARGS: return sizeof(L2hmcTrainSplitArgs);
     case L2HMC_STRUCT_TRAIN_STEP: return sizeof(L2hmcTrainStep);
+    case L2HMC_STRUCT_LADDER_ARGS: return sizeof(L2hmcLadderArgs);
   }
   return fail(L2HMC_ERR_ARG, "l2hmc_struct_bytes: unknown struct id%s");
 }
@@ -568,15 +569,8 @@ static bool env_f32_mfma() {
   return v != 0;
 }
 
-int l2hmc_trajectory(const L2hmcTrajectoryArgs* a_in, void* stream) {
-  if (!a_in) return fail(L2HMC_ERR_ARG, "args is NULL%s");
-  // variant 200 + v: geometry choice v with the f32-input MFMA forced (no f16x2 contraction anywhere)
-  L2hmcTrajectoryArgs a_loc = *a_in;
-  const bool force_f32 = a_loc.variant >= 200 || env_f32_mfma();
-  if (a_loc.variant >= 200) a_loc.variant -= 200;
-  const L2hmcTrajectoryArgs* a = &a_loc;
-  if (a->n_chains < 0 || a->d < 1 || a->T < 1) return fail(L2HMC_ERR_ARG, "bad n_chains / d / T%s");
-  if (a->n_chains == 0) return L2HMC_OK;
+// Argument checks and the kernel argument block shared by l2hmc_trajectory and l2hmc_trajectory_ladder (a has n_chains > 0).
+static int traj_setup(const L2hmcTrajectoryArgs* a, KArgs& k, int& KH) {
   if (!a->x || !a->masks || !a->trig) return fail(L2HMC_ERR_ARG, "x, masks, trig are required%s");
   if (!a->v && !(a->rng_flags & L2HMC_RNG_V)) return fail(L2HMC_ERR_ARG, "v is required unless L2HMC_RNG_V is set%s");
   if (a->step_begin < 0 || a->n_steps < 0 || a->step_begin + a->n_steps > a->T)
@@ -590,12 +584,11 @@ int l2hmc_trajectory(const L2hmcTrajectoryArgs* a_in, void* stream) {
   if (!a->alpha && !(a->eps_host > 0.f)) return fail(L2HMC_ERR_ARG, "eps must be > 0%s");
   int rc = check_energy(&a->energy, a->d);
   if (rc) return rc;
-  int KH = 3;
+  KH = 3;
   if (a->packed_nets) {
     if (l2hmc_packed_nets_floats(a->d, a->H) < 0) return L2HMC_ERR_UNSUPPORTED;
     KH = khid_of(a->H);
   }
-  KArgs k;
   memset(&k, 0, sizeof(k));
   k.packed = a->packed_nets;
   k.packed16 = (a->packed_nets && a->H <= 15) ? a->packed_nets + 2 * (size_t)net_floats(tiles_of(a->d)) + 2 * (size_t)lane_layout(a->d, a->H).total : nullptr;
@@ -620,6 +613,23 @@ int l2hmc_trajectory(const L2hmcTrajectoryArgs* a_in, void* stream) {
     k.ais_w = a->ais_w; k.ais_alpha = a->ais_alpha;
   }
   fill_energy(k, &a->energy);
+  return L2HMC_OK;
+}
+
+int l2hmc_trajectory(const L2hmcTrajectoryArgs* a_in, void* stream) {
+  if (!a_in) return fail(L2HMC_ERR_ARG, "args is NULL%s");
+  // variant 200 + v: geometry choice v with the f32-input MFMA forced (no f16x2 contraction anywhere)
+  L2hmcTrajectoryArgs a_loc = *a_in;
+  const bool force_f32 = a_loc.variant >= 200 || env_f32_mfma();
+  if (a_loc.variant >= 200) a_loc.variant -= 200;
+  const L2hmcTrajectoryArgs* a = &a_loc;
+  if (a->n_chains < 0 || a->d < 1 || a->T < 1) return fail(L2HMC_ERR_ARG, "bad n_chains / d / T%s");
+  if (a->n_chains == 0) return L2HMC_OK;
+  const bool has_u = a->u != nullptr || (a->rng_flags & L2HMC_RNG_U);
+  int KH = 3;
+  KArgs k;
+  int rc = traj_setup(a, k, KH);
+  if (rc) return rc;
   hipStream_t s = (hipStream_t)stream;
   // Wide targets (more than 8 dim-tiles, i.e. d > 128; `variant` 8 forces it from 4 tiles up): the
   // register-resident kernels carry 4 or 8 tiles of state per wave there and spill (d = 512: ~1.6k VGPRs);
@@ -728,6 +738,64 @@ int l2hmc_trajectory(const L2hmcTrajectoryArgs* a_in, void* stream) {
   const long long lds = plan_lds(k, a->packed_nets != nullptr, true, NW, DT);
   note_kernel("traj_kernel<%lld, %lld, %lld, %lld>", k.ekind, DT, NW, KH <= 3 ? 3 : 4);
   return dispatch(OP_TRAJ, k, DT, NW, KH, lds, s);
+}
+
+int l2hmc_trajectory_ladder(const L2hmcTrajectoryArgs* a_in, const L2hmcLadderArgs* l, void* stream) {
+  if (!a_in || !l) return fail(L2HMC_ERR_ARG, "args / ladder is NULL%s");
+  const int K = l->n_rungs;
+  if (K != 2 && K != 4 && K != 8 && K != 16) return fail(L2HMC_ERR_ARG, "ladder: n_rungs must be 2, 4, 8 or 16 (got %s%lld)", "", K);
+  for (int i = 0; i < K; ++i) {
+    const float t = l->temperatures[i];
+    if (!(t > 0.f) || !(t <= 3.402823466e38f) || (i > 0 && !(t >= l->temperatures[i - 1])))
+      return fail(L2HMC_ERR_ARG, "ladder: temperatures must be positive, finite and non-decreasing (rung %s%lld)", "", i);
+  }
+  if (l->n_rounds < 1 || l->proposals_per_round < 1 || (long long)l->n_rounds * l->proposals_per_round > 0x7fffffffLL)
+    return fail(L2HMC_ERR_ARG, "ladder: bad n_rounds / proposals_per_round%s");
+  if (!l->rung_of_row || l->reserved_ != 0) return fail(L2HMC_ERR_ARG, "ladder: rung_of_row is required (reserved_ must be 0)%s");
+  if (a_in->n_chains < 0 || a_in->d < 1 || a_in->T < 1) return fail(L2HMC_ERR_ARG, "bad n_chains / d / T%s");
+  if (a_in->n_chains % K != 0 || a_in->chain_offset % K != 0)
+    return fail(L2HMC_ERR_ARG, "ladder: n_chains and chain_offset must be multiples of n_rungs = %s%lld", "", K);
+  if (a_in->energy.temperature != 1.f) return fail(L2HMC_ERR_ARG, "ladder: energy.temperature must be 1 (the ladder replaces it)%s");
+  if (a_in->ais_beta || a_in->ais_v0 || a_in->ais_w || a_in->ais_alpha)
+    return fail(L2HMC_ERR_UNSUPPORTED, "ladder: AIS mode does not run on a ladder%s");
+  if (a_in->energy.anneal_beta != 0.f) return fail(L2HMC_ERR_UNSUPPORTED, "ladder: anneal_beta must be 0%s");
+  if (a_in->variant != 0 && !(a_in->variant >= 100 && a_in->variant < 200))
+    return fail(L2HMC_ERR_UNSUPPORTED, "ladder: variant must be 0 or 100 + v (the general kernel), got %s%lld", "", a_in->variant);
+  if (!a_in->u && !(a_in->rng_flags & L2HMC_RNG_U)) return fail(L2HMC_ERR_ARG, "ladder: needs u (or L2HMC_RNG_U)%s");
+  if (a_in->n_chains == 0) return L2HMC_OK;
+  L2hmcTrajectoryArgs a_loc = *a_in;
+  a_loc.n_proposals = l->n_rounds * l->proposals_per_round;
+  const L2hmcTrajectoryArgs* a = &a_loc;
+  int KH = 3;
+  KArgs k;
+  int rc = traj_setup(a, k, KH);
+  if (rc) return rc;
+  LadArgs lg;
+  memset(&lg, 0, sizeof(lg));
+  lg.K = K;
+  lg.M = l->proposals_per_round;
+  for (int i = 0; i < 16; ++i) lg.temp[i] = i < K ? l->temperatures[i] : l->temperatures[K - 1];
+  lg.round0 = l->round0;
+  lg.rung = l->rung_of_row; lg.trip = l->trip_state; lg.rung_hist = l->rung_hist;
+  lg.u = l->swap_u; lg.cold = l->cold_hist;
+  lg.acc = (long long*)l->swaps_accepted; lg.att = (long long*)l->swaps_attempted; lg.trips = (long long*)l->round_trips;
+  int DT, NW;
+  const int gv = a->variant >= 100 ? a->variant - 100 : 0;
+  if (!pick_geometry(a->d, a->n_chains, gv, DT, NW))
+    return fail(L2HMC_ERR_UNSUPPORTED, "d = %s%lld not supported with variant %lld", "", a->d, a->variant);
+  const long long lds = plan_lds(k, a->packed_nets != nullptr, true, NW, DT);
+  lg.o_lad = (int)(lds / 4);
+  note_kernel("traj_ladder_kernel<%lld, %lld, %lld, %lld>", k.ekind, DT, NW, KH <= 3 ? 3 : 4);
+  const long long ldsl = lds + 4LL * kLadLds;
+  hipStream_t s = (hipStream_t)stream;
+  switch (k.ekind) {
+    case L2HMC_ENERGY_GAUSS_DIAG: return launch_ladder_ek<1>(k, lg, DT, NW, KH, ldsl, s);
+    case L2HMC_ENERGY_GAUSS_DENSE: return launch_ladder_ek<2>(k, lg, DT, NW, KH, ldsl, s);
+    case L2HMC_ENERGY_GMM: return launch_ladder_ek<3>(k, lg, DT, NW, KH, ldsl, s);
+    case L2HMC_ENERGY_ROUGHWELL: return launch_ladder_ek<4>(k, lg, DT, NW, KH, ldsl, s);
+    case L2HMC_ENERGY_FUNNEL: return launch_ladder_ek<5>(k, lg, DT, NW, KH, ldsl, s);
+  }
+  return fail(L2HMC_ERR_ARG, "unknown energy kind%s");
 }
 
 int64_t l2hmc_workspace_bytes(int64_t n_chains, int32_t d, int32_t H) {

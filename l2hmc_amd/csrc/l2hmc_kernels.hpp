@@ -135,6 +135,20 @@ struct KArgs {
   unsigned long long* dbg;   // phase-timing buffer (profiling builds only, else NULL)
 };
 
+// Ladder mode (traj_ladder_kernel, l2hmc_trajectory_ladder): rows are ladder-major, K rungs per ladder; every M-th proposal
+// ends with a deterministic even-odd swap sweep.  A second kernel argument of the ladder kernel only, so KArgs -- and with it
+// the kernarg layout and code of every other kernel -- stays as it was.
+struct LadArgs {
+  int K, M;                  // rungs (2, 4, 8, 16), proposals per round
+  int o_lad;                 // LDS: the tile's ladder tables (kLadLds floats)
+  float temp[16];            // the ladder, by rung
+  unsigned long long round0; // global index of this launch's first round
+  signed char *rung, *trip, *rung_hist;   // (N) labels in/out, (N) trip states in/out or NULL, (R, N) or NULL
+  const float* u;            // (R, n_ladders, K / 2) injected swap uniforms, or NULL: Philox stream 2
+  float* cold;               // (R M, n_ladders, d) the rung-0 state of every ladder after every proposal, or NULL
+  long long *acc, *att, *trips;   // (K - 1) swap counters, (n_ladders) round trips: accumulated (+=), or NULL
+};
+
 // Phase timers: compiled in only with -DL2HMC_PHASE_TIMING (tools/phase_timing.py).  Wave w of
 // block 0 accumulates s_memtime deltas per phase into dbg[w * 16 + phase].
 #ifdef L2HMC_PHASE_TIMING
@@ -321,6 +335,15 @@ __device__ __forceinline__ void philox_dir_u(unsigned long long seed, long long 
   fwd = (r.x & 1u) != 0;
   u = (r.y >> 8) * 5.9604644775390625e-08f;
 }
+// swap uniform of pair (k, k + 1) of ladder `gladder` in global round `round`: stream 2 (parallel tempering),
+//   counter = (global ladder, 0xFFFFFFFF, round mod 2^32, (round >> 32) << 4 | (k >> 1) << 1 | 1),  u = (r.x >> 8) 2^-24.
+// Word 1 = 0xFFFFFFFF with word 3 odd is a counter neither other stream produces: stream 1 has word 1 = 0, stream 0 an even word 3.
+__device__ __forceinline__ float philox_swap_u(unsigned long long seed, long long gladder, unsigned long long round, int k) {
+  const U4 r = philox4x32_10(U4{(unsigned)gladder, 0xFFFFFFFFu, (unsigned)round,
+                                ((unsigned)(round >> 32) << 4) | ((unsigned)(k >> 1) << 1) | 1u},
+                             (unsigned)seed, (unsigned)(seed >> 32));
+  return (r.x >> 8) * 5.9604644775390625e-08f;
+}
 template <int DT, int NW>
 __device__ __forceinline__ void rng_state(const KArgs& A, long long gchain, unsigned long long prop,
                                           int w, int q, f4 (&z)[DT]) {
@@ -439,11 +462,13 @@ __device__ __forceinline__ void load_energy_regs(EnergyRegs<EK, DT>& er, const K
   }
 }
 
-template <int EK, int DT, int NW>
+// LAD (ladder mode): the temperature is this lane's chain's rung temperature `temp`, divided in exactly as the scalar path divides
+// by A.temperature (so equal rungs give the scalar path's bits), and `Uraw` receives this lane's share of the untempered U.
+template <int EK, int DT, int NW, bool LAD = false>
 __device__ __forceinline__ void grad_energy(const KArgs& A, float* smem, int w, int lane,
                                             const f4 (&x)[DT], f4 (&g)[DT], float& Upart,
                                             bool wantU, const EnergyRegs<EK, DT>* er = nullptr,
-                                            const float* beta_p = nullptr) {
+                                            const float* beta_p = nullptr, float temp = 1.f, float* Uraw = nullptr) {
   const int q = lane >> 4, DP = 16 * A.NT;
   const float beta_a = beta_p != nullptr ? *beta_p : A.beta;     // (AIS loop: the bridge moves every proposal)
   float U = 0.f;
@@ -573,7 +598,12 @@ __device__ __forceinline__ void grad_energy(const KArgs& A, float* smem, int w, 
     }
     U = (1.f - beta_a) * 0.5f * q + beta_a * U;
   }
-  if (A.temperature != 1.f) {
+  if constexpr (LAD) {
+    *Uraw = U;
+    U = U / temp;
+#pragma unroll
+    for (int t = 0; t < DT; ++t) g[t] = g[t] / temp;
+  } else if (A.temperature != 1.f) {
     U = U / A.temperature;
 #pragma unroll
     for (int t = 0; t < DT; ++t) g[t] = g[t] / A.temperature;
@@ -857,320 +887,36 @@ __device__ __forceinline__ void stage_energy(const KArgs& A, float* smem, int ti
 // ------------------------------------------------------------------------------------------
 // The fused trajectory kernel
 // ------------------------------------------------------------------------------------------
-template <int EK, int DT, int NW, int KH>
+// LDS of the ladder tables (floats at A.o_lad): temperature by rung, raw U by row, then ints: label by row, row by rung, trip state
+// by row, accepted / attempted swaps by pair, the "some row changed temperature" flag
+constexpr int kLadLds = 128;
+enum { LAD_TEMP = 0, LAD_U = 16, LAD_LAB = 32, LAD_INV = 48, LAD_TRIP = 64, LAD_ACC = 80, LAD_ATT = 96, LAD_FLAG = 112 };
+
+
 // (waves-per-SIMD hint 2 for DT <= 2 caps the kernel at 256 VGPRs, which makes the compiler keep
 // MFMA accumulators in VGPRs -- no v_accvgpr_read traffic; wide-DT kernels keep all 512.)
 #ifndef L2HMC_WAVES_PER_SIMD
 #define L2HMC_WAVES_PER_SIMD 2
 #endif
+template <int EK, int DT, int NW, int KH>
 __global__ __launch_bounds__(64 * NW, (DT <= 2 ? L2HMC_WAVES_PER_SIMD : 1)) void traj_kernel(const KArgs A) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   lds_poison(smem);
-  const int tid = threadIdx.x, lane = tid & 63, nthr = 64 * NW;
-  const int w = NW > 1 ? __builtin_amdgcn_readfirstlane(tid >> 6) : 0;
-  const int c = lane & 15, q = lane >> 4;
-  const long long chain = (long long)blockIdx.x * 16 + c;
-  const bool live = chain < A.N;
-  const int NT = A.NT, DP = 16 * NT;
-  const bool has_nets = A.packed != nullptr;
-  const int NF = net_floats(NT);
+  constexpr bool LAD = false;
+  const LadArgs* const L = nullptr;
+#include "traj_body.inc"
+}
 
-  // ---- prologue: stage weights / masks / time table / energy parameters into LDS ----------
-  constexpr bool WG = weights_in_global(DT);
-  // Layer-1 groups (the first 2 NT groups of each net) go straight from global memory into
-  // registers when L1W is resident, so only the rest of each net is staged in LDS.
-  const int skip = (L1W<DT>::RES && !WG) ? 2 * NT * 256 : 0;      // floats not staged per net
-  if (has_nets && !WG) {
-    const int per = (NF - skip) / 4;
-    f4* dst = reinterpret_cast<f4*>(smem);
-    for (int i = tid; i < 2 * per; i += nthr) {
-      const int net = i >= per, j = i - net * per;
-      dst[i] = reinterpret_cast<const f4*>(A.packed + (size_t)net * NF + skip)[j];
-    }
-  }
-  for (int i = tid; i < A.T * DP; i += nthr) {
-    const int row = i / DP, dim = i % DP;
-    smem[A.o_mask + i] = dim < A.d ? A.masks[row * A.d + dim] : 0.f;
-  }
-  for (int i = tid; i < 2 * A.T; i += nthr) smem[A.o_trig + i] = A.trig[i];
-  stage_energy<EK, weights_in_global(DT)>(A, smem, tid, nthr);
-
-  f4 x[DT], v[DT], g[DT];
-  load_state<DT, NW>(A.x, A, chain, live, w, q, x);
-  const float eps = A.alpha != nullptr ? expf(*A.alpha) : A.eps_host;
-  const float heps = 0.5f * eps;
-  const bool need_p = A.p_out != nullptr || A.x_next != nullptr || A.u != nullptr ||
-                      (A.rng_flags & L2HMC_RNG_U) != 0;
-  __syncthreads();
-
-  // bases such that `base + group * 256` addresses group `group` (the skipped layer-1 groups lie
-  // before the staged region and are never dereferenced through these)
-  const float* wx = WG ? A.packed : smem - skip;                    // XNet fragments
-  const float* wv = WG ? A.packed + NF : smem + (NF - skip) - skip;  // VNet fragments
-  if (has_nets) {
-    // time-embedding table TB[net][row s][unit row i] = W3[0,u] cos_s + W3[1,u] sin_s + b1+b2+b3
-    // from the packed tau fragment (lane (i, q): q = 0 -> W3[0], 1 -> W3[1], 2 -> biases)
-    for (int idx = tid; idx < 2 * A.T * 16; idx += nthr) {
-      const int net = idx / (A.T * 16), srow = (idx / 16) % A.T, i = idx & 15;
-      const float* tf = (net == 0 ? wx : wv) + (2 * NT * 64) * 4;
-      const float ct = smem[A.o_trig + 2 * srow], st = smem[A.o_trig + 2 * srow + 1];
-      smem[A.o_tb + idx] = fmaf(tf[i * 4], ct, fmaf(tf[(16 + i) * 4], st, tf[(32 + i) * 4]));
-    }
-    __syncthreads();
-  }
-  int pb = 0;
-  const f4 Z = splat(0.f);
-  float U_start;                 // this lane's share of U at the current state
-  EnergyRegs<EK, DT> er;
-  load_energy_regs<EK, DT, NW>(er, A, smem, w, lane);
-  grad_energy<EK, DT, NW>(A, smem, w, lane, x, g, U_start, need_p, &er);
-
-  // VNet layer-1 partial at the current (x, grad U): shared by the closing half-update of one
-  // step and the opening half-update of the next, and kept across proposals.
-  TailW<DT> tw;
-  L1W<DT> l1w;
-  if (has_nets) load_l1w<DT, NW>(l1w, A.packed, A.packed + NF, A, w, lane);
-  f4 pv[1] = {Z};
-  PT_DECL;
-  PT_MARK(0);      // prologue (staging + first grad)
-  if (has_nets && A.n_steps > 0) {
-    load_tail<DT, NW>(tw, wv, A, w, lane);
-    // (two independent accumulators: the MFMA chain is pipe-bound, not latency-bound)
-    pv[0] = l1_part<DT, NW>(wv, 0, A, w, lane, x, Z, l1w.va) + l1_part<DT, NW>(wv, NT, A, w, lane, g, Z, l1w.vb);
-    xchg<NW, 1>(pv, A, smem, w, lane, pb);
-  }
-
-  // ---- persistent sampler loop: M proposals per launch (M = 1: a single trajectory) ---------
-  // This proposal's draws (momenta, direction bit, accept uniform): either injected from HBM --
-  // then fetched one proposal ahead so the latency hides under the current trajectory -- or
-  // drawn in-kernel from the counter-based Philox stream.
-  const long long gchain = A.chain_off + chain;
-  const bool rng_v = (A.rng_flags & L2HMC_RNG_V) != 0, rng_d = (A.rng_flags & L2HMC_RNG_DIR) != 0;
-  const bool rng_u = (A.rng_flags & L2HMC_RNG_U) != 0;
-  f4 vn[DT];
-  if (!rng_v) load_state<DT, NW>(A.v, A, chain, live, w, q, vn);
-  bool fwd_n = (A.dir != nullptr && !rng_d) ? (live ? A.dir[chain] != 0 : true) : (A.dir_all != 0);
-  float u_n = (A.u != nullptr && !rng_u && live) ? A.u[chain] : 0.f;
-  const bool have_u = A.u != nullptr || rng_u;
-  // AIS mode (utils/ais.py:43-66, HMC transitions): per proposal the bridge moves to beta = ais_beta[m], the
-  // log-weight takes dbeta (|x|^2/2 - U_final(x)) at the CURRENT state, the momentum is drawn fresh or partially
-  // refreshed, and a rejected chain keeps its state with the NEGATED PROPOSED momentum (ais.py:63).
-  const bool ais = A.ais_beta != nullptr;
-  float ais_wacc = 0.f, ais_aacc = 0.f, beta_m = A.beta;
-  f4 vprev[DT];
-#pragma unroll
-  for (int t = 0; t < DT; ++t) vprev[t] = Z;
-  if (ais && A.ais_refresh >= 0.f) {
-    if (A.ais_v0 != nullptr) load_state<DT, NW>(A.ais_v0, A, chain, live, w, q, vprev);
-    else rng_state<DT, NW>(A, gchain, A.rng_prop0 - 1, w, q, vprev);
-  }
-  for (int m = 0; m < A.M; ++m) {
-  const long long moff = (long long)m * A.N;
-  const unsigned long long prop = A.rng_prop0 + (unsigned long long)m;
-  if (rng_v) {
-    rng_state<DT, NW>(A, gchain, prop, w, q, v);
-  } else {
-#pragma unroll
-    for (int t = 0; t < DT; ++t) v[t] = vn[t];
-  }
-  if (ais) {
-    beta_m = A.ais_beta[m];
-    const float one = 1.f;
-    float pr[2];
-    grad_energy<EK, DT, NW>(A, smem, w, lane, x, g, pr[0], true, &er, &one);      // U_final, grad U_final at x
-    pr[1] = 0.f;
-#pragma unroll
-    for (int t = 0; t < DT; ++t) pr[1] += 0.5f * hsum(x[t] * x[t]);
-    U_start = (1.f - beta_m) * pr[1] + beta_m * pr[0];                              // this lane's share of U_beta(x)
-#pragma unroll
-    for (int t = 0; t < DT; ++t) g[t] = x[t] * (1.f - beta_m) + g[t] * beta_m;
-    chain_allreduce<NW, 2>(pr, smem + A.o_red, w, lane);
-    ais_wacc += A.ais_dbeta * (-pr[0] + pr[1]);                                     // ais.py:58-59
-    if (A.ais_refresh >= 0.f) {                                                     // ais.py:55
-      const float keep = sqrtf(1.f - A.ais_refresh), mix = sqrtf(A.ais_refresh);
-#pragma unroll
-      for (int t = 0; t < DT; ++t) v[t] = vprev[t] * keep + v[t] * mix;
-    }
-  }
-  bool fwd = fwd_n;
-  float u_m = u_n;
-  if (rng_d || rng_u) {
-    bool fr;
-    float ur;
-    philox_dir_u(A.rng_seed, gchain, prop, fr, ur);
-    if (rng_d) fwd = fr;
-    if (rng_u) u_m = ur;
-  }
-  if (m + 1 < A.M) {
-    if (!rng_v) load_state<DT, NW>(A.v + (moff + A.N) * A.d, A, chain, live, w, q, vn);
-    if (A.dir != nullptr && !rng_d && live) fwd_n = A.dir[moff + A.N + chain] != 0;
-    if (A.u != nullptr && !rng_u && live) u_n = A.u[moff + A.N + chain];
-  }
-  const float sgn = fwd ? 1.f : -1.f;
-  // the start point: a rejected chain resumes from it (sampler.py:53-55)
-  f4 x0[DT], g0[DT];
-#pragma unroll
-  for (int t = 0; t < DT; ++t) { x0[t] = x[t]; g0[t] = g[t]; }
-  const f4 pv0 = pv[0];
-  float red[5];                  // U0, K0, U1, K1, logdet (per-lane partial sums)
-  red[0] = U_start;
-  red[1] = 0.f;
-#pragma unroll
-  for (int t = 0; t < DT; ++t) red[1] += 0.5f * hsum(v[t] * v[t]);
-  red[2] = 0.f;
-  f4 ldv = splat(0.f);
-
-  // folded constants: sgn eps log2(e) scales S of XNet, sgn (eps/2) log2(e) S of VNet, eps log2(e) Q
-  const float LOG2E = 1.4426950408889634f;
-  const float kSx = sgn * eps * LOG2E, kSv = sgn * heps * LOG2E, kQ = eps * LOG2E;
-  const f4 O = splat(1.f);
-
-  // schedule row of this chain at iteration `it`: forward chains walk 0..T-1, backward T-1..0
-  auto row_of = [&](int it) { const int sf = A.step_begin + it; return fwd ? sf : (A.T - 1 - sf); };
-  // time-embedding terms (XNet, VNet) and the first-kept mask of that row; all are PREFETCHED
-  // one step ahead so their LDS latency never sits on the critical path
-  auto tbx_of = [&](int s) { return lds4(smem + A.o_tb + s * 16 + 4 * q); };
-  auto tbv_of = [&](int s) { return lds4(smem + A.o_tb + (A.T + s) * 16 + 4 * q); };
-  auto mask_of = [&](int s, f4 (&k)[DT]) {
-#pragma unroll
-    for (int t = 0; t < DT; ++t) {
-      const bool ok = (w * DT + t) < NT;
-      const f4 m = ok ? lds4(smem + A.o_mask + s * DP + 16 * (w * DT + t) + 4 * q) : Z;
-      k[t] = sel4(fwd, m, O - m);             // forward keeps m first, backward keeps 1-m first
-    }
-  };
-  f4 k1[DT], k1n[DT];
-  f4 tbx = Z, tbv = Z, tbxn = Z, tbvn = Z;
-  if (A.n_steps > 0) {
-    if (has_nets) { tbx = tbx_of(row_of(0)); tbv = tbv_of(row_of(0)); }
-    mask_of(row_of(0), k1);
-  }
-
-  for (int it = 0; it < A.n_steps; ++it) {
-    f4 xin[DT], y[DT], vh[DT];
-    if (it + 1 < A.n_steps) {                 // prefetch the next step's schedule row
-      if (has_nets) { tbxn = tbx_of(row_of(it + 1)); tbvn = tbv_of(row_of(it + 1)); }
-      mask_of(row_of(it + 1), k1n);
-    }
-
-    if (has_nets) {
-      PT_MARK(1);  // step head
-      // ---- momentum half-update #1: VNet([x, grad U(x), t])  (dynamics.py:118-125 / :162-170)
-      net_tail<DT, KH>(tw, pv[0], tbv, kSv, kQ, [&](int t, f4 ES, f4 aS, f4 T, f4 EQ) {
-        vh[t] = v_half(v[t], g[t], ES, aS, T, EQ, heps, fwd, ldv);
-      });
-      PT_MARK(2);  // VNet tail #1
-
-      // ---- two masked position updates: XNet([v_h, kept * x, t])  (:127-145 / :172-190);
-      //      the v_h contraction is shared by both
-      load_tail<DT, NW>(tw, wx, A, w, lane);
-#pragma unroll
-      for (int t = 0; t < DT; ++t) xin[t] = k1[t] * x[t];
-      // the v_h contraction `pa` is computed once and enters both exchanges un-summed, so every
-      // exchange carries ONE partial vector per wave
-      const f4 pa = l1_part<DT, NW>(wx, 0, A, w, lane, vh, Z, l1w.xa);
-      f4 px[1];
-      px[0] = pa + l1_part<DT, NW>(wx, NT, A, w, lane, xin, Z, l1w.xb);
-      PT_MARK(3);  // XNet layer-1 partials (a, b)
-      xchg<NW, 1>(px, A, smem, w, lane, pb);
-      PT_MARK(4);  // exchange
-      net_tail<DT, KH>(tw, px[0], tbx, kSx, kQ, [&](int t, f4 ES, f4 aS, f4 T, f4 EQ) {
-        y[t] = x_half(x[t], k1[t], vh[t], ES, aS, T, EQ, eps, fwd, ldv);
-      });
-      PT_MARK(5);  // XNet tail #1
-#pragma unroll
-      for (int t = 0; t < DT; ++t) xin[t] = (O - k1[t]) * y[t];
-      f4 py[1];
-      py[0] = pa + l1_part<DT, NW>(wx, NT, A, w, lane, xin, Z, l1w.xb);
-      PT_MARK(6);  // XNet layer-1 partial (b only)
-      xchg<NW, 1>(py, A, smem, w, lane, pb);
-      PT_MARK(7);  // exchange
-      net_tail<DT, KH>(tw, py[0], tbx, kSx, kQ, [&](int t, f4 ES, f4 aS, f4 T, f4 EQ) {
-        x[t] = x_half(y[t], O - k1[t], vh[t], ES, aS, T, EQ, eps, fwd, ldv);
-      });
-      PT_MARK(8);  // XNet tail #2
-
-      // ---- momentum half-update #2 at the new position  (:147-153 / :192-199); its layer-1
-      //      partial is reused by half-update #1 of the next step
-      load_tail<DT, NW>(tw, wv, A, w, lane);
-      grad_energy<EK, DT, NW>(A, smem, w, lane, x, g, red[2], need_p && it == A.n_steps - 1, &er);
-      pv[0] = l1_part<DT, NW>(wv, 0, A, w, lane, x, Z, l1w.va) + l1_part<DT, NW>(wv, NT, A, w, lane, g, Z, l1w.vb);
-      PT_MARK(9);  // grad U + VNet layer-1 partials
-      xchg<NW, 1>(pv, A, smem, w, lane, pb);
-      PT_MARK(10); // exchange
-      net_tail<DT, KH>(tw, pv[0], tbv, kSv, kQ, [&](int t, f4 ES, f4 aS, f4 T, f4 EQ) {
-        v[t] = v_half(vh[t], g[t], ES, aS, T, EQ, heps, fwd, ldv);
-      });
-      PT_MARK(11); // VNet tail #2
-    } else {
-      // HMC mode: S = T = Q = 0 (dynamics.py:73-76)
-#pragma unroll
-      for (int t = 0; t < DT; ++t) {
-        vh[t] = v_half(v[t], g[t], O, Z, Z, O, heps, fwd, ldv);
-        y[t] = x_half(x[t], k1[t], vh[t], O, Z, Z, O, eps, fwd, ldv);
-        x[t] = x_half(y[t], O - k1[t], vh[t], O, Z, Z, O, eps, fwd, ldv);
-      }
-      grad_energy<EK, DT, NW>(A, smem, w, lane, x, g, red[2], need_p && it == A.n_steps - 1, &er, &beta_m);
-#pragma unroll
-      for (int t = 0; t < DT; ++t) v[t] = v_half(vh[t], g[t], O, Z, Z, O, heps, fwd, ldv);
-    }
-    tbx = tbxn;
-    tbv = tbvn;
-#pragma unroll
-    for (int t = 0; t < DT; ++t) k1[t] = k1n[t];
-  }
-  const float ld = hsum(ldv) * 0.6931471805599453f;   // the log-det was accumulated in log2 units
-
-  // ---- per-proposal epilogue: proposal, log-det, accept probability, MH select ---------------
-  const bool last = m == A.M - 1;
-  if (last) {
-    store_state<DT, NW>(A.x_out, A, chain, live, w, q, x);
-    store_state<DT, NW>(A.v_out, A, chain, live, w, q, v);
-  }
-  if (A.n_steps == 0) red[2] = red[0];
-  red[3] = 0.f;
-#pragma unroll
-  for (int t = 0; t < DT; ++t) red[3] += 0.5f * hsum(v[t] * v[t]);
-  red[4] = ld;
-  const float U_end = red[2];
-  chain_allreduce<NW, 5>(red, smem + A.o_red, w, lane);
-  const bool writer = live && w == 0 && lane < 16;
-  if (A.logjac_out != nullptr && writer) A.logjac_out[moff + chain] = red[4];
-  if (need_p) {
-    // dynamics.py:302-309
-    const float e_new = red[2] + red[3], e_old = red[0] + red[1];
-    const float val = e_old - e_new + red[4];
-    const float p = accept_prob(val);
-    if (A.p_out != nullptr && writer) A.p_out[moff + chain] = p;
-    if (have_u) {
-      const bool acc = live && (p - u_m) >= 0.f;                      // sampler.py:53-55
-#pragma unroll
-      for (int t = 0; t < DT; ++t) {
-        x[t] = sel4(acc, x[t], x0[t]);
-        g[t] = sel4(acc, g[t], g0[t]);
-      }
-      pv[0] = sel4(acc, pv[0], pv0);
-      U_start = acc ? U_end : U_start;
-      if (ais) {
-        ais_aacc += p;
-#pragma unroll
-        for (int t = 0; t < DT; ++t) vprev[t] = acc ? v[t] : -v[t];
-      }
-    } else {
-      U_start = U_end;
-    }
-  } else {
-    U_start = U_end;
-  }
-  if (A.x_hist != nullptr) store_state<DT, NW>(A.x_hist + moff * A.d, A, chain, live, w, q, x);
-  }  // proposals
-
-  PT_FLUSH(w, lane);
-  store_state<DT, NW>(A.x_next, A, chain, live, w, q, x);
-  if (ais && live && w == 0 && lane < 16) {
-    if (A.ais_w != nullptr) A.ais_w[chain] += ais_wacc;
-    if (A.ais_alpha != nullptr) A.ais_alpha[chain] += ais_aacc;
-  }
+// Parallel tempering (l2hmc_trajectory_ladder): rows are ladder-major, K | 16 rungs per ladder, so every ladder lies inside
+// one 16-chain tile.  Proposal m runs at the temperature of the row's current rung; after every M-th proposal the tile's
+// raw energies go to LDS and one lane per ladder runs the even-odd swap sweep, which relabels rows -- no state moves.
+template <int EK, int DT, int NW, int KH>
+__global__ __launch_bounds__(64 * NW, (DT <= 2 ? L2HMC_WAVES_PER_SIMD : 1)) void traj_ladder_kernel(const KArgs A, const LadArgs Lk) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  lds_poison(smem);
+  constexpr bool LAD = true;
+  const LadArgs* const L = &Lk;
+#include "traj_body.inc"
 }
 
 // energy / grad only  (Dynamics.energy, Dynamics.grad_energy)
@@ -1233,8 +979,8 @@ __global__ __launch_bounds__(64 * NW) void paccept_kernel(const KArgs A) {
 // ------------------------------------------------------------------------------------------
 const int kMaxLdsBytes = 160 * 1024;
 
-template <class K>
-int launch(K kern, const KArgs& k, int NW, long long lds_bytes, hipStream_t s) {
+template <class K, class... X>
+int launch(K kern, const KArgs& k, int NW, long long lds_bytes, hipStream_t s, const X&... extra) {
   if (lds_bytes > kMaxLdsBytes)
     return fail(L2HMC_ERR_UNSUPPORTED, "needs %s%lld bytes of LDS (> 160 KiB): d too large for the LDS-resident weight path", "", lds_bytes);
   if (lds_bytes > 48 * 1024) {
@@ -1244,7 +990,7 @@ int launch(K kern, const KArgs& k, int NW, long long lds_bytes, hipStream_t s) {
   }
   const long long blocks = (k.N + 15) / 16;
   if (blocks > 0x7fffffffLL) return fail(L2HMC_ERR_UNSUPPORTED, "too many chains%s");
-  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(64 * NW), (size_t)lds_bytes, s, k);
+  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(64 * NW), (size_t)lds_bytes, s, k, extra...);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(L2HMC_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
   return L2HMC_OK;
@@ -1279,6 +1025,20 @@ int launch_fast16_ek(const KArgs& k, int DT, int NW, int KH, long long lds, hipS
 // traj_tile_kernel (one wave per tile, 4 tiles per workgroup): elementwise targets only (traj_ek1.hip, traj_ek4.hip)
 template <int EK>
 int launch_tile_ek(const KArgs& k, int DT, int KH, int tpw, long long lds, hipStream_t s);
+
+// traj_ladder_kernel (parallel tempering), every geometry of the general kernel: one translation unit per energy kind
+// (traj_ladder_ek<k>.hip), apart from the plain kernels' units so that their code objects stay as they were
+template <int EK>
+int launch_ladder_ek(const KArgs& k, const LadArgs& l, int DT, int NW, int KH, long long lds, hipStream_t s);
+#define L2HMC_CALL_LADDER(DTc, NWc)                                                         \
+  if (KH <= 3) return launch(traj_ladder_kernel<E_, DTc, NWc, 3>, k, NWc, lds, s, l);       \
+  else return launch(traj_ladder_kernel<E_, DTc, NWc, 4>, k, NWc, lds, s, l);
+#define L2HMC_DEFINE_LAUNCH_LADDER(EKv)                                                                 \
+  template <>                                                                                           \
+  int launch_ladder_ek<EKv>(const KArgs& k, const LadArgs& l, int DT, int NW, int KH, long long lds, hipStream_t s) { \
+    constexpr int E_ = EKv;                                                                             \
+    L2HMC_GEOM_SWITCH(DT, NW, L2HMC_CALL_LADDER)                                                        \
+  }
 
 #define L2HMC_DEFINE_LAUNCH_EK(EKv)                                                              \
   template <>                                                                                    \

@@ -1,0 +1,6 @@
+// The ladder (parallel-tempering) form of the general trajectory kernel for energy kind 5 (funnel); see l2hmc_kernels.hpp.
+#include "l2hmc_kernels.hpp"
+
+namespace l2hmc {
+L2HMC_DEFINE_LAUNCH_LADDER(5)
+}  // namespace l2hmc

@@ -26,6 +26,21 @@ TF_FLOAT = torch.float32
 NP_FLOAT = np.float32
 
 
+def ladder_struct(spec):
+    """include/l2hmc.h L2hmcLadderArgs from the dict `tempering.ParallelTempering` builds (device tensors or None)."""
+    lg = _ffi.L2hmcLadderArgs()
+    temps = [float(t) for t in spec['temperatures']]
+    lg.n_rungs, lg.n_rounds, lg.proposals_per_round = len(temps), int(spec['rounds']), int(spec['proposals_per_round'])
+    for i, t in enumerate(temps):
+        lg.temperatures[i] = t
+    lg.round0 = int(spec.get('round0', 0))
+    lg.rung_of_row, lg.trip_state = _ffi.ptr(spec['rung_of_row']), _ffi.ptr(spec.get('trip_state'))
+    lg.swap_u, lg.cold_hist, lg.rung_hist = _ffi.ptr(spec.get('swap_u')), _ffi.ptr(spec.get('cold_hist')), _ffi.ptr(spec.get('rung_hist'))
+    lg.swaps_accepted, lg.swaps_attempted = _ffi.ptr(spec.get('accepted')), _ffi.ptr(spec.get('attempted'))
+    lg.round_trips = _ffi.ptr(spec.get('round_trips'))
+    return lg
+
+
 class _ZeroNet(object):
     """HMC mode: S = T = Q = 0 (dynamics.py:73-76)."""
 
@@ -574,14 +589,21 @@ class Dynamics(object):
         return torch.randn(x.shape, dtype=torch.float32, device=x.device, generator=self.generator)
 
     def run(self, x, v, step_begin, n_steps, direction=None, direction_all=1, u=None,
-            want=('x', 'v', 'logjac'), n_proposals=1, rng=None, aux=None, ais=None):
+            want=('x', 'v', 'logjac'), n_proposals=1, rng=None, aux=None, ais=None, ladder=None):
         """Launch `l2hmc_trajectory` (include/l2hmc.h).  Returns a dict of the requested
         outputs among x, v, logjac, p, x_next, x_hist.  With n_proposals = M > 1 the kernel
         runs M chained proposals (persistent sampler loop): v is (M, N, d), direction and u
         are (M, N), p / logjac come back as (M, N), x_hist as (M, N, d).
         rng = dict(seed=, proposal0=0, chain_offset=0): inputs passed as None among v /
-        direction / u are drawn in-kernel from the Philox stream (include/l2hmc.h)."""
+        direction / u are drawn in-kernel from the Philox stream (include/l2hmc.h).
+        ladder = the dict `tempering.ParallelTempering` builds: the same launch on a temperature ladder
+        (`l2hmc_trajectory_ladder`); n_proposals must then be rounds x proposals per round, and
+        `temperature` / `use_temperature` are ignored (every row runs at its rung's temperature)."""
         M = int(n_proposals)
+        if ladder is not None:
+            self._check_ladder()
+            if ais is not None:
+                raise ValueError("ladder= and ais= do not go together")
         if self._split:
             if M != 1 or rng is not None:
                 return self._run_split_chain(x, v, step_begin, n_steps, direction, direction_all, u, want, M, rng, aux)
@@ -625,7 +647,8 @@ class Dynamics(object):
                 raise ValueError("u must be %s" % (lead + (N,),))
         a = _ffi.L2hmcTrajectoryArgs()
         a.packed_nets = _ffi.ptr(self._packed_nets())
-        a.energy = self._fn.c_struct(x.device, self.temperature if self.use_temperature else 1.0, self.anneal_beta)
+        temp = 1.0 if ladder is not None else (self.temperature if self.use_temperature else 1.0)
+        a.energy = self._fn.c_struct(x.device, temp, self.anneal_beta)
         a.masks, a.trig = self._mask.data_ptr(), self._trig.data_ptr()
         if self.eps_override is None:
             a.alpha, a.eps_host = self.alpha.data_ptr(), 0.0
@@ -650,8 +673,21 @@ class Dynamics(object):
         a.x_hist = _ffi.ptr(out.get('x_hist'))
         a.variant = int(self.variant)
         a.n_proposals = M
+        if ladder is not None:
+            _ffi.check(_ffi.lib().l2hmc_trajectory_ladder(a, ladder_struct(ladder), _ffi.current_stream(x.device)))
+            return out
         _ffi.check(_ffi.lib().l2hmc_trajectory(a, _ffi.current_stream(x.device)))
         return out
+
+    def _check_ladder(self):
+        """What a temperature ladder (parallel tempering, `l2hmc_trajectory_ladder`) runs on: the fused general kernel."""
+        if self._split:
+            why = ("the VAE posterior" if self._vae else "a caller-supplied energy" if self._user else
+                   "caller-supplied nets" if self._user_nets else "nets wider than H = 15")
+            raise NotImplementedError("parallel tempering runs on the fused trajectory kernel; this Dynamics takes the GEMM "
+                                      "engine (%s)" % why)
+        if float(self.anneal_beta) != 0.0:
+            raise NotImplementedError("parallel tempering does not run on the AIS bridge (anneal_beta must be 0)")
 
     # ---- reference API -------------------------------------------------------------------------------
     def kinetic(self, v):
