@@ -436,35 +436,234 @@ int device_cus() {
   return cus;
 }
 
-bool pick_geometry(int d, long long N, int variant, int& DT, int& NW, int cus = 0) {
+bool pick_geometry(int d, long long N, int v, int& DT, int& NW, int cus = 0) {
   if (cus <= 0) cus = device_cus();        // (l2hmc_trajectory queries once and passes it down)
   const int NT = tiles_of(d);
-  if (NT <= 1) { DT = 1; NW = 1; return variant == 0 || variant == 1; }
-  if (variant == 2 && NT >= 3 && NT <= 4) { DT = 2; NW = 2; return true; }   // two waves x two tiles (fast kernel only)
+  if (NT <= 1) { DT = 1; NW = 1; return v == 0 || v == 1; }
+  if (v == 2 && NT >= 3 && NT <= 4) { DT = 2; NW = 2; return true; }   // two waves x two tiles (fast kernel only)
   if (NT <= 4) {
     // measured (tools/bench_configs.py, 16-chain tiles on 256 CUs): with 3-4 dim-tiles the 4-wave tile wins at
     // every chain count (1.7e9 vs 1.1e9 steps/s at d = 50..64); with 2 dim-tiles half of its waves idle, so it
     // only pays while there are fewer tiles than wave slots (N < 8192; 2x slower than one wave per tile above).
     // (Two waves x two tiles was tried for 3-4 dim-tiles: never faster than four waves x one tile.)
-    const bool want4 = variant == 4 || (variant == 0 && (NT >= 3 || N < 32LL * cus));
+    const bool want4 = v == 4 || (v == 0 && (NT >= 3 || N < 32LL * cus));
     if (want4) { DT = 1; NW = 4; } else { DT = NT <= 2 ? 2 : 4; NW = 1; }
-    return variant == 0 || variant == 1 || variant == 4;
+    return v == 0 || v == 1 || v == 4;
   }
-  if (variant == 1) return false;
+  if (v == 1) return false;
   NW = 4;
   DT = NT <= 8 ? 2 : (NT <= 16 ? 4 : 8);
   return NT <= 32;
 }
 
-int dispatch(int op, const KArgs& k, int DT, int NW, int KH, long long lds, hipStream_t s) {
-  switch (k.ekind) {
-    case L2HMC_ENERGY_GAUSS_DIAG: return launch_ek<1>(op, k, DT, NW, KH, lds, s);
-    case L2HMC_ENERGY_GAUSS_DENSE: return launch_ek<2>(op, k, DT, NW, KH, lds, s);
-    case L2HMC_ENERGY_GMM: return launch_ek<3>(op, k, DT, NW, KH, lds, s);
-    case L2HMC_ENERGY_ROUGHWELL: return launch_ek<4>(op, k, DT, NW, KH, lds, s);
-    case L2HMC_ENERGY_FUNNEL: return launch_ek<5>(op, k, DT, NW, KH, lds, s);
+// The environment's overrides of the selection rules, read at the top of every l2hmc_trajectory call (and nowhere else).
+struct EnvOverrides {
+  bool f32_mfma;   // L2HMC_F32_MFMA=1: every trajectory on the f32-input MFMA, as variant 200 + v does per call (read once per process)
+  int lane_res;    // L2HMC_LANE_RES=0/1/2: where the lane kernel keeps its weights, -1 = by the measured rule (read per call: tests switch it)
+};
+
+static EnvOverrides read_env() {
+  static const bool f32 = [] { const char* e = getenv("L2HMC_F32_MFMA"); return e && e[0] && e[0] != '0'; }();
+  const char* e = getenv("L2HMC_LANE_RES");
+  return {f32, (e != nullptr && e[0] >= '0' && e[0] <= '2') ? e[0] - '0' : -1};
+}
+
+// `variant` (include/l2hmc.h), decoded once: every selection rule reads these fields.
+struct Variant {
+  int value;       // the variant without its 200 (what the refusals quote)
+  int forced;      // the family asked for: FAM_LANE (32), FAM_WIDE (8), FAM_TILE (16), FAM_GENERAL (100 + v); else -1
+  bool all_auto;   // 0: the lane, wide and tile kernels by their measured rules too (33: the small / fast / general kernels only)
+  int geom;        // geometry value v of pick_geometry (0: by the chain count; 1, 2, 4 force one)
+  bool f32;        // the f32-input MFMA everywhere (200 + v, or L2HMC_F32_MFMA=1)
+};
+
+static Variant decode_variant(int variant, bool env_f32) {
+  Variant v;
+  v.f32 = variant >= 200 || env_f32;
+  v.value = variant >= 200 ? variant - 200 : variant;
+  v.forced = v.value >= 100 ? FAM_GENERAL : v.value == 32 ? FAM_LANE : v.value == 8 ? FAM_WIDE : v.value == 16 ? FAM_TILE : -1;
+  v.all_auto = v.value == 0;
+  v.geom = v.value >= 100 ? v.value - 100 : (v.value == 16 || v.value == 33) ? 0 : v.value;
+  return v;
+}
+
+// dense Gaussian on the LDS-resident-state kernel from the same width as the elementwise targets (measured, tools/probe_dense_wide.py:
+// x1.2-1.7 over the register-resident kernel at d = 160 ... 256, x6-8 at d = 384 / 512 where that one spills)
+#ifndef WIDE_DENSE_MIN_NT
+#define WIDE_DENSE_MIN_NT 8
+#endif
+
+// geometry v for the register-resident kernels
+static int plan_geometry(const L2hmcTrajectoryArgs& a, const Variant& v, int cus, TrajPlan& p) {
+  if (!pick_geometry(a.d, a.n_chains, v.geom, p.DT, p.NW, cus))
+    return fail(L2HMC_ERR_UNSUPPORTED, "d = %s%lld not supported with variant %lld", "", a.d, v.value);
+  return L2HMC_OK;
+}
+
+// the general kernel on the planned geometry (also the ladder kernel's tables, before its own)
+static void plan_general(const L2hmcTrajectoryArgs& a, KArgs& k, TrajPlan& p) {
+  p.family = FAM_GENERAL;
+  p.lds = plan_lds(k, a.packed_nets != nullptr, true, p.NW, p.DT);
+}
+
+// The kernel of one l2hmc_trajectory call: every selection rule, in order.  k comes from traj_setup and gets the LDS offsets of
+// the kernel planned (KH: its hidden k-steps); cus and env are read by the caller.  No HIP calls.
+static int plan_trajectory(const L2hmcTrajectoryArgs& a, KArgs& k, int KH, int cus, const EnvOverrides& env, TrajPlan& p) {
+  const Variant v = decode_variant(a.variant, env.f32_mfma);
+  p = TrajPlan();
+  p.ek = k.ekind;
+  p.KH = KH <= 3 ? 3 : 4;
+  const bool nets = a.packed_nets != nullptr, has_u = a.u != nullptr || (a.rng_flags & L2HMC_RNG_U);
+  const bool plain = k.beta == 1.f && k.temperature == 1.f;     // neither tempered nor annealed
+  // One chain per lane (traj_lane.hpp): when the chains alone fill the chip -- a wave is 64 of them -- the padding-free
+  // VALU form beats the MFMA tiles (variant 32 forces it: tests).  Measured (tools/bench_lane.py): d <= 2 from 65 536
+  // chains, d <= 4 from 131 072; wider states lose to the scalar-load latency of their larger nets.
+  const bool lane_able = nets && a.ais_beta == nullptr && plain && k.n_steps >= 1 && lane_supported(k.ekind, a.d, a.H, k.ncomp) &&
+                         (a.d <= 16 || a.x_next != nullptr || !has_u);
+  if (v.forced == FAM_LANE && !lane_able)
+    return fail(L2HMC_ERR_UNSUPPORTED, "variant 32 (one chain per lane) needs S/T/Q nets and a Gaussian / mixture / Rough-Well target with d <= 4%s");
+  const bool lane_auto = (a.d <= 2 && a.n_chains >= 256 * cus) || (a.d <= 4 && a.n_chains >= 512 * cus);
+  if (lane_able && (v.forced == FAM_LANE || (v.all_auto && lane_auto))) {
+    p.family = FAM_LANE;
+    // the dimension counts compiled: d <= 4 (measured, tools/bench_lane.py: from d = 8 on the scalar-load latency of a
+    // net's 2 x (2 d H + ...) weights -- 21 KB at d = 50, more than the 16 KB scalar cache -- makes this form lose to the tiles)
+    p.DP = a.d <= 2 ? 2 : 4;
+    p.HPR = lane_hu(a.H) == 10 ? 5 : 8;
+    // where the d <= 2, H <= 10 kernels keep their weights (traj_lane.hpp, RES; measured: profiles/r06_lane_resident.txt, results
+    // are bit-identical in all three forms): XNet's layer 2 and heads as VGPR pairs (1) while the chip holds at most two waves per
+    // SIMD -- x 1.11-1.19 from 16 384 to 131 072 chains --, scalar loads in the loop (0) beyond that (four waves per SIMD hide them,
+    // the resident forms cap the occupancy at two); the diagonal Gaussian, whose grad U re-reads its parameters by scalar loads
+    // inside every evaluation, takes all weights in VGPRs, four per register (2): x 2.4-3.5 at every chain count.
+    // L2HMC_LANE_RES=0/1/2 in the environment overrides the choice (A/B runs, tools/bench_lane_resident.py; tests).
+    if (p.DP == 2 && p.HPR == 5)
+      p.RES = env.lane_res >= 0 ? env.lane_res
+              : k.ekind == L2HMC_ENERGY_GAUSS_DIAG ? 2
+              : a.n_chains < 3LL * 64 * 1024 ? 1 : 0;          // (1024 SIMDs on gfx950: three waves each)
+    return L2HMC_OK;
   }
-  return fail(L2HMC_ERR_ARG, "unknown energy kind%s");
+  // Wide targets (more than 8 dim-tiles, i.e. d > 128; `variant` 8 forces it from 4 tiles up): the
+  // register-resident kernels carry 4 or 8 tiles of state per wave there and spill (d = 512: ~1.6k VGPRs);
+  // the LDS-resident-state kernel covers the elementwise energies that exist at this width.
+  const bool wide_dense = k.ekind == L2HMC_ENERGY_GAUSS_DENSE || k.ekind == L2HMC_ENERGY_GMM;      // (its precision fragments stream from L2: k.prec is the packed buffer)
+  const bool wide_kind = k.ekind == L2HMC_ENERGY_GAUSS_DIAG || k.ekind == L2HMC_ENERGY_ROUGHWELL || wide_dense;   // (mixtures: <= 4 tiles per wave)
+  const bool wide_able = nets && wide_kind && !(k.M > 1 && a.x_next == nullptr) && k.NT <= 32;
+  if (v.forced == FAM_WIDE && !(wide_able && k.NT >= 4))
+    return fail(L2HMC_ERR_UNSUPPORTED, "variant 8 (LDS-resident state) needs S/T/Q nets, a Gaussian or Rough-Well target, 64 <= d <= 512 and x_next when n_proposals > 1%s");
+  if (wide_able && (v.forced == FAM_WIDE || (v.all_auto && k.NT > (wide_dense ? WIDE_DENSE_MIN_NT : 8)))) {
+    KArgs kw = k;
+    // f16x2 contractions for the elementwise targets without a tempered / annealed energy, unless the f32-input MFMA is asked for
+    if (v.f32 || wide_dense || !plain) kw.packed16 = nullptr;
+    int nw;
+    const long long lds = plan_lds_wide(kw, nw);
+    if (lds <= kMaxLdsBytes) {
+      k = kw;
+      p.family = FAM_WIDE;
+      p.NW = nw;
+      p.KH = KH == 3 ? 3 : 4;                   // (this kernel's 3-step form serves exactly 3 k-steps)
+      p.f16 = kw.packed16 != nullptr;
+      p.lds = lds;
+      return L2HMC_OK;
+    }
+    if (v.forced == FAM_WIDE) return fail(L2HMC_ERR_UNSUPPORTED, "variant 8: %s%lld bytes of LDS needed (T x d too large)", "", lds);
+  }
+  int rc = plan_geometry(a, v, cus, p);
+  if (rc) return rc;
+  // The instruction-lean kernel (traj_fast.hpp) covers S/T/Q nets on register-resident geometries; the
+  // tempered / annealed energies (HMC-mode AIS) and zero-step calls stay on the general kernel.
+  const bool fast = nets && p.DT <= 2 && k.n_steps >= 1 && v.forced != FAM_GENERAL && plain;
+  // d <= 4 (SCG-2D, MoG-2D): one dimension per lane, S/T/Q in one MFMA row block (traj_small.hpp)
+  if (fast && a.d <= 4 && v.geom == 0 && k.ekind != L2HMC_ENERGY_FUNNEL && (k.ekind != L2HMC_ENERGY_GMM || k.ncomp <= 8)) {
+    // (f16x2 for the hidden layer and the head block unless the f32-input MFMA is asked for: every target this kernel serves --
+    //  Gaussians incl. dense, mixtures, Rough Well -- has a grad U that is linear or bounded in the state the range guard watches)
+    const long long lds = plan_lds_fast(k, 1, 1, !v.f32);
+    // (the per-step schedule records grow with T: past 160 KiB fall through to the fast / general kernel)
+    if (lds <= kMaxLdsBytes) {
+      p.family = FAM_SMALL;
+      p.f16 = !v.f32;
+      p.lds = lds;
+      return L2HMC_OK;
+    }
+  }
+  // many chains (>= 2 tiles per SIMD), 3-4 dimension slices, elementwise target: one wave per tile (traj_tile.hpp);
+  // variant 16 forces it
+  const bool tile_kind = k.ekind == L2HMC_ENERGY_GAUSS_DIAG || k.ekind == L2HMC_ENERGY_ROUGHWELL;
+  // (a rejected chain of this kernel resumes from the copy of its start point parked in x_next: u without x_next -- accept
+  //  decisions with nowhere to put the selected state -- stays on the four-wave kernel)
+  const bool tileable = nets && tile_kind && k.NT >= 3 && k.NT <= 4 && k.n_steps >= 1 && plain && !(has_u && a.x_next == nullptr) &&
+                        !v.f32;        // (its contractions are f16x2 throughout: traj_tile.hpp)
+  if (v.forced == FAM_TILE && !tileable)
+    return fail(L2HMC_ERR_UNSUPPORTED, "variant 16 (one wave per tile) needs S/T/Q nets, a diagonal-Gaussian or Rough-Well target, 33 <= d <= 64 and x_next whenever u is given%s");
+  if (tileable && (v.forced == FAM_TILE || (v.all_auto && a.n_chains >= 64LL * cus))) {
+    const long long lds = plan_lds_tile(k, k.NT);
+    if (lds <= kMaxLdsBytes) {
+      p.family = FAM_TILE;
+      p.DT = k.NT;
+      // tiles (waves) per workgroup: 4, two workgroups per CU -- unless the staged tables (the split head fragments are 51 KB,
+      // the schedule records grow with T) leave room for ONE workgroup only: then 8 tiles share it, from the chain count
+      // (128 per CU) at which 8-tile workgroups still cover every CU
+      p.tpw = (2 * lds > kMaxLdsBytes && a.n_chains >= 128LL * cus) ? 8 : 4;
+      p.half = a.d - 16 * (k.NT - 1) <= 2;      // the last slice holds <= 2 dimensions: transcendentals on 2 of 4 components
+      p.lds = lds;
+      return L2HMC_OK;
+    }
+    if (v.forced == FAM_TILE)
+      return fail(L2HMC_ERR_UNSUPPORTED, "variant 16: %s%lld bytes of LDS needed (T too large for the one-wave-per-tile kernel)", "", lds);
+  }
+  if (fast) {
+    // f16x2 (traj_fast.hpp): every contraction of the step loop as two f16 MFMAs on an exact hi / lo split of both operands --
+    // fp32-accurate while |states|, |activations|, |grad U| < 65504 (beyond: inf - inf = NaN, which the accept rule treats as a
+    // rejection).  The elementwise targets take it unless the caller asks for the f32-input MFMA (variant 200 + v, or
+    // L2HMC_F32_MFMA=1 in the environment); the funnel (grad U ~ e^{-x_0}) stays on f32 everywhere, the mixtures and dense
+    // Gaussians on the tile kernels (their d <= 4 kernel takes f16x2 for its nets: above).
+    p.family = FAM_FAST;
+    if (!v.f32 && tile_kind) {
+      p.lds = plan_lds_fast(k, p.NW, p.DT, true);
+      if (p.lds <= kMaxLdsBytes) {
+        p.f16 = 1;
+        return L2HMC_OK;
+      }
+    }
+    p.lds = plan_lds_fast(k, p.NW, p.DT);
+    if (p.lds <= kMaxLdsBytes) return L2HMC_OK;
+  }
+  plan_general(a, k, p);
+  return L2HMC_OK;
+}
+
+// l2hmc_last_kernel: the planned kernel with its template arguments
+static void note_plan(const TrajPlan& p) {
+  switch (p.family) {
+    case FAM_LANE:
+      if (p.RES != 0) return note_kernel("traj_lane_kernel<%lld, %lld, %lld, %lld>", p.ek, p.DP, p.HPR, p.RES);
+      return note_kernel("traj_lane_kernel<%lld, %lld, %lld>", p.ek, p.DP, p.HPR);
+    case FAM_WIDE: return note_kernel(p.f16 ? "traj_wide_kernel<f16x2>" : "traj_wide_kernel");
+    case FAM_SMALL: return note_kernel(p.f16 ? "traj_small_kernel<%lld, %lld, 1>" : "traj_small_kernel<%lld, %lld>", p.ek, p.KH);
+    case FAM_TILE:
+      return note_kernel(p.half ? "traj_tile_kernel<%lld, %lld, %lld, %lld, true>" : "traj_tile_kernel<%lld, %lld, %lld, %lld, false>",
+                         p.ek, p.DT, p.KH, p.tpw);
+    case FAM_FAST:
+      return note_kernel(p.f16 ? "traj_fast_kernel<%lld, %lld, %lld, %lld, 1>" : "traj_fast_kernel<%lld, %lld, %lld, %lld>", p.ek, p.DT,
+                         p.NW, p.KH);
+    case FAM_LADDER: return note_kernel("traj_ladder_kernel<%lld, %lld, %lld, %lld>", p.ek, p.DT, p.NW, p.KH);
+    default: return note_kernel("traj_kernel<%lld, %lld, %lld, %lld>", p.ek, p.DT, p.NW, p.KH);
+  }
+}
+
+// The plan's kernel, from the translation unit that holds it (l2hmc_kernels.hpp); lg: the ladder's arguments
+static int launch_plan(const TrajPlan& p, const KArgs& k, hipStream_t s, const LadArgs* lg = nullptr) {
+  return on_energy_kind(p.ek, [&](auto ek) {
+    constexpr int EK = decltype(ek)::value;
+    if (p.family == FAM_LADDER) return launch_ladder_ek<EK>(p, k, *lg, s);
+    if constexpr (EK != L2HMC_ENERGY_FUNNEL) {
+      if (p.family == FAM_LANE) return launch_lane_ek<EK>(p, k, s);
+      if (p.family == FAM_WIDE) return launch_wide_ek<EK>(p, k, s);
+    }
+    if constexpr (EK == L2HMC_ENERGY_GAUSS_DIAG || EK == L2HMC_ENERGY_ROUGHWELL) {
+      if (p.family == FAM_TILE) return launch_tile_ek<EK>(p, k, s);
+      if (p.family == FAM_FAST && p.f16) return launch_fast16_ek<EK>(p, k, s);
+    }
+    return launch_ek<EK>(p, k, s);           // general, fast, small, energy, p_accept
+  });
 }
 
 }  // namespace l2hmc
@@ -557,18 +756,6 @@ int l2hmc_pack_gaussian(const float* i_sigma, int32_t d, float* packed, void* st
   return L2HMC_OK;
 }
 
-// dense Gaussian on the LDS-resident-state kernel from the same width as the elementwise targets (measured, tools/probe_dense_wide.py:
-// x1.2-1.7 over the register-resident kernel at d = 160 ... 256, x6-8 at d = 384 / 512 where that one spills)
-#ifndef WIDE_DENSE_MIN_NT
-#define WIDE_DENSE_MIN_NT 8
-#endif
-
-// L2HMC_F32_MFMA=1 in the environment: every trajectory on the f32-input MFMA (as variant 200 + v does per call)
-static bool env_f32_mfma() {
-  static const int v = [] { const char* e = getenv("L2HMC_F32_MFMA"); return (e && e[0] && e[0] != '0') ? 1 : 0; }();
-  return v != 0;
-}
-
 // Argument checks and the kernel argument block shared by l2hmc_trajectory and l2hmc_trajectory_ladder (a has n_chains > 0).
 static int traj_setup(const L2hmcTrajectoryArgs* a, KArgs& k, int& KH) {
   if (!a->x || !a->masks || !a->trig) return fail(L2HMC_ERR_ARG, "x, masks, trig are required%s");
@@ -616,128 +803,21 @@ static int traj_setup(const L2hmcTrajectoryArgs* a, KArgs& k, int& KH) {
   return L2HMC_OK;
 }
 
-int l2hmc_trajectory(const L2hmcTrajectoryArgs* a_in, void* stream) {
-  if (!a_in) return fail(L2HMC_ERR_ARG, "args is NULL%s");
-  // variant 200 + v: geometry choice v with the f32-input MFMA forced (no f16x2 contraction anywhere)
-  L2hmcTrajectoryArgs a_loc = *a_in;
-  const bool force_f32 = a_loc.variant >= 200 || env_f32_mfma();
-  if (a_loc.variant >= 200) a_loc.variant -= 200;
-  const L2hmcTrajectoryArgs* a = &a_loc;
+int l2hmc_trajectory(const L2hmcTrajectoryArgs* a, void* stream) {
+  if (!a) return fail(L2HMC_ERR_ARG, "args is NULL%s");
+  const EnvOverrides env = read_env();
   if (a->n_chains < 0 || a->d < 1 || a->T < 1) return fail(L2HMC_ERR_ARG, "bad n_chains / d / T%s");
   if (a->n_chains == 0) return L2HMC_OK;
-  const bool has_u = a->u != nullptr || (a->rng_flags & L2HMC_RNG_U);
   int KH = 3;
   KArgs k;
   int rc = traj_setup(a, k, KH);
   if (rc) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  // Wide targets (more than 8 dim-tiles, i.e. d > 128; `variant` 8 forces it from 4 tiles up): the
-  // register-resident kernels carry 4 or 8 tiles of state per wave there and spill (d = 512: ~1.6k VGPRs);
-  // the LDS-resident-state kernel covers the elementwise energies that exist at this width.
-  // One chain per lane (traj_lane.hpp): when the chains alone fill the chip -- a wave is 64 of them -- the padding-free
-  // VALU form beats the MFMA tiles (variant 32 forces it: tests).  Measured (tools/bench_lane.py): d <= 2 from 65 536
-  // chains, d <= 4 from 131 072; wider states lose to the scalar-load latency of their larger nets.
-  const int cus = device_cus();                // once per call: every threshold below is a statement about tiles per CU
-  {
-    const bool has_u_ = a->u != nullptr || (a->rng_flags & L2HMC_RNG_U);
-    const bool lane_able = a->packed_nets != nullptr && a->ais_beta == nullptr && k.beta == 1.f && k.temperature == 1.f &&
-                           k.n_steps >= 1 &&
-                           lane_supported(k.ekind, a->d, a->H, k.ncomp) && (a->d <= 16 || a->x_next != nullptr || !has_u_);
-    if (a->variant == 32 && !lane_able)
-      return fail(L2HMC_ERR_UNSUPPORTED, "variant 32 (one chain per lane) needs S/T/Q nets and a Gaussian / mixture / Rough-Well target with d <= 4%s");
-    const bool lane_auto = ((a->d <= 2 && a->n_chains >= 256 * cus) || (a->d <= 4 && a->n_chains >= 512 * cus));
-    if (lane_able && (a->variant == 32 || (a->variant == 0 && lane_auto)))
-    {
-      note_kernel("traj_lane_kernel");
-      return launch_lane(k, s);
-    }
-  }
-  const bool wide_dense = k.ekind == L2HMC_ENERGY_GAUSS_DENSE || k.ekind == L2HMC_ENERGY_GMM;      // (its precision fragments stream from L2: k.prec is the packed buffer)
-  const bool wide_kind = k.ekind == L2HMC_ENERGY_GAUSS_DIAG || k.ekind == L2HMC_ENERGY_ROUGHWELL || wide_dense;   // (mixtures: <= 4 tiles per wave)
-  const bool wide_able = a->packed_nets != nullptr && wide_kind && !(k.M > 1 && a->x_next == nullptr) && k.NT <= 32;
-  if (a->variant == 8 && !(wide_able && k.NT >= 4))
-    return fail(L2HMC_ERR_UNSUPPORTED, "variant 8 (LDS-resident state) needs S/T/Q nets, a Gaussian or Rough-Well target, 64 <= d <= 512 and x_next when n_proposals > 1%s");
-  if (wide_able && (a->variant == 8 || (a->variant == 0 && k.NT > (wide_dense ? WIDE_DENSE_MIN_NT : 8)))) {
-    KArgs kw = k;
-    // f16x2 contractions for the elementwise targets without a tempered / annealed energy, unless the f32-input MFMA is asked for
-    if (force_f32 || wide_dense || k.beta != 1.f || k.temperature != 1.f) kw.packed16 = nullptr;
-    const long long ldsw = plan_lds_wide(kw);
-    if (ldsw <= 160 * 1024) {
-      note_kernel(kw.packed16 != nullptr ? "traj_wide_kernel<f16x2>" : "traj_wide_kernel");
-      return launch_wide(kw, KH, ldsw, s);
-    }
-    if (a->variant == 8) return fail(L2HMC_ERR_UNSUPPORTED, "variant 8: %s%lld bytes of LDS needed (T x d too large)", "", ldsw);
-  }
-  int DT, NW;
-  const int geom_variant = a->variant >= 100 ? a->variant - 100 : ((a->variant == 16 || a->variant == 33) ? 0 : a->variant);   // 100 + v: the round-1 kernel
-  if (!pick_geometry(a->d, a->n_chains, geom_variant, DT, NW, cus))
-    return fail(L2HMC_ERR_UNSUPPORTED, "d = %s%lld not supported with variant %lld", "", a->d, a->variant);
-  // The instruction-lean kernel (traj_fast.hpp) covers S/T/Q nets on register-resident geometries; the
-  // tempered / annealed energies (HMC-mode AIS) and zero-step calls stay on the general kernel.
-  const bool fast = a->packed_nets != nullptr && DT <= 2 && k.n_steps >= 1 && a->variant < 100 &&
-                    k.beta == 1.f && k.temperature == 1.f;
-  // d <= 4 (SCG-2D, MoG-2D): one dimension per lane, S/T/Q in one MFMA row block (traj_small.hpp)
-  const bool small = fast && a->d <= 4 && geom_variant == 0 && k.ekind != L2HMC_ENERGY_FUNNEL &&
-                     (k.ekind != L2HMC_ENERGY_GMM || k.ncomp <= 8);
-  if (small) {
-    // (f16x2 for the hidden layer and the head block unless the f32-input MFMA is asked for: every target this kernel serves --
-    //  Gaussians incl. dense, mixtures, Rough Well -- has a grad U that is linear or bounded in the state the range guard watches)
-    const long long ldss = plan_lds_fast(k, 1, 1, !force_f32);
-    // (the per-step schedule records grow with T: past 160 KiB fall through to the fast / general kernel)
-    if (ldss <= 160 * 1024) {
-      note_kernel(force_f32 ? "traj_small_kernel<%lld, %lld>" : "traj_small_kernel<%lld, %lld, 1>", k.ekind, KH <= 3 ? 3 : 4);
-      return dispatch(force_f32 ? OP_TRAJ_SMALL : OP_TRAJ_SMALL16, k, 1, 1, KH, ldss, s);
-    }
-  }
-  // many chains (>= 2 tiles per SIMD), 3-4 dimension slices, elementwise target: one wave per tile (traj_tile.hpp);
-  // variant 16 forces it
-  const bool tile_kind = k.ekind == L2HMC_ENERGY_GAUSS_DIAG || k.ekind == L2HMC_ENERGY_ROUGHWELL;
-  // (a rejected chain of this kernel resumes from the copy of its start point parked in x_next: u without x_next -- accept
-  //  decisions with nowhere to put the selected state -- stays on the four-wave kernel)
-  const bool tileable = a->packed_nets != nullptr && tile_kind && k.NT >= 3 && k.NT <= 4 && k.n_steps >= 1 &&
-                        k.beta == 1.f && k.temperature == 1.f && !(has_u && a->x_next == nullptr) &&
-                        !force_f32;        // (its contractions are f16x2 throughout: traj_tile.hpp)
-  if (a->variant == 16 && !tileable)
-    return fail(L2HMC_ERR_UNSUPPORTED, "variant 16 (one wave per tile) needs S/T/Q nets, a diagonal-Gaussian or Rough-Well target, 33 <= d <= 64 and x_next whenever u is given%s");
-  if (tileable && (a->variant == 16 || (a->variant == 0 && a->n_chains >= 64LL * cus))) {
-    const long long ldst = plan_lds_tile(k, k.NT);
-    if (ldst <= 160 * 1024) {
-      // tiles (waves) per workgroup: 4, two workgroups per CU -- unless the staged tables (the split head fragments are 51 KB,
-      // the schedule records grow with T) leave room for ONE workgroup only: then 8 tiles share it, from the chain count
-      // (128 per CU) at which 8-tile workgroups still cover every CU
-      const int tpw = (2 * ldst > 160 * 1024 && a->n_chains >= 128LL * cus) ? 8 : 4;
-      note_kernel(a->d - 16 * (k.NT - 1) <= 2 ? "traj_tile_kernel<%lld, %lld, %lld, %lld, true>" : "traj_tile_kernel<%lld, %lld, %lld, %lld, false>",
-                  k.ekind, k.NT, KH <= 3 ? 3 : 4, tpw);
-      if (k.ekind == L2HMC_ENERGY_GAUSS_DIAG) return launch_tile_ek<L2HMC_ENERGY_GAUSS_DIAG>(k, k.NT, KH, tpw, ldst, s);
-      return launch_tile_ek<L2HMC_ENERGY_ROUGHWELL>(k, k.NT, KH, tpw, ldst, s);
-    }
-    if (a->variant == 16)
-      return fail(L2HMC_ERR_UNSUPPORTED, "variant 16: %s%lld bytes of LDS needed (T too large for the one-wave-per-tile kernel)", "", ldst);
-  }
-  if (fast) {
-    // f16x2 (traj_fast.hpp): every contraction of the step loop as two f16 MFMAs on an exact hi / lo split of both operands --
-    // fp32-accurate while |states|, |activations|, |grad U| < 65504 (beyond: inf - inf = NaN, which the accept rule treats as a
-    // rejection).  The elementwise targets take it unless the caller asks for the f32-input MFMA (variant 200 + v, or
-    // L2HMC_F32_MFMA=1 in the environment); the funnel (grad U ~ e^{-x_0}) stays on f32 everywhere, the mixtures and dense
-    // Gaussians on the tile kernels (their d <= 4 kernel takes f16x2 for its nets: above).
-    const bool f16 = !force_f32 && (k.ekind == L2HMC_ENERGY_GAUSS_DIAG || k.ekind == L2HMC_ENERGY_ROUGHWELL);
-    if (f16) {
-      const long long lds16 = plan_lds_fast(k, NW, DT, true);
-      if (lds16 <= 160 * 1024) {
-        note_kernel("traj_fast_kernel<%lld, %lld, %lld, %lld, 1>", k.ekind, DT, NW, KH <= 3 ? 3 : 4);
-        if (k.ekind == L2HMC_ENERGY_GAUSS_DIAG) return launch_fast16_ek<L2HMC_ENERGY_GAUSS_DIAG>(k, DT, NW, KH, lds16, s);
-        return launch_fast16_ek<L2HMC_ENERGY_ROUGHWELL>(k, DT, NW, KH, lds16, s);
-      }
-    }
-    const long long ldsf = plan_lds_fast(k, NW, DT);
-    if (ldsf <= 160 * 1024) {
-      note_kernel("traj_fast_kernel<%lld, %lld, %lld, %lld>", k.ekind, DT, NW, KH <= 3 ? 3 : 4);
-      return dispatch(OP_TRAJ_FAST, k, DT, NW, KH, ldsf, s);
-    }
-  }
-  const long long lds = plan_lds(k, a->packed_nets != nullptr, true, NW, DT);
-  note_kernel("traj_kernel<%lld, %lld, %lld, %lld>", k.ekind, DT, NW, KH <= 3 ? 3 : 4);
-  return dispatch(OP_TRAJ, k, DT, NW, KH, lds, s);
+  TrajPlan p;
+  // (device_cus once per call: every chain-count threshold of the plan is a statement about tiles per CU)
+  rc = plan_trajectory(*a, k, KH, device_cus(), env, p);
+  if (rc) return rc;
+  note_plan(p);
+  return launch_plan(p, k, (hipStream_t)stream);
 }
 
 int l2hmc_trajectory_ladder(const L2hmcTrajectoryArgs* a_in, const L2hmcLadderArgs* l, void* stream) {
@@ -779,23 +859,17 @@ int l2hmc_trajectory_ladder(const L2hmcTrajectoryArgs* a_in, const L2hmcLadderAr
   lg.rung = l->rung_of_row; lg.trip = l->trip_state; lg.rung_hist = l->rung_hist;
   lg.u = l->swap_u; lg.cold = l->cold_hist;
   lg.acc = (long long*)l->swaps_accepted; lg.att = (long long*)l->swaps_attempted; lg.trips = (long long*)l->round_trips;
-  int DT, NW;
-  const int gv = a->variant >= 100 ? a->variant - 100 : 0;
-  if (!pick_geometry(a->d, a->n_chains, gv, DT, NW))
-    return fail(L2HMC_ERR_UNSUPPORTED, "d = %s%lld not supported with variant %lld", "", a->d, a->variant);
-  const long long lds = plan_lds(k, a->packed_nets != nullptr, true, NW, DT);
-  lg.o_lad = (int)(lds / 4);
-  note_kernel("traj_ladder_kernel<%lld, %lld, %lld, %lld>", k.ekind, DT, NW, KH <= 3 ? 3 : 4);
-  const long long ldsl = lds + 4LL * kLadLds;
-  hipStream_t s = (hipStream_t)stream;
-  switch (k.ekind) {
-    case L2HMC_ENERGY_GAUSS_DIAG: return launch_ladder_ek<1>(k, lg, DT, NW, KH, ldsl, s);
-    case L2HMC_ENERGY_GAUSS_DENSE: return launch_ladder_ek<2>(k, lg, DT, NW, KH, ldsl, s);
-    case L2HMC_ENERGY_GMM: return launch_ladder_ek<3>(k, lg, DT, NW, KH, ldsl, s);
-    case L2HMC_ENERGY_ROUGHWELL: return launch_ladder_ek<4>(k, lg, DT, NW, KH, ldsl, s);
-    case L2HMC_ENERGY_FUNNEL: return launch_ladder_ek<5>(k, lg, DT, NW, KH, ldsl, s);
-  }
-  return fail(L2HMC_ERR_ARG, "unknown energy kind%s");
+  TrajPlan p;
+  p.ek = k.ekind;
+  p.KH = KH <= 3 ? 3 : 4;
+  rc = plan_geometry(*a, decode_variant(a->variant, false), device_cus(), p);
+  if (rc) return rc;
+  plan_general(*a, k, p);
+  lg.o_lad = (int)(p.lds / 4);
+  p.family = FAM_LADDER;
+  p.lds += 4LL * kLadLds;
+  note_plan(p);
+  return launch_plan(p, k, (hipStream_t)stream, &lg);
 }
 
 int64_t l2hmc_workspace_bytes(int64_t n_chains, int32_t d, int32_t H) {
@@ -852,14 +926,16 @@ int l2hmc_energy(const L2hmcEnergy* energy, const float* x, int64_t n_chains, in
   if (n_chains == 0) return L2HMC_OK;
   int rc = check_energy(energy, d);
   if (rc) return rc;
-  int DT, NW;
-  if (!pick_geometry(d, n_chains, 0, DT, NW)) return fail(L2HMC_ERR_UNSUPPORTED, "d = %s%lld too large", "", d);
+  TrajPlan p;
+  p.family = FAM_ENERGY;
+  if (!pick_geometry(d, n_chains, 0, p.DT, p.NW)) return fail(L2HMC_ERR_UNSUPPORTED, "d = %s%lld too large", "", d);
   KArgs k;
   memset(&k, 0, sizeof(k));
   k.N = n_chains; k.d = d; k.NT = tiles_of(d); k.x = x; k.U_out = U_out; k.grad_out = grad_out;
   fill_energy(k, energy);
-  const long long lds = plan_lds(k, false, false, NW, DT);
-  return dispatch(OP_ENERGY, k, DT, NW, 3, lds, (hipStream_t)stream);
+  p.ek = k.ekind;
+  p.lds = plan_lds(k, false, false, p.NW, p.DT);
+  return launch_plan(p, k, (hipStream_t)stream);
 }
 
 int l2hmc_p_accept(const L2hmcEnergy* energy, const float* x0, const float* v0, const float* x1,
@@ -870,15 +946,17 @@ int l2hmc_p_accept(const L2hmcEnergy* energy, const float* x0, const float* v0, 
   if (n_chains == 0) return L2HMC_OK;
   int rc = check_energy(energy, d);
   if (rc) return rc;
-  int DT, NW;
-  if (!pick_geometry(d, n_chains, 0, DT, NW)) return fail(L2HMC_ERR_UNSUPPORTED, "d = %s%lld too large", "", d);
+  TrajPlan p;
+  p.family = FAM_PACCEPT;
+  if (!pick_geometry(d, n_chains, 0, p.DT, p.NW)) return fail(L2HMC_ERR_UNSUPPORTED, "d = %s%lld too large", "", d);
   KArgs k;
   memset(&k, 0, sizeof(k));
   k.N = n_chains; k.d = d; k.NT = tiles_of(d);
   k.x = x0; k.v = v0; k.x1 = x1; k.v1 = v1; k.logjac_in = logjac; k.p_out = p_out;
   fill_energy(k, energy);
-  const long long lds = plan_lds(k, false, false, NW, DT);
-  return dispatch(OP_PACCEPT, k, DT, NW, 3, lds, (hipStream_t)stream);
+  p.ek = k.ekind;
+  p.lds = plan_lds(k, false, false, p.NW, p.DT);
+  return launch_plan(p, k, (hipStream_t)stream);
 }
 
 int l2hmc_mh_select(const float* x, const float* Lx, const float* px, const float* u,

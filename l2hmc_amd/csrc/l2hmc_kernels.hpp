@@ -27,6 +27,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
+#include <type_traits>
 
 #include "../../include/l2hmc.h"
 
@@ -70,9 +71,8 @@ __device__ __forceinline__ void lds_poison(float* smem) {
 }
 int check_energy(const L2hmcEnergy* e, int d);
 struct KArgs;
-// traj_wide.hip: the LDS-resident-state kernel for d > 256 (elementwise energies)
-long long plan_lds_wide(KArgs& k);
-int launch_wide(const KArgs& k, int KH, long long lds, hipStream_t s);
+// traj_wide.hip: the LDS plan of the LDS-resident-state kernel for d > 256 (elementwise energies) and its waves per workgroup
+long long plan_lds_wide(KArgs& k, int& NW);
 
 // ------------------------------------------------------------------------------------------
 // Packed layouts (shared by host and device)
@@ -975,12 +975,31 @@ __global__ __launch_bounds__(64 * NW) void paccept_kernel(const KArgs A) {
 
 
 // ------------------------------------------------------------------------------------------
-// Launchers (one explicit instantiation per energy kind, in traj_ek<k>.hip)
+// Launch plans and launchers.  l2hmc_abi.hip plans a call (plan_trajectory: every selection rule) and hands the plan to the
+// translation unit that holds its kernel; the launcher templates are defined in traj_launch.hpp / traj_lane_inst.hpp /
+// traj_wide.hip and explicitly instantiated by those units only.
 // ------------------------------------------------------------------------------------------
 const int kMaxLdsBytes = 160 * 1024;
 
+// the kernel a plan launches (ENERGY, PACCEPT: l2hmc_energy, l2hmc_p_accept)
+enum Family { FAM_GENERAL, FAM_FAST, FAM_SMALL, FAM_TILE, FAM_WIDE, FAM_LANE, FAM_LADDER, FAM_ENERGY, FAM_PACCEPT };
+
+// Everything the launch of one call needs beyond KArgs: the family and its template arguments.
+struct TrajPlan {
+  int family = FAM_GENERAL;
+  int ek = 0;               // energy kind (EK)
+  int DT = 1, NW = 1;       // tiles per wave and waves per workgroup; tile: DT = dim-tiles; wide: NW only
+  int KH = 3;               // hidden k-steps of the nets, 3 or 4
+  int tpw = 4;              // tile: tiles (waves) per workgroup
+  bool half = false;        // tile: the last dimension slice holds <= 2 dimensions
+  int DP = 0, HPR = 0, RES = 0;   // lane: compiled dimensions, hidden units per register pair, weight residency
+  int f16 = 0;              // f16x2 contractions (PK / F16 of the fast, small and wide kernels)
+  long long lds = 0;        // dynamic LDS bytes
+};
+
+// One kernel launch: the LDS limit, the dynamic-LDS attribute above 48 KiB, the grid size, the launch and its error.
 template <class K, class... X>
-int launch(K kern, const KArgs& k, int NW, long long lds_bytes, hipStream_t s, const X&... extra) {
+int launch_kernel(K kern, long long blocks, int threads, long long lds_bytes, hipStream_t s, const X&... args) {
   if (lds_bytes > kMaxLdsBytes)
     return fail(L2HMC_ERR_UNSUPPORTED, "needs %s%lld bytes of LDS (> 160 KiB): d too large for the LDS-resident weight path", "", lds_bytes);
   if (lds_bytes > 48 * 1024) {
@@ -988,76 +1007,60 @@ int launch(K kern, const KArgs& k, int NW, long long lds_bytes, hipStream_t s, c
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
     if (e != hipSuccess) return fail(L2HMC_ERR_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(e));
   }
-  const long long blocks = (k.N + 15) / 16;
   if (blocks > 0x7fffffffLL) return fail(L2HMC_ERR_UNSUPPORTED, "too many chains%s");
-  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(64 * NW), (size_t)lds_bytes, s, k, extra...);
+  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(threads), (size_t)lds_bytes, s, args...);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(L2HMC_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
   return L2HMC_OK;
 }
 
-#define L2HMC_GEOM_SWITCH(DTv, NWv, CALL)                \
-  if (DTv == 1 && NWv == 1) { CALL(1, 1) }               \
-  else if (DTv == 2 && NWv == 1) { CALL(2, 1) }          \
-  else if (DTv == 4 && NWv == 1) { CALL(4, 1) }          \
-  else if (DTv == 1 && NWv == 4) { CALL(1, 4) }          \
-  else if (DTv == 2 && NWv == 4) { CALL(2, 4) }          \
-  else if (DTv == 4 && NWv == 4) { CALL(4, 4) }          \
-  else if (DTv == 8 && NWv == 4) { CALL(8, 4) }          \
-  else return fail(L2HMC_ERR_UNSUPPORTED, "no kernel for this geometry%s");
+// Template arguments from run-time values: f is a generic lambda called with std::integral_constant arguments, so every branch
+// names (and instantiates) one kernel.
+template <auto V> using ic = std::integral_constant<decltype(V), V>;
 
-enum { OP_TRAJ = 0, OP_ENERGY = 1, OP_PACCEPT = 2, OP_TRAJ_FAST = 3, OP_TRAJ_SMALL = 4, OP_TRAJ_SMALL16 = 5 };
+// f(ic<A>) if first, else f(ic<B>)
+template <auto A, auto B, class F>
+int on_either(bool first, F&& f) { return first ? f(ic<A>{}) : f(ic<B>{}); }
 
-#define L2HMC_FAST_SWITCH(DTv, NWv, CALL)                \
-  if (DTv == 1 && NWv == 1) { CALL(1, 1) }               \
-  else if (DTv == 2 && NWv == 1) { CALL(2, 1) }          \
-  else if (DTv == 1 && NWv == 4) { CALL(1, 4) }          \
-  else if (DTv == 2 && NWv == 4) { CALL(2, 4) }          \
-  else if (DTv == 2 && NWv == 2) { CALL(2, 2) }          \
-  else return fail(L2HMC_ERR_UNSUPPORTED, "no fast kernel for this geometry%s");
-
-// Declared here, defined (explicitly instantiated) once per energy kind.
-template <int EK>
-int launch_ek(int op, const KArgs& k, int DT, int NW, int KH, long long lds, hipStream_t s);
-// traj_fast_kernel<EK, DT, NW, KH, 1>: the f16x2 form of the instruction-lean kernel (traj_f16_ek1.hip, traj_f16_ek4.hip)
-template <int EK>
-int launch_fast16_ek(const KArgs& k, int DT, int NW, int KH, long long lds, hipStream_t s);
-// traj_tile_kernel (one wave per tile, 4 tiles per workgroup): elementwise targets only (traj_ek1.hip, traj_ek4.hip)
-template <int EK>
-int launch_tile_ek(const KArgs& k, int DT, int KH, int tpw, long long lds, hipStream_t s);
-
-// traj_ladder_kernel (parallel tempering), every geometry of the general kernel: one translation unit per energy kind
-// (traj_ladder_ek<k>.hip), apart from the plain kernels' units so that their code objects stay as they were
-template <int EK>
-int launch_ladder_ek(const KArgs& k, const LadArgs& l, int DT, int NW, int KH, long long lds, hipStream_t s);
-#define L2HMC_CALL_LADDER(DTc, NWc)                                                         \
-  if (KH <= 3) return launch(traj_ladder_kernel<E_, DTc, NWc, 3>, k, NWc, lds, s, l);       \
-  else return launch(traj_ladder_kernel<E_, DTc, NWc, 4>, k, NWc, lds, s, l);
-#define L2HMC_DEFINE_LAUNCH_LADDER(EKv)                                                                 \
-  template <>                                                                                           \
-  int launch_ladder_ek<EKv>(const KArgs& k, const LadArgs& l, int DT, int NW, int KH, long long lds, hipStream_t s) { \
-    constexpr int E_ = EKv;                                                                             \
-    L2HMC_GEOM_SWITCH(DT, NW, L2HMC_CALL_LADDER)                                                        \
+// f(ic<EK>) for a built-in energy kind (L2HMC_ENERGY_GAUSS_DIAG = 1 ... L2HMC_ENERGY_FUNNEL = 5)
+template <class F>
+int on_energy_kind(int ek, F&& f) {
+  switch (ek) {
+    case 1: return f(ic<1>{});
+    case 2: return f(ic<2>{});
+    case 3: return f(ic<3>{});
+    case 4: return f(ic<4>{});
+    case 5: return f(ic<5>{});
   }
+  return fail(L2HMC_ERR_ARG, "unknown energy kind%s");
+}
 
-#define L2HMC_DEFINE_LAUNCH_EK(EKv)                                                              \
-  template <>                                                                                    \
-  int launch_ek<EKv>(int op, const KArgs& k, int DT, int NW, int KH, long long lds, hipStream_t s) { \
-    if (op == OP_TRAJ) {                                                                         \
-      _Pragma("clang diagnostic push")                                                           \
-      L2HMC_GEOM_SWITCH(DT, NW, L2HMC_CALL_TRAJ_##EKv)                                           \
-      _Pragma("clang diagnostic pop")                                                            \
-    } else if (op == OP_TRAJ_FAST) {                                                             \
-      L2HMC_FAST_SWITCH(DT, NW, L2HMC_CALL_FAST_##EKv)                                           \
-    } else if (op == OP_TRAJ_SMALL) {                                                            \
-      L2HMC_CALL_SMALL_##EKv                                                                     \
-    } else if (op == OP_TRAJ_SMALL16) {                                                          \
-      L2HMC_CALL_SMALL16_##EKv                                                                   \
-    } else if (op == OP_ENERGY) {                                                                \
-      L2HMC_GEOM_SWITCH(DT, NW, L2HMC_CALL_EN_##EKv)                                             \
-    } else {                                                                                     \
-      L2HMC_GEOM_SWITCH(DT, NW, L2HMC_CALL_PA_##EKv)                                             \
-    }                                                                                            \
-  }
+// The compiled (DT, NW) geometries: general, energy, p_accept and ladder kernels; the instruction-lean kernel (traj_fast.hpp).
+template <int DT_, int NW_> struct Geom { static constexpr int DT = DT_, NW = NW_; };
+template <class... G> struct Geoms {};
+using GeneralGeoms = Geoms<Geom<1, 1>, Geom<2, 1>, Geom<4, 1>, Geom<1, 4>, Geom<2, 4>, Geom<4, 4>, Geom<8, 4>>;
+using FastGeoms = Geoms<Geom<1, 1>, Geom<2, 1>, Geom<1, 4>, Geom<2, 4>, Geom<2, 2>>;
+
+// f(ic<DT>, ic<NW>) for the geometry of the set; `what` names the kernel in the refusal ("" or "fast ")
+template <class... G, class F>
+int on_geometry(Geoms<G...>, int DT, int NW, const char* what, F&& f) {
+  int rc = L2HMC_OK;
+  const bool found = ((DT == G::DT && NW == G::NW && ((rc = f(ic<G::DT>{}, ic<G::NW>{})), true)) || ...);
+  return found ? rc : fail(L2HMC_ERR_UNSUPPORTED, "no %skernel for this geometry", what);
+}
+
+// The launchers, one per kind of translation unit; each launches the kernel plan p names, with k.
+template <int EK>   // traj_kernel, traj_fast_kernel (f32-input MFMA), traj_small_kernel, energy_kernel, paccept_kernel: traj_ek<EK>.hip
+int launch_ek(const TrajPlan& p, const KArgs& k, hipStream_t s);
+template <int EK>   // traj_fast_kernel<EK, ., ., ., 1>: traj_f16_ek<EK>.hip (diagonal Gaussian, Rough Well)
+int launch_fast16_ek(const TrajPlan& p, const KArgs& k, hipStream_t s);
+template <int EK>   // traj_tile_kernel: traj_tile_inst.hip (diagonal Gaussian, Rough Well)
+int launch_tile_ek(const TrajPlan& p, const KArgs& k, hipStream_t s);
+template <int EK>   // traj_ladder_kernel: traj_ladder_ek<EK>.hip, apart from the plain kernels' units so that their code objects stay as they were
+int launch_ladder_ek(const TrajPlan& p, const KArgs& k, const LadArgs& l, hipStream_t s);
+template <int EK>   // traj_wide_kernel: traj_wide.hip (Gaussians incl. dense, mixtures, Rough Well)
+int launch_wide_ek(const TrajPlan& p, const KArgs& k, hipStream_t s);
+template <int EK>   // traj_lane_kernel: traj_lane_a.hip (diagonal Gaussian), traj_lane_b.hip (Rough Well), traj_lane_c.hip (dense, mixtures)
+int launch_lane_ek(const TrajPlan& p, const KArgs& k, hipStream_t s);
 
 }  // namespace l2hmc

@@ -1,6 +1,6 @@
 // The ladder (parallel-tempering) form of the general trajectory kernel for energy kind 3 (gmm); see l2hmc_kernels.hpp.
-#include "l2hmc_kernels.hpp"
+#include "traj_launch.hpp"
 
 namespace l2hmc {
-L2HMC_DEFINE_LAUNCH_LADDER(3)
+template int launch_ladder_ek<3>(const TrajPlan& p, const KArgs& k, const LadArgs& l, hipStream_t s);
 }  // namespace l2hmc

@@ -576,8 +576,7 @@ __global__ __launch_bounds__(64, RES != 0 ? 2 : (DP <= 8 ? 4 : 2)) void traj_lan
   }
 }
 
-// the kernels this build instantiates: returns 0 if (ek, d, H) has none
-int launch_lane(const KArgs& k, hipStream_t s);
+// whether this build instantiates a kernel for (ek, d, H, ncomp) (traj_lane_c.hip)
 bool lane_supported(int ek, int d, int H, int ncomp);
 
 }  // namespace l2hmc

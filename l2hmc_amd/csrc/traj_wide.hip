@@ -564,38 +564,27 @@ static int wide_waves(const KArgs& k) {
   return 2 * 4 * wide_lds_floats(t, 4) <= L2HMC_WIDE_LDS_PER_CU ? 4 : 8;
 }
 
-long long plan_lds_wide(KArgs& k) { return 4 * wide_lds_floats(k, wide_waves(k)); }
-
-template <int EK, int KH, int NW, int PK = 0>
-static int launch_wide_t(const KArgs& k, long long lds, hipStream_t s) {
-  auto kern = traj_wide_kernel<EK, KH, NW, PK>;
-  if (lds > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)lds);
-    if (e != hipSuccess) return fail(L2HMC_ERR_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-  }
-  hipLaunchKernelGGL(kern, dim3((unsigned)((k.N + 15) / 16)), dim3(64 * NW), (size_t)lds, s, k);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(L2HMC_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
-  return L2HMC_OK;
+long long plan_lds_wide(KArgs& k, int& NW) {
+  NW = wide_waves(k);
+  return 4 * wide_lds_floats(k, NW);
 }
 
-int launch_wide(const KArgs& k, int KH, long long lds, hipStream_t s) {
-  const bool diag = k.ekind == L2HMC_ENERGY_GAUSS_DIAG, dense = k.ekind == L2HMC_ENERGY_GAUSS_DENSE, w8 = wide_waves(k) == 8;
-#define L2HMC_WIDE(EKv)                                                                      \
-  (KH == 3 ? (w8 ? launch_wide_t<EKv, 3, 8>(k, lds, s) : launch_wide_t<EKv, 3, 4>(k, lds, s)) \
-           : (w8 ? launch_wide_t<EKv, 4, 8>(k, lds, s) : launch_wide_t<EKv, 4, 4>(k, lds, s)))
-  if (dense) return L2HMC_WIDE(L2HMC_ENERGY_GAUSS_DENSE);
-  if (k.ekind == L2HMC_ENERGY_GMM) return L2HMC_WIDE(L2HMC_ENERGY_GMM);
-  if (k.packed16 != nullptr) {            // the elementwise targets with f16x2 contractions (the dispatcher clears it for variant 200 + v)
-#define L2HMC_WIDE16(EKv)                                                                          \
-  (KH == 3 ? (w8 ? launch_wide_t<EKv, 3, 8, 1>(k, lds, s) : launch_wide_t<EKv, 3, 4, 1>(k, lds, s)) \
-           : (w8 ? launch_wide_t<EKv, 4, 8, 1>(k, lds, s) : launch_wide_t<EKv, 4, 4, 1>(k, lds, s)))
-    return diag ? L2HMC_WIDE16(L2HMC_ENERGY_GAUSS_DIAG) : L2HMC_WIDE16(L2HMC_ENERGY_ROUGHWELL);
-#undef L2HMC_WIDE16
-  }
-  return diag ? L2HMC_WIDE(L2HMC_ENERGY_GAUSS_DIAG) : L2HMC_WIDE(L2HMC_ENERGY_ROUGHWELL);
-#undef L2HMC_WIDE
+// PK = 1 (p.f16) for the elementwise targets with f16x2 contractions (the planner clears it for variant 200 + v)
+template <int EK>
+int launch_wide_ek(const TrajPlan& p, const KArgs& k, hipStream_t s) {
+  return on_either<3, 4>(p.KH == 3, [&](auto KH) {
+    return on_either<8, 4>(p.NW == 8, [&](auto NW) {
+      auto go = [&](auto kern) { return launch_kernel(kern, (k.N + 15) / 16, 64 * NW, p.lds, s, k); };
+      if constexpr (EK == L2HMC_ENERGY_GAUSS_DIAG || EK == L2HMC_ENERGY_ROUGHWELL) {
+        if (p.f16) return go(traj_wide_kernel<EK, KH, NW, 1>);
+      }
+      return go(traj_wide_kernel<EK, KH, NW>);
+    });
+  });
 }
+template int launch_wide_ek<L2HMC_ENERGY_GAUSS_DIAG>(const TrajPlan& p, const KArgs& k, hipStream_t s);
+template int launch_wide_ek<L2HMC_ENERGY_GAUSS_DENSE>(const TrajPlan& p, const KArgs& k, hipStream_t s);
+template int launch_wide_ek<L2HMC_ENERGY_GMM>(const TrajPlan& p, const KArgs& k, hipStream_t s);
+template int launch_wide_ek<L2HMC_ENERGY_ROUGHWELL>(const TrajPlan& p, const KArgs& k, hipStream_t s);
 
 }  // namespace l2hmc

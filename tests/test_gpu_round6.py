@@ -408,11 +408,11 @@ def test_f16x2_range_is_wide_and_its_overflow_is_loud():
 
 # ---- one chain per lane (csrc/traj_lane.hpp): where the weights live must not change a bit ---------------------------------------
 @pytest.mark.parametrize("case", ["scg2d", "mog2d", "ring4", "rough2_ne", "diag2"])
-def test_lane_kernel_weight_residency_forms_are_bit_identical(case, monkeypatch):
+def test_lane_kernel_residency_forms_are_bit_identical_and_named_by_res(case, monkeypatch):
     """traj_lane_kernel<., 2, 5, RES>: weights by scalar loads in the loop (RES 0), XNet's layer 2 and heads as VGPR pairs (1), every
     weight of both nets in VGPRs four per register behind a DPP quad broadcast (2).  The three forms run the same FMAs on the same
     operands in the same order: direction-mixed proposals with an MH step on a ragged chain count (two full waves and a part)
-    must agree BIT FOR BIT, and sit on the reference fixture like every other kernel."""
+    must agree BIT FOR BIT, and sit on the reference fixture like every other kernel.  l2hmc_last_kernel names the form that ran."""
     import torch
     from l2hmc_amd import _ffi, propose
     if case == "diag2":                                   # no d = 2 diagonal fixture: the strongly anisotropic Gaussian of scg2d's nets
@@ -426,12 +426,13 @@ def test_lane_kernel_weight_residency_forms_are_bit_identical(case, monkeypatch)
     idx = rng.randint(0, n0, size=N)
     x, v = to_dev(g["x"][idx] + 0.01 * rng.randn(N, 2).astype(np.float32)), to_dev(g["v"][idx])
     direction, u = to_dev(rng.randint(0, 2, size=N).astype(np.uint8)), to_dev(rng.rand(N).astype(np.float32))
+    ek = {"scg2d": 2, "mog2d": 3, "ring4": 3, "rough2_ne": 4, "diag2": 1}[case]      # (scg2d: a dense precision)
     outs = []
     for res in ("0", "1", "2"):
         monkeypatch.setenv("L2HMC_LANE_RES", res)
         dyn = hip_dynamics(g, 32)
         Lx, Lv, px, o = propose(x, dyn, do_mh_step=True, direction=direction, v=v, u=u)
-        assert _ffi.last_kernel() == "traj_lane_kernel"
+        assert _ffi.last_kernel() == "traj_lane_kernel<%d, 2, 5%s>" % (ek, "" if res == "0" else ", " + res)
         assert np.isfinite(to_np(Lx)).all() and 0.05 < float(px.mean()) <= 1.0
         outs.append([t for t in (Lx, Lv, px, o[0]) if t is not None])
     for other in outs[1:]:
