@@ -20,8 +20,14 @@ itself through torch.distributed.run with N ranks on 127.0.0.1 -- one process pe
 
 Prints ONE JSON line on rank 0 (contract in the task statement) incl. `roofline` (dominant
 kernel = traj_fast_kernel, MFMA-bound: algorithmic fp32 flops / launch duration vs the 157.3
-TFLOP/s fp32-MFMA peak) and `cpu_baseline` (the reference algorithm restated op by op on torch-CPU,
-all host cores, both directions computed like sampler.py:35-36; rank 0, N=1 only).
+TFLOP/s fp32-MFMA peak).  A plain run does only what that line needs: set up, preheat and warm up, time the steps,
+dump the outputs if asked, print.
+
+`--full` adds every leg that takes runs of its own (each can still be skipped with its `--no-...` option): at N = 1 the
+roofline `sweep` (8192 and 65 536 chains), `config4` (Rough Well), `config5` (the VAE engine, with its trained sampler),
+`ess` (SCG-2D ESS/sec of HMC and of L2HMC samplers trained in the run) and `cpu_baseline` (the reference algorithm
+restated op by op on torch-CPU, all host cores, both directions computed like sampler.py:35-36); at N > 1
+`strong65536` and `dist` below (`dist` also at N = 1 with `--force-dist`).
 
 The timed region is exactly `--steps` proposals; `ms_per_step` is its wall time per proposal, so a caller can size
 `--steps` for a timed region of the length it wants.  `--dump-outputs DIR` writes what the timed path hands its caller
@@ -30,9 +36,9 @@ as DIR/<name>.npy in float32.  All inputs are seeded, so with the same arguments
 output.
 
 Multi-GPU: `--gpus N` alone is weak scaling (`--chains` per GPU; the bench line); `--total-chains C` makes the line
-strong scaling (C chains split over the N ranks).  At N > 1 two extra keys: `strong65536` = the north star's operating
-point, ICG-50 with 65 536 chains IN TOTAL split over the ranks (value, rank 0's roofline fraction, ratio to the committed
-N = 1 rate), and `dist` = the collectives of the path: ESS of chains sharded over the ranks (one all-reduce of the
+strong scaling (C chains split over the N ranks).  At N > 1 `--full` adds two keys: `strong65536` = the north star's
+operating point, ICG-50 with 65 536 chains IN TOTAL split over the ranks (value, rank 0's roofline fraction, ratio to the
+committed N = 1 rate), and `dist` = the collectives of the path: ESS of chains sharded over the ranks (one all-reduce of the
 autocovariance partial sums + mean accept) and a timed training step (flat-gradient all-reduce).
 """
 import argparse
@@ -526,6 +532,9 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the last step's chain state and accept probability as "
                          "DIR/x.npy and DIR/accept_prob.npy (float32; suffix _rank<r> when N > 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run every leg that takes runs of its own (sweep, config4, config5, ess, "
+                         "cpu_baseline at N = 1; strong65536, dist at N > 1); the --no-... options skip single legs")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-ess", action="store_true", help="skip the SCG-2D ESS/sec leg (N=1) / the dist leg (N>1)")
     ap.add_argument("--no-sweep", action="store_true", help="skip the 65 536-chain roofline point (N=1 only)")
@@ -537,7 +546,8 @@ def main():
                     help="Adam steps for the L2HMC sampler of the ESS leg (0 = HMC only)")
     ap.add_argument("--ess-seeds", type=int, default=10, help="independent trainings of the ESS leg (0.25 s each)")
     ap.add_argument("--force-dist", action="store_true",
-                    help="initialise RCCL and run the `dist` leg even at N = 1 (exercises the collectives on a 1-GPU box)")
+                    help="initialise RCCL even at N = 1, and with --full run the `dist` leg (exercises the collectives "
+                         "on a 1-GPU box)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo for a rehearsal)")
     ap.add_argument("--one-device", action="store_true",
                     help="rehearsal of the N > 1 code path on a 1-GPU box: every rank uses cuda:0 (with --backend gloo)")
@@ -736,7 +746,7 @@ def main():
                 bool(torch.isfinite(r2.bufs[r2.flip]).all()), _ffi.last_kernel())     # (the library names what it launched)
 
     strong_out = None
-    if world > 1 and not strong and not args.no_sweep:
+    if args.full and world > 1 and not strong and not args.no_sweep:
         # the north star's operating point: ICG-50, 65 536 chains IN TOTAL over the ranks (every rank takes part)
         tot = 65536
         lo, hi = sharding.shard_range(tot, rank, world)
@@ -766,7 +776,7 @@ def main():
             strong_out["speedup_vs_committed_n1_constant"] = strong_out["value"] / v1["value"]
 
     dist_out = None
-    if use_dist and not args.no_ess:
+    if args.full and use_dist and not args.no_ess:
         dist_out = dist_leg(dev, rank, world)
 
     if rank == 0:
@@ -827,7 +837,7 @@ def main():
                     # wave counter ticks in quad-cycles); read from the committed summary like `traffic`, not measured live
                     out["roofline"]["mfma_pipe_busy"] = t["mfma_pipe_busy"]
                     out["roofline"]["mfma_pipe_busy_source"] = t.get("mfma_pipe_busy_source", t["source"])
-        if world == 1 and not args.no_sweep and not strong and n == CHAINS:
+        if args.full and world == 1 and not args.no_sweep and not strong and n == CHAINS:
             # the same kernel at the north star's chain count: what the MFMA roof fraction becomes once the
             # chip is filled (4096 chains are ONE workgroup per CU, one wave per SIMD)
             sweep = []
@@ -839,9 +849,9 @@ def main():
                               "frac": a2 / PEAK_F32_MFMA_TFLOPS, "launch_us": 1e3 * ms2 / nl2,
                               "mean_accept_prob": p2, "state_finite": fin2})
             out["sweep"] = sweep
-        if world == 1 and not args.no_config4 and not strong and n == CHAINS and not args.force_dist:
+        if args.full and world == 1 and not args.no_config4 and not strong and n == CHAINS and not args.force_dist:
             out["config4"] = config4_leg(dev)
-        if world == 1 and not args.no_config5 and not strong and n == CHAINS and not args.force_dist:
+        if args.full and world == 1 and not args.no_config5 and not strong and n == CHAINS and not args.force_dist:
             out["config5"] = config5_leg(dev)
             if not args.no_config5_trained:
                 # config 5 as BASELINE.json words it ("trained sampler"): train the sampler with the reference's update, then
@@ -850,7 +860,7 @@ def main():
                 import bench_config5_trained
                 out["config5"]["trained"] = bench_config5_trained.run(dev, updates=200, mh_steps=250,
                                                                        hmc_eps=(0.075, 0.1, 0.175))
-        if world == 1 and not args.no_ess and not args.force_dist:
+        if args.full and world == 1 and not args.no_ess and not args.force_dist:
             out["ess"] = ess_leg(dev, args.ess_train_steps, args.ess_seeds)
         if strong_out is not None:
             out["strong65536"] = strong_out
@@ -861,7 +871,7 @@ def main():
             out["strong65536_speedup_same_run"] = strong_out.get("speedup_same_run")
         if dist_out is not None:
             out["dist"] = dist_out
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline_subprocess()
         # ---- what is judged, as flat top-level scalars next to the nested keys (a parsed record that keeps only top-level
         #      scalars still carries the operating points) ----

@@ -145,12 +145,12 @@ def test_separate_aux_branches_take_the_general_path():
 
 
 def test_bench_dist_leg_over_rccl_world_size_1(tmp_path):
-    """bench.py --force-dist: process group on backend nccl (= RCCL), the sharded-ESS all-reduces and the
+    """bench.py --full --force-dist: process group on backend nccl (= RCCL), the sharded-ESS all-reduces and the
     flat-gradient all-reduce of a training step run on the GPU box's one GPU; --steps 20 times exactly 20 steps, and
     --dump-outputs writes the last timed step's chain state and accept probabilities."""
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29533", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--force-dist", "--steps", "20", "--warmup", "5",
-                        "--no-cpu-baseline", "--no-sweep", "--dump-outputs", str(tmp_path)],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--force-dist", "--steps", "20",
+                        "--warmup", "5", "--no-cpu-baseline", "--no-sweep", "--dump-outputs", str(tmp_path)],
                        capture_output=True, text=True, timeout=280, env=env)
     assert r.returncode == 0, r.stderr[-800:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -161,6 +161,27 @@ def test_bench_dist_leg_over_rccl_world_size_1(tmp_path):
     x, p = np.load(str(tmp_path / "x.npy")), np.load(str(tmp_path / "accept_prob.npy"))
     assert x.dtype == np.float32 and x.shape == (4096, 50) and np.all(np.isfinite(x))
     assert p.dtype == np.float32 and p.shape == (4096,) and np.all((p >= 0) & (p <= 1)) and 0.01 < p.mean() < 1.0
+
+
+def test_plain_bench_run_prints_the_headline_without_the_full_legs(tmp_path):
+    """bench.py without --full: ONE line with the headline of exactly --steps timed proposals and the main run's roofline,
+    no key of the legs that take runs of their own, and --dump-outputs writes the last timed step's arrays."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=280)
+    assert r.returncode == 0, r.stderr[-800:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, lines
+    out = json.loads(lines[0])
+    assert out["metric"] == "chain_leapfrog_steps_per_sec" and out["unit"] == "chain\u00b7leapfrog-steps/s"
+    assert out["higher_is_better"] is True and out["dtype"] == "f32" and out["steps"] == 20 and out["warmup"] == 5
+    assert out["value"] > 1e8 and out["config"]["state_finite"] and out["config"]["timed_steps"] == 20
+    assert abs(out["value"] * out["ms_per_step"] * 1e-3 - 4096 * 10) < 1e-6 * 4096 * 10
+    assert 0.0 < out["roofline"]["frac"] < 1.0
+    for key in ("sweep", "config4", "config5", "ess", "cpu_baseline", "strong65536", "dist"):
+        assert key not in out, key
+    assert sorted(os.listdir(str(tmp_path))) == ["accept_prob.npy", "x.npy"]
+    x = np.load(str(tmp_path / "x.npy"))
+    assert x.dtype == np.float32 and x.shape == (4096, 50) and np.all(np.isfinite(x))
 
 
 def test_vae_sampler_loop_with_library_philox_matches_injected_draws_and_oracle():

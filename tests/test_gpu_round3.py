@@ -219,8 +219,8 @@ def test_bench_launches_its_own_ranks_the_way_the_driver_calls_it():
     """`python bench.py --gpus 2` with NO torchrun and no WORLD_SIZE (the driver's plain invocation): bench.py becomes the
     launcher, two ranks start through torch.distributed.run, rank 0 prints ONE JSON line.  Rehearsed on the 1-GPU box with
     both ranks on cuda:0 over gloo (`--one-device --backend gloo`; on the 8-GPU node the same path runs one rank per GPU
-    over RCCL).  Checks the weak-scaling headline, the `strong65536` key (65 536 chains in total over the ranks) and the
-    `dist` key (sharded ESS + flat-gradient all-reduce)."""
+    over RCCL).  Checks the weak-scaling headline and, with `--full`, the `strong65536` key (65 536 chains in total over
+    the ranks) and the `dist` key (sharded ESS + flat-gradient all-reduce)."""
     import json
     import os
     import subprocess
@@ -229,7 +229,7 @@ def test_bench_launches_its_own_ranks_the_way_the_driver_calls_it():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--one-device", "--backend", "gloo",
-                        "--steps", "20", "--warmup", "5"], capture_output=True, text=True, timeout=560, env=env)
+                        "--steps", "20", "--warmup", "5", "--full"], capture_output=True, text=True, timeout=560, env=env)
     assert r.returncode == 0, r.stderr[-1500:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, lines

@@ -8,7 +8,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-BENCH="python $R/bench.py"
+BENCH="python $R/bench.py --full"
 
 timeout 400 $BENCH > $OUT/bench.json 2> $OUT/bench.err
 tail -c 2500 $OUT/bench.json

@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$R/gpurun_out/r02b
 rm -rf $OUT; mkdir -p $OUT
 cd $R
-timeout 300 python bench.py > $OUT/bench.json 2> $OUT/bench.err
+timeout 300 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 timeout 100 python tools/bench_vae.py 8192 2>/dev/null | tail -1 > $OUT/vae.txt
 timeout 100 python tools/bench_vae.py 512 2>/dev/null | tail -1 >> $OUT/vae.txt
 cd /tmp && export TMPDIR=/tmp

@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/r03
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-BENCH="python $R/bench.py"
+BENCH="python $R/bench.py --full"
 LEAN="--no-cpu-baseline --no-ess --no-sweep --no-config5"
 
 timeout 500 $BENCH > $OUT/bench.json 2> $OUT/bench.err

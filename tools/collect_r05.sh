@@ -11,7 +11,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$R/gpurun_out/r05
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-BENCH="python $R/bench.py"
+BENCH="python $R/bench.py --full"
 LEAN="--no-cpu-baseline --no-ess --no-sweep --no-config5 --no-config4"
 PART=${PART:-bench config4 rest vae}
 

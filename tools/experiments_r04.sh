@@ -153,7 +153,7 @@ for rep in 1 2; do
   done
 done
 } | tee $OUT/timing.txt
-timeout 300 python bench.py --force-dist --steps 20 --warmup 5 --no-cpu-baseline --no-sweep --no-config5 --no-config4 2>/dev/null | grep "^{" > $OUT/bench_force_dist.json
+timeout 300 python bench.py --full --force-dist --steps 20 --warmup 5 --no-cpu-baseline --no-sweep --no-config5 --no-config4 2>/dev/null | grep "^{" > $OUT/bench_force_dist.json
 python - <<PY
 import json
 o=json.load(open("$OUT/bench_force_dist.json"))
@@ -175,7 +175,7 @@ done
 } | tee $OUT/timing.txt
 timeout 900 python -m pytest tests/test_gpu_parity.py tests/test_gpu_round3.py tests/test_gpu_round4.py -q -x -m gpu -p no:cacheprovider \
    -k "full_size or config4 or tempered or tile_kernel or sample_chain or reversibility" 2>&1 | tail -6 | tee $OUT/tests.txt
-timeout 300 python bench.py --force-dist --steps 20 --warmup 5 --no-cpu-baseline --no-sweep --no-config5 --no-config4 2>/dev/null | grep "^{" > $OUT/bench_force_dist.json
+timeout 300 python bench.py --full --force-dist --steps 20 --warmup 5 --no-cpu-baseline --no-sweep --no-config5 --no-config4 2>/dev/null | grep "^{" > $OUT/bench_force_dist.json
 python - <<PY
 import json
 o=json.load(open("$OUT/bench_force_dist.json"))
@@ -342,7 +342,7 @@ cd $R
 timeout 900 python -m pytest tests -m gpu -q -p no:cacheprovider 2>&1 | tail -8 > $OUT/gpu_tests.txt
 cat $OUT/gpu_tests.txt
 timeout 200 python -c "import __graft_entry__ as g; g.smoke(); print('smoke OK')" 2>&1 | tail -3 | tee $OUT/smoke.txt
-timeout 600 python bench.py > $OUT/bench.json 2> $OUT/bench.err
+timeout 600 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 tail -c 600 $OUT/bench.json
 for rep in 1 2; do timeout 200 python tools/bench_vae.py 8192 1 2>&1 | grep -v amdgpu; done | tee $OUT/vae.txt
 timeout 200 python tools/bench_vae.py 6144 1 2>&1 | grep -v amdgpu | tee -a $OUT/vae.txt
