@@ -41,7 +41,9 @@ enum {
   L2HMC_ENERGY_GAUSS_DENSE = 2, /* Gaussian, dense precision      distributions.py:41-57,31-32 */
   L2HMC_ENERGY_GMM = 3,         /* mixture of Gaussians           distributions.py:104-134     */
   L2HMC_ENERGY_ROUGHWELL = 4,   /* rough well                     distributions.py:84-97       */
-  L2HMC_ENERGY_FUNNEL = 5       /* Gaussian funnel                distributions.py:155-180     */
+  L2HMC_ENERGY_FUNNEL = 5,      /* Gaussian funnel                distributions.py:155-180     */
+  /* (6 is the Python binding's tag of the VAE decoder posterior, which runs on the GEMM engine) */
+  L2HMC_ENERGY_LOGISTIC = 7     /* Bayesian logistic regression   (l2hmc_pack_logistic)        */
 };
 
 /* One S/T/Q network in the reference's own parameter layout: `Linear` keeps W as
@@ -67,6 +69,14 @@ typedef struct L2hmcNet {
  *                that holds the caller's double passes float(eps * eps); 0 = derive from the float `eta`
  *                (identical whenever eps is exactly a float; last-bit different for e.g. eps = 0.1)
  *   FUNNEL     : eta = sigma (distributions.py:155-180; clip = 4 sigma)
+ *   LOGISTIC   : Bayesian logistic regression on n data rows x_i (d features) with labels y_i in {0, 1} and a N(0, sigma^2 I)
+ *                prior:  U(w) = sum_i [softplus(x_i . w) - y_i x_i . w] + |w|^2 / (2 sigma^2),
+ *                        grad U = X^T (sigmoid(X w) - y) + w / sigma^2;
+ *                n_comp = n (>= 1), mu = the buffer written by l2hmc_pack_logistic, eta = sigma^2 (> 0), prec = logc = NULL
+ *                (ignored), easy = 0 (ignored).  d <= 128.  Runs on the general trajectory kernel (and its ladder, energy and
+ *                p_accept forms) only -- `variant` 8, 16, 32 return L2HMC_ERR_UNSUPPORTED; the training entry points return
+ *                L2HMC_ERR_UNSUPPORTED for it.  The packed data is staged in LDS when it fits, else streamed from L2
+ *                (L2HMC_LOGISTIC_LDS=0 in the environment: always streamed)
  * temperature divides U and grad U (dynamics.py:204-212); 1.0 when unused.
  * anneal_beta in (0, 1): the AIS bridge of utils/ais.py:46-47 with the standard-normal initial
  * energy its caller uses (eval_vae.py:55-56):  U := (1 - beta) |x|^2 / 2 + beta U(x);  0 (or 1) = off. */
@@ -218,6 +228,15 @@ int64_t l2hmc_packed_gaussian_floats(int32_t d);
 /* i_sigma: (d, d) fp32 precision matrix `Gaussian.i_sigma.astype('float32')`
  * (distributions.py:48,52); packs (S + S^T)/2 in fragment order. */
 int l2hmc_pack_gaussian(const float* i_sigma, int32_t d, float* packed, void* stream);
+
+/* Bayesian logistic regression data (L2HMC_ENERGY_LOGISTIC) in the order the kernels read it: X (n_data, d) row-major and
+ * y (n_data) in {0, 1}, both device float32, padded to 16-row blocks.  Per block the rows as the A operand of the logits
+ * X w (contraction over the d features), the same rows as the A operand of the gradient X^T r (contraction over the rows),
+ * then the block's 16 labels; rows beyond n_data are zero and the kernels mask them by n_comp = n_data (they would
+ * otherwise add softplus(0) = log 2 each).  Run once per data set.  L2HMC_ERR_ARG: n_data < 1 or > 1048576, d outside
+ * 1 ... 128, a NULL buffer. */
+int64_t l2hmc_packed_logistic_floats(int32_t n_data, int32_t d);
+int l2hmc_pack_logistic(const float* X, const float* y, int32_t n_data, int32_t d, float* packed, void* stream);
 
 /* The fused generalised-leapfrog trajectory:
  *   Dynamics.forward / .backward           dynamics.py:246-300  (n_steps = T)

@@ -10,6 +10,8 @@ from .dynamics import Dynamics  # noqa: F401
 from .sampler import chain_operator, propose, sample_chain, tf_accept  # noqa: F401
 from . import tempering  # noqa: F401
 from .tempering import ParallelTempering, geometric_ladder  # noqa: F401
+from .distributions import LogisticRegression  # noqa: F401
 
 __all__ = ["Dynamics", "propose", "tf_accept", "chain_operator", "sample_chain", "ParallelTempering", "geometric_ladder",
+           "LogisticRegression",
            "layers", "distributions", "func_utils", "losses", "tempering"]

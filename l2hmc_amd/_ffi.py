@@ -13,6 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.abspath(os.environ["L2HMC_LIB"]) if os.environ.get("L2HMC_LIB") else os.path.join(_HERE, "csrc", "libl2hmc_hip.so")
 
 ENERGY_GAUSS_DIAG, ENERGY_GAUSS_DENSE, ENERGY_GMM, ENERGY_ROUGHWELL, ENERGY_FUNNEL = 1, 2, 3, 4, 5
+ENERGY_LOGISTIC = 7       # Bayesian logistic regression (6 is vae.ENERGY_VAE, the Python-side tag of the decoder posterior)
 
 _fp = C.c_void_p  # device pointers travel as integers
 
@@ -135,6 +136,8 @@ SYMBOLS = {
                                   _fp, _fp]),
     "l2hmc_packed_gaussian_floats": (C.c_int64, [C.c_int32]),
     "l2hmc_pack_gaussian": (C.c_int, [_fp, C.c_int32, _fp, _fp]),
+    "l2hmc_packed_logistic_floats": (C.c_int64, [C.c_int32, C.c_int32]),
+    "l2hmc_pack_logistic": (C.c_int, [_fp, _fp, C.c_int32, C.c_int32, _fp, _fp]),
     "l2hmc_trajectory": (C.c_int, [C.POINTER(L2hmcTrajectoryArgs), _fp]),
     "l2hmc_trajectory_ladder": (C.c_int, [C.POINTER(L2hmcTrajectoryArgs), C.POINTER(L2hmcLadderArgs), _fp]),
     "l2hmc_energy": (C.c_int, [C.POINTER(L2hmcEnergy), _fp, C.c_int64, C.c_int32, _fp, _fp, _fp]),

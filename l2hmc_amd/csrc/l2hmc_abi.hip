@@ -128,6 +128,26 @@ __global__ void pack_gauss_kernel(const float* S, int d, int NT, float* out) {
   out[idx] = (a < d && b < d) ? 0.5f * (S[a * d + b] + S[b * d + a]) : 0.f;
 }
 
+// logistic-regression data in fragment order (l2hmc_pack_logistic; layout at logistic_block_floats): thread = one float
+__global__ void pack_logistic_kernel(const float* X, const float* y, int n, int d, int NT, long long total, float* out) {
+  const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= total) return;
+  const int BS = logistic_block_floats(NT);
+  const int ib = (int)(idx / BS), o = (int)(idx % BS);
+  float val = 0.f;
+  if (o < 512 * NT) {
+    const int tr = o < 256 * NT, oo = tr ? o : o - 256 * NT;       // XA groups, then XT groups
+    const int tg = oo >> 8, lane = (oo >> 2) & 63, r = oo & 3;
+    const int i = tr ? 16 * ib + (lane & 15) : 16 * ib + 4 * (lane >> 4) + r;
+    const int k = tr ? 16 * tg + 4 * (lane >> 4) + r : 16 * tg + (lane & 15);
+    if (i < n && k < d) val = X[(long long)i * d + k];
+  } else {
+    const int i = 16 * ib + (o - 512 * NT);
+    if (i < n) val = y[i];
+  }
+  out[idx] = val;
+}
+
 // sum 1 / v and sum v in double: one workgroup, fixed order (thread t takes elements t, t + 256, ...; butterfly inside each
 // wave, the four wave sums added in wave order: one barrier)
 __global__ __launch_bounds__(256) void loss_terms_kernel(const float* v1, long long n, float scale, double inv_n, double* out3) {
@@ -319,7 +339,8 @@ long long plan_lds(KArgs& k, bool with_nets, bool with_schedule, int NW, int DT)
   if (NW > 1) o += 2LL * NW * 256;       // 2 buffers x NW waves x 1 partial vector
   k.xb_stride = DP + 4;
   k.o_XB = (int)o;
-  if (NW > 1 && (k.ekind == L2HMC_ENERGY_GAUSS_DENSE || k.ekind == L2HMC_ENERGY_GMM))
+  const bool lr = k.ekind == L2HMC_ENERGY_LOGISTIC;
+  if (NW > 1 && (k.ekind == L2HMC_ENERGY_GAUSS_DENSE || k.ekind == L2HMC_ENERGY_GMM || lr))
     o += 16LL * k.xb_stride;
   k.o_red = (int)o;
   o += (long long)NW * 16 * 8;
@@ -330,8 +351,20 @@ long long plan_lds(KArgs& k, bool with_nets, bool with_schedule, int NW, int DT)
   if (k.ekind == L2HMC_ENERGY_GAUSS_DIAG) o += DP;
   if ((k.ekind == L2HMC_ENERGY_GAUSS_DENSE || k.ekind == L2HMC_ENERGY_GMM) && !wg)
     o += (long long)nc * gauss_floats(NT);
+  if (lr && NW > 1) o += (long long)NW * NT * 256;      // logistic regression: every wave's partial gradient of all tiles
   k.o_logc = (int)o;
   o += round4(nc);
+  if (lr) {
+    // the data fragments staged in LDS when they fit beside everything else (the ladder's tables included), else streamed
+    // from L2 by every gradient; L2HMC_LOGISTIC_LDS=0 in the environment always streams (read per call: tests run both paths)
+    const long long need = logistic_floats(k.ncomp, k.d);
+    const char* env = getenv("L2HMC_LOGISTIC_LDS");
+    k.easy = !(env != nullptr && env[0] == '0') && (o + need + kLadLds) * 4 <= kMaxLdsBytes;
+    if (k.easy) {
+      k.o_mu = (int)o;
+      o += need;
+    }
+  }
   return o * 4;
 }
 
@@ -400,6 +433,14 @@ int check_energy(const L2hmcEnergy* e, int d) {
     case L2HMC_ENERGY_FUNNEL:
       if (!(e->eta > 0.f) || d < 2) return fail(L2HMC_ERR_ARG, "funnel needs sigma > 0 and d >= 2%s");
       break;
+    case L2HMC_ENERGY_LOGISTIC:
+      if (!e->mu) return fail(L2HMC_ERR_ARG, "logistic regression needs the packed data (mu, l2hmc_pack_logistic)%s");
+      if (e->n_comp < 1 || e->n_comp > kLogisticMaxRows)
+        return fail(L2HMC_ERR_ARG, "logistic regression needs 1 <= n_comp = n_data <= 1048576 (got %s%lld)", "", e->n_comp);
+      if (d > kLogisticMaxDim) return fail(L2HMC_ERR_ARG, "logistic regression supports d <= 128 (got %s%lld)", "", d);
+      if (!(e->eta > 0.f) || !(e->eta <= 3.402823466e38f))
+        return fail(L2HMC_ERR_ARG, "logistic regression needs eta = prior variance sigma^2 > 0 and finite%s");
+      break;
     default:
       return fail(L2HMC_ERR_ARG, "unknown energy kind %s%lld", "", e->kind);
   }
@@ -410,8 +451,8 @@ int check_energy(const L2hmcEnergy* e, int d) {
 
 void fill_energy(KArgs& k, const L2hmcEnergy* e) {
   k.ekind = e->kind;
-  k.ncomp = e->kind == L2HMC_ENERGY_GMM ? e->n_comp : 1;
-  k.easy = e->easy;
+  k.ncomp = (e->kind == L2HMC_ENERGY_GMM || e->kind == L2HMC_ENERGY_LOGISTIC) ? e->n_comp : 1;
+  k.easy = e->kind == L2HMC_ENERGY_LOGISTIC ? 0 : e->easy;     // (logistic regression: "staged in LDS", set by plan_lds)
   k.mu = e->mu;
   k.prec = e->prec;
   k.logc = e->logc;
@@ -456,6 +497,23 @@ bool pick_geometry(int d, long long N, int v, int& DT, int& NW, int cus = 0) {
   return NT <= 32;
 }
 
+// Logistic regression: four waves per 16-chain tile, 1 or 2 state tiles each -- the data contractions dominate the kernel and its
+// waves split the data blocks among themselves (one wave per tile would stream all of X alone).  Geometry v = 1 (variant 101):
+// one wave, d <= 16 only (wider one-wave forms carry 2-4 tiles of state next to the contraction's fragments and spill).
+bool pick_geometry_logistic(int d, int v, int& DT, int& NW) {
+  if (d > kLogisticMaxDim || (v != 0 && v != 1 && v != 4)) return false;
+  DT = tiles_of(d) <= 4 ? 1 : 2;
+  NW = 4;
+  if (v == 1) {
+    DT = NW = 1;
+    return tiles_of(d) <= 1;
+  }
+  return v == 0 || DT == 1;
+}
+bool pick_geometry_of(int ekind, int d, long long N, int v, int& DT, int& NW, int cus = 0) {
+  return ekind == L2HMC_ENERGY_LOGISTIC ? pick_geometry_logistic(d, v, DT, NW) : pick_geometry(d, N, v, DT, NW, cus);
+}
+
 // The environment's overrides of the selection rules, read at the top of every l2hmc_trajectory call (and nowhere else).
 struct EnvOverrides {
   bool f32_mfma;   // L2HMC_F32_MFMA=1: every trajectory on the f32-input MFMA, as variant 200 + v does per call (read once per process)
@@ -495,7 +553,7 @@ static Variant decode_variant(int variant, bool env_f32) {
 
 // geometry v for the register-resident kernels
 static int plan_geometry(const L2hmcTrajectoryArgs& a, const Variant& v, int cus, TrajPlan& p) {
-  if (!pick_geometry(a.d, a.n_chains, v.geom, p.DT, p.NW, cus))
+  if (!pick_geometry_of(a.energy.kind, a.d, a.n_chains, v.geom, p.DT, p.NW, cus))
     return fail(L2HMC_ERR_UNSUPPORTED, "d = %s%lld not supported with variant %lld", "", a.d, v.value);
   return L2HMC_OK;
 }
@@ -515,6 +573,17 @@ static int plan_trajectory(const L2hmcTrajectoryArgs& a, KArgs& k, int KH, int c
   p.KH = KH <= 3 ? 3 : 4;
   const bool nets = a.packed_nets != nullptr, has_u = a.u != nullptr || (a.rng_flags & L2HMC_RNG_U);
   const bool plain = k.beta == 1.f && k.temperature == 1.f;     // neither tempered nor annealed
+  // logistic regression: the general kernel only (the data contractions live in its grad U)
+  const bool lr = k.ekind == L2HMC_ENERGY_LOGISTIC;
+  if (lr && (v.forced == FAM_LANE || v.forced == FAM_WIDE || v.forced == FAM_TILE))
+    return fail(L2HMC_ERR_UNSUPPORTED, "variant %s%lld: the logistic-regression target runs on the general kernel only (variant 0 or 100 + v)",
+                "", v.value);
+  if (lr) {
+    int rc = plan_geometry(a, v, cus, p);
+    if (rc) return rc;
+    plan_general(a, k, p);
+    return L2HMC_OK;
+  }
   // One chain per lane (traj_lane.hpp): when the chains alone fill the chip -- a wave is 64 of them -- the padding-free
   // VALU form beats the MFMA tiles (variant 32 forces it: tests).  Measured (tools/bench_lane.py): d <= 2 from 65 536
   // chains, d <= 4 from 131 072; wider states lose to the scalar-load latency of their larger nets.
@@ -654,7 +723,7 @@ static int launch_plan(const TrajPlan& p, const KArgs& k, hipStream_t s, const L
   return on_energy_kind(p.ek, [&](auto ek) {
     constexpr int EK = decltype(ek)::value;
     if (p.family == FAM_LADDER) return launch_ladder_ek<EK>(p, k, *lg, s);
-    if constexpr (EK != L2HMC_ENERGY_FUNNEL) {
+    if constexpr (EK != L2HMC_ENERGY_FUNNEL && EK != L2HMC_ENERGY_LOGISTIC) {
       if (p.family == FAM_LANE) return launch_lane_ek<EK>(p, k, s);
       if (p.family == FAM_WIDE) return launch_wide_ek<EK>(p, k, s);
     }
@@ -751,6 +820,23 @@ int l2hmc_pack_gaussian(const float* i_sigma, int32_t d, float* packed, void* st
   const int NT = tiles_of(d), n = gauss_floats(NT);
   hipLaunchKernelGGL(pack_gauss_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream,
                      i_sigma, d, NT, packed);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(L2HMC_ERR_HIP, "pack launch: %s", hipGetErrorString(e));
+  return L2HMC_OK;
+}
+
+int64_t l2hmc_packed_logistic_floats(int32_t n_data, int32_t d) {
+  if (n_data < 1 || n_data > kLogisticMaxRows) return fail(L2HMC_ERR_ARG, "logistic regression: 1 <= n_data <= 1048576 (got %s%lld)", "", n_data);
+  if (d < 1 || d > kLogisticMaxDim) return fail(L2HMC_ERR_ARG, "logistic regression: 1 <= d <= 128 (got %s%lld)", "", d);
+  return logistic_floats(n_data, d);
+}
+
+int l2hmc_pack_logistic(const float* X, const float* y, int32_t n_data, int32_t d, float* packed, void* stream) {
+  const int64_t n = l2hmc_packed_logistic_floats(n_data, d);
+  if (n < 0) return (int)n;
+  if (!X || !y || !packed) return fail(L2HMC_ERR_ARG, "l2hmc_pack_logistic: NULL argument%s");
+  hipLaunchKernelGGL(pack_logistic_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, X, y, n_data, d,
+                     tiles_of(d), (long long)n, packed);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(L2HMC_ERR_HIP, "pack launch: %s", hipGetErrorString(e));
   return L2HMC_OK;
@@ -928,7 +1014,7 @@ int l2hmc_energy(const L2hmcEnergy* energy, const float* x, int64_t n_chains, in
   if (rc) return rc;
   TrajPlan p;
   p.family = FAM_ENERGY;
-  if (!pick_geometry(d, n_chains, 0, p.DT, p.NW)) return fail(L2HMC_ERR_UNSUPPORTED, "d = %s%lld too large", "", d);
+  if (!pick_geometry_of(energy->kind, d, n_chains, 0, p.DT, p.NW)) return fail(L2HMC_ERR_UNSUPPORTED, "d = %s%lld too large", "", d);
   KArgs k;
   memset(&k, 0, sizeof(k));
   k.N = n_chains; k.d = d; k.NT = tiles_of(d); k.x = x; k.U_out = U_out; k.grad_out = grad_out;
@@ -948,7 +1034,7 @@ int l2hmc_p_accept(const L2hmcEnergy* energy, const float* x0, const float* v0, 
   if (rc) return rc;
   TrajPlan p;
   p.family = FAM_PACCEPT;
-  if (!pick_geometry(d, n_chains, 0, p.DT, p.NW)) return fail(L2HMC_ERR_UNSUPPORTED, "d = %s%lld too large", "", d);
+  if (!pick_geometry_of(energy->kind, d, n_chains, 0, p.DT, p.NW)) return fail(L2HMC_ERR_UNSUPPORTED, "d = %s%lld too large", "", d);
   KArgs k;
   memset(&k, 0, sizeof(k));
   k.N = n_chains; k.d = d; k.NT = tiles_of(d);

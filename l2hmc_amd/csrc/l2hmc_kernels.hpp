@@ -91,6 +91,17 @@ __host__ __device__ inline int gauss_floats(int NT) { return NT * NT * 256; }
 __host__ __device__ inline int net_f16_floats(int NT) { return net_groups(NT) * 512; }
 
 inline int tiles_of(int d) { return (d + 15) / 16; }
+
+// Bayesian logistic regression (L2HMC_ENERGY_LOGISTIC), packed by l2hmc_pack_logistic: per 16-row data block ib,
+// logistic_block_floats(NT) floats --
+//   NT groups "XA", lane (i, q), k-step r:  X[16 ib + i][16 tg + 4 q + r]   A operand of the logits L^T = X w^T (over features)
+//   NT groups "XT", lane (k, q), k-step r:  X[16 ib + 4 q + r][16 tg + k]   A operand of the gradient g^T = X^T r (over rows)
+//   the block's 16 labels
+// Rows beyond n_data are zero (and masked by the kernels: each would add softplus(0) = log 2 to U).
+constexpr int kLogisticMaxRows = 1 << 20;
+constexpr int kLogisticMaxDim = 128;      // the general kernel's register-resident geometries (NW * DT <= 8 tiles)
+__host__ __device__ inline int logistic_block_floats(int NT) { return 512 * NT + 16; }
+inline long long logistic_floats(int n, int d) { return (long long)((n + 15) / 16) * logistic_block_floats(tiles_of(d)); }
 inline int khid_of(int H) { return (H + 1 + 3) / 4; }
 
 // ------------------------------------------------------------------------------------------
@@ -114,7 +125,8 @@ struct KArgs {
   unsigned rng_flags;        // L2HMC_RNG_*: which draws come from the in-kernel Philox
   unsigned long long rng_seed, rng_prop0;
   long long chain_off;
-  // energy
+  // energy (logistic regression: mu = the packed data (global), ncomp = n_data, eta = sigma^2, easy = 1 when the data is
+  // staged in LDS at o_mu; o_XB / o_prec: the state and gradient exchanges between the waves)
   int ekind, ncomp, easy;
   const float *mu, *prec, *logc;
   float eta, temperature;
@@ -462,6 +474,103 @@ __device__ __forceinline__ void load_energy_regs(EnergyRegs<EK, DT>& er, const K
   }
 }
 
+// Bayesian logistic regression: grad U = X^T (sigmoid(X w) - y) + w / sigma^2 for the 16 chains of the tile (S-layout), and this
+// lane's share of U's data term.  Two f32-input MFMA contractions per 16-row data block, no cross-lane traffic between them:
+//   logits    L^T[i, c] = sum_k XA[i, k] x^T[k, c]  -- the state tiles are the B operand, as for a net layer; the result is in
+//             C/D layout, lane (c, q) holding rows 16 ib + 4 q + r,
+//   gradient  g^T[k, c] += sum_i XT[k, i] r^T[i, c] -- and that C/D layout of the residuals r = sigmoid(L) - y is exactly the
+//             B operand (k-step r = row 4 q + r) of this contraction.
+// Wave w takes the data blocks w, w + NW, ... over ALL NT state tiles: with NW > 1 the state goes to LDS first (the exchange of
+// dense_matvec), and every wave's partial gradient of all tiles comes back through LDS, summed over the waves in wave order.
+// STAGED: the fragments are read from LDS (staged by stage_energy), else streamed from global memory / L2.
+template <int DT, int NW, bool STAGED>
+__device__ __forceinline__ float logistic_grad(const KArgs& A, float* smem, int w, int lane, const f4 (&x)[DT], f4 (&g)[DT],
+                                               bool wantU) {
+  constexpr int NTM = NW * DT;              // compiled tiles (>= A.NT)
+  const int NT = A.NT, n = A.ncomp, nblk = (n + 15) >> 4, BS = logistic_block_floats(NT);
+  const int c = lane & 15, q = lane >> 4;
+  const float* P;
+  if constexpr (STAGED) P = smem + A.o_mu;
+  else P = A.mu;
+  const float* XB = smem + A.o_XB;
+  if constexpr (NW > 1) {
+#pragma unroll
+    for (int t = 0; t < DT; ++t) {
+      const int tg = w * DT + t;
+      if (tg < NT) *reinterpret_cast<f4*>(smem + A.o_XB + c * A.xb_stride + 16 * tg + 4 * q) = x[t];
+    }
+    __syncthreads();
+  }
+  f4 gp[NTM];
+#pragma unroll
+  for (int tg = 0; tg < NTM; ++tg) gp[tg] = splat(0.f);
+  float Ud = 0.f;
+  for (int ib = NW > 1 ? w : 0; ib < nblk; ib += NW) {
+    const float* blk = P + (size_t)ib * BS;
+    f4 xa[NTM], xt[NTM];
+#pragma unroll
+    for (int tg = 0; tg < NTM; ++tg) {
+      xa[tg] = tg < NT ? lds4(blk + (tg * 64 + lane) * 4) : splat(0.f);
+      xt[tg] = tg < NT ? lds4(blk + ((NT + tg) * 64 + lane) * 4) : splat(0.f);
+    }
+    const f4 y = lds4(blk + 512 * NT + 4 * q);
+    f4 L = splat(0.f);
+#pragma unroll
+    for (int tg = 0; tg < NTM; ++tg) {
+      if (tg < NT) {
+        // the state as the B operand: this wave's own registers, or (NW > 1) the exchanged tile
+        f4 B;
+        if constexpr (NW > 1) B = lds4(XB + c * A.xb_stride + 16 * tg + 4 * q);
+        else B = x[tg];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) L = MFMA16(xa[tg][r], B[r], L);
+      }
+    }
+    // r = sigmoid(L) - y with e = exp(-|L|): sigmoid = 1 / (1 + e) (L >= 0) or e / (1 + e); softplus(L) = max(L, 0) + log(1 + e)
+    const int row0 = 16 * ib + 4 * q;
+    f4 res;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const float l = L[r];
+      const float e = fexp(-fabsf(l));
+      const float inv = __builtin_amdgcn_rcpf(1.f + e);
+      const float sg = l >= 0.f ? inv : e * inv;
+      const bool live = row0 + r < n;
+      res[r] = live ? sg - y[r] : 0.f;
+      if (wantU) Ud += live ? fmaf(-y[r], l, fmaxf(l, 0.f) + 0.6931471805599453f * __builtin_amdgcn_logf(1.f + e)) : 0.f;
+    }
+#pragma unroll
+    for (int tg = 0; tg < NTM; ++tg) {
+      if (tg < NT) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) gp[tg] = MFMA16(xt[tg][r], res[r], gp[tg]);
+      }
+    }
+  }
+  if constexpr (NW == 1) {
+#pragma unroll
+    for (int t = 0; t < DT; ++t) g[t] = gp[t];
+  } else {
+    // (the previous call's reads of this area finished before every wave passed the state exchange's barrier above)
+    float* PX = smem + A.o_prec;
+#pragma unroll
+    for (int tg = 0; tg < NTM; ++tg)
+      if (tg < NT) *reinterpret_cast<f4*>(PX + ((w * NT + tg) * 64 + lane) * 4) = gp[tg];
+    __syncthreads();
+#pragma unroll
+    for (int t = 0; t < DT; ++t) {
+      const int tg = w * DT + t;
+      f4 sum = splat(0.f);
+      if (tg < NT) {
+#pragma unroll
+        for (int ww = 0; ww < NW; ++ww) sum += lds4(PX + ((ww * NT + tg) * 64 + lane) * 4);
+      }
+      g[t] = sum;
+    }
+  }
+  return Ud;
+}
+
 // LAD (ladder mode): the temperature is this lane's chain's rung temperature `temp`, divided in exactly as the scalar path divides
 // by A.temperature (so equal rungs give the scalar path's bits), and `Uraw` receives this lane's share of the untempered U.
 template <int EK, int DT, int NW, bool LAD = false>
@@ -583,6 +692,17 @@ __device__ __forceinline__ void grad_energy(const KArgs& A, float* smem, int w, 
         g[0].x = gv;
         const float lp = (vv / sigma) * (vv / sigma);
         U = 0.5f * (lp + sum_sq / s_eff + n * logf(6.283185307179586f * s_eff));
+      }
+    }
+  } else if constexpr (EK == L2HMC_ENERGY_LOGISTIC) {
+    {
+      // data term (the NLL of the labels), then the N(0, sigma^2 I) prior; padded dimensions hold x = 0 and add nothing
+      U = A.easy ? logistic_grad<DT, NW, true>(A, smem, w, lane, x, g, wantU) : logistic_grad<DT, NW, false>(A, smem, w, lane, x, g, wantU);
+      const float iv = 1.f / A.eta;
+#pragma unroll
+      for (int t = 0; t < DT; ++t) {
+        U += 0.5f * iv * hsum(x[t] * x[t]);
+        g[t] = g[t] + x[t] * iv;
       }
     }
   } else {
@@ -881,6 +1001,13 @@ __device__ __forceinline__ void stage_energy(const KArgs& A, float* smem, int ti
     }
     if (EK == L2HMC_ENERGY_GMM)
       for (int i = tid; i < nc; i += nthr) smem[A.o_logc + i] = A.logc[i];
+  } else if (EK == L2HMC_ENERGY_LOGISTIC) {
+    if (A.easy) {
+      const int n4 = ((A.ncomp + 15) >> 4) * logistic_block_floats(A.NT) / 4;
+      const f4* src = reinterpret_cast<const f4*>(A.mu);
+      f4* dst = reinterpret_cast<f4*>(smem + A.o_mu);
+      for (int i = tid; i < n4; i += nthr) dst[i] = src[i];
+    }
   }
 }
 
@@ -898,8 +1025,12 @@ enum { LAD_TEMP = 0, LAD_U = 16, LAD_LAB = 32, LAD_INV = 48, LAD_TRIP = 64, LAD_
 #ifndef L2HMC_WAVES_PER_SIMD
 #define L2HMC_WAVES_PER_SIMD 2
 #endif
+// (logistic regression keeps all 512 at every DT: its data contractions hold the state of every tile of the workgroup, the
+//  prefetched fragments and the partial gradients on top of the trajectory's registers -- under the 256 cap they spilled)
+template <int EK, int DT>
+constexpr int traj_waves_per_simd() { return (DT <= 2 && EK != L2HMC_ENERGY_LOGISTIC) ? L2HMC_WAVES_PER_SIMD : 1; }
 template <int EK, int DT, int NW, int KH>
-__global__ __launch_bounds__(64 * NW, (DT <= 2 ? L2HMC_WAVES_PER_SIMD : 1)) void traj_kernel(const KArgs A) {
+__global__ __launch_bounds__(64 * NW, (traj_waves_per_simd<EK, DT>())) void traj_kernel(const KArgs A) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   lds_poison(smem);
   constexpr bool LAD = false;
@@ -911,7 +1042,7 @@ __global__ __launch_bounds__(64 * NW, (DT <= 2 ? L2HMC_WAVES_PER_SIMD : 1)) void
 // one 16-chain tile.  Proposal m runs at the temperature of the row's current rung; after every M-th proposal the tile's
 // raw energies go to LDS and one lane per ladder runs the even-odd swap sweep, which relabels rows -- no state moves.
 template <int EK, int DT, int NW, int KH>
-__global__ __launch_bounds__(64 * NW, (DT <= 2 ? L2HMC_WAVES_PER_SIMD : 1)) void traj_ladder_kernel(const KArgs A, const LadArgs Lk) {
+__global__ __launch_bounds__(64 * NW, (traj_waves_per_simd<EK, DT>())) void traj_ladder_kernel(const KArgs A, const LadArgs Lk) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   lds_poison(smem);
   constexpr bool LAD = true;
@@ -1022,7 +1153,7 @@ template <auto V> using ic = std::integral_constant<decltype(V), V>;
 template <auto A, auto B, class F>
 int on_either(bool first, F&& f) { return first ? f(ic<A>{}) : f(ic<B>{}); }
 
-// f(ic<EK>) for a built-in energy kind (L2HMC_ENERGY_GAUSS_DIAG = 1 ... L2HMC_ENERGY_FUNNEL = 5)
+// f(ic<EK>) for a built-in energy kind (L2HMC_ENERGY_GAUSS_DIAG = 1 ... L2HMC_ENERGY_FUNNEL = 5, L2HMC_ENERGY_LOGISTIC = 7)
 template <class F>
 int on_energy_kind(int ek, F&& f) {
   switch (ek) {
@@ -1031,6 +1162,7 @@ int on_energy_kind(int ek, F&& f) {
     case 3: return f(ic<3>{});
     case 4: return f(ic<4>{});
     case 5: return f(ic<5>{});
+    case 7: return f(ic<7>{});
   }
   return fail(L2HMC_ERR_ARG, "unknown energy kind%s");
 }
@@ -1039,6 +1171,8 @@ int on_energy_kind(int ek, F&& f) {
 template <int DT_, int NW_> struct Geom { static constexpr int DT = DT_, NW = NW_; };
 template <class... G> struct Geoms {};
 using GeneralGeoms = Geoms<Geom<1, 1>, Geom<2, 1>, Geom<4, 1>, Geom<1, 4>, Geom<2, 4>, Geom<4, 4>, Geom<8, 4>>;
+// logistic regression (d <= 128): four waves with one or two state tiles each, and one wave for d <= 16 (variant 101)
+using LogisticGeoms = Geoms<Geom<1, 1>, Geom<1, 4>, Geom<2, 4>>;
 using FastGeoms = Geoms<Geom<1, 1>, Geom<2, 1>, Geom<1, 4>, Geom<2, 4>, Geom<2, 2>>;
 
 // f(ic<DT>, ic<NW>) for the geometry of the set; `what` names the kernel in the refusal ("" or "fast ")

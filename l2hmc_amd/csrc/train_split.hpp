@@ -797,6 +797,9 @@ int l2hmc_train_split_grad(const L2hmcTrainSplitArgs* a, void* stream) {
       return fail(L2HMC_ERR_UNSUPPORTED, "a built-in energy excludes decoder / aux_encoder / aux%s");
     if ((rc = check_energy(a->energy, d))) return rc;
     const int ek = a->energy->kind;
+    if (ek == L2HMC_ENERGY_LOGISTIC)
+      return fail(L2HMC_ERR_UNSUPPORTED, "no training on the logistic-regression target (its Hessian-vector products are not "
+                  "implemented): train on the same likelihood as a caller-supplied energy%s");
     if ((ek == L2HMC_ENERGY_GAUSS_DENSE || ek == L2HMC_ENERGY_GMM) && !a->hess)
       return fail(L2HMC_ERR_ARG, "dense Gaussian / mixture: hess = the RAW (n_comp, d, d) precisions%s");
     if (ek == L2HMC_ENERGY_GMM && a->energy->n_comp > HVP_MAXC)

@@ -13,19 +13,31 @@ int launch_tiles(K kern, int NW, const TrajPlan& p, const KArgs& k, hipStream_t 
   return launch_kernel(kern, (k.N + 15) / 16, 64 * NW, p.lds, s, k, extra...);
 }
 
+// the general kernel's geometries for energy kind EK (logistic regression: d <= 128, at most 8 tiles per workgroup)
+template <int EK>
+using GeneralGeomsOf = std::conditional_t<EK == L2HMC_ENERGY_LOGISTIC, LogisticGeoms, GeneralGeoms>;
+
 template <int EK>
 int launch_ek(const TrajPlan& p, const KArgs& k, hipStream_t s) {
+  // (logistic regression: the general, energy and p_accept kernels only -- no instruction-lean or small-d form)
+  if constexpr (EK == L2HMC_ENERGY_LOGISTIC) {
+    if (p.family != FAM_GENERAL && p.family != FAM_ENERGY && p.family != FAM_PACCEPT)
+      return fail(L2HMC_ERR_UNSUPPORTED, "the logistic-regression target runs on the general kernel only%s");
+  }
   switch (p.family) {
     case FAM_GENERAL:
-      return on_geometry(GeneralGeoms{}, p.DT, p.NW, "", [&](auto DT, auto NW) {
+      return on_geometry(GeneralGeomsOf<EK>{}, p.DT, p.NW, "", [&](auto DT, auto NW) {
         return on_either<3, 4>(p.KH == 3, [&](auto KH) { return launch_tiles(traj_kernel<EK, DT, NW, KH>, NW, p, k, s); });
       });
     case FAM_FAST:
-      return on_geometry(FastGeoms{}, p.DT, p.NW, "fast ", [&](auto DT, auto NW) {
-        return on_either<3, 4>(p.KH == 3, [&](auto KH) { return launch_tiles(traj_fast_kernel<EK, DT, NW, KH>, NW, p, k, s); });
-      });
+      if constexpr (EK != L2HMC_ENERGY_LOGISTIC) {     // (refused above: not instantiated)
+        return on_geometry(FastGeoms{}, p.DT, p.NW, "fast ", [&](auto DT, auto NW) {
+          return on_either<3, 4>(p.KH == 3, [&](auto KH) { return launch_tiles(traj_fast_kernel<EK, DT, NW, KH>, NW, p, k, s); });
+        });
+      }
+      break;
     case FAM_SMALL:
-      if constexpr (EK == L2HMC_ENERGY_FUNNEL) {
+      if constexpr (EK == L2HMC_ENERGY_FUNNEL || EK == L2HMC_ENERGY_LOGISTIC) {
         return fail(L2HMC_ERR_UNSUPPORTED, "no small-d kernel for the funnel%s");
       } else {
         return on_either<3, 4>(p.KH == 3, [&](auto KH) {
@@ -33,9 +45,9 @@ int launch_ek(const TrajPlan& p, const KArgs& k, hipStream_t s) {
         });
       }
     case FAM_ENERGY:
-      return on_geometry(GeneralGeoms{}, p.DT, p.NW, "", [&](auto DT, auto NW) { return launch_tiles(energy_kernel<EK, DT, NW>, NW, p, k, s); });
+      return on_geometry(GeneralGeomsOf<EK>{}, p.DT, p.NW, "", [&](auto DT, auto NW) { return launch_tiles(energy_kernel<EK, DT, NW>, NW, p, k, s); });
     case FAM_PACCEPT:
-      return on_geometry(GeneralGeoms{}, p.DT, p.NW, "", [&](auto DT, auto NW) { return launch_tiles(paccept_kernel<EK, DT, NW>, NW, p, k, s); });
+      return on_geometry(GeneralGeomsOf<EK>{}, p.DT, p.NW, "", [&](auto DT, auto NW) { return launch_tiles(paccept_kernel<EK, DT, NW>, NW, p, k, s); });
   }
   return fail(L2HMC_ERR_UNSUPPORTED, "no kernel for this plan%s");
 }
@@ -49,7 +61,7 @@ int launch_fast16_ek(const TrajPlan& p, const KArgs& k, hipStream_t s) {
 
 template <int EK>
 int launch_ladder_ek(const TrajPlan& p, const KArgs& k, const LadArgs& l, hipStream_t s) {
-  return on_geometry(GeneralGeoms{}, p.DT, p.NW, "", [&](auto DT, auto NW) {
+  return on_geometry(GeneralGeomsOf<EK>{}, p.DT, p.NW, "", [&](auto DT, auto NW) {
     return on_either<3, 4>(p.KH == 3, [&](auto KH) { return launch_tiles(traj_ladder_kernel<EK, DT, NW, KH>, NW, p, k, s, l); });
   });
 }

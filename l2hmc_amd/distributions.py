@@ -162,6 +162,73 @@ class UserEnergy(EnergyFunction):
         return self.evaluate(x, aux=aux)[0].to(torch.float32)
 
 
+class LogisticEnergy(EnergyFunction):
+    """U(w) = sum_i [softplus(x_i . w) - y_i x_i . w] + |w|^2 / (2 prior_var) on the fused kernels (L2HMC_ENERGY_LOGISTIC): the
+    data set is packed into the kernels' fragment order once per device (`l2hmc_pack_logistic`)."""
+
+    def __init__(self, X, y, prior_var):
+        n, d = X.shape
+        EnergyFunction.__init__(self, _ffi.ENERGY_LOGISTIC, d, n_comp=n, eta=prior_var)
+        self._host = {'X': X, 'y': y}
+
+    def _buffers(self, device):
+        key = str(device)
+        if key not in self._dev:
+            L = _ffi.lib()
+            X = torch.as_tensor(self._host['X'], device=device)
+            y = torch.as_tensor(self._host['y'], device=device)
+            n, d = X.shape
+            packed = torch.empty(_ffi.check(L.l2hmc_packed_logistic_floats(n, d)), dtype=torch.float32, device=device)
+            _ffi.check(L.l2hmc_pack_logistic(X.data_ptr(), y.data_ptr(), n, d, packed.data_ptr(), _ffi.current_stream(device)))
+            self._dev[key] = {'mu': packed, 'prec': None, 'logc': None, '_X': X, '_y': y}
+        return self._dev[key]
+
+
+class LogisticRegression(object):
+    """Bayesian logistic regression: labels y_i in {0, 1} with P(y_i = 1 | w) = sigmoid(x_i . w) and a N(0, prior_var I) prior
+    on the weights w (d = X.shape[1] <= 128 features; add a column of ones for an intercept).  The posterior's energy
+
+        U(w) = sum_i [softplus(x_i . w) - y_i x_i . w] + |w|^2 / (2 prior_var)
+
+    and its gradient X^T (sigmoid(X w) - y) + w / prior_var are fused into the trajectory kernels (two f32 MFMA contractions
+    over the data per gradient): HMC and L2HMC sampling, parallel tempering and AIS run on it like on any built-in target.
+    Training a sampler on it is not fused: train on the same likelihood written as a torch callable, then load the state."""
+
+    def __init__(self, X, y, prior_var=1.0):
+        X = np.asarray(X, dtype=np.float64)
+        y = np.asarray(y, dtype=np.float64)
+        if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1:
+            raise ValueError("X must be (n_data, d) with n_data, d >= 1, got shape %s" % (X.shape,))
+        n, d = X.shape
+        if d > 128:
+            raise ValueError("LogisticRegression supports d <= 128 features (got %d)" % d)
+        if n > 1 << 20:
+            raise ValueError("LogisticRegression supports at most 1048576 data rows (got %d)" % n)
+        if y.shape != (n,):
+            raise ValueError("y must be (n_data,) = (%d,), got shape %s" % (n, y.shape))
+        if not np.all(np.isfinite(X)):
+            raise ValueError("X must be finite")
+        if not np.all((y == 0.0) | (y == 1.0)):
+            raise ValueError("labels y must be 0 or 1")
+        prior_var = float(prior_var)
+        if not (np.isfinite(prior_var) and prior_var > 0.0):
+            raise ValueError("prior_var must be finite and > 0, got %r" % (prior_var,))
+        self.X = np.ascontiguousarray(X, dtype=np.float32)
+        self.y = np.ascontiguousarray(y, dtype=np.float32)
+        self.prior_var = prior_var
+        self.dim = d
+
+    def get_energy_function(self):
+        return LogisticEnergy(self.X, self.y, self.prior_var)
+
+    def log_density(self, W):
+        """Unnormalised log posterior -U(w) of each row of W (n_w, d), in float64."""
+        W = np.asarray(W, dtype=np.float64)
+        L = W @ self.X.astype(np.float64).T
+        nll = np.logaddexp(0.0, L) - L * self.y.astype(np.float64)
+        return -(nll.sum(axis=1) + 0.5 * np.square(W).sum(axis=1) / self.prior_var)
+
+
 def as_device_f32(x, device=None):
     """numpy / torch input -> contiguous float32 tensor on the GPU."""
     if not isinstance(x, torch.Tensor):

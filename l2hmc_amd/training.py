@@ -63,6 +63,13 @@ def _refuse_annealed(dynamics):
 
 class Trainer(object):
     def __new__(cls, dynamics, *args, **kwargs):
+        fn = getattr(dynamics, "_fn", None)
+        if fn is not None and getattr(fn, "kind", None) == _ffi.ENERGY_LOGISTIC:
+            raise NotImplementedError(
+                "no trainer runs on the fused logistic-regression target (its Hessian-vector products are not implemented). "
+                "Train with the same likelihood written as a torch callable -- Dynamics(d, fn, ...) with fn(w) = "
+                "sum(softplus(X w) - y X w) + |w|^2 / (2 prior_var) trains on the GEMM-engine trainer -- then load the trained "
+                "state_dict() into the Dynamics on the fused LogisticRegression energy to sample")
         if getattr(dynamics, "_user_nets", False):
             # dynamics.py:78-79 + SCGExperiment.ipynb raw 178-181: the reference minimises over whatever variables net_factory
             # created.  Arbitrary callables train on the GEMM-engine trainer, their adjoints by callback (ABI 6 net_vjp_cb).
