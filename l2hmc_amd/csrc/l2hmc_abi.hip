@@ -1068,15 +1068,11 @@ int l2hmc_loss_terms(const float* v1, int64_t n, float scale, double inv_n, doub
 
 int l2hmc_adam_step(float* params, const float* grad, float* m, float* v, int64_t n, float lr, float beta1,
                     float beta2, float epsilon, int64_t step, int32_t last_is_log_eps, void* stream) {
-  if (!params || !grad || !m || !v || n < 0 || step < 1 || !(lr >= 0.f) || !(beta1 >= 0.f && beta1 < 1.f) ||
-      !(beta2 >= 0.f && beta2 < 1.f) || !(epsilon > 0.f))
+  if (!params || !grad || !m || !v || n < 0 || !adam_args_ok(lr, beta1, beta2, epsilon, step))
     return fail(L2HMC_ERR_ARG, "l2hmc_adam_step: bad argument%s");
   if (n == 0) return L2HMC_OK;
-  // lr_t = lr sqrt(1 - beta2^t) / (1 - beta1^t)   (TF1 Adam: epsilon is added to sqrt(v), uncorrected)
-  const double t = (double)step;
-  const float lr_t = (float)((double)lr * sqrt(1.0 - pow((double)beta2, t)) / (1.0 - pow((double)beta1, t)));
   hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, params, grad,
-                     m, v, (long long)n, lr_t, beta1, beta2, epsilon, last_is_log_eps);
+                     m, v, (long long)n, adam_lr_t(lr, beta1, beta2, step), beta1, beta2, epsilon, last_is_log_eps);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(L2HMC_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
   return L2HMC_OK;

@@ -53,6 +53,15 @@ inline float roughwell_den(const L2hmcEnergy* e) {
   return e->easy ? e->eta : (float)((double)e->eta * (double)e->eta);
 }
 void note_kernel(const char* fmt, long long a = 0, long long b = 0, long long c = 0, long long d = 0);   // -> l2hmc_last_kernel
+// Adam's host side (l2hmc_adam_step, l2hmc_adam_step_terms, l2hmc_train_step): the hyper-parameters it accepts, and the
+// bias-corrected step size lr_t = lr sqrt(1 - beta2^t) / (1 - beta1^t) (TF1 Adam: epsilon is added to sqrt(v), uncorrected)
+inline bool adam_args_ok(float lr, float beta1, float beta2, float epsilon, int64_t step) {
+  return step >= 1 && lr >= 0.f && (beta1 >= 0.f && beta1 < 1.f) && (beta2 >= 0.f && beta2 < 1.f) && epsilon > 0.f;
+}
+inline float adam_lr_t(float lr, float beta1, float beta2, int64_t step) {
+  const double t = (double)step;
+  return (float)((double)lr * sqrt(1.0 - pow((double)beta2, t)) / (1.0 - pow((double)beta1, t)));
+}
 
 // Debug builds with -DL2HMC_LDS_POISON (tools/build_variant_full.sh poison -DL2HMC_LDS_POISON): every kernel that works out of
 // dynamic LDS first fills ALL of it with NaN bit patterns.  LDS is not cleared between workgroups, so a kernel that reads a word

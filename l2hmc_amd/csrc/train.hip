@@ -981,45 +981,109 @@ __device__ __forceinline__ float relu_f(float a) { return fmaxf(a, 0.f); }
 #include "train_fast.hpp"
 #include "train_small.hpp"
 
-// d <= 4 targets (the notebook's own SCG-2D training among them): one dimension per lane (train_small.hpp)
-inline bool train_small_ok(int ek, int d, int H) {
-  return d <= 4 && H <= 15 && (ek == L2HMC_ENERGY_GAUSS_DIAG || ek == L2HMC_ENERGY_GAUSS_DENSE || ek == L2HMC_ENERGY_ROUGHWELL ||
-                               ek == L2HMC_ENERGY_GMM);
-}
-template <int EK>
-int launch_train_small(const TArgs& k, int KH, unsigned blocks, long long lds, hipStream_t s) {
-  const bool tp = k.itemp != 1.f;
-  if (KH <= 3) {
-    if (tp) hipLaunchKernelGGL((train_small_kernel<EK, 3, true>), dim3(blocks), dim3(128), (size_t)lds, s, k);
-    else hipLaunchKernelGGL((train_small_kernel<EK, 3, false>), dim3(blocks), dim3(128), (size_t)lds, s, k);
-  } else {
-    if (tp) hipLaunchKernelGGL((train_small_kernel<EK, 4, true>), dim3(blocks), dim3(128), (size_t)lds, s, k);
-    else hipLaunchKernelGGL((train_small_kernel<EK, 4, false>), dim3(blocks), dim3(128), (size_t)lds, s, k);
+// The training kernel of one call: its family (FAM_SMALL, FAM_FAST or FAM_GENERAL) and template arguments
+struct TrainPlan {
+  int family = FAM_GENERAL;
+  int ek = 0;               // energy kind (EK)
+  int NW = 1;               // fast: waves per workgroup
+  int KH = 3;               // small, fast: hidden k-steps of the nets, 3 or 4
+  long long lds = 0;        // dynamic LDS bytes (of a refusal: the bytes it quotes)
+};
+enum { TRAIN_PLANNED, TRAIN_NO_FUNNEL, TRAIN_NO_LDS };
+
+// Every selection rule of the training entry points and of l2hmc_train_fused_lds_bytes (variant 0), in order; nc: mixture
+// components (>= 1).  Returns TRAIN_PLANNED or the rule that refused (each caller words its own message).  No HIP calls.
+static int plan_train(int ek, int nc, int d, int H, int T, int variant, TrainPlan& p) {
+  p = TrainPlan();
+  p.ek = ek;
+  p.KH = khid_of(H) <= 3 ? 3 : 4;
+  // d <= 4 targets (the notebook's own SCG-2D training among them): one dimension per lane (train_small.hpp)
+  const bool small = d <= 4 && H <= 15 && (ek == L2HMC_ENERGY_GAUSS_DIAG || ek == L2HMC_ENERGY_GAUSS_DENSE ||
+                                           ek == L2HMC_ENERGY_ROUGHWELL || ek == L2HMC_ENERGY_GMM);
+  // geometry of the register-resident kernel (train_fast.hpp) for this problem, or 0 if it stays on train_kernel
+  // (variant 100: the general tile kernel)
+  int nw = 0;
+  if (variant < 100 && H <= 15) {
+    if (ek == L2HMC_ENERGY_GAUSS_DIAG || ek == L2HMC_ENERGY_ROUGHWELL) nw = d <= 16 ? 1 : (d <= 64 ? 4 : 0);
+    if (ek == L2HMC_ENERGY_GAUSS_DENSE || ek == L2HMC_ENERGY_FUNNEL) nw = d <= 16 ? 1 : 0;
   }
+  const long long lds_small = 4LL * ts_layout(T).total, lds_fast = nw ? 4LL * tf_layout(T, nw).total : 0;
+  if (variant == 0 && small && lds_small <= 48 * 1024) {
+    p.family = FAM_SMALL;
+    p.lds = lds_small;
+  } else if (nw && lds_fast <= kMaxLdsBytes) {
+    p.family = FAM_FAST;
+    p.NW = nw;
+    p.lds = lds_fast;
+  } else if (ek == L2HMC_ENERGY_FUNNEL) {       // the general tile kernel has no funnel Hessian-vector product
+    p.lds = lds_fast;
+    return TRAIN_NO_FUNNEL;
+  } else {
+    p.lds = 4LL * train_layout(d, H, T, ek, ek == L2HMC_ENERGY_GMM ? nc : 1).total;
+    if (p.lds > kMaxLdsBytes) return TRAIN_NO_LDS;
+  }
+  return TRAIN_PLANNED;
+}
+
+// l2hmc_last_kernel: the planned kernel with its template arguments
+static void note_train_plan(const TrainPlan& p) {
+  if (p.family == FAM_SMALL) note_kernel("train_small_kernel<%lld, %lld>", p.ek, p.KH);
+  else if (p.family == FAM_FAST) note_kernel("train_fast_kernel<%lld, %lld, %lld>", p.ek, p.NW, p.KH);
+  else note_kernel("train_kernel");
+}
+
+// The planned gradient kernel on `blocks` workgroups of 16 chains.  Compiled: train_small_kernel for kinds 1-4;
+// train_fast_kernel for the elementwise kinds (1, 4) with one or four waves, the dense Gaussian and the funnel (2, 5) with one.
+static int launch_train(const TrainPlan& p, const TArgs& k, long long blocks, hipStream_t s) {
+  return on_either<true, false>(k.itemp != 1.f, [&](auto TEMP) {
+    if (p.family == FAM_GENERAL) return launch_kernel(train_kernel<TEMP>, blocks, TTHREADS, p.lds, s, k);
+    return on_either<3, 4>(p.KH == 3, [&](auto KH) {
+      return on_either<1, 4>(p.NW == 1, [&](auto NW) {
+        return on_energy_kind(p.ek, [&](auto ek) {
+          constexpr int EK = decltype(ek)::value;
+          if constexpr (NW == 1 && EK != L2HMC_ENERGY_FUNNEL && EK != L2HMC_ENERGY_LOGISTIC) {
+            if (p.family == FAM_SMALL) return launch_kernel(train_small_kernel<EK, KH, TEMP>, blocks, 128, p.lds, s, k);
+          }
+          if constexpr (EK == L2HMC_ENERGY_GAUSS_DIAG || EK == L2HMC_ENERGY_ROUGHWELL ||
+                        (NW == 1 && (EK == L2HMC_ENERGY_GAUSS_DENSE || EK == L2HMC_ENERGY_FUNNEL))) {
+            if (p.family == FAM_FAST) return launch_kernel(train_fast_kernel<EK, NW, KH, TEMP>, blocks, 64 * NW, p.lds, s, k);
+          }
+          return fail(L2HMC_ERR_UNSUPPORTED, "no training kernel for this plan%s");
+        });
+      });
+    });
+  });
+}
+
+// Floats at the head of the workspace that a launch of `family` checkpoints into; its per-workgroup gradient slots follow them.
+inline long long train_ckpt_floats(int family, int NW, long long N, int d, int T) {
+  if (family == FAM_GENERAL) return (long long)T * N * CKPT * d;         // (T, N, 5, d)
+  const long long blocks = (N + TC - 1) / TC;                             // (blocks, T, TF_CK, NW x 64 lanes) float4
+  return blocks * T * TF_CK * ((family == FAM_FAST ? NW : 1) * 256);
+}
+
+// The sum of `slots` per-workgroup gradients at part, in slot order (two levels past kReduceChunk slots: still deterministic):
+// added to grad by train_reduce_kernel (f = NULL), or written to grad by train_final_kernel with the rest of the step f describes.
+static int reduce_slots(float* part, int slots, int n_grad, float* grad, const FinalArgs* f, hipStream_t s) {
+  if (slots > kReduceChunk) {
+    const int chunks = (slots + kReduceChunk - 1) / kReduceChunk;
+    float* part2 = part + (long long)slots * n_grad;
+    hipLaunchKernelGGL(train_reduce_kernel, dim3((n_grad + 255) / 256, chunks), dim3(256), 0, s, part, slots, n_grad,
+                       kReduceChunk, part2, 0);
+    part = part2;
+    slots = chunks;
+  }
+  if (f == nullptr) {
+    hipLaunchKernelGGL(train_reduce_kernel, dim3((n_grad + 255) / 256, 1), dim3(256), 0, s, part, slots, n_grad, slots, grad, 1);
+  } else {
+    // (the loss block is always launched -- it idles without outputs -- so that the select blocks sit at fixed indices)
+    const long long mh_blocks = f->u != nullptr ? (f->n_head * f->d + 255) / 256 : 0;
+    hipLaunchKernelGGL(train_final_kernel, dim3((unsigned)((n_grad + 255) / 256 + 1 + mh_blocks)), dim3(256), 0, s, part, slots,
+                       n_grad, grad, *f);
+  }
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(L2HMC_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
   return L2HMC_OK;
-}
-
-// geometry of the register-resident kernel for this problem, or 0 if it stays on train_kernel
-inline int train_fast_waves(int ek, int d, int H) {
-  if (H > 15) return 0;
-  if (ek == L2HMC_ENERGY_GAUSS_DIAG || ek == L2HMC_ENERGY_ROUGHWELL) return d <= 16 ? 1 : (d <= 64 ? 4 : 0);
-  if (ek == L2HMC_ENERGY_GAUSS_DENSE || ek == L2HMC_ENERGY_FUNNEL) return d <= 16 ? 1 : 0;
-  return 0;
-}
-
-template <int EK, int NW>
-int launch_train_fast(const TArgs& k, int KH, unsigned blocks, long long lds, hipStream_t s) {
-  auto go = [&](auto kern) -> int {
-    if (lds > 48 * 1024) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return fail(L2HMC_ERR_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-    }
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(64 * NW), (size_t)lds, s, k);
-    return L2HMC_OK;
-  };
-  const bool tp = k.itemp != 1.f;
-  if (KH <= 3) return tp ? go(train_fast_kernel<EK, NW, 3, true>) : go(train_fast_kernel<EK, NW, 3, false>);
-  return tp ? go(train_fast_kernel<EK, NW, 4, true>) : go(train_fast_kernel<EK, NW, 4, false>);
 }
 
 }  // namespace l2hmc
@@ -1040,11 +1104,11 @@ void l2hmc_train_read_timers(unsigned long long* out) {
 
 int64_t l2hmc_train_workspace_floats(int64_t n_chains, int32_t d, int32_t H, int32_t T) {
   if (n_chains < 0 || d < 1 || H < 1 || T < 1) return fail(L2HMC_ERR_ARG, "l2hmc_train_workspace_floats: bad argument%s");
-  // per-step checkpoints of every chain, then one flat partial gradient per 16-chain workgroup
+  // per-step checkpoints of every chain (the larger of train_kernel's and four-wave train_fast_kernel's), then one flat
+  // partial gradient per 16-chain workgroup and one per chunk of the two-level reduction
   const int64_t blocks = (n_chains + TC - 1) / TC, chunks = (blocks + kReduceChunk - 1) / kReduceChunk;
-  // checkpoints: (T, N, 5, d) for train_kernel; (blocks, T, 5, NW x 64 lanes) float4 for train_fast_kernel
-  const int64_t ck_old = (int64_t)T * n_chains * CKPT * d, ck_fast = blocks * T * TF_CK * (4 * 256);
-  return (ck_old > ck_fast ? ck_old : ck_fast) + (blocks + chunks) * (2LL * net_params(d, H) + 1);
+  const int64_t ck_general = train_ckpt_floats(FAM_GENERAL, 1, n_chains, d, T), ck_fast = train_ckpt_floats(FAM_FAST, 4, n_chains, d, T);
+  return (ck_general > ck_fast ? ck_general : ck_fast) + (blocks + chunks) * (2LL * net_params(d, H) + 1);
 }
 
 int64_t l2hmc_train_grad_floats(int32_t d, int32_t H) {
@@ -1058,16 +1122,12 @@ int64_t l2hmc_train_fused_lds_bytes(int32_t ek, int32_t n_comp, int32_t d, int32
       ek != L2HMC_ENERGY_ROUGHWELL && ek != L2HMC_ENERGY_FUNNEL)
     return fail(L2HMC_ERR_UNSUPPORTED, "no fused training kernel for this energy kind%s");
   if (d > 4096 || H > 4096) return fail(L2HMC_ERR_UNSUPPORTED, "fused training kernel: d / H too large%s");
-  const long long lds_small = 4LL * ts_layout(T).total;
-  if (train_small_ok(ek, d, H) && lds_small <= 48 * 1024) return lds_small;
-  const int fnw = train_fast_waves(ek, d, H);
-  const long long lds_fast = fnw ? 4LL * tf_layout(T, fnw).total : 0;
-  if (fnw && lds_fast <= 160 * 1024) return lds_fast;
-  if (ek == L2HMC_ENERGY_FUNNEL) return fail(L2HMC_ERR_UNSUPPORTED, "funnel: the fused trainer holds 2 <= d <= 16, H <= 15%s");
-  const long long lds = 4LL * train_layout(d, H, T, ek, ek == L2HMC_ENERGY_GMM ? (n_comp < 1 ? 1 : n_comp) : 1).total;
-  if (lds > 160 * 1024)
-    return fail(L2HMC_ERR_UNSUPPORTED, "fused training kernel needs %s%lld bytes of LDS (> 160 KiB)", "", lds);
-  return lds;
+  TrainPlan p;
+  switch (plan_train(ek, n_comp < 1 ? 1 : n_comp, d, H, T, 0, p)) {
+    case TRAIN_NO_FUNNEL: return fail(L2HMC_ERR_UNSUPPORTED, "funnel: the fused trainer holds 2 <= d <= 16, H <= 15%s");
+    case TRAIN_NO_LDS: return fail(L2HMC_ERR_UNSUPPORTED, "fused training kernel needs %s%lld bytes of LDS (> 160 KiB)", "", p.lds);
+  }
+  return p.lds;
 }
 
 static int train_launch(const L2hmcTrainArgs* a, const L2hmcTrainStep* st, void* stream) {
@@ -1077,11 +1137,12 @@ static int train_launch(const L2hmcTrainArgs* a, const L2hmcTrainStep* st, void*
       return fail(L2HMC_ERR_ARG, "l2hmc_train_step: bad x_head / n_head%s");
     if ((st->u != nullptr) != (st->x_next != nullptr)) return fail(L2HMC_ERR_ARG, "l2hmc_train_step: u and x_next go together%s");
     if (st->u != nullptr && st->n_head < 1) return fail(L2HMC_ERR_ARG, "l2hmc_train_step: the Metropolis select needs n_head >= 1%s");
-    if (st->theta != nullptr && (!st->m || !st->v || st->step < 1 || !(st->lr >= 0.f) || !(st->beta1 >= 0.f && st->beta1 < 1.f) ||
-                                 !(st->beta2 >= 0.f && st->beta2 < 1.f) || !(st->epsilon > 0.f)))
+    if (st->theta != nullptr && (!st->m || !st->v || !adam_args_ok(st->lr, st->beta1, st->beta2, st->epsilon, st->step)))
       return fail(L2HMC_ERR_ARG, "l2hmc_train_step: bad optimiser arguments%s");
   }
   if (a->n_chains < 0 || a->d < 1 || a->T < 1 || a->H < 1) return fail(L2HMC_ERR_ARG, "bad n_chains / d / H / T%s");
+  const int n_grad = 2 * net_params(a->d, a->H) + 1;
+  hipStream_t s = (hipStream_t)stream;
   if (a->n_chains == 0) {
     if (st == nullptr) return L2HMC_OK;
     // An EMPTY shard of a sharded optimiser step (fewer chains than ranks): its slice of the one all-reduce must still be a
@@ -1089,15 +1150,10 @@ static int train_launch(const L2hmcTrainArgs* a, const L2hmcTrainStep* st, void*
     // early return left the previous step's already-reduced gradient there, which every rank then added again).
     if (st->theta != nullptr) return fail(L2HMC_ERR_ARG, "l2hmc_train_step: an optimiser update needs at least one chain%s");
     if (!a->grad || !(a->scale > 0.f) || !(a->inv_n > 0.f)) return fail(L2HMC_ERR_ARG, "l2hmc_train_step: NULL grad / bad scale, inv_n%s");
-    const int n_grad0 = 2 * net_params(a->d, a->H) + 1;
     FinalArgs f;
     memset(&f, 0, sizeof(f));
     f.scale = a->scale; f.inv_n = (double)a->inv_n; f.terms = st->terms; f.loss = st->loss;
-    hipLaunchKernelGGL(train_final_kernel, dim3((unsigned)((n_grad0 + 255) / 256 + 1)), dim3(256), 0, (hipStream_t)stream, a->grad, 0,
-                       n_grad0, a->grad, f);
-    hipError_t e0 = hipGetLastError();
-    if (e0 != hipSuccess) return fail(L2HMC_ERR_HIP, "kernel launch: %s", hipGetErrorString(e0));
-    return L2HMC_OK;
+    return reduce_slots(a->grad, 0, n_grad, a->grad, &f, s);
   }
   if (a->d > 4096 || a->H > 4096) return fail(L2HMC_ERR_UNSUPPORTED, "training kernel: d / H too large (got d = %s%lld, H = %lld)", "", a->d, a->H);
   if (!a->xnet || !a->vnet || !a->masks || !a->trig || !a->x || !a->v || !a->Lx || !a->p || !a->v1 ||
@@ -1135,91 +1191,36 @@ static int train_launch(const L2hmcTrainArgs* a, const L2hmcTrainStep* st, void*
 #ifdef L2HMC_DBG_EPILOGUE_SELECT
   k.u = nullptr; k.x_next = nullptr;
 #endif
-  const unsigned blocks = (unsigned)((a->n_chains + TC - 1) / TC);
-  hipStream_t s = (hipStream_t)stream;
-  const int n_grad = 2 * net_params(a->d, a->H) + 1;
-  float* part;
-  const int fnw = a->variant >= 100 ? 0 : train_fast_waves(ek, a->d, a->H);     // variant 100: the general tile kernel
-  const long long lds_fast = fnw ? 4LL * tf_layout(a->T, fnw).total : 0;
-  const long long lds_small = 4LL * ts_layout(a->T).total;
-  if (a->variant == 0 && train_small_ok(ek, a->d, a->H) && lds_small <= 48 * 1024) {     // d <= 4: one dimension per lane
-    const int KH = khid_of(a->H);
-    if (ek == L2HMC_ENERGY_GAUSS_DIAG) launch_train_small<L2HMC_ENERGY_GAUSS_DIAG>(k, KH, blocks, lds_small, s);
-    else if (ek == L2HMC_ENERGY_GAUSS_DENSE) launch_train_small<L2HMC_ENERGY_GAUSS_DENSE>(k, KH, blocks, lds_small, s);
-    else if (ek == L2HMC_ENERGY_GMM) launch_train_small<L2HMC_ENERGY_GMM>(k, KH, blocks, lds_small, s);
-    else launch_train_small<L2HMC_ENERGY_ROUGHWELL>(k, KH, blocks, lds_small, s);
-    part = a->workspace + (long long)blocks * a->T * TF_CK * 256;
-    note_kernel("train_small_kernel<%lld, %lld>", ek, KH <= 3 ? 3 : 4);
-  } else if (fnw && lds_fast <= 160 * 1024) {    // register-resident kernel (train_fast.hpp)
-    const int KH = khid_of(a->H);
-    int rc;
-    if (ek == L2HMC_ENERGY_GAUSS_DIAG) rc = fnw == 1 ? launch_train_fast<L2HMC_ENERGY_GAUSS_DIAG, 1>(k, KH, blocks, lds_fast, s)
-                                                     : launch_train_fast<L2HMC_ENERGY_GAUSS_DIAG, 4>(k, KH, blocks, lds_fast, s);
-    else if (ek == L2HMC_ENERGY_ROUGHWELL) rc = fnw == 1 ? launch_train_fast<L2HMC_ENERGY_ROUGHWELL, 1>(k, KH, blocks, lds_fast, s)
-                                                         : launch_train_fast<L2HMC_ENERGY_ROUGHWELL, 4>(k, KH, blocks, lds_fast, s);
-    else if (ek == L2HMC_ENERGY_FUNNEL) rc = launch_train_fast<L2HMC_ENERGY_FUNNEL, 1>(k, KH, blocks, lds_fast, s);
-    else rc = launch_train_fast<L2HMC_ENERGY_GAUSS_DENSE, 1>(k, KH, blocks, lds_fast, s);
-    if (rc) return rc;
-    part = a->workspace + (long long)blocks * a->T * TF_CK * (fnw * 256);
-    note_kernel("train_fast_kernel<%lld, %lld, %lld>", ek, fnw, KH <= 3 ? 3 : 4);
-  } else {
-    if (ek == L2HMC_ENERGY_FUNNEL)               // the general tile kernel has no funnel Hessian-vector product
+  TrainPlan p;
+  switch (plan_train(ek, k.ncomp, a->d, a->H, a->T, a->variant, p)) {
+    case TRAIN_NO_FUNNEL:
       return fail(L2HMC_ERR_UNSUPPORTED, "funnel training runs on the register-resident kernel only (d <= 16, H <= 15, "
-                  "its LDS plan <= 160 KiB; needs %s%lld bytes here)", "", lds_fast);
-    const TLayout L = train_layout(a->d, a->H, a->T, ek, k.ncomp);
-    const long long lds = 4LL * L.total;
-    if (lds > 160 * 1024)
-      return fail(L2HMC_ERR_UNSUPPORTED, "training kernel needs %s%lld bytes of LDS (> 160 KiB): d / H too large for the 16-chain tile", "", lds);
-    if (lds > 48 * 1024) {
-      hipError_t e = hipFuncSetAttribute(k.itemp != 1.f ? reinterpret_cast<const void*>(train_kernel<true>)
-                                                         : reinterpret_cast<const void*>(train_kernel<false>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return fail(L2HMC_ERR_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-    }
-    if (k.itemp != 1.f) hipLaunchKernelGGL(train_kernel<true>, dim3(blocks), dim3(TTHREADS), (size_t)lds, s, k);
-    else hipLaunchKernelGGL(train_kernel<false>, dim3(blocks), dim3(TTHREADS), (size_t)lds, s, k);
-    note_kernel("train_kernel");
-    part = a->workspace + (long long)a->T * a->n_chains * CKPT * a->d;
+                  "its LDS plan <= 160 KiB; needs %s%lld bytes here)", "", p.lds);
+    case TRAIN_NO_LDS:
+      return fail(L2HMC_ERR_UNSUPPORTED, "training kernel needs %s%lld bytes of LDS (> 160 KiB): d / H too large for the 16-chain tile", "", p.lds);
   }
-  const float* last = part;
-  int last_slots = (int)blocks;
-  if (blocks > (unsigned)kReduceChunk) {      // two levels, both in slot order: still deterministic
-    const int chunks = (int)((blocks + kReduceChunk - 1) / kReduceChunk);
-    float* part2 = part + (long long)blocks * n_grad;
-    hipLaunchKernelGGL(train_reduce_kernel, dim3((n_grad + 255) / 256, chunks), dim3(256), 0, s, part, (int)blocks,
-                       n_grad, kReduceChunk, part2, 0);
-    last = part2;
-    last_slots = chunks;
+  note_train_plan(p);
+  const long long blocks = (a->n_chains + TC - 1) / TC;
+  const int rc = launch_train(p, k, blocks, s);
+  if (rc) return rc;
+  float* part = a->workspace + train_ckpt_floats(p.family, p.NW, a->n_chains, a->d, a->T);
+  if (st == nullptr) return reduce_slots(part, (int)blocks, n_grad, a->grad, nullptr, s);
+  FinalArgs f;
+  memset(&f, 0, sizeof(f));
+  f.x0 = st->x_head; f.Lx = a->Lx; f.p = a->p; f.u = st->u; f.x_next = st->x_next; f.d = a->d;
+  f.v1 = a->v1; f.n_v1 = a->n_chains; f.scale = a->scale; f.n_head = st->n_head;
+  // the args carry inv_n as the float the kernel differentiates with; the reported loss is a double (l2hmc_loss_terms takes a
+  // double 1 / chains): when the float is the rounding of 1 / integer -- it always is from the host layer -- use that integer
+  const double inv_f = (double)a->inv_n, cnt = nearbyint(1.0 / inv_f);
+  f.inv_n = (cnt >= 1.0 && (float)(1.0 / cnt) == a->inv_n) ? 1.0 / cnt : inv_f;
+  f.terms = st->terms; f.loss = st->loss;
+  if (st->theta != nullptr) {
+    f.lr_t = adam_lr_t(st->lr, st->beta1, st->beta2, st->step);
+    f.theta = st->theta; f.m = st->m; f.v = st->v; f.b1 = st->beta1; f.b2 = st->beta2; f.eps = st->epsilon;
+    f.last_is_log_eps = st->train_alpha != 0;
+    f.n_par = st->train_alpha ? n_grad : n_grad - 1;
   }
-  if (st == nullptr) {
-    hipLaunchKernelGGL(train_reduce_kernel, dim3((n_grad + 255) / 256, 1), dim3(256), 0, s, last, last_slots, n_grad,
-                       last_slots, a->grad, 1);
-  } else {
-    FinalArgs f;
-    memset(&f, 0, sizeof(f));
-    // (the loss block is always launched -- it idles without outputs -- so that the select blocks sit at fixed indices)
-    const long long mh_blocks = st->u != nullptr ? (st->n_head * a->d + 255) / 256 : 0;
-    f.x0 = st->x_head; f.Lx = a->Lx; f.p = a->p; f.u = st->u; f.x_next = st->x_next; f.d = a->d;
-    f.v1 = a->v1; f.n_v1 = a->n_chains; f.scale = a->scale; f.n_head = st->n_head;
-    // the args carry inv_n as the float the kernel differentiates with; the reported loss is a double (l2hmc_loss_terms takes a
-    // double 1 / chains): when the float is the rounding of 1 / integer -- it always is from the host layer -- use that integer
-    const double inv_f = (double)a->inv_n, cnt = nearbyint(1.0 / inv_f);
-    f.inv_n = (cnt >= 1.0 && (float)(1.0 / cnt) == a->inv_n) ? 1.0 / cnt : inv_f;
-    f.terms = st->terms; f.loss = st->loss;
-    if (st->theta != nullptr) {
-      // lr_t = lr sqrt(1 - beta2^t) / (1 - beta1^t)   (TF1 Adam, as l2hmc_adam_step)
-      const double t = (double)st->step;
-      f.lr_t = (float)((double)st->lr * sqrt(1.0 - pow((double)st->beta2, t)) / (1.0 - pow((double)st->beta1, t)));
-      f.theta = st->theta; f.m = st->m; f.v = st->v; f.b1 = st->beta1; f.b2 = st->beta2; f.eps = st->epsilon;
-      f.last_is_log_eps = st->train_alpha != 0;
-      f.n_par = st->train_alpha ? n_grad : n_grad - 1;
-    }
-    hipLaunchKernelGGL(train_final_kernel, dim3((unsigned)((n_grad + 255) / 256 + 1 + mh_blocks)), dim3(256), 0, s, last, last_slots,
-                       n_grad, a->grad, f);
-  }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(L2HMC_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
-  return L2HMC_OK;
+  return reduce_slots(part, (int)blocks, n_grad, a->grad, &f, s);
 }
 
 int l2hmc_train_propose_grad(const L2hmcTrainArgs* a, void* stream) { return train_launch(a, nullptr, stream); }
@@ -1245,14 +1246,11 @@ __global__ void adam_terms_kernel(float* p, const float* g, float* m, float* v, 
 int l2hmc_adam_step_terms(float* params, const float* grad, float* m, float* v, int64_t n, float lr, float beta1,
                           float beta2, float epsilon, int64_t step, int32_t last_is_log_eps, const float* terms6,
                           float scale, double* loss_out, void* stream) {
-  if (!params || !grad || !m || !v || n < 1 || step < 1 || !(lr >= 0.f) || !(beta1 >= 0.f && beta1 < 1.f) ||
-      !(beta2 >= 0.f && beta2 < 1.f) || !(epsilon > 0.f) || (terms6 != nullptr) != (loss_out != nullptr) ||
-      (terms6 != nullptr && !(scale > 0.f)))
+  if (!params || !grad || !m || !v || n < 1 || !adam_args_ok(lr, beta1, beta2, epsilon, step) ||
+      (terms6 != nullptr) != (loss_out != nullptr) || (terms6 != nullptr && !(scale > 0.f)))
     return fail(L2HMC_ERR_ARG, "l2hmc_adam_step_terms: bad argument%s");
-  const double t = (double)step;
-  const float lr_t = (float)((double)lr * sqrt(1.0 - pow((double)beta2, t)) / (1.0 - pow((double)beta1, t)));
   hipLaunchKernelGGL(adam_terms_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, params, grad, m, v,
-                     (long long)n, lr_t, beta1, beta2, epsilon, last_is_log_eps, terms6, scale, loss_out);
+                     (long long)n, adam_lr_t(lr, beta1, beta2, step), beta1, beta2, epsilon, last_is_log_eps, terms6, scale, loss_out);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(L2HMC_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
   return L2HMC_OK;

@@ -59,6 +59,25 @@ def test_argument_validation_without_gpu():
     assert L.l2hmc_train_fused_lds_bytes(99, 1, 2, 10, 10) == -2 and L.l2hmc_train_fused_lds_bytes(G, 1, 0, 10, 10) == -1
 
 
+def test_fused_trainer_query_pins_each_family_and_refusal():
+    """`l2hmc_train_fused_lds_bytes` answers from the launch's own plan (`plan_train`, csrc/train.hip): the dynamic LDS of
+    the kernel it picks -- the d <= 4 kernel (train_small.hpp), the register-resident kernel with one or four waves
+    (train_fast.hpp), the general tile kernel -- or the rule that refused.  Pure host logic, no launch."""
+    L = _ffi.lib()
+    G, D, M, R, F = (_ffi.ENERGY_GAUSS_DIAG, _ffi.ENERGY_GAUSS_DENSE, _ffi.ENERGY_GMM, _ffi.ENERGY_ROUGHWELL, _ffi.ENERGY_FUNNEL)
+    for args, lds in (((G, 1, 2, 10, 10), 31728), ((D, 1, 4, 15, 5), 30976),            # d <= 4
+                      ((G, 1, 16, 10, 10), 26512), ((F, 1, 16, 10, 40), 32512),         # register-resident, one wave
+                      ((G, 1, 50, 10, 10), 89488),                                      # ... four waves
+                      ((M, 2, 5, 10, 10), 31232), ((R, 1, 17, 16, 10), 67888)):         # general tile kernel
+        assert L.l2hmc_train_fused_lds_bytes(*args) == lds, args
+    for args, msg in (((F, 1, 17, 10, 10), b"funnel: the fused trainer holds 2 <= d <= 16"),
+                      ((R, 1, 128, 10, 10), b"needs 300144 bytes of LDS (> 160 KiB)"),
+                      ((G, 1, 4097, 10, 10), b"d / H too large"),
+                      ((99, 1, 2, 10, 10), b"no fused training kernel for this energy kind")):
+        assert L.l2hmc_train_fused_lds_bytes(*args) == -2, args
+        assert msg in L.l2hmc_last_error(), (args, L.l2hmc_last_error())
+
+
 def test_struct_layout_matches_header():
     # field order / sizes of the ctypes mirrors (x86-64: pointers 8, ints 4, natural alignment)
     assert ctypes.sizeof(_ffi.L2hmcNet) == 16 * 8
