@@ -1,5 +1,5 @@
-"""Bayesian logistic regression (needs a GPU): HMC and parallel tempering on the fused target against the same likelihood on the
-slow path.
+"""Bayesian logistic regression (needs a GPU): HMC, a trained L2HMC sampler and parallel tempering on the fused target against
+the same likelihood on the slow path.
 
 A seeded synthetic data set of German-credit shape -- n = 1000 rows, d = 25 standardised features (an intercept column and 24
 Gaussian ones), labels drawn from a known weight vector -- nothing is read from disk or the network.  The posterior
@@ -7,7 +7,10 @@ U(w) = sum_i [softplus(x_i . w) - y_i x_i . w] + |w|^2 / 2 is sampled by HMC (T 
 `LogisticRegression(X, y).get_energy_function()` -- U and grad U fused into the trajectory kernel -- and by the same HMC with U
 written as a torch callable (U and grad U from torch between launches).  Both report effective samples per second (the
 second half of each chain; the smallest per-coordinate ESS, from the integrated autocorrelation time); a 4-rung
-parallel-tempering ladder on the fused target reports the same for its cold rung, with its swap rates and round trips.
+parallel-tempering ladder on the fused target reports the same for its cold rung, with its swap rates and round trips.  A
+trained-sampler leg trains the S/T/Q nets on the fused target (`LogisticTrainer`: the training kernel's logistic-regression
+form, `train_steps` optimiser steps), then samples with them (`sample_chain` on the same Dynamics) and reports the same
+figure, with the training time beside it; which sampler wins depends on the posterior and the training budget.
 
     python examples/logistic_regression.py
 """
@@ -19,7 +22,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 
-from l2hmc_amd import Dynamics, LogisticRegression, ParallelTempering, geometric_ladder, sample_chain
+from l2hmc_amd import Dynamics, LogisticRegression, LogisticTrainer, ParallelTempering, geometric_ladder, layers, sample_chain
 
 
 def german_credit_shape(n=1000, d=25, seed=0):
@@ -60,7 +63,7 @@ def run(dyn, x0, M, seed):
     return time.perf_counter() - t0, float(p.mean()), hist[M // 2:].cpu().numpy().astype(np.float64)
 
 
-def main(chains=4096, proposals=400, slow_proposals=40, seed=1):
+def main(chains=4096, proposals=400, slow_proposals=40, seed=1, train_steps=500):
     X, y, w_true = german_credit_shape()
     n, d = X.shape
     model = LogisticRegression(X, y, prior_var=1.0)
@@ -91,6 +94,27 @@ def main(chains=4096, proposals=400, slow_proposals=40, seed=1):
     print("slow   HMC: %d chains x %d proposals in %.3f s, accept %.3f, min ESS %.0f -> %.0f ESS/s" % (
         chains, slow_proposals, ts, accs, ess_s, ess_s / ts))
     print("fused / slow, time per proposal: x %.1f" % ((ts / slow_proposals) / (t / proposals)))
+
+    # a trained sampler on the same fused target: the nets' parameter tensors are the Dynamics' own, so it samples as it is
+    torch.manual_seed(seed)
+    np.random.seed(seed)
+    l2 = Dynamics(d, model.get_energy_function(), T=T, eps=eps, net_factory=layers.stq_network(10))
+    tr = LogisticTrainer(l2, seed=seed)
+    xt = x0[:1024].clone()
+    tr.step(xt)                                                     # warm-up
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(train_steps):
+        loss, px, xt, _ = tr.step(xt)
+    torch.cuda.synchronize()
+    tt = time.perf_counter() - t0
+    sample_chain(x0, l2, 2, seed=seed)
+    tl, accl, hl = run(l2, x0, proposals, seed)
+    ess_l = min_ess(hl)
+    print("fused L2HMC: trained %d steps on 1024 chains in %.2f s (loss %.4g, step size %.4f); %d chains x %d proposals in %.3f s, "
+          "accept %.3f, min ESS %.0f -> %.0f ESS/s (HMC above: %.0f)" % (
+              train_steps, tt, float(loss), float(torch.exp(l2.alpha.detach()).reshape(-1)[0]), chains, proposals, tl, accl, ess_l,
+              ess_l / tl, ess / t))
 
     ladder = geometric_ladder(1.0, 4.0, 4)
     ParallelTempering(fused, ladder, chains // 4, seed=seed).run(x0, 2, 1)      # warm-up (the ladder kernel's first launch)

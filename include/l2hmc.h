@@ -446,7 +446,8 @@ int l2hmc_p_accept_energies(const float* U0, const float* v0, const float* U1, c
  * per-rank gradients simply all-reduce(sum).  The nets are the RAW reference-layout weights
  * (not the packed buffer); for the dense Gaussian `energy.prec` is the raw (d, d) precision.
  * Targets with analytic Hessian-vector products: Gaussian (diag / dense), GMM (prec = RAW (k,d,d)
- * precisions, logc, n_comp <= 8), Rough Well; any d, H whose 16-chain tile fits the 160 KiB LDS
+ * precisions, logc, n_comp <= 8), Rough Well, logistic regression (see l2hmc_train_logistic_lds_bytes below);
+ * any d, H whose 16-chain tile fits the 160 KiB LDS
  * (d = 50, H = 10 uses 122 KiB; larger shapes return L2HMC_ERR_UNSUPPORTED).  Every chain runs in
  * its own direction.
  * energy.temperature is honoured: the dynamics, the accept probability and the gradient are those of
@@ -485,6 +486,14 @@ int64_t l2hmc_train_grad_floats(int32_t d, int32_t H);
  * L2HMC_ERR_UNSUPPORTED when no fused kernel holds it (d / H beyond the 16-chain tile's 160 KiB plan, the funnel beyond
  * d = 16): the host then trains on the GEMM engine (l2hmc_train_split_grad below), which takes any d and H. */
 int64_t l2hmc_train_fused_lds_bytes(int32_t energy_kind, int32_t n_comp, int32_t d, int32_t H, int32_t T);
+/* Logistic regression (L2HMC_ENERGY_LOGISTIC) trains on a form of the general tile kernel of its own (l2hmc_last_kernel:
+ * "train_kernel<7>"): energy.mu = the packed data (l2hmc_pack_logistic), 1 <= energy.n_comp = n_data <= 2^20, energy.eta =
+ * sigma^2 > 0 and finite, d <= 128 -- the trajectory entry's rules.  grad U, U and the Hessian-vector product
+ * H(w) u = X^T [s (1 - s) (X u)] + u / sigma^2 are f32 MFMA contractions over the data streamed from L2, split over the four
+ * waves and summed in wave order (no atomics).  This query gives the dynamic LDS bytes of that kernel (> 0),
+ * L2HMC_ERR_UNSUPPORTED with the bytes quoted in l2hmc_last_error when the 16-chain tile does not fit 160 KiB (d = 50, H = 10,
+ * T = 10 does), L2HMC_ERR_ARG on bad arguments.  (l2hmc_train_fused_lds_bytes keeps refusing kind 7.) */
+int64_t l2hmc_train_logistic_lds_bytes(int32_t n_data, int32_t d, int32_t H, int32_t T);
 int l2hmc_train_propose_grad(const L2hmcTrainArgs* args, void* stream);
 
 /* One optimiser step's device work in as few launches as the data flow allows (ABI 4; SCGExperiment.ipynb raw 156-181,

@@ -11,7 +11,8 @@ from .sampler import chain_operator, propose, sample_chain, tf_accept  # noqa: F
 from . import tempering  # noqa: F401
 from .tempering import ParallelTempering, geometric_ladder  # noqa: F401
 from .distributions import LogisticRegression  # noqa: F401
+from .training import LogisticTrainer  # noqa: F401
 
 __all__ = ["Dynamics", "propose", "tf_accept", "chain_operator", "sample_chain", "ParallelTempering", "geometric_ladder",
-           "LogisticRegression",
+           "LogisticRegression", "LogisticTrainer",
            "layers", "distributions", "func_utils", "losses", "tempering"]

@@ -110,7 +110,8 @@ struct TLayout {
   int Wx, Wv, Gx, Gv, Ge, Msk, Trg, Mu, Pr, Lc, Ex, md, mh, wv, yv, cs, total;
   int ldd, ldh, P;
 };
-__host__ __device__ inline TLayout train_layout(int d, int H, int T, int ek, int nc) {
+// (data_global: the energy's data stays in global memory -- logistic regression -- so no mean / precision area is planned)
+__host__ __device__ inline TLayout train_layout(int d, int H, int T, int ek, int nc, bool data_global = false) {
   TLayout L;
   auto up4 = [](int n) { return (n + 3) / 4 * 4; };
   L.ldd = pitch(d); L.ldh = pitch(H); L.P = net_params(d, H);
@@ -122,9 +123,9 @@ __host__ __device__ inline TLayout train_layout(int d, int H, int T, int ek, int
   L.Ge = L.Gx + 2 * L.P; p += 4;
   L.Msk = p; p += up4(T * d);
   L.Trg = p; p += up4(2 * T);
-  L.Mu = p; p += up4(nc * d);
+  L.Mu = p; p += data_global ? 0 : up4(nc * d);
   const int npr = ek == L2HMC_ENERGY_GAUSS_DIAG ? d : (ek == L2HMC_ENERGY_ROUGHWELL ? 0 : nc * d * d);
-  L.Pr = p; p += up4(npr);
+  L.Pr = p; p += data_global ? 0 : up4(npr);
   L.Lc = p; p += up4(nc);
   L.Ex = p; p += 4 * up4(d);               // exp(lam_s), exp(lam_q) of the X net, then of the V net
   L.md = p; p += N_MD * TC * L.ldd;
@@ -416,7 +417,103 @@ __device__ __forceinline__ void t_net_bwd(const TCtx& X, const float* W, float* 
   TT_MARK(8);
 }
 
-template <bool TEMP>                             // TEMP: as train_fast_kernel (train_fast.hpp)
+// ---- Bayesian logistic regression on the tile's (16, ldd) LDS matrices (train_kernel<TEMP, true>) ------------------------
+// One wave's share of  X^T f(X z)  for the 16 chains: it takes the 16-row data blocks wave, wave + 4, ... of the packed data P
+// (l2hmc_pack_logistic, layout at logistic_block_floats; streamed from global memory / L2) over all tD state tiles and leaves
+// its partial (16, ldd) result in `part`; the caller sums the four partials in wave order.  Per block two f32 MFMA contractions
+// with no LDS trip between them, exactly as logistic_grad (l2hmc_kernels.hpp) runs them in the trajectory kernel:
+//   logits  L^T[i, c] = sum_k XA[i, k] z[c, k]   -- B operand: lane (c, q) reads z[c][16 tg + 4 q + r] from the LDS matrix; the
+//           result is in C/D layout, lane (c, q) holding data rows 4 q + r of the block,
+//   result  o^T[k, c] += sum_i XT[k, i] f[i, c]  -- that C/D layout is the B operand (k-step r = row 4 q + r) of this one, so
+//           the factor f is applied in registers:  !HV: f = sigmoid(L) - y  (the data term of grad U);
+//           HV: f = s (1 - s) (X u), a third contraction M^T = XA u^T sharing the A operand (the data term of Hessian(z) u).
+// A padded data row is a zero row of XA and a zero column of XT: it adds nothing to either result and is masked only in U
+// (softplus(0) = log 2 per row).  wantU (!HV, wave-uniform): this lane's share of the data term of U goes to Upart[wave * 64 + lane].
+// sigmoid / softplus are logistic_grad's forms (one v_exp_f32, one v_rcp_f32, log1p as v_log_f32(1 + e)).
+constexpr int TLNT = kLogisticMaxDim / 16;      // compiled state tiles (>= tD)
+template <bool HV>
+__device__ __forceinline__ void t_logistic(const TCtx& X, const float* P, int n, const float* z, const float* u, float* part,
+                                           float* Upart, bool wantU) {
+  const int NT = X.tD, nblk = (n + 15) >> 4, BS = logistic_block_floats(NT);
+  const int c = X.r, q = X.g, lane = X.lane, d = X.d, ldd = X.ldd;
+  // the B operands of the state (and of the direction): elements beyond d are zero (the pad columns of a row are not data)
+  f4 zb[TLNT], ub[TLNT], acc[TLNT];
+#pragma unroll
+  for (int tg = 0; tg < TLNT; ++tg) {
+    const int k0 = 16 * tg + 4 * q;
+    zb[tg] = f4{0.f, 0.f, 0.f, 0.f};
+    ub[tg] = f4{0.f, 0.f, 0.f, 0.f};
+    acc[tg] = f4{0.f, 0.f, 0.f, 0.f};
+    if (tg < NT) {
+      const int kc = k0 < ldd ? k0 : 0;
+      const f4 zz = ld4(z + c * ldd + kc);
+      zb[tg] = f4{k0 < d ? zz.x : 0.f, k0 + 1 < d ? zz.y : 0.f, k0 + 2 < d ? zz.z : 0.f, k0 + 3 < d ? zz.w : 0.f};
+      if constexpr (HV) {
+        const f4 uu = ld4(u + c * ldd + kc);
+        ub[tg] = f4{k0 < d ? uu.x : 0.f, k0 + 1 < d ? uu.y : 0.f, k0 + 2 < d ? uu.z : 0.f, k0 + 3 < d ? uu.w : 0.f};
+      }
+    }
+  }
+  float Ud = 0.f;
+  for (int ib = X.wave; ib < nblk; ib += TNW) {
+    const float* blk = P + (size_t)ib * BS;
+    f4 xa[TLNT], xt[TLNT];
+#pragma unroll
+    for (int tg = 0; tg < TLNT; ++tg) {
+      xa[tg] = tg < NT ? ld4(blk + (tg * 64 + lane) * 4) : f4{0.f, 0.f, 0.f, 0.f};
+      xt[tg] = tg < NT ? ld4(blk + ((NT + tg) * 64 + lane) * 4) : f4{0.f, 0.f, 0.f, 0.f};
+    }
+    f4 y = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (!HV) y = ld4(blk + 512 * NT + 4 * q);
+    f4 L = {0.f, 0.f, 0.f, 0.f}, M = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int tg = 0; tg < TLNT; ++tg) {
+      if (tg < NT) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          L = MFMA16(xa[tg][r], zb[tg][r], L);
+          if constexpr (HV) M = MFMA16(xa[tg][r], ub[tg][r], M);
+        }
+      }
+    }
+    // e = exp(-|L|): sigmoid = 1 / (1 + e) (L >= 0) or e / (1 + e); softplus(L) = max(L, 0) + log(1 + e)
+    const int row0 = 16 * ib + 4 * q;
+    f4 f;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const float l = L[r];
+      const float e = fexp(-fabsf(l));
+      const float inv = __builtin_amdgcn_rcpf(1.f + e);
+      const float sg = l >= 0.f ? inv : e * inv;
+      if constexpr (HV) {
+        f[r] = sg * (1.f - sg) * M[r];
+      } else {
+        f[r] = sg - y[r];
+        if (wantU && row0 + r < n) Ud += fmaf(-y[r], l, fmaxf(l, 0.f) + 0.6931471805599453f * __builtin_amdgcn_logf(1.f + e));
+      }
+    }
+#pragma unroll
+    for (int tg = 0; tg < TLNT; ++tg) {
+      if (tg < NT) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[tg] = MFMA16(xt[tg][r], f[r], acc[tg]);
+      }
+    }
+  }
+#pragma unroll
+  for (int tg = 0; tg < TLNT; ++tg) {
+    const int k0 = 16 * tg + 4 * q;
+    if (tg < NT && k0 < ldd) st4(part + c * ldd + k0, acc[tg]);
+  }
+  if constexpr (!HV) {
+    if (wantU) Upart[X.wave * 64 + lane] = Ud;
+  }
+}
+
+// TEMP: as train_fast_kernel (train_fast.hpp).  LOGI: the logistic-regression form (energy kind 7) -- grad U, U and the
+// Hessian-vector product are t_logistic's contractions over the packed data at A.mu (A.ncomp rows, A.eta = sigma^2); every
+// line of it sits under `if constexpr (LOGI)`, so the other instantiations compile to the code they had without it.
+template <bool TEMP, bool LOGI = false>
 __global__ __launch_bounds__(TTHREADS) void train_kernel(const TArgs A) {
   const float itemp = TEMP ? A.itemp : 1.f;
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -425,7 +522,7 @@ __global__ __launch_bounds__(TTHREADS) void train_kernel(const TArgs A) {
   const int d = A.d, H = A.H, T = A.T;
   const int ek = A.ekind;
   const int nc = ek == L2HMC_ENERGY_GMM ? A.ncomp : 1;
-  const TLayout L = train_layout(d, H, T, ek, nc);
+  const TLayout L = train_layout(d, H, T, ek, nc, LOGI);
   const int P = L.P, ldd = L.ldd;
   float *Wx = smem + L.Wx, *Wv = smem + L.Wv, *Gx = smem + L.Gx, *Gv = smem + L.Gv, *Ge = smem + L.Ge;
   float *Msk = smem + L.Msk, *Trg = smem + L.Trg, *Mu = smem + L.Mu, *Pr = smem + L.Pr, *Lc = smem + L.Lc;
@@ -467,7 +564,7 @@ __global__ __launch_bounds__(TTHREADS) void train_kernel(const TArgs A) {
     for (int i = tid; i < 2 * P + 4; i += TTHREADS) Gx[i] = 0.f;
     for (int i = tid; i < T * d; i += TTHREADS) Msk[i] = A.masks[i];
     for (int i = tid; i < 2 * T; i += TTHREADS) Trg[i] = A.trig[i];
-    if (ek != L2HMC_ENERGY_ROUGHWELL) {
+    if (!LOGI && ek != L2HMC_ENERGY_ROUGHWELL) {
       for (int i = tid; i < nc * d; i += TTHREADS) Mu[i] = A.mu[i];
       // (temperature: a Gaussian's U, grad U and Hessian are linear in its precision -- the tempered target is the Gaussian
       //  of precision P / temperature, so the precision is scaled here; the mixture scales its outputs instead)
@@ -498,8 +595,8 @@ __global__ __launch_bounds__(TTHREADS) void train_kernel(const TArgs A) {
   const float rw_den = A.den;
   // U / temperature: the Gaussians carry it in Pr (staging); Rough Well and the mixture multiply their finished outputs by
   // the wave-uniform 1 / temperature (the constant 1 in the untempered instantiation: folded away, the plain energy's code)
-  const float rs = ek == L2HMC_ENERGY_ROUGHWELL || ek == L2HMC_ENERGY_GMM ? itemp : 1.f;
-  const bool EL = ek == L2HMC_ENERGY_GAUSS_DIAG || ek == L2HMC_ENERGY_ROUGHWELL;   // elementwise grad / Hessian
+  const float rs = LOGI || ek == L2HMC_ENERGY_ROUGHWELL || ek == L2HMC_ENERGY_GMM ? itemp : 1.f;
+  const bool EL = !LOGI && (ek == L2HMC_ENERGY_GAUSS_DIAG || ek == L2HMC_ENERGY_ROUGHWELL);   // elementwise grad / Hessian
   float deps = 0.f;           // this thread's share of d loss / d eps
   int s_me = 0;               // step index of this thread's chain at iteration X.it
 
@@ -545,8 +642,25 @@ __global__ __launch_bounds__(TTHREADS) void train_kernel(const TArgs A) {
     for (int comp = 0; comp < nc; ++comp) w[comp] /= sum;
     return m + logf(sum);
   };
-  // g <- grad U(z) for the dense / mixture kinds (oracle/l2hmc_train_oracle.py *Target.grad); ends with a barrier
-  auto gradU_full = [&](const float* z, float* g) {
+  // logistic regression: the four waves' partial sums go to matrices that are idle while a gradient or a Hessian-vector
+  // product runs -- d zs, d zt, d zq (MDS ...: written by the *_half_bwd phases, consumed by t_net_bwd) and the ts cache (MTS:
+  // rewritten by the next t_net_fwd, its last readers are the *_half_fwd / *_half_bwd phases) -- and are added in wave order
+  auto lr_part = [&](int w) { return X.D(w < 3 ? MDS + w : MTS); };
+  auto lr_sum = [&](int q) { return ((lr_part(0)[q] + lr_part(1)[q]) + lr_part(2)[q]) + lr_part(3)[q]; };
+  // g <- grad U(z) for the dense / mixture kinds (oracle/l2hmc_train_oracle.py *Target.grad); ends with a barrier.
+  // (wantU, logistic regression only: also leave the data term of U(z) in WV / YV for energyU)
+  auto gradU_full = [&](const float* z, float* g, bool wantU = false) {
+    if constexpr (LOGI) {
+      t_logistic<false>(X, A.mu, A.ncomp, z, nullptr, lr_part(X.wave), WV, wantU);
+      __syncthreads();
+      const float iv = 1.f / A.eta;
+      for (int k = kb; k < d; k += 16) {
+        const int q = c * ldd + k;
+        g[q] = (lr_sum(q) + z[q] * iv) * rs;
+      }
+      __syncthreads();
+      return;
+    }
     if (ek == L2HMC_ENERGY_GMM) gmm_logw(z);
     const float* zrow = z + c * ldd;
     float w[KC];
@@ -567,7 +681,12 @@ __global__ __launch_bounds__(TTHREADS) void train_kernel(const TArgs A) {
   auto energyU = [&](const float* z, const float* g, int cc) {
     const float* zrow = z + cc * ldd;
     float u = 0.f;
-    if (ek == L2HMC_ENERGY_ROUGHWELL) {
+    if constexpr (LOGI) {      // the lanes' shares of the last gradU_full(z, ., true) in (wave, q) order, then the prior
+      for (int i = 0; i < 4 * TNW; ++i) u += WV[16 * i + cc];
+      float s = 0.f;
+      for (int k = 0; k < d; ++k) s += zrow[k] * zrow[k];
+      u += 0.5f * (1.f / A.eta) * s;
+    } else if (ek == L2HMC_ENERGY_ROUGHWELL) {
       for (int k = 0; k < d; ++k) u += 0.5f * zrow[k] * zrow[k] + A.eta * cosf(zrow[k] / rw_den);
     } else if (ek == L2HMC_ENERGY_GMM) {
       float w[KC];
@@ -579,6 +698,17 @@ __global__ __launch_bounds__(TTHREADS) void train_kernel(const TArgs A) {
   };
   // out <- Hessian(z) vec for the dense / mixture kinds (needs WV of the same z); ends with a barrier
   auto hessvec_full = [&](const float* z, const float* vec, float* out) {
+    if constexpr (LOGI) {
+      t_logistic<true>(X, A.mu, A.ncomp, z, vec, lr_part(X.wave), nullptr, false);
+      __syncthreads();
+      const float iv = 1.f / A.eta;
+      for (int k = kb; k < d; k += 16) {
+        const int q = c * ldd + k;
+        out[q] = (lr_sum(q) + vec[q] * iv) * rs;
+      }
+      __syncthreads();
+      return;
+    }
     const float* zrow = z + c * ldd;
     const float* vrow = vec + c * ldd;
     if (ek == L2HMC_ENERGY_GMM) {
@@ -663,7 +793,7 @@ __global__ __launch_bounds__(TTHREADS) void train_kernel(const TArgs A) {
     ldm[q] = 0.f;
     if (EL) mg[q] = g_elem(mx[q], k);
   EW_END
-  if (!EL) gradU_full(mx, mg);
+  if (!EL) gradU_full(mx, mg, true);
   if (tid < TC) {
     float K0 = 0.f;
     for (int k = 0; k < d; ++k) K0 += 0.5f * mv[tid * ldd + k] * mv[tid * ldd + k];
@@ -681,7 +811,7 @@ __global__ __launch_bounds__(TTHREADS) void train_kernel(const TArgs A) {
     x_half_fwd(mx, true, my, it);
     t_net_fwd(X, Wx, mvh, tmp);
     x_half_fwd(my, false, mxo, it);
-    if (!EL) gradU_full(mxo, mg);
+    if (!EL) gradU_full(mxo, mg, it == T - 1);
     t_net_fwd(X, Wv, mxo, mg);
     v_half_fwd(mvh, mv, false);
     { float* t = mx; mx = mxo; mxo = t; }            // x <- x'
@@ -1008,7 +1138,12 @@ static int plan_train(int ek, int nc, int d, int H, int T, int variant, TrainPla
     if (ek == L2HMC_ENERGY_GAUSS_DENSE || ek == L2HMC_ENERGY_FUNNEL) nw = d <= 16 ? 1 : 0;
   }
   const long long lds_small = 4LL * ts_layout(T).total, lds_fast = nw ? 4LL * tf_layout(T, nw).total : 0;
-  if (variant == 0 && small && lds_small <= 48 * 1024) {
+  if (ek == L2HMC_ENERGY_LOGISTIC) {
+    // logistic regression: the tile kernel's own form (train_kernel<TEMP, true>) at every d, H and variant.  Its LDS plan is
+    // train_layout without a mean / precision area: the data streams from L2, the waves' partial sums reuse idle matrices
+    p.lds = 4LL * train_layout(d, H, T, ek, 1, true).total;
+    if (p.lds > kMaxLdsBytes) return TRAIN_NO_LDS;
+  } else if (variant == 0 && small && lds_small <= 48 * 1024) {
     p.family = FAM_SMALL;
     p.lds = lds_small;
   } else if (nw && lds_fast <= kMaxLdsBytes) {
@@ -1029,13 +1164,16 @@ static int plan_train(int ek, int nc, int d, int H, int T, int variant, TrainPla
 static void note_train_plan(const TrainPlan& p) {
   if (p.family == FAM_SMALL) note_kernel("train_small_kernel<%lld, %lld>", p.ek, p.KH);
   else if (p.family == FAM_FAST) note_kernel("train_fast_kernel<%lld, %lld, %lld>", p.ek, p.NW, p.KH);
+  else if (p.ek == L2HMC_ENERGY_LOGISTIC) note_kernel("train_kernel<%lld>", p.ek);
   else note_kernel("train_kernel");
 }
 
 // The planned gradient kernel on `blocks` workgroups of 16 chains.  Compiled: train_small_kernel for kinds 1-4;
-// train_fast_kernel for the elementwise kinds (1, 4) with one or four waves, the dense Gaussian and the funnel (2, 5) with one.
+// train_fast_kernel for the elementwise kinds (1, 4) with one or four waves, the dense Gaussian and the funnel (2, 5) with one;
+// the logistic-regression form of train_kernel for kind 7.
 static int launch_train(const TrainPlan& p, const TArgs& k, long long blocks, hipStream_t s) {
   return on_either<true, false>(k.itemp != 1.f, [&](auto TEMP) {
+    if (p.ek == L2HMC_ENERGY_LOGISTIC) return launch_kernel(train_kernel<TEMP, true>, blocks, TTHREADS, p.lds, s, k);
     if (p.family == FAM_GENERAL) return launch_kernel(train_kernel<TEMP>, blocks, TTHREADS, p.lds, s, k);
     return on_either<3, 4>(p.KH == 3, [&](auto KH) {
       return on_either<1, 4>(p.NW == 1, [&](auto NW) {
@@ -1130,6 +1268,15 @@ int64_t l2hmc_train_fused_lds_bytes(int32_t ek, int32_t n_comp, int32_t d, int32
   return p.lds;
 }
 
+int64_t l2hmc_train_logistic_lds_bytes(int32_t n_data, int32_t d, int32_t H, int32_t T) {
+  if (n_data < 1 || n_data > kLogisticMaxRows || d < 1 || d > kLogisticMaxDim || H < 1 || H > 4096 || T < 1)
+    return fail(L2HMC_ERR_ARG, "l2hmc_train_logistic_lds_bytes: bad argument (1 <= n_data <= 1048576, 1 <= d <= 128, H, T >= 1)%s");
+  TrainPlan p;
+  if (plan_train(L2HMC_ENERGY_LOGISTIC, 1, d, H, T, 0, p) == TRAIN_NO_LDS)
+    return fail(L2HMC_ERR_UNSUPPORTED, "logistic-regression training kernel needs %s%lld bytes of LDS (> 160 KiB)", "", p.lds);
+  return p.lds;
+}
+
 static int train_launch(const L2hmcTrainArgs* a, const L2hmcTrainStep* st, void* stream) {
   if (!a) return fail(L2HMC_ERR_ARG, "args is NULL%s");
   if (st != nullptr) {
@@ -1161,11 +1308,19 @@ static int train_launch(const L2hmcTrainArgs* a, const L2hmcTrainStep* st, void*
     return fail(L2HMC_ERR_ARG, "l2hmc_train_propose_grad: NULL pointer%s");
   const int ek = a->energy.kind;
   if (ek != L2HMC_ENERGY_GAUSS_DIAG && ek != L2HMC_ENERGY_GAUSS_DENSE && ek != L2HMC_ENERGY_GMM &&
-      ek != L2HMC_ENERGY_ROUGHWELL && ek != L2HMC_ENERGY_FUNNEL)
-    return fail(L2HMC_ERR_UNSUPPORTED, "training supports the Gaussian, GMM, Rough-Well and funnel targets (analytic Hessian-vector products)%s");
+      ek != L2HMC_ENERGY_ROUGHWELL && ek != L2HMC_ENERGY_FUNNEL && ek != L2HMC_ENERGY_LOGISTIC)
+    return fail(L2HMC_ERR_UNSUPPORTED, "training supports the Gaussian, GMM, Rough-Well, funnel and logistic-regression targets (analytic Hessian-vector products)%s");
+  if (ek == L2HMC_ENERGY_LOGISTIC) {        // the trajectory entry's rules for this kind (check_energy, l2hmc_abi.hip)
+    if (!a->energy.mu) return fail(L2HMC_ERR_ARG, "logistic regression needs the packed data (mu, l2hmc_pack_logistic)%s");
+    if (a->energy.n_comp < 1 || a->energy.n_comp > kLogisticMaxRows)
+      return fail(L2HMC_ERR_ARG, "logistic regression needs 1 <= n_comp = n_data <= 1048576 (got %s%lld)", "", a->energy.n_comp);
+    if (a->d > kLogisticMaxDim) return fail(L2HMC_ERR_ARG, "logistic regression supports d <= 128 (got %s%lld)", "", a->d);
+    if (!(a->energy.eta > 0.f) || !(a->energy.eta <= 3.402823466e38f))
+      return fail(L2HMC_ERR_ARG, "logistic regression needs eta = prior variance sigma^2 > 0 and finite%s");
+  }
   if (ek == L2HMC_ENERGY_FUNNEL && (a->d > 16 || a->d < 2 || a->H > 15 || a->variant >= 100 || !(a->energy.eta > 0.f)))
     return fail(L2HMC_ERR_UNSUPPORTED, "funnel training: 2 <= d <= 16, H <= 15, sigma > 0 (register-resident kernel only)%s");
-  if (ek != L2HMC_ENERGY_ROUGHWELL && ek != L2HMC_ENERGY_FUNNEL && (!a->energy.mu || !a->energy.prec))
+  if (ek != L2HMC_ENERGY_ROUGHWELL && ek != L2HMC_ENERGY_FUNNEL && ek != L2HMC_ENERGY_LOGISTIC && (!a->energy.mu || !a->energy.prec))
     return fail(L2HMC_ERR_ARG, "energy needs mu and prec (RAW (d,d) precisions for the dense / GMM kinds)%s");
   if (ek == L2HMC_ENERGY_GMM && (!a->energy.logc || a->energy.n_comp < 1 || a->energy.n_comp > KC))
     return fail(L2HMC_ERR_ARG, "GMM training needs logc and 1 <= n_comp <= 8%s");
@@ -1182,7 +1337,7 @@ static int train_launch(const L2hmcTrainArgs* a, const L2hmcTrainStep* st, void*
   k.N = a->n_chains; k.d = a->d; k.H = a->H; k.T = a->T; k.x = a->x; k.v = a->v;
   k.dir = a->direction; k.dir_all = a->direction_all; k.ekind = a->energy.kind;
   k.mu = a->energy.mu; k.prec = a->energy.prec; k.logc = a->energy.logc; k.eta = a->energy.eta;
-  k.ncomp = ek == L2HMC_ENERGY_GMM ? a->energy.n_comp : 1; k.easy = a->energy.easy;
+  k.ncomp = (ek == L2HMC_ENERGY_GMM || ek == L2HMC_ENERGY_LOGISTIC) ? a->energy.n_comp : 1; k.easy = a->energy.easy;
   k.den = roughwell_den(&a->energy);
   k.itemp = 1.f / a->energy.temperature;
   k.scale = a->scale; k.inv_n = a->inv_n;

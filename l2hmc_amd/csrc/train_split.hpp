@@ -798,8 +798,9 @@ int l2hmc_train_split_grad(const L2hmcTrainSplitArgs* a, void* stream) {
     if ((rc = check_energy(a->energy, d))) return rc;
     const int ek = a->energy->kind;
     if (ek == L2HMC_ENERGY_LOGISTIC)
-      return fail(L2HMC_ERR_UNSUPPORTED, "no training on the logistic-regression target (its Hessian-vector products are not "
-                  "implemented): train on the same likelihood as a caller-supplied energy%s");
+      return fail(L2HMC_ERR_UNSUPPORTED, "the GEMM engine does not train on the logistic-regression target (its Hessian-vector "
+                  "product lives in l2hmc_train_propose_grad's tile kernel): train there, or on the same likelihood as a "
+                  "caller-supplied energy%s");
     if ((ek == L2HMC_ENERGY_GAUSS_DENSE || ek == L2HMC_ENERGY_GMM) && !a->hess)
       return fail(L2HMC_ERR_ARG, "dense Gaussian / mixture: hess = the RAW (n_comp, d, d) precisions%s");
     if (ek == L2HMC_ENERGY_GMM && a->energy->n_comp > HVP_MAXC)

@@ -192,7 +192,9 @@ class LogisticRegression(object):
 
     and its gradient X^T (sigmoid(X w) - y) + w / prior_var are fused into the trajectory kernels (two f32 MFMA contractions
     over the data per gradient): HMC and L2HMC sampling, parallel tempering and AIS run on it like on any built-in target.
-    Training a sampler on it is not fused: train on the same likelihood written as a torch callable, then load the state."""
+    A sampler trains on it with `LogisticTrainer` (the tile training kernel's logistic-regression form: the Hessian-vector
+    product is one more contraction over the data); shapes beyond that kernel's LDS plan train on the same likelihood written
+    as a torch callable."""
 
     def __init__(self, X, y, prior_var=1.0):
         X = np.asarray(X, dtype=np.float64)

@@ -61,15 +61,22 @@ def _refuse_annealed(dynamics):
                                   "(anneal_beta) Dynamics is not supported")
 
 
+_LOGISTIC_ROUTE = ("For shapes beyond the fused kernel, train with the same likelihood written as a torch callable -- "
+                   "Dynamics(d, fn, ...) with fn(w) = sum(softplus(X w) - y X w) + |w|^2 / (2 prior_var) trains on the GEMM-engine "
+                   "trainer -- then load the trained state_dict() into the Dynamics on the fused LogisticRegression energy to "
+                   "sample")
+
+
 class Trainer(object):
     def __new__(cls, dynamics, *args, **kwargs):
         fn = getattr(dynamics, "_fn", None)
         if fn is not None and getattr(fn, "kind", None) == _ffi.ENERGY_LOGISTIC:
-            raise NotImplementedError(
-                "no trainer runs on the fused logistic-regression target (its Hessian-vector products are not implemented). "
-                "Train with the same likelihood written as a torch callable -- Dynamics(d, fn, ...) with fn(w) = "
-                "sum(softplus(X w) - y X w) + |w|^2 / (2 prior_var) trains on the GEMM-engine trainer -- then load the trained "
-                "state_dict() into the Dynamics on the fused LogisticRegression energy to sample")
+            # (a class of its own, not a dispatch from here: LogisticTrainer, and only it, passes)
+            if not (isinstance(cls, type) and issubclass(cls, LogisticTrainer)):
+                raise NotImplementedError(
+                    "the fused logistic-regression target trains on LogisticTrainer(dynamics) (the tile kernel's "
+                    "logistic-regression form, H <= 15, d / H / T within its LDS plan), not on Trainer. " + _LOGISTIC_ROUTE)
+            return object.__new__(cls)
         if getattr(dynamics, "_user_nets", False):
             # dynamics.py:78-79 + SCGExperiment.ipynb raw 178-181: the reference minimises over whatever variables net_factory
             # created.  Arbitrary callables train on the GEMM-engine trainer, their adjoints by callback (ABI 6 net_vjp_cb).
@@ -226,10 +233,10 @@ class Trainer(object):
             prec = buf["prec"]
         elif fn.kind in (_ffi.ENERGY_GAUSS_DENSE, _ffi.ENERGY_GMM):
             prec = buf["_raw"]                         # RAW (k, d, d) precisions, not the MFMA packing
-        elif fn.kind in (_ffi.ENERGY_ROUGHWELL, _ffi.ENERGY_FUNNEL):
-            prec = None
+        elif fn.kind in (_ffi.ENERGY_ROUGHWELL, _ffi.ENERGY_FUNNEL, _ffi.ENERGY_LOGISTIC):
+            prec = None                                # (logistic regression: mu = the packed data, n_comp = rows, eta = prior variance)
         else:
-            raise NotImplementedError("training supports the Gaussian, GMM, Rough-Well and funnel targets")
+            raise NotImplementedError("training supports the Gaussian, GMM, Rough-Well, funnel and logistic-regression targets")
         a = _ffi.L2hmcTrainArgs()
         a.xnet, a.vnet = C.pointer(xs), C.pointer(vs)
         _refuse_annealed(dyn)
@@ -449,6 +456,34 @@ class Trainer(object):
         dyn._packed_key = None                          # the weights changed under the packed-fragment cache
         self._raise_if_stale()
         return lt[2], p12[:N], x_next, lr
+
+
+class LogisticTrainer(Trainer):
+    """`Trainer` for a `Dynamics` on a `LogisticRegression` energy with the fused S/T/Q nets (H <= 15): same constructor
+    arguments, `step`, `loss_and_grad`, `state_dict`, sharded all-reduce, native Adam and `use_temperature`.  The gradient
+    kernel is the logistic-regression form of the general tile kernel (`train_kernel<7>`): grad U, U and the Hessian-vector
+    product  H(w) u = X^T [s (1 - s) (X u)] + u / prior_var  are f32 MFMA contractions over the packed data, streamed from
+    L2.  The trained parameter tensors are the `Dynamics`' own: sample with it as it is.  A shape whose 16-chain tile does
+    not fit the kernel's LDS plan (`l2hmc_train_logistic_lds_bytes`) is refused with the torch-callable route."""
+
+    def __init__(self, dynamics, *args, **kwargs):
+        fn = getattr(dynamics, "_fn", None)
+        if fn is None or getattr(fn, "kind", None) != _ffi.ENERGY_LOGISTIC:
+            raise NotImplementedError("LogisticTrainer trains a Dynamics on a LogisticRegression energy: use Trainer(dynamics)")
+        if dynamics.hmc:
+            raise ValueError("an HMC-mode Dynamics has nothing to train")
+        _refuse_annealed(dynamics)
+        if getattr(dynamics, "_split", False) or getattr(dynamics, "_user_nets", False):
+            raise NotImplementedError("LogisticTrainer needs the fused S/T/Q nets (H <= 15, no caller-supplied nets). "
+                                      + _LOGISTIC_ROUTE)
+        L = _ffi.lib()
+        n, d, H, T = int(fn.n_comp), int(dynamics.x_dim), int(dynamics.H), int(dynamics.T)
+        rc = L.l2hmc_train_logistic_lds_bytes(n, d, H, T)
+        if rc == -2:                                       # L2HMC_ERR_UNSUPPORTED (include/l2hmc.h): the message quotes the bytes
+            raise NotImplementedError("no fused logistic-regression training kernel for n_data = %d, d = %d, H = %d, T = %d: %s. %s"
+                                      % (n, d, H, T, L.l2hmc_last_error().decode(), _LOGISTIC_ROUTE))
+        self.lds_bytes = _ffi.check(rc)
+        Trainer.__init__(self, dynamics, *args, **kwargs)
 
 
 _MLP_FIELDS = ("W1", "b1", "W2", "b2", "W3", "b3")
