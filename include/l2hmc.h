@@ -652,6 +652,27 @@ int64_t l2hmc_autocov_workspace_doubles(int64_t steps, int64_t n_chains, int32_t
 int l2hmc_autocov(const float* X, int64_t steps, int64_t n_chains, int32_t d, double scale,
                   int64_t n_total, double* sums_out, double* A_out, double* workspace, void* stream);
 
+/* Per-coordinate convergence diagnostics of a recorded chain history X (steps, N, d) kept on the device: the raw sums behind
+ * split R-hat and the effective sample size of Vehtari, Gelman, Simpson, Carpenter, Buerkner (2021), without rank
+ * normalisation (l2hmc_amd/diagnostics.py `finish` turns them into numbers on the host).  Unlike l2hmc_autocov the series are
+ * centred with their own means and the lag sums are kept apart by coordinate.
+ *   split = 1: Mh = steps / 2 and every chain is two series, rows [0, Mh) and [steps - Mh, steps) (an odd `steps` drops the
+ *              middle row): C = 2 N series per coordinate, first halves then second halves.  split = 0: Mh = steps, C = N.
+ *   mean_out (C, d)          m[c, k]  = mean_t x                                   (float64 accumulation)
+ *   m2_out   (C, d)          M2[c, k] = sum_t (x_t - m)^2                          (float64 accumulation)
+ *   G_out    (d, max_lag+1)  G[k, t]  = sum_c sum_{i < Mh - t} (x_i - m[c, k]) (x_{i+t} - m[c, k])
+ *                            (values centred in float64; products in float32 chunks of 32 steps folded into float64)
+ * These are what ranks that hold different chains all-reduce (G as it is, sum_c m, sum_c m^2, sum_c M2 and the count C).
+ * `workspace`: l2hmc_chain_stats_workspace_doubles(...) doubles, required -- every block writes its partial sums there and
+ * they are added in block order: no floating-point atomics, the outputs are bitwise reproducible.
+ * Its size does not grow with n_chains but with d: about 1024 blocks' worth of min(d, 256) (max_lag + 1) doubles, and the block
+ * count is a multiple of d / gcd(256, d) -- 7.7 MB at d = 25, 67 MB at d = 512, 536 MB at d = 511 with max_lag = 255 and split = 1.
+ * L2HMC_ERR_ARG (before any launch): a NULL pointer, steps / n_chains < 1, d outside 1 .. 512, split not 0 / 1, Mh < 4,
+ * C < 2, max_lag outside 0 .. Mh - 1.  A non-finite value makes the sums of its own coordinate non-finite, nothing else. */
+int64_t l2hmc_chain_stats_workspace_doubles(int64_t steps, int64_t n_chains, int32_t d, int32_t max_lag, int32_t split);
+int l2hmc_chain_stats(const float* X, int64_t steps, int64_t n_chains, int32_t d, int32_t max_lag, int32_t split,
+                      double* mean_out, double* m2_out, double* G_out, double* workspace, void* stream);
+
 /* Binding check.  The argument structs grow by trailing fields from one ABI version to the next (and
  * l2hmc_pack_nets' buffer by the lane layout: always size it with l2hmc_packed_nets_floats).  A binding built
  * against an older header would pass shorter structs, so besides comparing l2hmc_abi_version() with the

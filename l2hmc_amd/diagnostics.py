@@ -1,0 +1,171 @@
+"""Per-coordinate convergence diagnostics of a recorded history (steps, chains, dim): split R-hat and the effective sample size
+in the form of Vehtari, Gelman, Simpson, Carpenter, Buerkner (2021) / Stan, without rank normalisation.
+
+Unlike `func_utils.acl_spectrum` / `ESS` (the reference's diagnostic: no mean subtraction, one number summed over every
+coordinate) the series are centred with their own means, every coordinate gets its own numbers, and the chains are compared
+with each other -- what a posterior whose mean is not 0 needs.
+
+    s = summarize(x_hist[burn_in:])          # x_hist of sample_chain / Dynamics.run, cold_hist of ParallelTempering.run
+    s.max_rhat, s.min_ess, s.rhat, s.ess, s.mean, s.sd, s.truncated
+
+A ROCm tensor goes to the HIP kernels behind `l2hmc_chain_stats` (csrc/chain_stats.hip) where it lies -- a first-axis slice of a
+history is contiguous -- and only the per-coordinate sums (3 d + d (max_lag + 1) numbers) come back; a numpy history is computed in float64 numpy (the convention
+of `func_utils`: there is no CPU path for sampling, but diagnostics of a numpy history are host arithmetic).
+
+The estimator.  With `split` every chain becomes two, rows [0, Mh) and [M - Mh, M) with Mh = M // 2: C = 2 N series of length
+Mh per coordinate (first halves, then second halves); without it Mh = M, C = N.  Per series: mean m and M2 = sum (x - m)^2.  Per
+coordinate: W = mean_c M2 / (Mh - 1), B = Mh var_c(m), varp = (Mh - 1) / Mh W + B / Mh, rhat = sqrt(varp / W); lag sums
+G[t] = sum_c sum_{i < Mh - t} (x_i - m_c)(x_{i+t} - m_c), rho_t = 1 - (W - G[t] / (C (Mh - 1))) / varp; pairs
+P_j = rho_2j + rho_2j+1 up to the first P_j <= 0 (none within max_lag: `truncated`, ask for more lags), replaced by their running
+minimum; tau = -1 + 2 sum P; ess = C Mh / tau.
+"""
+import numpy as np
+
+DEFAULT_MAX_LAG = 255
+MAX_DEVICE_DIM = 512          # l2hmc_chain_stats: d <= 512
+
+
+def _is_device_tensor(X):
+    try:
+        import torch
+        return isinstance(X, torch.Tensor) and X.is_cuda
+    except ImportError:
+        return False
+
+
+def _shape(M, N, split, max_lag):
+    """(Mh, C, max_lag) of a (M, N, .) history, or ValueError."""
+    Mh = M // 2 if split else M
+    C = 2 * N if split else N
+    if Mh < 4 or C < 2:
+        raise ValueError("diagnostics need >= 4 steps per (split) chain and >= 2 chains (got %d, %d)" % (Mh, C))
+    if max_lag is None:
+        max_lag = min(Mh - 1, DEFAULT_MAX_LAG)
+    max_lag = int(max_lag)
+    if not 0 <= max_lag <= Mh - 1:
+        raise ValueError("max_lag must be in 0 .. steps per chain - 1 = %d (got %d)" % (Mh - 1, max_lag))
+    return Mh, C, max_lag
+
+
+def _device_sums(X, Mh, C, max_lag, split):
+    import torch
+    from . import _ffi
+    X = X.detach()
+    if X.dtype != torch.float32 or not X.is_contiguous():
+        X = X.to(torch.float32).contiguous()
+    M, N, d = X.shape
+    L = _ffi.lib()
+    ws = torch.empty(_ffi.check(L.l2hmc_chain_stats_workspace_doubles(M, N, d, max_lag, int(split))), dtype=torch.float64,
+                     device=X.device)
+    mean = torch.empty((C, d), dtype=torch.float64, device=X.device)
+    m2 = torch.empty((C, d), dtype=torch.float64, device=X.device)
+    G = torch.empty((d, max_lag + 1), dtype=torch.float64, device=X.device)
+    with torch.cuda.device(X.device):
+        _ffi.check(L.l2hmc_chain_stats(X.data_ptr(), M, N, d, max_lag, int(split), mean.data_ptr(), m2.data_ptr(),
+                                       G.data_ptr(), ws.data_ptr(), _ffi.current_stream(X.device)))
+    return mean, m2, G
+
+
+def _host_sums(X, Mh, max_lag, split):
+    X = np.asarray(X)
+    if X.dtype != np.float64:
+        X = X.astype(np.float64)
+    M = X.shape[0]
+    S = np.concatenate([X[:Mh], X[M - Mh:]], axis=1) if split else X             # (Mh, C, d)
+    with np.errstate(all="ignore"):                         # a non-finite entry makes its own coordinate NaN, quietly
+        mean = S.mean(axis=0)
+        Z = S - mean
+        m2 = np.einsum("tck,tck->ck", Z, Z)
+        G = np.empty((X.shape[2], max_lag + 1))
+        for t in range(max_lag + 1):
+            G[:, t] = np.einsum("tck,tck->k", Z[:Mh - t], Z[t:])
+    return mean, m2, G
+
+
+def chain_sums(X, max_lag=None, split=True):
+    """The raw sums of a (M, N, d) history: {'mean': (C, d), 'm2': (C, d), 'G': (d, max_lag + 1), 'n_steps': Mh, 'n_chains': C}.
+    A ROCm tensor -> HIP kernels, float64 device tensors (bitwise reproducible); numpy -> float64 numpy."""
+    if len(X.shape) != 3:
+        raise ValueError("a history is (steps, chains, dim); got shape %s" % (tuple(X.shape),))
+    M, N, d = (int(v) for v in X.shape)
+    Mh, C, max_lag = _shape(M, N, split, max_lag)
+    if d < 1:
+        raise ValueError("a history needs dim >= 1")
+    if _is_device_tensor(X):
+        if d > MAX_DEVICE_DIM:
+            raise ValueError("the diagnostic kernels hold dim <= %d (got %d)" % (MAX_DEVICE_DIM, d))
+        mean, m2, G = _device_sums(X, Mh, C, max_lag, split)
+    else:
+        try:
+            import torch
+            if isinstance(X, torch.Tensor):
+                X = X.detach().numpy()
+        except ImportError:
+            pass
+        mean, m2, G = _host_sums(X, Mh, max_lag, split)
+    return {"mean": mean, "m2": m2, "G": G, "n_steps": Mh, "n_chains": C}
+
+
+def _np(a):
+    return a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a, dtype=np.float64)
+
+
+def reduce_sums(sums):
+    """The per-coordinate reductions `finish` works from -- and ranks that hold different chains add up:
+    {'count': C, 'sum_mean': sum_c m, 'sum_mean_sq': sum_c m^2, 'sum_m2': sum_c M2, 'G', 'n_steps'} (float64 numpy).  Device
+    sums are reduced over chains on the device: 3 d + d (max_lag + 1) numbers come to the host, not the (C, d) arrays."""
+    mean, m2 = sums["mean"], sums["m2"]
+    if hasattr(mean, "detach"):
+        mean, m2 = mean.double(), m2.double()
+        parts = (mean.sum(dim=0), (mean * mean).sum(dim=0), m2.sum(dim=0))
+    else:
+        mean, m2 = np.asarray(mean, dtype=np.float64), np.asarray(m2, dtype=np.float64)
+        parts = (mean.sum(axis=0), (mean * mean).sum(axis=0), m2.sum(axis=0))
+    return {"count": float(mean.shape[0]), "sum_mean": _np(parts[0]), "sum_mean_sq": _np(parts[1]), "sum_m2": _np(parts[2]),
+            "G": _np(sums["G"]).astype(np.float64), "n_steps": int(sums["n_steps"])}
+
+
+class Summary(dict):
+    """The result of `summarize`: a dict whose entries also read as attributes (it pickles and copies like a dict)."""
+
+    def __getattr__(self, name):
+        try:
+            return self[name]
+        except KeyError:
+            raise AttributeError(name) from None
+
+
+def finish(sums):
+    """Steps 3, 5, 6 of the estimator on the host in float64 (d (max_lag + 1) numbers: not a kernel), from `chain_sums`'
+    result or from its `reduce_sums` form (the sharded path all-reduces that form).  A coordinate with W = 0 or a non-finite
+    entry gets rhat = ess = NaN, the others are untouched."""
+    r = sums if "sum_mean" in sums else reduce_sums(sums)
+    C, Mh, G = float(r["count"]), int(r["n_steps"]), np.asarray(r["G"], dtype=np.float64)
+    d, nlag = G.shape
+    with np.errstate(all="ignore"):
+        mean = r["sum_mean"] / C
+        W = r["sum_m2"] / C / (Mh - 1)
+        B = Mh * (r["sum_mean_sq"] - r["sum_mean"] ** 2 / C) / (C - 1)
+        varp = (Mh - 1) / Mh * W + B / Mh
+        ok = np.isfinite(W) & np.isfinite(varp) & np.isfinite(G).all(axis=1) & (W > 0)
+        rhat = np.where(ok, np.sqrt(varp / W), np.nan)
+        rho = 1.0 - (W[:, None] - G / (C * (Mh - 1))) / varp[:, None]
+        n_pairs = nlag // 2                                   # a trailing unpaired lag is ignored
+        P = rho[:, 0:2 * n_pairs:2] + rho[:, 1:2 * n_pairs:2]
+        P = np.where(ok[:, None], P, 1.0)                     # placeholders: the coordinate is NaN below
+        stop = P <= 0
+        K = np.where(stop.any(axis=1), stop.argmax(axis=1), n_pairs) if n_pairs else np.zeros(d, dtype=np.int64)
+        Pm = np.minimum.accumulate(P, axis=1) if n_pairs else P
+        tau = -1.0 + 2.0 * np.where(np.arange(n_pairs)[None, :] < K[:, None], Pm, 0.0).sum(axis=1)
+        ess = np.where(ok, C * Mh / tau, np.nan)
+        sd = np.sqrt(varp)
+    truncated = ok & (K == n_pairs)
+    return Summary(mean=mean, sd=sd, rhat=rhat, ess=ess, truncated=truncated, n_steps=Mh, n_chains=int(round(C)),
+                   max_lag=nlag - 1, min_ess=float(np.min(ess)) if d else float("nan"),
+                   max_rhat=float(np.max(rhat)) if d else float("nan"))
+
+
+def summarize(X, max_lag=None, split=True):
+    """Per-coordinate `mean`, `sd`, `rhat`, `ess`, `truncated` of a (steps, chains, dim) history, with `n_steps`, `n_chains`,
+    `max_lag`, `min_ess` and `max_rhat` (NaN when any coordinate is degenerate: a constant or non-finite series)."""
+    return finish(chain_sums(X, max_lag=max_lag, split=split))

@@ -3,8 +3,9 @@
 Chains never interact on the sampling path (every tensor is (N, ...) with no
 cross-chain term), so the chain batch is cut into contiguous blocks -- rank r owns rows
 [r*N/W, (r+1)*N/W) -- and the leapfrog kernels run with NO data-path collective.  The only
-exchanges are small statistics: the mean accept probability and the autocovariance partial
-sums behind ESS (utils/func_utils.py:45-54,114-120), each ONE flat all-reduce.  Backend
+exchanges are small statistics: the mean accept probability, the autocovariance partial
+sums behind ESS (utils/func_utils.py:45-54,114-120) and the per-coordinate sums behind split R-hat /
+ESS (`diagnostics`), each ONE flat all-reduce.  Backend
 "nccl" is RCCL over xGMI on the GPU box; "gloo" is used by the CPU tests.
 """
 import numpy as np
@@ -74,3 +75,22 @@ def ess(X_local, scale, n_total):
     """ESS per MH step (utils/func_utils.py:118-120) of sharded chains."""
     from .func_utils import ESS
     return float(ESS(acl_spectrum(X_local, scale, n_total)))
+
+
+def diagnostics(X_local, max_lag=None, split=True):
+    """`diagnostics.summarize` (split R-hat, per-coordinate ESS) for chains sharded over ranks: every rank forms the raw
+    sums of its own chains (a ROCm tensor: the HIP kernels, the history stays in HBM), ONE all-reduce of
+    [count | sum_c m | sum_c m^2 | sum_c M2 | G] per coordinate, then `diagnostics.finish`; equals the single-process value
+    on the concatenated chains.  Ranks may hold different numbers of chains (each at least one; two without `split`), but
+    the same number of steps, and must pass the same `max_lag`."""
+    from . import diagnostics as dg
+    r = dg.reduce_sums(dg.chain_sums(X_local, max_lag=max_lag, split=split))
+    d, nlag = r["G"].shape
+    flat = torch.from_numpy(np.concatenate([[r["count"]], r["sum_mean"], r["sum_mean_sq"], r["sum_m2"], r["G"].ravel()]))
+    if isinstance(X_local, torch.Tensor) and X_local.is_cuda and world()[1] > 1 and dist.get_backend() != "gloo":
+        flat = _allreduce_sum(flat.to(X_local.device)).cpu()
+    else:
+        flat = _allreduce_sum(flat)
+    flat = flat.numpy()
+    return dg.finish({"count": float(flat[0]), "sum_mean": flat[1:1 + d], "sum_mean_sq": flat[1 + d:1 + 2 * d],
+                      "sum_m2": flat[1 + 2 * d:1 + 3 * d], "G": flat[1 + 3 * d:].reshape(d, nlag), "n_steps": r["n_steps"]})
