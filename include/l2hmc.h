@@ -673,6 +673,48 @@ int64_t l2hmc_chain_stats_workspace_doubles(int64_t steps, int64_t n_chains, int
 int l2hmc_chain_stats(const float* X, int64_t steps, int64_t n_chains, int32_t d, int32_t max_lag, int32_t split,
                       double* mean_out, double* m2_out, double* G_out, double* workspace, void* stream);
 
+/* Warm-up: the step size eps = exp(*alpha) adapted on the device between launches of the sampler loop (csrc/adapt.hip;
+ * l2hmc_amd/warmup.py drives it).  Every trajectory entry point reads *alpha from device memory when its kernel starts, so a
+ * kernel that rewrites *alpha in place sets the step size of the next launch on the same stream: no host read, no synchronise,
+ * no allocation, and no prepared copy of anything holds eps.
+ *
+ * `state`: L2HMC_ADAPT_STATE_DOUBLES device doubles.
+ *   [0] phase (0 search, 1 averaging, 2 finished)   [1] dir (0, +1, -1)   [2] t   [3] log_eps   [4] log_eps_bar   [5] H_bar
+ *   [6] mu   [7] last mean accept   [8] updates seen   [9..14] target, gamma, t0, kappa, log_eps_min, log_eps_max   [15] 0
+ *
+ * l2hmc_adapt_init reads *alpha on the device and writes the state: log_eps = (double) *alpha (not clamped), everything else 0;
+ *   search = 0 starts in phase 1 with mu = log_eps + ln 10.
+ * l2hmc_adapt_update takes p, the p_out of the window just run ((M, N) flattened: n floats), and does, in this order and in
+ *   float64:
+ *     a = (sum of p_i, a non-finite p_i counted as 0) / n
+ *     phase 0 (Hoffman & Gelman 2014, Alg. 4, on the mean over chains):  d = a > 0.5 ? +1 : -1;  if dir == 0: dir = d;
+ *       if d == dir: log_eps = clamp(log_eps + dir ln 2), and a clamp that binds starts averaging (below) at the clamped value;
+ *       else start averaging: phase = 1, mu = log_eps + ln 10, t = 0, H_bar = 0, log_eps_bar = 0 (log_eps stays).
+ *     phase 1 (Alg. 5):  t += 1;  w = 1 / (t + t0);  H_bar = (1 - w) H_bar + w (target - a);
+ *       log_eps = clamp(mu - sqrt(t) / gamma H_bar);  e = t^-kappa;  log_eps_bar = e log_eps + (1 - e) log_eps_bar.
+ *     phase 2: nothing.
+ *     then *alpha = (float) log_eps, state[7] = a, state[8] += 1 and, if trace_row4 is given,
+ *       trace_row4 = {a, log_eps the window ran at, log_eps now set, phase after}.
+ *   mode L2HMC_ADAPT_REDUCE alone only writes sums2 = {sum of p_i, n}; L2HMC_ADAPT_APPLY alone takes a = sums2[0] / sums2[1] and
+ *   ignores p and n -- what ranks run around ONE all-reduce of the two doubles; mode 3 does both in one launch (and writes sums2
+ *   when it is given).  The sum has a fixed order (csrc/adapt.hip) and uses no floating-point atomics: state, alpha and trace are
+ *   bitwise reproducible.  Windows of up to L2HMC_ADAPT_SINGLE_BLOCK_MAX values are one launch of one workgroup and need no
+ *   workspace (l2hmc_adapt_workspace_doubles returns 0; NULL is fine); larger ones take a second small kernel and
+ *   l2hmc_adapt_workspace_doubles(n) doubles (at most 1024).
+ * l2hmc_adapt_finish: if t >= 1 then log_eps = log_eps_bar; phase = 2; *alpha = (float) log_eps.
+ * L2HMC_ERR_ARG (before any launch): a NULL p (when reducing) / state / alpha (when applying), n < 1, a mode outside 1 .. 3,
+ * one mode bit alone without sums2, n beyond the single-workgroup form without workspace; init: search not 0 / 1, target
+ * outside (0, 1), gamma / t0 / kappa not positive, log_eps_min >= log_eps_max. */
+#define L2HMC_ADAPT_STATE_DOUBLES 16
+#define L2HMC_ADAPT_SINGLE_BLOCK_MAX 65536
+enum { L2HMC_ADAPT_REDUCE = 1, L2HMC_ADAPT_APPLY = 2 };   /* mode bits; 3 = both in one launch */
+int64_t l2hmc_adapt_workspace_doubles(int64_t n);
+int l2hmc_adapt_init(double* state, const float* alpha, int32_t search, double target_accept, double gamma, double t0,
+                     double kappa, double log_eps_min, double log_eps_max, void* stream);
+int l2hmc_adapt_update(const float* p, int64_t n, int32_t mode, double* sums2, double* state, float* alpha, double* trace_row4,
+                       double* workspace, void* stream);
+int l2hmc_adapt_finish(double* state, float* alpha, void* stream);
+
 /* Binding check.  The argument structs grow by trailing fields from one ABI version to the next (and
  * l2hmc_pack_nets' buffer by the lane layout: always size it with l2hmc_packed_nets_floats).  A binding built
  * against an older header would pass shorter structs, so besides comparing l2hmc_abi_version() with the

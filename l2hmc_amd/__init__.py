@@ -13,7 +13,8 @@ from .tempering import ParallelTempering, geometric_ladder  # noqa: F401
 from .distributions import LogisticRegression  # noqa: F401
 from .training import LogisticTrainer  # noqa: F401
 from .diagnostics import summarize  # noqa: F401
+from .warmup import warmup  # noqa: F401  (the function; its module stays importable as `from l2hmc_amd.warmup import ...`)
 
 __all__ = ["Dynamics", "propose", "tf_accept", "chain_operator", "sample_chain", "ParallelTempering", "geometric_ladder",
-           "LogisticRegression", "LogisticTrainer", "summarize", "diagnostics",
+           "LogisticRegression", "LogisticTrainer", "summarize", "diagnostics", "warmup",
            "layers", "distributions", "func_utils", "losses", "tempering"]

@@ -4,8 +4,8 @@ Chains never interact on the sampling path (every tensor is (N, ..
 cross-chain term), so the chain batch is cut into contiguous blocks -- rank r owns rows
 [r*N/W, (r+1)*N/W) -- and the leapfrog kernels run with NO data-path collective.  The only
 exchanges are small statistics: the mean accept probability, the autocovariance partial
-sums behind ESS (utils/func_utils.py:45-54,114-120) and the per-coordinate sums behind split R-hat /
-ESS (`diagnostics`), each ONE flat all-reduce.  Backend
+sums behind ESS (utils/func_utils.py:45-54,114-120), the per-coordinate sums behind split R-hat /
+ESS (`diagnostics`) and the two doubles per window of the step-size warm-up (`warmup`), each ONE flat all-reduce.  Backend
 "nccl" is RCCL over xGMI on the GPU box; "gloo" is used by the CPU tests.
 """
 import numpy as np
@@ -94,3 +94,20 @@ def diagnostics(X_local, max_lag=None, split=True):
     flat = flat.numpy()
     return dg.finish({"count": float(flat[0]), "sum_mean": flat[1:1 + d], "sum_mean_sq": flat[1 + d:1 + 2 * d],
                       "sum_m2": flat[1 + 2 * d:1 + 3 * d], "G": flat[1 + 3 * d:].reshape(d, nlag), "n_steps": r["n_steps"]})
+
+
+def warmup(x_local, dynamics, n_updates=100, *, n_total=None, **kwargs):
+    """`warmup.warmup` (step size by dual averaging, on the device) for chains sharded over ranks: per window every rank
+    reduces its own accept probabilities to {sum, count} (`l2hmc_adapt_update`, mode REDUCE), ONE all-reduce of the two
+    doubles, then every rank applies the same update (mode APPLY) -- so every rank holds bit-identical state and alpha.
+    `n_total`: chains over all ranks (default: this rank's count times the world size); the Philox `chain_offset` comes
+    from `shard_range`, so a seeded run draws the same numbers however the chains are sharded."""
+    from .warmup import warmup as _warmup
+    if "chain_offset" in kwargs:
+        raise TypeError("sharding.warmup derives chain_offset from shard_range")
+    rank, size = world()
+    n_local = int(x_local.shape[0])
+    lo, hi = shard_range(n_local * size if n_total is None else n_total, rank, size)
+    if hi - lo != n_local:
+        raise ValueError("rank %d owns chains [%d, %d) of %s but was given %d" % (rank, lo, hi, n_total, n_local))
+    return _warmup(x_local, dynamics, n_updates, chain_offset=lo, _allreduce=_allreduce_sum, **kwargs)
