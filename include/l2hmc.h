@@ -673,6 +673,26 @@ int64_t l2hmc_chain_stats_workspace_doubles(int64_t steps, int64_t n_chains, int
 int l2hmc_chain_stats(const float* X, int64_t steps, int64_t n_chains, int32_t d, int32_t max_lag, int32_t split,
                       double* mean_out, double* m2_out, double* G_out, double* workspace, void* stream);
 
+/* Bayesian logistic regression: the per-row sums behind the posterior predictive, the lppd and WAIC over every recorded draw
+ * (csrc/predictive.hip; l2hmc_amd/predictive.py `finish` turns them into numbers on the host).
+ *   draws   (n_draws, d) float32 row-major on the device, read in place: a first-axis slice of a recorded history (M, N, d)
+ *           viewed as (M N, d) is fine -- only 4-byte alignment is needed.
+ *   packed  the buffer l2hmc_pack_logistic wrote for (X, y) with the same d (its labels are used; pack zeros when there are
+ *           none: the first sum does not depend on them), 16-byte aligned.
+ *   sums    (4, n_data) float64, with l = x_i . w_s, z = (2 y_i - 1) l, both over the draws s:
+ *             [0] sum sigmoid(l)   [1] sum lik, lik = sigmoid(z)   [2] sum ll, ll = log lik = -softplus(-z)   [3] sum ll^2
+ *           The logits are float32 (f32-input MFMA, features past d contribute zero), sigmoid / softplus use the hardware
+ *           exp, log and reciprocal in float32; every value is converted to float64 BEFORE it is added and ll^2 is formed in
+ *           float64.  sum lik = 0 (every draw's likelihood below float32's range) is a value, not an error: the caller reports it.
+ * `workspace`: l2hmc_logistic_predict_workspace_doubles(...) doubles, required -- every wave writes its partial sums there
+ * and a second kernel adds them in a fixed order: no floating-point atomics, two calls give identical bits.  At most about
+ * 4096 x 256 x 4 doubles whatever the shape, 4 n_data when n_data is large.
+ * L2HMC_ERR_ARG (before any launch): n_draws < 2, n_data outside 1 .. 1048576, d outside 1 .. 128, n_draws > 2^40 / d, a NULL
+ * or misaligned pointer. */
+int64_t l2hmc_logistic_predict_workspace_doubles(int64_t n_draws, int32_t n_data, int32_t d);
+int l2hmc_logistic_predict(const float* draws, int64_t n_draws, int32_t d, const float* packed, int32_t n_data,
+                           double* sums /* (4, n_data) */, double* workspace, void* stream);
+
 /* Warm-up: the step size eps = exp(*alpha) adapted on the device between launches of the sampler loop (csrc/adapt.hip;
  * l2hmc_amd/warmup.py drives it).  Every trajectory entry point reads *alpha from device memory when its kernel starts, so a
  * kernel that rewrites *alpha in place sets the step size of the next launch on the same stream: no host read, no synchronise,

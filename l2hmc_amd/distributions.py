@@ -230,6 +230,17 @@ class LogisticRegression(object):
         nll = np.logaddexp(0.0, L) - L * self.y.astype(np.float64)
         return -(nll.sum(axis=1) + 0.5 * np.square(W).sum(axis=1) / self.prior_var)
 
+    def predict_proba(self, draws, X=None):
+        """The posterior predictive P(y = 1) of every row of X (default: the model's own rows) under the draws -- a recorded
+        history (M, N, d) or a matrix (S, d); a ROCm tensor is read where it lies (`predictive.predict_proba`)."""
+        from . import predictive
+        return predictive.predict_proba(draws, self.X if X is None else X)
+
+    def waic(self, draws):
+        """WAIC of this model's own data under the draws (`predictive.waic`): a `Summary` with elpd_waic, p_waic, lppd, se."""
+        from . import predictive
+        return predictive.waic(draws, self.X, self.y)
+
 
 def as_device_f32(x, device=None):
     """numpy / torch input -> contiguous float32 tensor on the GPU."""

@@ -5,7 +5,7 @@ cross-chain term), so the chain batch is cut into contiguous blocks -- rank r ow
 [r*N/W, (r+1)*N/W) -- and the leapfrog kernels run with NO data-path collective.  The only
 exchanges are small statistics: the mean accept probability, the autocovariance partial
 sums behind ESS (utils/func_utils.py:45-54,114-120), the per-coordinate sums behind split R-hat /
-ESS (`diagnostics`) and the two doubles per window of the step-size warm-up (`warmup`), each ONE flat all-reduce.  Backend
+ESS (`diagnostics`), the four per-row sums behind the posterior predictive and WAIC (`predictive`) and the two doubles per window of the step-size warm-up (`warmup`), each ONE flat all-reduce.  Backend
 "nccl" is RCCL over xGMI on the GPU box; "gloo" is used by the CPU tests.
 """
 import numpy as np
@@ -94,6 +94,24 @@ def diagnostics(X_local, max_lag=None, split=True):
     flat = flat.numpy()
     return dg.finish({"count": float(flat[0]), "sum_mean": flat[1:1 + d], "sum_mean_sq": flat[1 + d:1 + 2 * d],
                       "sum_m2": flat[1 + 2 * d:1 + 3 * d], "G": flat[1 + 3 * d:].reshape(d, nlag), "n_steps": r["n_steps"]})
+
+
+def predictive(draws_local, X, y=None):
+    """`predictive.finish(predictive.pointwise_sums(...))` (posterior predictive, lppd, WAIC) for chains sharded over ranks:
+    every rank forms the four per-row sums of its own draws (a ROCm tensor: the HIP kernel, the history stays in HBM), ONE
+    all-reduce of [n_draws | sum_p | sum_lik | sum_ll | sum_ll2], then `finish`; equals the single-process value on the
+    concatenated draws.  Every rank passes the same rows X (and labels y); ranks may hold different numbers of draws."""
+    from . import predictive as pd
+    s = pd.pointwise_sums(draws_local, X, y)
+    n = s["sum_p"].shape[0]
+    flat = torch.from_numpy(np.concatenate([[float(s["n_draws"])], s["sum_p"], s["sum_lik"], s["sum_ll"], s["sum_ll2"]]))
+    if isinstance(draws_local, torch.Tensor) and draws_local.is_cuda and world()[1] > 1 and dist.get_backend() != "gloo":
+        flat = _allreduce_sum(flat.to(draws_local.device)).cpu()
+    else:
+        flat = _allreduce_sum(flat)
+    flat = flat.numpy()
+    return pd.finish({"n_draws": int(round(flat[0])), "sum_p": flat[1:1 + n], "sum_lik": flat[1 + n:1 + 2 * n],
+                      "sum_ll": flat[1 + 2 * n:1 + 3 * n], "sum_ll2": flat[1 + 3 * n:1 + 4 * n]})
 
 
 def warmup(x_local, dynamics, n_updates=100, *, n_total=None, **kwargs):
