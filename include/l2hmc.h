@@ -673,6 +673,47 @@ int64_t l2hmc_chain_stats_workspace_doubles(int64_t steps, int64_t n_chains, int
 int l2hmc_chain_stats(const float* X, int64_t steps, int64_t n_chains, int32_t d, int32_t max_lag, int32_t split,
                       double* mean_out, double* m2_out, double* G_out, double* workspace, void* stream);
 
+/* The same sums for the indicator series y = ((double) x <= thresholds[k]) ? 1 : 0 of every coordinate k, applied as the value
+ * is loaded (no indicator history is written): what the effective sample size of a quantile estimate is made of (Vehtari et
+ * al. 2021, `ess_quantile`; l2hmc_amd/quantiles.py).  `thresholds`: d float64 on the device.  The contract, the argument checks
+ * and the workspace size are those of l2hmc_chain_stats; a NaN value or threshold gives y = 0. */
+int l2hmc_chain_stats_below(const float* X, int64_t steps, int64_t n_chains, int32_t d, int32_t max_lag, int32_t split,
+                            const double* thresholds /* (d), device */, double* mean_out, double* m2_out, double* G_out,
+                            double* workspace, void* stream);
+
+/* Exact order statistics of every coordinate of a history kept on the device (csrc/order_stats.hip; l2hmc_amd/quantiles.py
+ * builds quantiles, tail-ESS and the quantile MCSE on them).
+ *   X       (n_draws, d) float32, contiguous, read in place: element (i, k) at X[i d + k] -- a recorded history (M, N, d) with
+ *           n_draws = M N, or a first-axis slice of one.
+ *   ranks   (n_ranks, d) int64 on the device, 0-based; every coordinate has its own.
+ *   values  (n_ranks, d) float32: values[r, k] is the element a full ascending sort of coordinate k puts at position
+ *           ranks[r, k] -- one of the input's own values, exact.  -0 sorts before +0, every NaN after +inf (and comes back as a
+ *           NaN); a rank at or past n_draws gives the maximum, a negative one the minimum.
+ *   n_nan   (d) int64: the NaNs of each coordinate.
+ * Method: most-significant-digit radix select on the monotone key of a float (bits ^ 0xFFFFFFFF when negative, else
+ * bits | 0x80000000) in l2hmc_order_stats_passes() passes of log2 l2hmc_order_stats_bins() bits.  A pass is a COUNT -- the
+ * history is read once per coordinate / rank group (64 (coordinate, rank) pairs fit one group; pass 0 needs no rank groups) and
+ * hist[r, k, :] receives the histogram of the next digit of the keys that share the prefix of (r, k) -- and an ADVANCE that
+ * picks the digit in which the remaining rank falls.  Counts are integers added with integer atomics: every output is bitwise
+ * reproducible, and histograms of different draws simply add (ranks that hold different draws all-reduce `hist`, and n_nan in
+ * pass 0, between the two halves).  Nothing returns to the host between passes; nothing is allocated.
+ *   workspace   l2hmc_order_stats_workspace_bytes(d, n_ranks) bytes, 16-byte aligned: hist | remaining | prefix.
+ *   prefix      (n_ranks, d) uint32, zero before pass 0 (not read in pass 0: may be NULL there);
+ *   remaining   (n_ranks, d) int64, the ranks before pass 0; both are updated by every advance.
+ * l2hmc_order_stats is exactly count, advance for pass 0, 1, ... on the workspace: both routes give the same bits.
+ * L2HMC_ERR_ARG (before any launch): n_draws < 1, d outside 1 .. 512, n_ranks outside 1 .. 32, n_draws > 2^40 / d, a pass
+ * outside 0 .. passes - 1, a NULL pointer that the pass needs. */
+int32_t l2hmc_order_stats_passes(void);
+int32_t l2hmc_order_stats_bins(void);                         /* bins of the widest pass */
+int64_t l2hmc_order_stats_workspace_bytes(int32_t d, int32_t n_ranks);
+int l2hmc_order_stats(const float* X, int64_t n_draws, int32_t d, const int64_t* ranks, int32_t n_ranks, float* values,
+                      int64_t* n_nan, void* workspace, void* stream);
+int l2hmc_order_stats_count(const float* X, int64_t n_draws, int32_t d, int32_t n_ranks, int32_t pass, const uint32_t* prefix,
+                            int64_t* hist /* (n_ranks, d, bins), zeroed by the call */,
+                            int64_t* n_nan /* written in pass 0, else may be NULL */, void* stream);
+int l2hmc_order_stats_advance(const int64_t* hist, int64_t* remaining, uint32_t* prefix, int32_t d, int32_t n_ranks,
+                              int32_t pass, float* values /* written after the last pass, else may be NULL */, void* stream);
+
 /* Bayesian logistic regression: the per-row sums behind the posterior predictive, the lppd and WAIC over every recorded draw
  * (csrc/predictive.hip; l2hmc_amd/predictive.py `finish` turns them into numbers on the host).
  *   draws   (n_draws, d) float32 row-major on the device, read in place: a first-axis slice of a recorded history (M, N, d)

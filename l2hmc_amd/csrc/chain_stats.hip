@@ -22,6 +22,10 @@
 //           workspace.
 //   pass 3  chain_lagsum_reduce_kernel: G[k, t] = the blocks' partials added in block order.  No floating-point atomics anywhere:
 //           the result is bitwise reproducible.
+//
+// l2hmc_chain_stats_below: the same three passes on the indicator series y = [x <= thresholds[coordinate]] (the effective sample
+// size of a quantile estimate, l2hmc_amd/quantiles.py).  The device functions take the transform as a functor (CsValue, CsBelow);
+// chain_moments_below_kernel and chain_lagsum_below_kernel are kernels of their own, pass 3 is shared as it is.
 #include "l2hmc_kernels.hpp"
 
 namespace l2hmc {
@@ -74,36 +78,62 @@ static bool chain_stats_plan(const char* who, int64_t steps, int64_t n_chains, i
   return true;
 }
 
+// What a series is made of: the recorded value itself, or (l2hmc_chain_stats_below) the indicator of "at or below the
+// coordinate's threshold", applied as the value is loaded.  The comparison is in float64: an indicator flips discretely.
+struct CsValue {
+  __device__ __forceinline__ float operator()(float v) const { return v; }
+};
+struct CsBelow {
+  double thr;
+  __device__ __forceinline__ float operator()(float v) const { return (double)v <= thr ? 1.f : 0.f; }
+};
+
 // ---- pass 1 ---------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kCsThreads) void chain_moments_kernel(const float* __restrict__ X, long long J, long long Mh,
-                                                                   long long row1, double* __restrict__ mean_out,
-                                                                   double* __restrict__ m2_out) {
-  const long long j = (long long)blockIdx.x * kCsThreads + threadIdx.x;
-  if (j >= J) return;
+template <class F>
+__device__ __forceinline__ void cs_moments(const float* __restrict__ X, long long J, long long Mh, long long row1, long long j,
+                                           double* __restrict__ mean_out, double* __restrict__ m2_out, const F f) {
   const float* col = X + (blockIdx.y ? row1 : 0) * J + j;
   double s = 0.0;
   long long t = 0;
   for (; t + 8 <= Mh; t += 8) {                       // 8 independent loads in flight per thread, added in row order
     float v[8];
 #pragma unroll
-    for (int u = 0; u < 8; ++u) v[u] = col[(t + u) * J];
+    for (int u = 0; u < 8; ++u) v[u] = f(col[(t + u) * J]);
 #pragma unroll
     for (int u = 0; u < 8; ++u) s += (double)v[u];
   }
-  for (; t < Mh; ++t) s += (double)col[t * J];
+  for (; t < Mh; ++t) s += (double)f(col[t * J]);
   const double m = s / (double)Mh;
   double q = 0.0;
   for (t = 0; t + 8 <= Mh; t += 8) {
     float v[8];
 #pragma unroll
-    for (int u = 0; u < 8; ++u) v[u] = col[(t + u) * J];
+    for (int u = 0; u < 8; ++u) v[u] = f(col[(t + u) * J]);
 #pragma unroll
     for (int u = 0; u < 8; ++u) { const double c = (double)v[u] - m; q = fma(c, c, q); }
   }
-  for (; t < Mh; ++t) { const double c = (double)col[t * J] - m; q = fma(c, c, q); }
+  for (; t < Mh; ++t) { const double c = (double)f(col[t * J]) - m; q = fma(c, c, q); }
   const long long o = (long long)blockIdx.y * J + j;  // (C, d) with chain = half * N + n
   mean_out[o] = m;
   m2_out[o] = q;
+}
+
+__global__ __launch_bounds__(kCsThreads) void chain_moments_kernel(const float* __restrict__ X, long long J, long long Mh,
+                                                                   long long row1, double* __restrict__ mean_out,
+                                                                   double* __restrict__ m2_out) {
+  const long long j = (long long)blockIdx.x * kCsThreads + threadIdx.x;
+  if (j >= J) return;
+  cs_moments(X, J, Mh, row1, j, mean_out, m2_out, CsValue());
+}
+
+__global__ __launch_bounds__(kCsThreads) void chain_moments_below_kernel(const float* __restrict__ X, long long J, long long Mh,
+                                                                         long long row1, int d,
+                                                                         const double* __restrict__ thresholds,
+                                                                         double* __restrict__ mean_out,
+                                                                         double* __restrict__ m2_out) {
+  const long long j = (long long)blockIdx.x * kCsThreads + threadIdx.x;
+  if (j >= J) return;
+  cs_moments(X, J, Mh, row1, j, mean_out, m2_out, CsBelow{thresholds[j % d]});
 }
 
 // ---- pass 2 ---------------------------------------------------------------------------------------------------------------
@@ -115,16 +145,16 @@ __device__ __forceinline__ float cs_centre(float v, double m, float keep) { retu
 // every load is in bounds.  A value past the end enters as 0 through a wave-uniform factor, not a branch: the loads of a whole
 // block of 32 steps are independent of its arithmetic and can all be in flight.  (A series with a non-finite last row is NaN
 // with or without the factor.)  kFirst: tau0 = 0, x_t is the ring's head and is not loaded again.
-template <bool kFirst>
+template <bool kFirst, class F>
 __device__ __forceinline__ void cs_series(const float* __restrict__ X, long long o, long long J, long long tau0, long long Mh,
-                                          double m, double (&dacc)[kCsLags]) {
+                                          double m, double (&dacc)[kCsLags], const F f) {
   float w[kCsLags], acc[kCsLags];
   const long long last = Mh - 1;
   long long o0 = o, o1 = o + (tau0 < last ? tau0 : last) * J;
 #pragma unroll
   for (int l = 0; l < kCsLags; ++l) {
     const long long r = tau0 + l;
-    w[l] = cs_centre(X[o1], m, r < Mh ? 1.f : 0.f);
+    w[l] = cs_centre(f(X[o1]), m, r < Mh ? 1.f : 0.f);
     o1 += r < last ? J : 0;
     asm volatile("" : "+v"(o1));
     if (l % 8 == 7) __builtin_amdgcn_sched_barrier(0);       // 8 loads in flight at a time, not 32 addresses and values
@@ -138,12 +168,12 @@ __device__ __forceinline__ void cs_series(const float* __restrict__ X, long long
       if (kFirst) {
         x0 = w[u];
       } else {
-        x0 = cs_centre(X[o0], m, t < Mh ? 1.f : 0.f);
+        x0 = cs_centre(f(X[o0]), m, t < Mh ? 1.f : 0.f);
         o0 += t < last ? J : 0;
       }
 #pragma unroll
       for (int l = 0; l < kCsLags; ++l) acc[l] = fmaf(x0, w[(u + l) % kCsLags], acc[l]);
-      w[u] = cs_centre(X[o1], m, t1 < Mh ? 1.f : 0.f);
+      w[u] = cs_centre(f(X[o1]), m, t1 < Mh ? 1.f : 0.f);
       o1 += t1 < last ? J : 0;
       // keep the walk a vector add per step: left alone, the compiler forms 64 row offsets u J in scalar registers, runs out of
       // them and moves them through lanes of a vector register inside the loop
@@ -154,10 +184,11 @@ __device__ __forceinline__ void cs_series(const float* __restrict__ X, long long
   }
 }
 
-__global__ __launch_bounds__(kCsThreads) void chain_lagsum_kernel(const float* __restrict__ X, long long J, long long Mh,
-                                                                  long long row1, int d, int nslot, long long nchunks,
-                                                                  int max_lag, const double* __restrict__ mean,
-                                                                  double* __restrict__ part) {
+// kBelow: the series are indicators of "at or below thresholds[coordinate]" (a thread's coordinate never changes across chunks)
+template <bool kBelow>
+__device__ __forceinline__ void cs_lagsum(const float* __restrict__ X, long long J, long long Mh, long long row1, int d, int nslot,
+                                          long long nchunks, int max_lag, const double* __restrict__ mean,
+                                          const double* __restrict__ thresholds, double* __restrict__ part) {
   __shared__ double sm[kCsLdsLags][kCsThreads];
   const int tid = threadIdx.x;
   const long long nb = gridDim.x, tau0 = (long long)blockIdx.y * kCsLags;
@@ -175,8 +206,14 @@ __global__ __launch_bounds__(kCsThreads) void chain_lagsum_kernel(const float* _
     // out of this loop and held in ~100 vector registers across it.  They cost a scalar compare each: recompute them per chunk.
     long long mh = Mh;
     asm volatile("" : "+s"(mh));
-    if (tau0 == 0) cs_series<true>(base, j, J, tau0, mh, m, dacc);
-    else cs_series<false>(base, j, J, tau0, mh, m, dacc);
+    if constexpr (kBelow) {
+      const CsBelow f{thresholds[j % d]};
+      if (tau0 == 0) cs_series<true>(base, j, J, tau0, mh, m, dacc, f);
+      else cs_series<false>(base, j, J, tau0, mh, m, dacc, f);
+    } else {
+      if (tau0 == 0) cs_series<true>(base, j, J, tau0, mh, m, dacc, CsValue());
+      else cs_series<false>(base, j, J, tau0, mh, m, dacc, CsValue());
+    }
   }
 
   // threads tid, tid + d, tid + 2 d, ... hold the same coordinate: add them in that order, 8 lags per round
@@ -196,6 +233,21 @@ __global__ __launch_bounds__(kCsThreads) void chain_lagsum_kernel(const float* _
       if (lag < nlag) part[(blk * nslot + slot) * nlag + lag] = a;
     }
   }
+}
+
+__global__ __launch_bounds__(kCsThreads) void chain_lagsum_kernel(const float* __restrict__ X, long long J, long long Mh,
+                                                                  long long row1, int d, int nslot, long long nchunks,
+                                                                  int max_lag, const double* __restrict__ mean,
+                                                                  double* __restrict__ part) {
+  cs_lagsum<false>(X, J, Mh, row1, d, nslot, nchunks, max_lag, mean, nullptr, part);
+}
+
+__global__ __launch_bounds__(kCsThreads) void chain_lagsum_below_kernel(const float* __restrict__ X, long long J, long long Mh,
+                                                                        long long row1, int d, int nslot, long long nchunks,
+                                                                        int max_lag, const double* __restrict__ mean,
+                                                                        const double* __restrict__ thresholds,
+                                                                        double* __restrict__ part) {
+  cs_lagsum<true>(X, J, Mh, row1, d, nslot, nchunks, max_lag, mean, thresholds, part);
 }
 
 // ---- pass 3 ---------------------------------------------------------------------------------------------------------------
@@ -241,6 +293,27 @@ int l2hmc_chain_stats(const float* X, int64_t steps, int64_t n_chains, int32_t d
                      p.row0[1], mean_out, m2_out);
   hipLaunchKernelGGL(chain_lagsum_kernel, dim3((unsigned)p.nb, (unsigned)p.ntile, (unsigned)p.halves), dim3(kCsThreads), 0, s, X,
                      p.J, p.Mh, p.row0[1], (int)d, p.nslot, p.nchunks, (int)max_lag, (const double*)mean_out, workspace);
+  hipLaunchKernelGGL(chain_lagsum_reduce_kernel, dim3((unsigned)((d * nlag + 255) / 256)), dim3(256), 0, s,
+                     (const double*)workspace, p.nb * p.halves, p.nb, (int)d, p.nslot, nlag, G_out);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(L2HMC_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
+  return L2HMC_OK;
+}
+
+int l2hmc_chain_stats_below(const float* X, int64_t steps, int64_t n_chains, int32_t d, int32_t max_lag, int32_t split,
+                            const double* thresholds, double* mean_out, double* m2_out, double* G_out, double* workspace,
+                            void* stream) {
+  ChainStatsPlan p;
+  if (!chain_stats_plan("l2hmc_chain_stats_below", steps, n_chains, d, max_lag, split, p)) return L2HMC_ERR_ARG;
+  if (!X || !thresholds || !mean_out || !m2_out || !G_out || !workspace)
+    return fail(L2HMC_ERR_ARG, "l2hmc_chain_stats_below: X, thresholds, mean_out, m2_out, G_out and workspace are required%s");
+  hipStream_t s = (hipStream_t)stream;
+  const long long nlag = (long long)max_lag + 1;
+  hipLaunchKernelGGL(chain_moments_below_kernel, dim3((unsigned)p.nchunks, (unsigned)p.halves), dim3(kCsThreads), 0, s, X, p.J,
+                     p.Mh, p.row0[1], (int)d, thresholds, mean_out, m2_out);
+  hipLaunchKernelGGL(chain_lagsum_below_kernel, dim3((unsigned)p.nb, (unsigned)p.ntile, (unsigned)p.halves), dim3(kCsThreads), 0,
+                     s, X, p.J, p.Mh, p.row0[1], (int)d, p.nslot, p.nchunks, (int)max_lag, (const double*)mean_out, thresholds,
+                     workspace);
   hipLaunchKernelGGL(chain_lagsum_reduce_kernel, dim3((unsigned)((d * nlag + 255) / 256)), dim3(256), 0, s,
                      (const double*)workspace, p.nb * p.halves, p.nb, (int)d, p.nslot, nlag, G_out);
   hipError_t e = hipGetLastError();

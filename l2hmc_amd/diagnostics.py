@@ -47,7 +47,8 @@ def _shape(M, N, split, max_lag):
     return Mh, C, max_lag
 
 
-def _device_sums(X, Mh, C, max_lag, split):
+def _device_sums(X, Mh, C, max_lag, split, thresholds=None):
+    """`thresholds` (d float64): the sums of the indicator series [x <= thresholds[k]] (`l2hmc_chain_stats_below`)."""
     import torch
     from . import _ffi
     X = X.detach()
@@ -61,8 +62,13 @@ def _device_sums(X, Mh, C, max_lag, split):
     m2 = torch.empty((C, d), dtype=torch.float64, device=X.device)
     G = torch.empty((d, max_lag + 1), dtype=torch.float64, device=X.device)
     with torch.cuda.device(X.device):
-        _ffi.check(L.l2hmc_chain_stats(X.data_ptr(), M, N, d, max_lag, int(split), mean.data_ptr(), m2.data_ptr(),
-                                       G.data_ptr(), ws.data_ptr(), _ffi.current_stream(X.device)))
+        if thresholds is None:
+            _ffi.check(L.l2hmc_chain_stats(X.data_ptr(), M, N, d, max_lag, int(split), mean.data_ptr(), m2.data_ptr(),
+                                           G.data_ptr(), ws.data_ptr(), _ffi.current_stream(X.device)))
+        else:
+            thr = torch.as_tensor(np.ascontiguousarray(thresholds, dtype=np.float64)).to(X.device)
+            _ffi.check(L.l2hmc_chain_stats_below(X.data_ptr(), M, N, d, max_lag, int(split), thr.data_ptr(), mean.data_ptr(),
+                                                 m2.data_ptr(), G.data_ptr(), ws.data_ptr(), _ffi.current_stream(X.device)))
     return mean, m2, G
 
 
@@ -82,7 +88,17 @@ def _host_sums(X, Mh, max_lag, split):
     return mean, m2, G
 
 
-def chain_sums(X, max_lag=None, split=True):
+def chain_sums_below(X, thresholds, max_lag=None, split=True):
+    """`chain_sums` of the indicator series y = [x <= thresholds[k]] (compared in float64) of a (M, N, d) history, which is
+    never written out: what the effective sample size of a quantile estimate is computed from (`quantiles.describe`).  A NaN
+    value or threshold gives y = 0."""
+    thresholds = np.asarray(thresholds, dtype=np.float64)
+    if thresholds.shape != (int(X.shape[-1]),):
+        raise ValueError("thresholds must be (dim,) = (%d,); got shape %s" % (int(X.shape[-1]), thresholds.shape))
+    return chain_sums(X, max_lag=max_lag, split=split, _thresholds=thresholds)
+
+
+def chain_sums(X, max_lag=None, split=True, _thresholds=None):
     """The raw sums of a (M, N, d) history: {'mean': (C, d), 'm2': (C, d), 'G': (d, max_lag + 1), 'n_steps': Mh, 'n_chains': C}.
     A ROCm tensor -> HIP kernels, float64 device tensors (bitwise reproducible); numpy -> float64 numpy."""
     if len(X.shape) != 3:
@@ -94,7 +110,7 @@ def chain_sums(X, max_lag=None, split=True):
     if _is_device_tensor(X):
         if d > MAX_DEVICE_DIM:
             raise ValueError("the diagnostic kernels hold dim <= %d (got %d)" % (MAX_DEVICE_DIM, d))
-        mean, m2, G = _device_sums(X, Mh, C, max_lag, split)
+        mean, m2, G = _device_sums(X, Mh, C, max_lag, split, _thresholds)
     else:
         try:
             import torch
@@ -102,6 +118,9 @@ def chain_sums(X, max_lag=None, split=True):
                 X = X.detach().numpy()
         except ImportError:
             pass
+        if _thresholds is not None:
+            with np.errstate(invalid="ignore"):
+                X = (np.asarray(X).astype(np.float64) <= _thresholds).astype(np.float64)
         mean, m2, G = _host_sums(X, Mh, max_lag, split)
     return {"mean": mean, "m2": m2, "G": G, "n_steps": Mh, "n_chains": C}
 

@@ -5,7 +5,7 @@ cross-chain term), so the chain batch is cut into contiguous blocks -- rank r ow
 [r*N/W, (r+1)*N/W) -- and the leapfrog kernels run with NO data-path collective.  The only
 exchanges are small statistics: the mean accept probability, the autocovariance partial
 sums behind ESS (utils/func_utils.py:45-54,114-120), the per-coordinate sums behind split R-hat /
-ESS (`diagnostics`), the four per-row sums behind the posterior predictive and WAIC (`predictive`) and the two doubles per window of the step-size warm-up (`warmup`), each ONE flat all-reduce.  Backend
+ESS (`diagnostics`), the integer digit histograms behind posterior quantiles (`describe`), the four per-row sums behind the posterior predictive and WAIC (`predictive`) and the two doubles per window of the step-size warm-up (`warmup`), each ONE flat all-reduce.  Backend
 "nccl" is RCCL over xGMI on the GPU box; "gloo" is used by the CPU tests.
 """
 import numpy as np
@@ -84,16 +84,47 @@ def diagnostics(X_local, max_lag=None, split=True):
     on the concatenated chains.  Ranks may hold different numbers of chains (each at least one; two without `split`), but
     the same number of steps, and must pass the same `max_lag`."""
     from . import diagnostics as dg
-    r = dg.reduce_sums(dg.chain_sums(X_local, max_lag=max_lag, split=split))
+    return _finish_chain_sums(dg.chain_sums(X_local, max_lag=max_lag, split=split), X_local)
+
+
+def _on_device_collective(X_local):
+    return isinstance(X_local, torch.Tensor) and X_local.is_cuda and world()[1] > 1 and dist.get_backend() != "gloo"
+
+
+def _finish_chain_sums(sums, X_local):
+    """`diagnostics.finish` of this rank's `chain_sums` after ONE all-reduce of their per-coordinate reductions."""
+    from . import diagnostics as dg
+    r = dg.reduce_sums(sums)
     d, nlag = r["G"].shape
     flat = torch.from_numpy(np.concatenate([[r["count"]], r["sum_mean"], r["sum_mean_sq"], r["sum_m2"], r["G"].ravel()]))
-    if isinstance(X_local, torch.Tensor) and X_local.is_cuda and world()[1] > 1 and dist.get_backend() != "gloo":
+    if _on_device_collective(X_local):
         flat = _allreduce_sum(flat.to(X_local.device)).cpu()
     else:
         flat = _allreduce_sum(flat)
     flat = flat.numpy()
     return dg.finish({"count": float(flat[0]), "sum_mean": flat[1:1 + d], "sum_mean_sq": flat[1 + d:1 + 2 * d],
                       "sum_m2": flat[1 + 2 * d:1 + 3 * d], "G": flat[1 + 3 * d:].reshape(d, nlag), "n_steps": r["n_steps"]})
+
+
+def describe(X_local, probs=(0.05, 0.5, 0.95), max_lag=None, split=True):
+    """`quantiles.describe` (quantiles, `ess_quantile`, `ess_tail`, `mcse_quantile` on top of `diagnostics`) for chains sharded
+    over ranks.  The exchanges: one all-reduce of [S_local]; per `order_statistics` call (two: the quantiles, the MCSE
+    positions) one all-reduce of the integer digit histograms per radix pass, between `l2hmc_order_stats_count` and
+    `l2hmc_order_stats_advance` (the first carries n_nan); the single all-reduce of `diagnostics` per chain-sums call (one for
+    the values, one per quantile's indicator series).  Integer histograms add exactly, so the quantiles are bit-identical to
+    the single-process value on the concatenated chains; the `ess_*` agree to all-reduce rounding.  Ranks may hold different
+    numbers of chains, but the same number of steps, and must pass the same `probs` and `max_lag`."""
+    from . import quantiles as qt
+
+    def allreduce(t):
+        # integer counts: a backend that cannot reduce device tensors (gloo) gets them on the host
+        if t.is_cuda and not _on_device_collective(X_local):
+            return _allreduce_sum(t.cpu())
+        if not t.is_cuda and _on_device_collective(X_local):
+            return _allreduce_sum(t.to(X_local.device)).cpu()
+        return _allreduce_sum(t)
+    return qt._describe(X_local, probs, max_lag, split, allreduce=allreduce,
+                        finish=lambda sums: _finish_chain_sums(sums, X_local))
 
 
 def predictive(draws_local, X, y=None):
