@@ -55,9 +55,12 @@ class EnergyFunction(object):
             self._dev[key] = buf
         return self._dev[key]
 
-    def c_struct(self, device, temperature=1.0, anneal_beta=0.0):
+    def c_struct(self, device, temperature=1.0, anneal_beta=0.0, raw_prec=False):
+        """include/l2hmc.h L2hmcEnergy over this device's buffers.  raw_prec: the RAW (k, d, d) precisions of a dense Gaussian /
+        mixture instead of their MFMA packing (what the fused training kernels read); the other kinds have one form only."""
         b = self._buffers(device)
-        return _ffi.L2hmcEnergy(self.kind, self.n_comp, _ffi.ptr(b['mu']), _ffi.ptr(b['prec']),
+        prec = b['_raw'] if raw_prec and '_raw' in b else b['prec']
+        return _ffi.L2hmcEnergy(self.kind, self.n_comp, _ffi.ptr(b['mu']), _ffi.ptr(prec),
                                 _ffi.ptr(b['logc']), self.eta, int(self.easy), float(temperature),
                                 float(anneal_beta), self.den, 0)
 
@@ -102,7 +105,7 @@ class UserEnergy(EnergyFunction):
     def _buffers(self, device):
         raise NotImplementedError("a caller-supplied energy has no fused-kernel parameters")
 
-    def c_struct(self, device, temperature=1.0, anneal_beta=0.0):
+    def c_struct(self, device, temperature=1.0, anneal_beta=0.0, raw_prec=False):
         raise NotImplementedError("a caller-supplied energy runs through L2hmcSplitArgs.energy_cb, not L2hmcEnergy")
 
     def _call(self, f, x, aux):

@@ -265,6 +265,66 @@ class Dynamics(object):
         self.mask = sd['mask']
         self._packed_key = None
 
+    # ---- what every launch tells the library about this Dynamics (the sampler's launches below, the trainers' in training.py) ----
+    def _temperature(self):
+        """dynamics.py:204-205: U / temperature if `use_temperature`, else the plain U."""
+        return float(self.temperature) if self.use_temperature else 1.0
+
+    def _net_structs(self):
+        """The (XNet, VNet) pair of include/l2hmc.h L2hmcNet over the parameter tensors' current addresses.  An args struct only
+        POINTS at them (`C.pointer`): the caller's frame holds the pair until the library call has returned."""
+        return tuple(_ffi.L2hmcNet(*[w[k].data_ptr() for k in _ffi.NET_FIELDS]) for w in (self._xw, self._vw))
+
+    def _set_step_size(self, a):
+        """alpha / eps_host of an args struct: eps = exp(alpha) read on the device, or `eps_override` from the host."""
+        if self.eps_override is None:
+            a.alpha, a.eps_host = self.alpha.data_ptr(), 0.0
+        else:
+            a.alpha, a.eps_host = None, float(self.eps_override)
+
+    @staticmethod
+    def _ws_view(ws):
+        """view(ptr, n, cols, ld): the (n, cols) block with row stride `ld` at device address `ptr` inside the workspace tensor
+        `ws` -- the library hands its callbacks addresses inside the workspace: they are viewed, not copied."""
+        base = ws.data_ptr()
+
+        def view(ptr, n, cols, ld):
+            return ws.as_strided((n, cols), (ld, 1), (ptr - base) // 4)
+        return view
+
+    def _energy_callbacks(self, ws, temperature, anneal_beta, aux, cb_error):
+        """(energy_cb, hvp_cb): the Python bodies of include/l2hmc.h's L2hmcEnergyCallback / L2hmcHvpCallback for this Dynamics'
+        caller-supplied energy, working on views of the workspace tensor `ws` the library points into (torch enqueues on its
+        current stream, which is the stream the library was given).  energy_cb writes grad [(1 - b) |x|^2 / 2 + b U] /
+        temperature (b = anneal_beta: such an energy anneals itself, `UserEnergy.evaluate`) and, where asked, U as float64;
+        hvp_cb the Hessian-vector product of U / temperature (the trainer's launches only: the sampler ignores it)."""
+        fn, view, base = self._fn, self._ws_view(ws), ws.data_ptr()
+
+        def energy_cb(_user, xp, ldx, n, dd, Up, gp, ldg, _stream):
+            try:
+                U, g = fn.evaluate(view(xp, n, dd, ldx), temperature, want_U=bool(Up), want_grad=True, aux=aux,
+                                   anneal_beta=anneal_beta)
+                if tuple(g.shape) != (n, dd):
+                    raise ValueError("grad_energy must return shape (N, d), got %s" % (tuple(g.shape),))
+                view(gp, n, dd, ldg).copy_(g)
+                if Up:
+                    o = (Up - base) // 4
+                    ws[o:o + 2 * n].view(torch.float64).copy_(U)
+                return 0
+            except Exception as e:                     # never let an exception cross the C frame
+                cb_error.append(e)
+                return 1
+
+        def hvp_cb(_user, xp, ldx, up, ldu, n, dd, hp, ldh, _stream):
+            try:
+                hv = fn.hvp(view(xp, n, dd, ldx), view(up, n, dd, ldu), aux=aux)
+                view(hp, n, dd, ldh).copy_(hv / temperature if temperature != 1.0 else hv)
+                return 0
+            except Exception as e:
+                cb_error.append(e)
+                return 1
+        return energy_cb, hvp_cb
+
     def _net_callbacks(self, ws, direction, aux, cb_error):
         """(net_cb, net_vjp_cb): the Python bodies of include/l2hmc.h's L2hmcNetCallback / L2hmcNetVjpCallback for this
         Dynamics' caller-supplied nets (dynamics.py:69-79: any callable [a, b, tau, aux] -> [S, T, Q]), working on views of the
@@ -273,11 +333,11 @@ class Dynamics(object):
         grad must not hang a graph on the persistent workspace); net_vjp_cb RE-evaluates the net on the kept inputs with
         autograd on and runs ONE backward: the inputs' cotangents go to the library, the parameters' gradients accumulate
         in their `.grad` (which the trainer aliases to its flat gradient vector)."""
-        base, T = ws.data_ptr(), self.T
+        view, T = self._ws_view(ws), self.T
         fwd_mask = (direction != 0) if direction is not None else None
 
         def inputs(net, abp, ldab, n, dd, it, dall):
-            ab = ws.as_strided((n, 2 * dd), (ldab, 1), (abp - base) // 4)
+            ab = view(abp, n, 2 * dd, ldab)
             if fwd_mask is not None:
                 tau = self._trig[torch.where(fwd_mask, it, T - 1 - it)]
             else:
@@ -299,7 +359,7 @@ class Dynamics(object):
         def net_cb(_user, net, abp, ldab, n, dd, it, _dirp, dall, outp, _stream):
             try:
                 fn, a, b, tau = inputs(net, abp, ldab, n, dd, it, dall)
-                out = ws.as_strided((n, 3 * dd), (3 * dd, 1), (outp - base) // 4)
+                out = view(outp, n, 3 * dd, 3 * dd)
                 for i, t in enumerate(outputs(fn([a, b, tau, aux]), n, dd)):
                     out[:, i * dd:(i + 1) * dd] = t
                 return 0
@@ -312,8 +372,8 @@ class Dynamics(object):
                 with torch.no_grad():
                     fn, a, b, tau = inputs(net, abp, ldab, n, dd, it, dall)
                     a, b = a.clone().requires_grad_(True), b.clone().requires_grad_(True)
-                    dstq = ws.as_strided((n, 3 * dd), (3 * dd, 1), (dstqp - base) // 4)
-                    dab = ws.as_strided((n, 2 * dd), (ld_dab, 1), (dabp - base) // 4)
+                    dstq = view(dstqp, n, 3 * dd, 3 * dd)
+                    dab = view(dabp, n, 2 * dd, ld_dab)
                 with torch.enable_grad():
                     stq = outputs(fn([a, b, tau, aux]), n, dd)
                     live = [(t, dstq[:, i * dd:(i + 1) * dd]) for i, t in enumerate(stq) if t.requires_grad]
@@ -341,13 +401,12 @@ class Dynamics(object):
             n = _ffi.check(L.l2hmc_packed_nets_floats(self.x_dim, self.H))
             if self._packed is None or self._packed.numel() != n:
                 self._packed = torch.empty(n, dtype=torch.float32, device=self.device)
-            structs = []
             for w in (self._xw, self._vw):
                 for k in _ffi.NET_FIELDS:
                     if not w[k].is_contiguous():
                         raise ValueError("net parameter %s must be contiguous" % k)
-                structs.append(_ffi.L2hmcNet(*[w[k].data_ptr() for k in _ffi.NET_FIELDS]))
-            _ffi.check(L.l2hmc_pack_nets(structs[0], structs[1], self.x_dim, self.H,
+            xs, vs = self._net_structs()
+            _ffi.check(L.l2hmc_pack_nets(xs, vs, self.x_dim, self.H,
                                          self._packed.data_ptr(), _ffi.current_stream(self.device)))
             self._packed_key = key
         return self._packed
@@ -444,8 +503,7 @@ class Dynamics(object):
         if self.hmc or self._user_nets:               # (HMC, either direction: the inverse leapfrog is the step with -eps)
             xs = vs = enc = None
         else:
-            xs = _ffi.L2hmcNet(*[self._xw[k].data_ptr() for k in _ffi.NET_FIELDS])
-            vs = _ffi.L2hmcNet(*[self._vw[k].data_ptr() for k in _ffi.NET_FIELDS])
+            xs, vs = self._net_structs()
             enc = mlp3_struct(self._xw['aux_encoder']) if self._xw['aux_encoder'] is not None else None
         L = _ffi.lib()
         H_ws = 4 if self._user_nets else max(self.H, 1)    # (caller-supplied nets: the library plans no hidden activations)
@@ -457,39 +515,21 @@ class Dynamics(object):
         a = _ffi.L2hmcSplitArgs()
         a.xnet = C.pointer(xs) if xs is not None else None
         a.vnet = C.pointer(vs) if vs is not None else None
-        # (a caller-supplied energy anneals itself inside the callback -- evaluate(..., anneal_beta=) below; the library
-        #  refuses bce_scale next to energy_cb)
+        # (a caller-supplied energy anneals itself inside the callback -- `_energy_callbacks`; the library refuses bce_scale
+        #  next to energy_cb)
         a.H, a.hmc, a.bce_scale = H_ws, int(self.hmc), (0.0 if self._user else float(self.anneal_beta))
         a.aux_encoder = C.pointer(enc) if enc is not None else None
         cb_error = []
         if self._vae:
             a.decoder, a.aux = C.pointer(dec), aux.data_ptr()
         elif self._user:
-            ws, temp, beta = self._split_ws, (float(self.temperature) if self.use_temperature else 1.0), float(self.anneal_beta)
-            base = ws.data_ptr()
-
-            def energy_cb(_user, xp, ldx, n, dd, Up, gp, ldg, _stream):
-                # (the library hands over addresses inside the workspace tensor: view them, no copies besides the
-                #  results; torch enqueues on its current stream, which is the stream the library was given)
-                try:
-                    xv = ws.as_strided((n, dd), (ldx, 1), (xp - base) // 4)
-                    U, g = self._fn.evaluate(xv, temp, want_U=bool(Up), want_grad=True, aux=aux, anneal_beta=beta)
-                    if tuple(g.shape) != (n, dd):
-                        raise ValueError("grad_energy must return shape (N, d), got %s" % (tuple(g.shape),))
-                    ws.as_strided((n, dd), (ldg, 1), (gp - base) // 4).copy_(g)
-                    if Up:
-                        o = (Up - base) // 4
-                        ws[o:o + 2 * n].view(torch.float64).copy_(U)
-                    return 0
-                except Exception as e:                       # never let an exception cross the C frame
-                    cb_error.append(e)
-                    return 1
+            energy_cb = self._energy_callbacks(self._split_ws, self._temperature(), float(self.anneal_beta), aux, cb_error)[0]
             cb = _ffi.ENERGY_CALLBACK(energy_cb)             # (kept alive by this frame for the duration of the call)
             a.energy_cb = C.cast(cb, C.c_void_p)
             if self._aux_nets:
                 a.aux = aux.data_ptr()
         else:                                        # built-in target (utils/distributions.py) under wide nets
-            en = self._fn.c_struct(x.device, float(self.temperature) if self.use_temperature else 1.0, self.anneal_beta)
+            en = self._fn.c_struct(x.device, self._temperature(), self.anneal_beta)
             a.energy = C.pointer(en)
         if self._user_nets:
             # the caller's nets (dynamics.py:69-79: any callable [a, b, tau, aux] -> [S, T, Q]): evaluated here, on views of the
@@ -499,10 +539,7 @@ class Dynamics(object):
             ncb = _ffi.NET_CALLBACK(net_cb)              # (kept alive by this frame for the duration of the call)
             a.net_cb = C.cast(ncb, C.c_void_p)
         a.masks, a.trig = self._mask.data_ptr(), self._trig.data_ptr()
-        if self.eps_override is None:
-            a.alpha, a.eps_host = self.alpha.data_ptr(), 0.0
-        else:
-            a.alpha, a.eps_host = None, float(self.eps_override)
+        self._set_step_size(a)
         a.n_chains, a.d, a.T = N, d, self.T
         a.step_begin, a.n_steps = int(step_begin), int(n_steps)
         a.x, a.v = x.data_ptr(), v.data_ptr()
@@ -647,13 +684,10 @@ class Dynamics(object):
                 raise ValueError("u must be %s" % (lead + (N,),))
         a = _ffi.L2hmcTrajectoryArgs()
         a.packed_nets = _ffi.ptr(self._packed_nets())
-        temp = 1.0 if ladder is not None else (self.temperature if self.use_temperature else 1.0)
+        temp = 1.0 if ladder is not None else self._temperature()
         a.energy = self._fn.c_struct(x.device, temp, self.anneal_beta)
         a.masks, a.trig = self._mask.data_ptr(), self._trig.data_ptr()
-        if self.eps_override is None:
-            a.alpha, a.eps_host = self.alpha.data_ptr(), 0.0
-        else:
-            a.alpha, a.eps_host = None, float(self.eps_override)
+        self._set_step_size(a)
         a.n_chains, a.d, a.H, a.T = N, d, self.H, self.T
         a.step_begin, a.n_steps = int(step_begin), int(n_steps)
         a.x, a.v = x.data_ptr(), _ffi.ptr(v)
@@ -700,9 +734,9 @@ class Dynamics(object):
         if self._vae:
             return self._fn.evaluate(x, aux=aux, anneal_beta=self.anneal_beta)[0]
         if self._user:
-            return self._fn.evaluate(as_device_f32(x, self.device), self.temperature if self.use_temperature else 1.0,
+            return self._fn.evaluate(as_device_f32(x, self.device), self._temperature(),
                                      aux=aux, anneal_beta=self.anneal_beta)[0].to(torch.float32)
-        return self._fn.evaluate(x, self.temperature if self.use_temperature else 1.0,
+        return self._fn.evaluate(x, self._temperature(),
                                  anneal_beta=self.anneal_beta)[0]
 
     def grad_energy(self, x, aux=None):
@@ -711,9 +745,9 @@ class Dynamics(object):
         if self._vae:
             return self._fn.evaluate(x, want_U=False, want_grad=True, aux=aux, anneal_beta=self.anneal_beta)[1]
         if self._user:
-            return self._fn.evaluate(as_device_f32(x, self.device), self.temperature if self.use_temperature else 1.0,
+            return self._fn.evaluate(as_device_f32(x, self.device), self._temperature(),
                                      want_U=False, want_grad=True, aux=aux, anneal_beta=self.anneal_beta)[1]
-        return self._fn.evaluate(x, self.temperature if self.use_temperature else 1.0,
+        return self._fn.evaluate(x, self._temperature(),
                                  want_U=False, want_grad=True, anneal_beta=self.anneal_beta)[1]
 
     def hamiltonian(self, x, v, aux=None):
@@ -761,7 +795,7 @@ class Dynamics(object):
                                                           lj.data_ptr(), N, d, p.data_ptr(),
                                                           _ffi.current_stream(x0.device)))
             return p
-        e = self._fn.c_struct(x0.device, self.temperature if self.use_temperature else 1.0, self.anneal_beta)
+        e = self._fn.c_struct(x0.device, self._temperature(), self.anneal_beta)
         _ffi.check(_ffi.lib().l2hmc_p_accept(e, x0.data_ptr(), v0.data_ptr(), x1.data_ptr(),
                                              v1.data_ptr(), lj.data_ptr(), N, d, p.data_ptr(),
                                              _ffi.current_stream(x0.device)))

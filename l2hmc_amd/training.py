@@ -32,15 +32,6 @@ import torch.distributed as dist
 from . import _ffi
 from .distributions import as_device_f32
 
-_SHAPES = (("W1", "dH"), ("b1", "H"), ("W2", "dH"), ("b2", "H"), ("W3", "2H"), ("b3", "H"),
-           ("W4", "HH"), ("b4", "H"), ("Ws", "Hd"), ("bs", "d"), ("Wt", "Hd"), ("bt", "d"),
-           ("Wq", "Hd"), ("bq", "d"), ("lam_s", "d"), ("lam_q", "d"))
-
-
-def _numel(code, d, H):
-    return {"dH": d * H, "H": H, "2H": 2 * H, "HH": H * H, "Hd": H * d, "d": d}[code]
-
-
 RNG_STREAM = "philox4x32-10/hw-boxmuller"       # (l2hmc_kernels.hpp philox_normal4; "…/libm-normals" up to ABI 3)
 
 
@@ -99,45 +90,53 @@ class Trainer(object):
 
     def __init__(self, dynamics, lr=1e-3, decay_steps=1000, decay_rate=0.96, scale=0.1,
                  beta1=0.9, beta2=0.999, epsilon=1e-8, seed=0):
+        self._init_state(dynamics, lr, decay_steps, decay_rate, scale, beta1, beta2, epsilon, seed)
+        self.n_grad = _ffi.check(_ffi.lib().l2hmc_train_grad_floats(dynamics.x_dim, dynamics.H))
+        self._bind_theta([w[k] for w in (dynamics._xw, dynamics._vw) for k in _ffi.NET_FIELDS])
+
+    def _init_state(self, dynamics, lr, decay_steps, decay_rate, scale, beta1, beta2, epsilon, seed):
+        """What every trainer starts from: the refusals (before any other attribute of `dynamics` is read), the
+        hyper-parameters and the per-instance state.  `scale` may be None: SplitTrainer's default depends on the objective."""
         if dynamics.hmc:
             raise ValueError("an HMC-mode Dynamics has nothing to train")
         _refuse_annealed(dynamics)
         train_temperature(dynamics)
-        self.dyn, self.scale = dynamics, float(scale)
+        self.dyn, self.scale = dynamics, (None if scale is None else float(scale))
         self.lr0, self.decay_steps, self.decay_rate = float(lr), int(decay_steps), float(decay_rate)
         self.beta1, self.beta2, self.epsilon = float(beta1), float(beta2), float(epsilon)
         self.seed = int(seed)
-        d, H = dynamics.x_dim, dynamics.H
-        dev = dynamics.device
-        L = _ffi.lib()
-        self.n_grad = _ffi.check(L.l2hmc_train_grad_floats(d, H))
-        self._alloc_flat(dev)                                                           # self.flat: the gradient
-        # flat parameter vector [XNet | VNet | alpha]; every net parameter becomes a VIEW of it, so the
-        # native Adam update is seen by the layers, by `Dynamics` and by its packed-weight cache
-        self.theta = torch.zeros(self.n_grad, dtype=torch.float32, device=dev)
-        self.slots, off = [], 0
-        with torch.no_grad():
-            for w in (dynamics._xw, dynamics._vw):
-                for name, code in _SHAPES:
-                    n = _numel(code, d, H)
-                    t = w[name]
-                    view = self.theta[off:off + n].view(t.shape)
-                    view.copy_(t)
-                    t.data = view
-                    self.slots.append((t, off, n))
-                    off += n
-            assert off + 1 == self.n_grad
-            self.train_alpha = bool(getattr(dynamics.alpha, "requires_grad", False))
-            self.theta[-1].copy_(dynamics.alpha.reshape(()))
-            dynamics.alpha.data = self.theta[-1].view(dynamics.alpha.shape)
-        self.m = torch.zeros_like(self.theta)
-        self.v = torch.zeros_like(self.theta)
         self.global_step = 0
         self._ws = None
         self.variant = 0             # 100: force the general tile kernel (l2hmc.h)
         self._io = None              # per-N buffers of step()
-        self._layout = None
-        self._auto_layout = None
+        self._layout = self._auto_layout = None          # the shard layout: declared (`set_sharding`) / discovered (`_shard`)
+        self._stale = self._reduced = None               # what `_raise_if_stale` / `_check_reduced_count` have to report
+
+    def _bind_theta(self, params, tail=()):
+        """The flat parameter vector [params | alpha | tail] of `self.n_grad` floats (what the library says the gradient of
+        this sampler holds), its gradient `self.flat` and Adam's moments.  Every tensor is copied into `theta` and becomes a
+        VIEW of it, so the native Adam update is seen by the layers, by `Dynamics` and by its packed-weight cache; all but
+        alpha get a slot (tensor, offset, n) -- alpha's entry of the gradient holds d / d eps, not its `.grad`
+        (`_publish_grads`)."""
+        alpha = self.dyn.alpha
+        self._alloc_flat(self.dyn.device)                                               # self.flat: the gradient
+        self.theta = torch.zeros(self.n_grad, dtype=torch.float32, device=self.dyn.device)
+        self.slots, off = [], 0
+        with torch.no_grad():
+            for t in list(params) + [alpha] + list(tail):
+                n = t.numel()
+                view = self.theta[off:off + n].view(t.shape)
+                view.copy_(t)
+                t.data = view
+                if t is alpha:
+                    self.alpha_index = off
+                else:
+                    self.slots.append((t, off, n))
+                off += n
+        assert off == self.n_grad, (off, self.n_grad)
+        self.train_alpha = bool(getattr(alpha, "requires_grad", False))
+        self.m = torch.zeros_like(self.theta)
+        self.v = torch.zeros_like(self.theta)
 
     N_TAIL = 8                       # floats behind the gradient in the all-reduced buffer (6 used)
 
@@ -225,28 +224,15 @@ class Trainer(object):
             out = (torch.empty_like(start), torch.empty(N, dtype=torch.float32, device=dyn.device),
                    torch.empty(N, dtype=torch.float32, device=dyn.device))
         Lx, p, v1 = out
-        xs = _ffi.L2hmcNet(*[dyn._xw[k].data_ptr() for k in _ffi.NET_FIELDS])
-        vs = _ffi.L2hmcNet(*[dyn._vw[k].data_ptr() for k in _ffi.NET_FIELDS])
-        fn = dyn._fn
-        buf = fn._buffers(dyn.device)
-        if fn.kind == _ffi.ENERGY_GAUSS_DIAG:
-            prec = buf["prec"]
-        elif fn.kind in (_ffi.ENERGY_GAUSS_DENSE, _ffi.ENERGY_GMM):
-            prec = buf["_raw"]                         # RAW (k, d, d) precisions, not the MFMA packing
-        elif fn.kind in (_ffi.ENERGY_ROUGHWELL, _ffi.ENERGY_FUNNEL, _ffi.ENERGY_LOGISTIC):
-            prec = None                                # (logistic regression: mu = the packed data, n_comp = rows, eta = prior variance)
-        else:
-            raise NotImplementedError("training supports the Gaussian, GMM, Rough-Well, funnel and logistic-regression targets")
+        nets = dyn._net_structs()                      # (returned as `keep`: the args struct only points at them)
         a = _ffi.L2hmcTrainArgs()
-        a.xnet, a.vnet = C.pointer(xs), C.pointer(vs)
+        a.xnet, a.vnet = C.pointer(nets[0]), C.pointer(nets[1])
         _refuse_annealed(dyn)
-        a.energy = _ffi.L2hmcEnergy(fn.kind, fn.n_comp, _ffi.ptr(buf["mu"]), _ffi.ptr(prec), _ffi.ptr(buf["logc"]),
-                                    fn.eta, int(fn.easy), train_temperature(dyn), 0.0, fn.den, 0)
+        # the fused kernels read the RAW (k, d, d) precisions of a dense Gaussian / mixture, not the MFMA packing
+        # (logistic regression: mu = the packed data, n_comp = rows, eta = prior variance)
+        a.energy = dyn._fn.c_struct(dyn.device, train_temperature(dyn), 0.0, raw_prec=True)
         a.masks, a.trig = dyn._mask.data_ptr(), dyn._trig.data_ptr()
-        if dyn.eps_override is None:
-            a.alpha, a.eps_host = dyn.alpha.data_ptr(), 0.0
-        else:
-            a.alpha, a.eps_host = None, float(dyn.eps_override)
+        dyn._set_step_size(a)
         a.n_chains, a.d, a.H, a.T = N, d, dyn.H, dyn.T
         a.x, a.v = start.data_ptr(), v.data_ptr()
         a.direction, a.direction_all = direction.data_ptr(), 1
@@ -254,7 +240,7 @@ class Trainer(object):
         a.Lx, a.p, a.v1 = Lx.data_ptr(), p.data_ptr(), v1.data_ptr()
         a.grad, a.workspace = self.flat.data_ptr(), self._ws.data_ptr()
         a.variant = int(self.variant)
-        return a, (xs, vs, buf), (Lx, p, v1)
+        return a, nets, (Lx, p, v1)
 
     def _world(self):
         return dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
@@ -292,9 +278,9 @@ class Trainer(object):
         if world == 1:
             return N, 0
         self._check_reduced_count()
-        if getattr(self, "_layout", None) is not None:
+        if self._layout is not None:
             return self._layout
-        auto = getattr(self, "_auto_layout", None)
+        auto = self._auto_layout
         if auto is None:
             rank = dist.get_rank()
             counts = torch.zeros(world, dtype=torch.float64, device=self.dyn.device)
@@ -311,7 +297,7 @@ class Trainer(object):
                   "re-enter the layout exchange together")
 
     def _raise_if_stale(self):
-        st = getattr(self, "_stale", None)
+        st = self._stale
         if st is not None:
             self._stale = None
             raise RuntimeError(self._STALE_MSG % st)
@@ -329,7 +315,7 @@ class Trainer(object):
         self._reduced = (host, ev, int(n_total), float(hi_scale))
 
     def _check_reduced_count(self):
-        red = getattr(self, "_reduced", None)
+        red = self._reduced
         if red is None:
             return
         host, ev, expect, hi_scale = red
@@ -386,12 +372,21 @@ class Trainer(object):
         # chains [x; z] (each chain's term still weighted 1 / n_total) instead of two half-empty ones
         Lxz, pxz, v12 = self._propose_grad(torch.cat([x, z]), torch.cat([xv, zv]), torch.cat([xd, zd]), n_total)
         loss = self._reduce_and_loss(v12, N, n_total, world)      # (sharded: the ONE collective of a training step)
-        for t, off, n in self.slots:
-            t.grad = self.flat[off:off + n].view(t.shape)
-        if self.train_alpha:
-            self.dyn.alpha.grad = (self.flat[-1] * torch.exp(dyn.alpha.detach())).reshape(dyn.alpha.shape)
+        self._publish_grads()
         self._raise_if_stale()
         return loss, Lxz[:N], pxz[:N]
+
+    def _alias_grads(self):
+        """`.grad` of every slot's tensor = its run of the flat gradient (a view: what lands in `self.flat` is seen there)."""
+        for t, off, n in self.slots:
+            t.grad = self.flat[off:off + n].view(t.shape)
+
+    def _publish_grads(self):
+        """Leave the gradient in `.grad` of every parameter; alpha's entry of the flat gradient holds d / d eps."""
+        self._alias_grads()
+        if self.train_alpha:
+            alpha = self.dyn.alpha
+            alpha.grad = (self.flat[self.alpha_index] * torch.exp(alpha.detach())).reshape(alpha.shape)
 
     def _buffers(self, N, d):
         if self._io is None or self._io["N"] != N:
@@ -406,23 +401,30 @@ class Trainer(object):
                         "v1": torch.empty(2 * N, dtype=f32, device=dev)}
         return self._io
 
+    def _step_draws(self, x):
+        """The head of every `step`: the per-N buffers, the shard layout and the step's ONE `l2hmc_rng_fill` -- z, v_x, v_z
+        (rows 1..3 of W), the direction bits of both proposals (rows 1, 2 of dir) and the accept uniforms (row 0 of u), at
+        stream position (seed, 3 * global_step, global chain).  Returns (x on the device, the buffers, global chain count)."""
+        dyn = self.dyn
+        x = as_device_f32(x, dyn.device)
+        N, d = x.shape
+        io = self._buffers(N, d)
+        n_total, chain_off = self._shard(N)
+        _ffi.check(_ffi.lib().l2hmc_rng_fill(self.seed, 3 * self.global_step, chain_off, N, d, 3, io["W"][1].data_ptr(),
+                                             io["dir"].data_ptr(), io["u"].data_ptr(), _ffi.current_stream(dyn.device)))
+        return x, io, n_total
+
     def step(self, x, u=None):
         """One optimiser step like nb raw 262-268: returns (loss, px, x_next, lr) where x_next is
         the MH-selected continuation of the chains.  Three launches (module docstring); sharded: + ONE all-reduce and
         the Adam launch behind it."""
         dyn = self.dyn
-        x = as_device_f32(x, dyn.device)
+        x, io, n_total = self._step_draws(x)
         N, d = x.shape
         L = _ffi.lib()
         s = _ffi.current_stream(dyn.device)
-        io = self._buffers(N, d)
         W = io["W"]
         world = self._world()
-        n_total, chain_off = self._shard(N)
-        # z, v_x, v_z (rows 1..3 of W), the direction bits of both proposals (rows 1, 2 of dir) and the
-        # accept uniforms (row 0 of u): one call, stream position = (seed, 3 * global_step, global chain)
-        _ffi.check(L.l2hmc_rng_fill(self.seed, 3 * self.global_step, chain_off, N, d, 3, W[1].data_ptr(),
-                                    io["dir"].data_ptr(), io["u"].data_ptr(), s))
         # (the accept probabilities, the selected states and the loss go to FRESH tensors -- allocations, not launches)
         p12 = torch.empty(2 * N, dtype=torch.float32, device=dyn.device)
         x_next = torch.empty_like(x)
@@ -503,97 +505,46 @@ class SplitTrainer(Trainer):
 
     def __init__(self, dynamics, lr=1e-3, decay_steps=1000, decay_rate=0.96, scale=None,
                  beta1=0.9, beta2=0.999, epsilon=1e-8, seed=0, clip_norm=None):
-        if dynamics.hmc:
-            raise ValueError("an HMC-mode Dynamics has nothing to train")
-        _refuse_annealed(dynamics)
-        train_temperature(dynamics)
+        self._init_state(dynamics, lr, decay_steps, decay_rate, scale, beta1, beta2, epsilon, seed)
         from .vae import mlp3_struct
         self._mlp3_struct = mlp3_struct
-        self.dyn = dynamics
         self.vae = bool(dynamics._vae)
         self.user = bool(getattr(dynamics, "_user", False))     # U, grad U and Hessian-vector products by callback (slow path)
         # the VAE experiment's sampler (mnist_vae.py:185-262): the built-in decoder posterior, or the same model handed
         # over as a plain closure energy(z, aux) with the image-conditioned nets
         self.image_sampler = self.vae or (self.user and dynamics._xw is not None and dynamics._xw["aux_encoder"] is not None)
-        self.scale = float(scale) if scale is not None else (1.0 if self.image_sampler else 0.1)
+        if self.scale is None:
+            self.scale = 1.0 if self.image_sampler else 0.1
         if self.image_sampler and self.scale != 1.0:
             # mnist_vae.py:207-226 has no scale (its loss is mean(1/v) - mean(v)); the composed-proposal branch of
             # sampler_loss_and_grad forms its cotangents for exactly that objective
             raise ValueError("the image-conditioned sampler objective (mnist_vae.py:207-226) has no `scale`: leave it at 1")
         self.clip_norm = clip_norm if clip_norm is not None else (5.0 if self.image_sampler else None)   # mnist_vae.py:258
-        self.lr0, self.decay_steps, self.decay_rate = float(lr), int(decay_steps), float(decay_rate)
-        self.beta1, self.beta2, self.epsilon = float(beta1), float(beta2), float(epsilon)
-        self.seed = int(seed)
-        d, H = dynamics.x_dim, dynamics.H
         dev = dynamics.device
-        L = _ffi.lib()
         self.unets = bool(getattr(dynamics, "_user_nets", False))
         self.enc = None if self.unets else dynamics._xw["aux_encoder"]
-        enc_s = mlp3_struct(self.enc) if self.enc is not None else None
         if self.unets:
             # Arbitrary callables (dynamics.py:69-79): the variables are whatever the nets expose -- the layer kit's
             # `parameters()` or a torch Module's named_parameters() (`Dynamics.parameters`).  Flat vector [those, in order |
             # alpha]; every one of them becomes a view of theta (the native Adam update is seen by the caller's nets) and its
             # `.grad` a view of the flat gradient (the caller's autograd accumulates straight into what is all-reduced).
-            plist = [(k, t) for k, t in dynamics.parameters() if k != "alpha"]
-            seen, uniq = set(), []
-            for k, t in plist:                       # (one tensor shared by both nets is one variable)
-                if t.data_ptr() not in seen:
+            seen, params = set(), []
+            for k, t in dynamics.parameters():       # (one tensor shared by both nets is one variable)
+                if k != "alpha" and t.data_ptr() not in seen:
                     seen.add(t.data_ptr())
-                    uniq.append((k, t))
-            if not uniq:
+                    if t.dtype != torch.float32 or t.device != dev:
+                        raise ValueError("net parameter %s must be float32 on %s" % (k, dev))
+                    params.append(t)
+            if not params:
                 raise ValueError("the caller-supplied nets expose no parameters (layer-kit parameters() or torch Module "
                                  "named_parameters()): nothing to train")
-            for k, t in uniq:
-                if t.dtype != torch.float32 or t.device != dev:
-                    raise ValueError("net parameter %s must be float32 on %s" % (k, dev))
-            self._uparams = uniq
-            self.n_grad = sum(int(t.numel()) for _, t in uniq) + 1
+            self.n_grad = sum(t.numel() for t in params) + 1
         else:
-            self.n_grad = _ffi.check(L.l2hmc_train_split_grad_floats(d, H, C.byref(enc_s) if enc_s is not None else None))
-        self._alloc_flat(dev)
-        self.theta = torch.zeros(self.n_grad, dtype=torch.float32, device=dev)
-        self.slots, off = [], 0
-        with torch.no_grad():
-            if self.unets:
-                for k, t in self._uparams:
-                    n = int(t.numel())
-                    view = self.theta[off:off + n].view(t.shape)
-                    view.copy_(t)
-                    t.data = view
-                    self.slots.append((t, off, n))
-                    off += n
-            for w in (() if self.unets else (dynamics._xw, dynamics._vw)):
-                for name, code in _SHAPES:
-                    n = _numel(code, d, H)
-                    t = w[name]
-                    view = self.theta[off:off + n].view(t.shape)
-                    view.copy_(t)
-                    t.data = view
-                    self.slots.append((t, off, n))
-                    off += n
-            self.alpha_index = off
-            self.train_alpha = bool(getattr(dynamics.alpha, "requires_grad", False))
-            self.theta[off].copy_(dynamics.alpha.reshape(()))
-            dynamics.alpha.data = self.theta[off].view(dynamics.alpha.shape)
-            off += 1
-            if self.enc is not None:
-                for name in _MLP_FIELDS:
-                    t = self.enc[name]
-                    n = t.numel()
-                    view = self.theta[off:off + n].view(t.shape)
-                    view.copy_(t)
-                    t.data = view
-                    self.slots.append((t, off, n))
-                    off += n
-            assert off == self.n_grad, (off, self.n_grad)
-        self.m = torch.zeros_like(self.theta)
-        self.v = torch.zeros_like(self.theta)
-        self.global_step = 0
-        self._ws = None
-        self.variant = 0
-        self._io = None
-        self._layout = None
+            enc_s = mlp3_struct(self.enc) if self.enc is not None else None
+            self.n_grad = _ffi.check(_ffi.lib().l2hmc_train_split_grad_floats(dynamics.x_dim, dynamics.H,
+                                                                              C.byref(enc_s) if enc_s is not None else None))
+            params = [w[k] for w in (dynamics._xw, dynamics._vw) for k in _ffi.NET_FIELDS]
+        self._bind_theta(params, [self.enc[k] for k in _MLP_FIELDS] if self.enc is not None else ())
 
     def lr_at(self, step):
         if self.image_sampler and self.decay_steps <= 0:
@@ -613,7 +564,7 @@ class SplitTrainer(Trainer):
                                                                C.byref(enc_s) if enc_s is not None else None,
                                                                C.byref(dec_s) if dec_s is not None else None))
         if self._ws is None or self._ws.numel() < need:
-            self._ws = None
+            self._ws = None                            # (frees the old workspace BEFORE the larger one is allocated, not after)
             self._ws = torch.empty(int(need), dtype=torch.float32, device=dyn.device)
         if out is None:
             out = (torch.empty_like(start), torch.empty(N, dtype=torch.float32, device=dyn.device),
@@ -621,20 +572,17 @@ class SplitTrainer(Trainer):
         Lx, p, v1 = out
         a = _ffi.L2hmcTrainSplitArgs()
         cb_error = []
-        keep_nets = None
         if self.unets:
             # forward by net_cb, reverse by net_vjp_cb (include/l2hmc.h, ABI 6): the parameters' `.grad` are views of self.flat
             # (set here, before the caller's autograd accumulates into them in place)
-            for t, off, n in self.slots:
-                t.grad = self.flat[off:off + n].view(t.shape)
+            self._alias_grads()
             ncb, vcb = dyn._net_callbacks(self._ws, direction, None if aux is None else as_device_f32(aux, dyn.device), cb_error)
             keep_nets = (_ffi.NET_CALLBACK(ncb), _ffi.NET_VJP_CALLBACK(vcb))           # alive for the duration of the call
             a.net_cb, a.net_vjp_cb = C.cast(keep_nets[0], C.c_void_p), C.cast(keep_nets[1], C.c_void_p)
             a.H = 0
         else:
-            xs = _ffi.L2hmcNet(*[dyn._xw[k].data_ptr() for k in _ffi.NET_FIELDS])
-            vs = _ffi.L2hmcNet(*[dyn._vw[k].data_ptr() for k in _ffi.NET_FIELDS])
-            a.xnet, a.vnet, a.H = C.pointer(xs), C.pointer(vs), dyn.H
+            keep_nets = dyn._net_structs()                                             # alive for the duration of the call
+            a.xnet, a.vnet, a.H = C.pointer(keep_nets[0]), C.pointer(keep_nets[1]), dyn.H
         a.aux_encoder = C.pointer(enc_s) if enc_s is not None else None
         keep = None
         _refuse_annealed(dyn)
@@ -644,39 +592,12 @@ class SplitTrainer(Trainer):
         # and the energy_scale term of the VAE objective is formed from the plain U (mnist_vae.py:209)
         tcar = _ffi.L2hmcEnergy(0, 0, None, None, None, 0.0, 0, tau, 0.0, 0.0, 0) if tau != 1.0 else None
         if self.user:
-            fn, ws = dyn._fn, self._ws
-            base = ws.data_ptr()
             if self.enc is not None:
                 if aux is None:
                     raise ValueError("the image-conditioned sampler needs aux=")
                 aux = as_device_f32(aux, dyn.device)
                 a.aux = aux.data_ptr()
-
-            def view(ptr, n, dd, ld):             # an (n, dd) block of the workspace the library points at
-                return ws.as_strided((n, dd), (ld, 1), (ptr - base) // 4)
-
-            def energy_cb(_user, xp, ldx, n, dd, Up, gp, ldg, _stream):
-                try:
-                    U, g = fn.evaluate(view(xp, n, dd, ldx), tau, want_U=bool(Up), want_grad=True, aux=aux)
-                    if tuple(g.shape) != (n, dd):
-                        raise ValueError("grad_energy must return shape (N, d), got %s" % (tuple(g.shape),))
-                    view(gp, n, dd, ldg).copy_(g)
-                    if Up:
-                        o = (Up - base) // 4
-                        ws[o:o + 2 * n].view(torch.float64).copy_(U)
-                    return 0
-                except Exception as e:            # never let an exception cross the C frame
-                    cb_error.append(e)
-                    return 1
-
-            def hvp_cb(_user, xp, ldx, up, ldu, n, dd, hp, ldh, _stream):
-                try:
-                    hv = fn.hvp(view(xp, n, dd, ldx), view(up, n, dd, ldu), aux=aux)
-                    view(hp, n, dd, ldh).copy_(hv / tau if tau != 1.0 else hv)
-                    return 0
-                except Exception as e:
-                    cb_error.append(e)
-                    return 1
+            energy_cb, hvp_cb = dyn._energy_callbacks(self._ws, tau, 0.0, aux, cb_error)
             keep = (_ffi.ENERGY_CALLBACK(energy_cb), _ffi.HVP_CALLBACK(hvp_cb))     # alive for the duration of the call
             a.energy_cb, a.hvp_cb = C.cast(keep[0], C.c_void_p), C.cast(keep[1], C.c_void_p)
             a.energy = C.pointer(tcar) if tcar is not None else None
@@ -695,10 +616,7 @@ class SplitTrainer(Trainer):
             if fn.kind in (_ffi.ENERGY_GAUSS_DENSE, _ffi.ENERGY_GMM):
                 a.hess = fn._buffers(dyn.device)["_raw"].data_ptr()
         a.masks, a.trig = dyn._mask.data_ptr(), dyn._trig.data_ptr()
-        if dyn.eps_override is None:
-            a.alpha, a.eps_host = dyn.alpha.data_ptr(), 0.0
-        else:
-            a.alpha, a.eps_host = None, float(dyn.eps_override)
+        dyn._set_step_size(a)
         a.n_chains, a.d, a.T = N, d, dyn.T
         a.x, a.v = start.data_ptr(), v.data_ptr()
         a.direction, a.direction_all = direction.data_ptr(), 1
@@ -720,18 +638,10 @@ class SplitTrainer(Trainer):
         _ffi.check(rc)
         return Lx, p, v1
 
-    def _publish_grads(self):
-        for t, off, n in self.slots:
-            t.grad = self.flat[off:off + n].view(t.shape)
-        if self.train_alpha:
-            self.dyn.alpha.grad = (self.flat[self.alpha_index] * torch.exp(self.dyn.alpha.detach())).reshape(self.dyn.alpha.shape)
-
     def loss_and_grad(self, x, z=None, draws=None):
         if self.image_sampler:
             raise TypeError("the VAE sampler's objective needs the images: use sampler_loss_and_grad")
-        loss, Lx, px = Trainer.loss_and_grad(self, x, z, draws)
-        self._publish_grads()
-        return loss, Lx, px
+        return Trainer.loss_and_grad(self, x, z, draws)
 
     def _adam(self, lr):
         """TF1 Adam over the flat vector; alpha's entry holds d/d eps and is turned into d/d alpha first."""
@@ -758,16 +668,12 @@ class SplitTrainer(Trainer):
         if self.image_sampler:
             raise TypeError("the VAE sampler trains with sampler_step(aux, latent_q, log_sigma)")
         dyn = self.dyn
-        x = as_device_f32(x, dyn.device)
+        x, io, n_total = self._step_draws(x)
         N, d = x.shape
         L = _ffi.lib()
         s = _ffi.current_stream(dyn.device)
-        io = self._buffers(N, d)
         W = io["W"]
         world = self._world()
-        n_total, chain_off = self._shard(N)
-        _ffi.check(L.l2hmc_rng_fill(self.seed, 3 * self.global_step, chain_off, N, d, 3, W[1].data_ptr(),
-                                    io["dir"].data_ptr(), io["u"].data_ptr(), s))
         W[0].copy_(x)
         self.flat.zero_()
         self._propose_grad(W[0:2].view(2 * N, d), W[2:4].view(2 * N, d), io["dir"][1:3].view(2 * N), n_total,

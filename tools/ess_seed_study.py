@@ -19,7 +19,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from l2hmc_amd import Dynamics, _ffi, distributions, func_utils, layers, sample_chain     # noqa: E402
-from l2hmc_amd.training import Trainer, _SHAPES                                             # noqa: E402
+from l2hmc_amd.training import Trainer                                                      # noqa: E402
 
 DEV = torch.device("cuda:0")
 COV = np.array([[50.05, -49.95], [-49.95, 50.05]])
@@ -96,7 +96,7 @@ def sweep(n_seeds, train_steps=5000):
 
 # ---- float64 replay of one training --------------------------------------------------------------------------------------------
 def flat_of(nets):
-    return np.concatenate([np.asarray(nets[n][k], np.float64).ravel() for n in ("xnet", "vnet") for k, _ in _SHAPES])
+    return np.concatenate([np.asarray(nets[n][k], np.float64).ravel() for n in ("xnet", "vnet") for k in _ffi.NET_FIELDS])
 
 
 def replay(seed, train_steps=5000, checkpoints=(1, 10, 50, 200, 1000, 2000, 5000)):
