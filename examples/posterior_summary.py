@@ -5,7 +5,9 @@ One seeded synthetic data set (1000 rows, d = 8 features) is sampled with HMC --
 `sample_chain(record=True)` records the history on the device -- and `describe` reads the recorded history where it lies:
 per coefficient the mean and sd, the 5 % / 50 % / 95 % quantiles (exact order statistics: a radix select, no sort and no
 copy), split R-hat, the effective sample sizes of the mean and of the interval ends (`ess_tail`), and the Monte Carlo standard
-errors that say how many digits of the table are worth printing.
+errors that say how many digits of the table are worth printing.  Under the table: how the coefficients are related (the
+largest entries of the posterior correlation matrix) and what the run is worth as a whole (`multi_ess`, the multivariate
+effective sample size), from one more read of the same history.
 
     python examples/posterior_summary.py
 """
@@ -16,7 +18,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
 
-from l2hmc_amd import Dynamics, LogisticRegression, describe, sample_chain, warmup
+from l2hmc_amd import Dynamics, LogisticRegression, describe, multi_ess, sample_chain, warmup
 
 
 def synthetic(n=1000, d=8, seed=0):
@@ -46,6 +48,11 @@ def main(chains=1024, updates=60, proposals=400, seed=1):
             s.ess_tail[k], s.mcse_mean[k], max(s.mcse_quantile[0, k], s.mcse_quantile[2, k])))
     inside = (s.quantiles[0] <= w_true) & (w_true <= s.quantiles[2])
     print("%d of %d true coefficients lie inside their 90 %% interval" % (inside.sum(), d))
+    m = multi_ess(hist[proposals // 4:])
+    pairs = sorted(((abs(m.corr[i, j]), i, j) for i in range(d) for j in range(i + 1, d)), reverse=True)[:5]
+    print("largest posterior correlations: " + ", ".join("(%d, %d) %+.3f" % (i, j, m.corr[i, j]) for _, i, j in pairs))
+    print("multivariate ESS %.0f of %d draws (%d batches of %d steps); smallest per-coefficient batch-means ESS %.0f" % (
+        m.multi_ess, m.n_draws, m.n_batches, m.batch_size, m.ess_batch.min()))
 
 
 if __name__ == "__main__":

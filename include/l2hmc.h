@@ -734,6 +734,29 @@ int64_t l2hmc_logistic_predict_workspace_doubles(int64_t n_draws, int32_t n_data
 int l2hmc_logistic_predict(const float* draws, int64_t n_draws, int32_t d, const float* packed, int32_t n_data,
                            double* sums /* (4, n_data) */, double* workspace, void* stream);
 
+/* The raw first and second moments of a recorded history X (steps, N, d) kept on the device (csrc/moment_sums.hip): what the
+ * posterior covariance and the multivariate effective sample size of Vats, Flegal & Jones (2019) are made of
+ * (l2hmc_amd/multivariate.py `finish` turns them into numbers on the host, and ranks that hold different chains add them).
+ *   sum_out         (d)     sum over all steps * n_chains draws of x
+ *   cross_out       (d, d)  sum of x x^T; both triangles are written and carry identical bits
+ *   batch_sum_out   (d)     sum over the batches of the batch MEAN ybar        -- NULL if and only if batch = 0
+ *   batch_cross_out (d, d)  sum over the batches of ybar ybar^T, symmetric too -- NULL if and only if batch = 0
+ * A batch is `batch` consecutive steps of ONE chain; a chain has a = steps / batch of them, over rows [steps - a batch, steps):
+ * a leading remainder belongs to no batch (it still counts in sum_out and cross_out).  batch = 0 computes no batch sums, and
+ * then steps x n_chains may be any factorisation of the rows of a (draws, d) array.
+ * Arithmetic: every value is widened to float64 (exactly) before anything else happens to it; every product and every sum is
+ * float64 on the matrix pipe (v_mfma_f64_16x16x4_f64), so the products are exact; a batch mean is a float64 sum divided once.
+ * `workspace`: l2hmc_moment_sums_workspace_doubles(...) doubles, required -- every block writes its partial sums there and a
+ * second kernel adds them in block order: no floating-point atomics, two calls give identical bits.  At most about
+ * 256 blocks x 3 panels x 2 x 4352 doubles (53 MB, 64 < d <= 128 with batches); 1.4 MB at d = 25.
+ * A non-finite entry makes the rows and columns of its own coordinate non-finite and nothing else: lanes past d or past the
+ * last chain select an exact 0 and never multiply what they loaded.
+ * L2HMC_ERR_ARG (before any launch): d outside 1 .. 128, steps or n_chains < 1, batch outside 0 .. steps,
+ * n_chains > 2^40 / d or steps > 2^31, a required pointer NULL, batch outputs given with batch = 0 or missing with batch > 0. */
+int64_t l2hmc_moment_sums_workspace_doubles(int64_t steps, int64_t n_chains, int32_t d, int64_t batch);
+int l2hmc_moment_sums(const float* X, int64_t steps, int64_t n_chains, int32_t d, int64_t batch, double* sum_out,
+                      double* cross_out, double* batch_sum_out, double* batch_cross_out, double* workspace, void* stream);
+
 /* Warm-up: the step size eps = exp(*alpha) adapted on the device between launches of the sampler loop (csrc/adapt.hip;
  * l2hmc_amd/warmup.py drives it).  Every trajectory entry point reads *alpha from device memory when its kernel starts, so a
  * kernel that rewrites *alpha in place sets the step size of the next launch on the same stream: no host read, no synchronise,

@@ -5,7 +5,7 @@ Python surface = the reference's `utils/dynamics.py`, `utils/sampler.py`, `utils
 `utils/notebook_utils.get_hmc_samples`, `utils/ais.py`); compute = the
 hand-written HIP kernels of `csrc/` behind the C ABI of `include/l2hmc.h`.
 """
-from . import _ffi, diagnostics, distributions, func_utils, layers, losses, predictive, quantiles  # noqa: F401
+from . import _ffi, diagnostics, distributions, func_utils, layers, losses, multivariate, predictive, quantiles  # noqa: F401
 from .dynamics import Dynamics  # noqa: F401
 from .sampler import chain_operator, propose, sample_chain, tf_accept  # noqa: F401
 from . import tempering  # noqa: F401
@@ -15,8 +15,10 @@ from .training import LogisticTrainer  # noqa: F401
 from .diagnostics import summarize  # noqa: F401
 from .predictive import waic  # noqa: F401
 from .quantiles import describe  # noqa: F401
+from .multivariate import covariance, multi_ess  # noqa: F401
 from .warmup import warmup  # noqa: F401  (the function; its module stays importable as `from l2hmc_amd.warmup import ...`)
 
 __all__ = ["Dynamics", "propose", "tf_accept", "chain_operator", "sample_chain", "ParallelTempering", "geometric_ladder",
            "LogisticRegression", "LogisticTrainer", "summarize", "diagnostics", "warmup", "predictive", "waic", "quantiles", "describe",
+           "multivariate", "covariance", "multi_ess",
            "layers", "distributions", "func_utils", "losses", "tempering"]

@@ -180,6 +180,8 @@ SYMBOLS = {
     "l2hmc_order_stats": (C.c_int, [_fp, C.c_int64, C.c_int32, _fp, C.c_int32, _fp, _fp, _fp, _fp]),
     "l2hmc_order_stats_count": (C.c_int, [_fp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _fp, _fp, _fp, _fp]),
     "l2hmc_order_stats_advance": (C.c_int, [_fp, _fp, _fp, C.c_int32, C.c_int32, C.c_int32, _fp, _fp]),
+    "l2hmc_moment_sums_workspace_doubles": (C.c_int64, [C.c_int64, C.c_int64, C.c_int32, C.c_int64]),
+    "l2hmc_moment_sums": (C.c_int, [_fp, C.c_int64, C.c_int64, C.c_int32, C.c_int64, _fp, _fp, _fp, _fp, _fp, _fp]),
     "l2hmc_logistic_predict_workspace_doubles": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
     "l2hmc_logistic_predict": (C.c_int, [_fp, C.c_int64, C.c_int32, _fp, C.c_int32, _fp, _fp, _fp]),
     "l2hmc_adapt_workspace_doubles": (C.c_int64, [C.c_int64]),

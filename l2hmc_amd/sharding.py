@@ -5,7 +5,7 @@ cross-chain term), so the chain batch is cut into contiguous blocks -- rank r ow
 [r*N/W, (r+1)*N/W) -- and the leapfrog kernels run with NO data-path collective.  The only
 exchanges are small statistics: the mean accept probability, the autocovariance partial
 sums behind ESS (utils/func_utils.py:45-54,114-120), the per-coordinate sums behind split R-hat /
-ESS (`diagnostics`), the integer digit histograms behind posterior quantiles (`describe`), the four per-row sums behind the posterior predictive and WAIC (`predictive`) and the two doubles per window of the step-size warm-up (`warmup`), each ONE flat all-reduce.  Backend
+ESS (`diagnostics`), the integer digit histograms behind posterior quantiles (`describe`), the four per-row sums behind the posterior predictive and WAIC (`predictive`), the raw moments behind the posterior covariance and the multivariate ESS (`multivariate`) and the two doubles per window of the step-size warm-up (`warmup`), each ONE flat all-reduce.  Backend
 "nccl" is RCCL over xGMI on the GPU box; "gloo" is used by the CPU tests.
 """
 import numpy as np
@@ -143,6 +143,38 @@ def predictive(draws_local, X, y=None):
     flat = flat.numpy()
     return pd.finish({"n_draws": int(round(flat[0])), "sum_p": flat[1:1 + n], "sum_lik": flat[1 + n:1 + 2 * n],
                       "sum_ll": flat[1 + 2 * n:1 + 3 * n], "sum_ll2": flat[1 + 3 * n:1 + 4 * n]})
+
+
+def multivariate(X_local, batch_size=None):
+    """`multivariate.multi_ess` (posterior covariance, correlation, multivariate ESS) for chains sharded over ranks: every
+    rank forms the raw moments of its own chains (a ROCm tensor: the HIP kernels, the history stays in HBM), ONE all-reduce of
+    [n | sum | cross | A | batch_sum | batch_cross] (each number as a head of 24 bits and a float64 rest), then
+    `multivariate.finish`; equals the single-process value on the concatenated chains up to the rounding of the all-reduce.  Ranks may hold different numbers of chains, but the same
+    number of steps, and must pass the same `batch_size`."""
+    from . import multivariate as mv
+    s = mv.moment_sums(X_local, mv._batch_size(X_local, batch_size))
+    d = int(X_local.shape[-1])
+    wide = np.concatenate([[s["n_draws"]], mv._wide(s["sum"]), mv._wide(s["cross"]).ravel(), [s["n_batches"]],
+                           mv._wide(s["batch_sum"]), mv._wide(s["batch_cross"]).ravel()]).astype(np.longdouble)
+    # every number travels as two float64: a head of 24 significant bits, whose sums over ranks are exact, and the rest (for a
+    # device sum, what float64 holds beyond the head; for a numpy sum, what long double holds) -- still ONE all-reduce.  The
+    # head is cut by scaling, so it has the range of float64 and a finite moment stays finite
+    with np.errstate(all="ignore"):
+        frac, expo = np.frexp(wide)
+        hi = np.ldexp(np.rint(frac * 2.0 ** 24) / 2.0 ** 24, expo).astype(np.float64)
+        lo = np.where(np.isfinite(hi), wide - hi, 0.0).astype(np.float64)
+    flat = torch.from_numpy(np.concatenate([hi, lo]))
+    if _on_device_collective(X_local):
+        flat = _allreduce_sum(flat.to(X_local.device)).cpu()
+    else:
+        flat = _allreduce_sum(flat)
+    flat = flat.numpy()
+    m = wide.shape[0]
+    flat = flat[:m].astype(np.longdouble) + flat[m:].astype(np.longdouble)
+    o = 1 + d + d * d
+    return mv.finish({"n_draws": int(round(float(flat[0]))), "sum": flat[1:1 + d], "cross": flat[1 + d:o].reshape(d, d),
+                      "batch_size": s["batch_size"], "n_batches": int(round(float(flat[o]))), "batch_sum": flat[o + 1:o + 1 + d],
+                      "batch_cross": flat[o + 1 + d:].reshape(d, d)})
 
 
 def warmup(x_local, dynamics, n_updates=100, *, n_total=None, **kwargs):

@@ -1,0 +1,47 @@
+#!/usr/bin/env python
+"""Worst deviation of the device's raw moments (`multivariate.moment_sums`, csrc/moment_sums.hip) and of `multi_ess` from the
+two-pass float64 restatement of tests/multivariate_case.py, per fixture: the sums as a fraction of their gate
+1e-10 sqrt(raw_ii raw_jj), multi_ess relative, next to the first-order bound 2 B tests/test_gpu_multivariate.py derives.
+
+    python tools/multivariate_accuracy.py > profiles/multivariate_accuracy.txt"""
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np
+import torch
+
+from l2hmc_amd import multivariate
+from tests import multivariate_case as mc
+from tests.test_gpu_multivariate import FIXTURES, mess_bound
+
+
+def main():
+    assert torch.cuda.is_available(), "multivariate_accuracy needs a GPU"
+    print("fixture shape               batch   sums: worst fraction of the gate   multi_ess      relative deviation   "
+          "bound 2 B   cond(Sigma)")
+    worst_sum = worst_ess = 0.0
+    for name in FIXTURES + ["R"]:
+        X = mc.history(name)
+        Xd = torch.as_tensor(np.array(X)).cuda()
+        b = mc.default_batch(X.shape[0])
+        ref = mc.reference(X, b)
+        got = multivariate.moment_sums(Xd, b)
+        frac = 0.0
+        for vec, mat, count in (("sum", "cross", ref["n_draws"]), ("batch_sum", "batch_cross", ref["n_batches"])):
+            gv, gm = mc.sum_gates(np.diag(ref[mat]), count)
+            frac = max(frac, float(np.max(np.abs(got[vec].cpu().numpy() - ref[vec]) / gv)),
+                       float(np.max(np.abs(got[mat].cpu().numpy() - ref[mat]) / gm)))
+        s = multivariate.finish(got)
+        e = abs(s.multi_ess - ref["multi_ess"]) / ref["multi_ess"]
+        worst_sum, worst_ess = max(worst_sum, frac), max(worst_ess, e)
+        print("%-7s %-19s %-7d %-34.3g %-14.6g %-20.3g %-11.3g %.3g" % (
+            name, "x".join(str(v) for v in X.shape), b, frac, s.multi_ess, e, 2 * mess_bound(ref),
+            np.linalg.cond(ref["cov_asymptotic"])))
+        sys.stdout.flush()
+    print("worst over all fixtures: sums %.3g of their gate, multi_ess %.3g relative" % (worst_sum, worst_ess))
+
+
+if __name__ == "__main__":
+    main()
