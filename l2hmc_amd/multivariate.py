@@ -158,7 +158,9 @@ def finish(sums):
                          "of the asymptotic covariance would be singular -- use a smaller batch_size or more chains" % (A, d))
     sb, Cb = _wide(sums["batch_sum"]), _wide(sums["batch_cross"])
     with np.errstate(all="ignore"):
-        Q = (Cb - np.outer(mu_w, sb) - np.outer(sb, mu_w) + A * np.outer(mu_w, mu_w)).astype(np.float64)
+        # the two mean terms are added to each other first: a + b is b + a bit for bit, (c - a) - b is not (c - b) - a, and
+        # Sigma is promised as symmetric as `batch_cross` is
+        Q = (Cb - (np.outer(mu_w, sb) + np.outer(sb, mu_w)) + A * np.outer(mu_w, mu_w)).astype(np.float64)
         Sigma = b * Q / (A - 1)
         Sigma[~finite, :] = np.nan
         Sigma[:, ~finite] = np.nan

@@ -44,6 +44,47 @@ def fixture(name):
     return ar1(M, N, phis, seed, mean, sd), max_lag
 
 
+def spread(d):
+    """(phi, mean, sd) that differ in every coordinate -- phi 0 .. 0.9, mean -2 .. 2, sd 0.05 .. 2 -- so that a series read under
+    another coordinate's mean, or added to another coordinate's sum, moves G[k, 0] by orders of magnitude, and a chunk of 256
+    columns dropped or added twice moves it by one part in the number of chunks (>= 1 / 600 in the fixtures below)."""
+    phi = np.array([0.0, 0.5, 0.9]) if d == 3 else np.linspace(0, 0.9, d)
+    return phi, np.linspace(-2, 2, d), np.linspace(0.05, 2, d)
+
+
+# The shapes that reach the branches of csrc/chain_stats.hip's plan which "A" .. "F" do not (they all get one column chunk per
+# block, and d <= 130).  With J = N d columns in chunks of 256, `halves` 2 when split, ntile = max_lag // 32 + 1 lag tiles and
+# period = d / gcd(256, d), the plan is nb = ceil(ceil(1024 / (ntile halves)) / period) period blocks along x, at most the number
+# of chunks; block b walks the chunks b, b + nb, ...  tests/test_diagnostics_cpu.py reads nb back from the workspace size and
+# holds every name to the branch stated here.
+# name -> (M, N, d, seed, max_lag, split)
+PLAN_FIXTURES = {
+    # 514 chunks, period 3, nb = 513: block 0 alone walks a second chunk, the ragged last one (3 live columns)
+    "two-chunks-d3": (64, 43777, 3, 10, 31, True),
+    # odd M (the middle row is dropped), 2 lag tiles, 259 chunks, nb = 258: the tile that reloads x_t carried across chunks
+    "two-tiles-d3": (130, 22017, 3, 11, 63, True),
+    # period 15, 516 chunks, nb = 270, 2 lag tiles (the second holds lags 32 and 33), Mh = 35 odd: most blocks walk 2 chunks
+    "period15-d60": (70, 2200, 60, 12, 33, True),
+    # period 65, 559 chunks, nb = 520: several chunks with d < 256 not dividing 256, threads tid and tid + d added
+    "period65-d130": (64, 1100, 130, 13, 31, True),
+    # period 257, 516 chunks, nb = 514: a block holds 256 of 257 coordinates AND walks two chunks
+    "period257-d257": (64, 513, 257, 23, 31, True),
+    # the widest history the entry accepts: period 2, 600 chunks, nb = 512
+    "period2-d512": (64, 300, 512, 33, 31, True),
+    # unsplit, period 75, 528 chunks, nb = 1050 clamped to 528: d > 256 with one chunk per block
+    "one-chunk-d300": (40, 450, 300, 16, 31, False),
+    # 24 chunks of which a block holds 256 of 300 coordinates; small enough for every path
+    "tiny-d300": (16, 20, 300, 17, 7, True),
+}
+
+
+def plan_fixture(name):
+    """(X float32, max_lag, split)"""
+    M, N, d, seed, max_lag, split = PLAN_FIXTURES[name]
+    phi, mean, sd = spread(d)
+    return ar1(M, N, phi, seed, mean, sd), max_lag, split
+
+
 def split_chains(X, split=True):
     """(Mh, C, d) float64"""
     X = np.asarray(X, dtype=np.float64)
@@ -67,6 +108,29 @@ def reference_sums(X, max_lag, split=True):
         for t in range(max_lag + 1):
             G[:, t] += (z[:Mh - t] * z[t:]).sum(axis=0)
     return mean, m2, G
+
+
+def reference_sums_columns(X, max_lag, split=True):
+    """`reference_sums` with every chain at once: the same definition -- centre per (chain, coordinate) in float64, then for each
+    lag the products (z[:Mh - t] * z[t:]) summed over steps and chains -- for the histories of PLAN_FIXTURES, whose 87 554
+    series the chain-by-chain loop cannot walk in a test's time.  tests/test_diagnostics_cpu.py holds it to `reference_sums`."""
+    S = split_chains(X, split)
+    Mh, C, d = S.shape
+    mean = S.sum(axis=0) / Mh
+    Z = S - mean
+    m2 = np.einsum("tck,tck->ck", Z, Z)
+    G = np.empty((d, max_lag + 1))
+    for t in range(max_lag + 1):
+        G[:, t] = np.einsum("tck,tck->k", Z[:Mh - t], Z[t:])
+    return mean, m2, G
+
+
+def reference_summary_columns(X, max_lag, split=True):
+    """`reference_summary` on top of `reference_sums_columns`"""
+    mean, m2, G = reference_sums_columns(X, max_lag, split)
+    out = reference_finish(mean, m2, G, split_chains(X[:, :1], split).shape[0])
+    out["sums"] = (mean, m2, G)
+    return out
 
 
 def reference_finish(mean, m2, G, Mh):

@@ -16,13 +16,40 @@ from tests import diagnostics_case as dc
 GATE = 1e-10          # of sqrt(raw_ii raw_jj): 2^-53 x the longest chain of additions (<= the 4e5 rows of "C") = 4.4e-11
 G_FIXTURE = (64, 32, np.linspace(0, 0.6, 100), 6, np.linspace(-3, 3, 100), 1.0)
 ROTATION_HISTORY = (1024, 64, [0.0, 0.3, 0.5, 0.6], 7, [0.0, 5.0, -3.0, 1.0], [1.0, 0.1, 2.0, 1.0])
+# The shapes that reach the branches of csrc/moment_sums.hip's plan which the fixtures above do not (they have at most 1000
+# chains and T = ceil(d / 16) = 1, 2 or 7 tiles).  A block is 4 waves x 4 chains: nchunks = ceil(chains / 16) chunks over
+# nbx = min(nchunks, 256) blocks (block b walks chunk b, b + 256, ...), the steps cut into nseg = min(ceil(256 / nbx), steps //
+# batch) segments after the rem = steps % batch leading rows that belong to no batch.  d <= 64: one panel of T tiles; above, a
+# panel of tiles [0, 4), one of the T - 4 others and an off-diagonal one.  Every coordinate has its own phi, mean and sd
+# (diagnostics_case.spread).  tests/test_multivariate_cpu.py reads nbx nseg back from the workspace size.
+# name -> (steps, chains, d, batch, seed)
+PLAN_FIXTURES = {
+    # 258 chunks > 256, nseg = 1, rem = 1: blocks 0 and 1 walk a second chunk and start it with the leading remainder again;
+    # chunk 257 has one live chain, in wave 0
+    "two-chunks-d17": (21, 4113, 17, 4, 20),
+    # 257 chunks across the three panels of T = 5 (the off-diagonal one is <4, 1>), rem = 0
+    "two-chunks-d70": (12, 4100, 70, 3, 21),
+    # 33 chains = 2 chunks and one chain, nseg = 6, rem = 4; A = 198 batches > d
+    "panel-d40": (40, 33, 40, 6, 22),        # T = 3, one panel
+    "panel-d64": (40, 33, 64, 6, 23),        # T = 4, one panel, every column live
+    "panel-d65": (40, 33, 65, 6, 24),        # T = 5: second diagonal panel of 1 tile with one live column, off-diagonal <4, 1>
+    "panel-d96": (40, 33, 96, 6, 25),        # T = 6: second diagonal panel of 2 tiles, off-diagonal <4, 2>
+    "panel-d113": (40, 33, 113, 6, 26),      # T = 8, the last tile with one live column, off-diagonal <4, 4>
+    "panel-d128": (40, 33, 128, 6, 27),      # T = 8, the widest history the entry accepts
+}
 _CACHE = {}
 
 
 def history(name):
-    """float32 (steps, chains, d): the fixtures of diagnostics_case, "G" (d = 100) and "R" (the rotation history)."""
+    """float32 (steps, chains, d): the fixtures of diagnostics_case, "G" (d = 100), "R" (the rotation history) and
+    PLAN_FIXTURES."""
     if name not in _CACHE:
-        X = dc.ar1(*G_FIXTURE) if name == "G" else dc.ar1(*ROTATION_HISTORY) if name == "R" else dc.fixture(name)[0]
+        if name in PLAN_FIXTURES:
+            steps, chains, d, _, seed = PLAN_FIXTURES[name]
+            phi, mean, sd = dc.spread(d)
+            X = dc.ar1(steps, chains, phi, seed, mean, sd)
+        else:
+            X = dc.ar1(*G_FIXTURE) if name == "G" else dc.ar1(*ROTATION_HISTORY) if name == "R" else dc.fixture(name)[0]
         X.setflags(write=False)
         _CACHE[name] = X
     return _CACHE[name]

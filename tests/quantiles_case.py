@@ -35,6 +35,38 @@ def adversarial():
     return Y, max_lag
 
 
+# The shapes that reach the branches of csrc/order_stats.hip's plan which the fixtures of diagnostics_case do not; the plan of
+# each is derived in tests/test_gpu_quantiles.py.  name -> (M, N, d, seed)
+PLAN_FIXTURES = {
+    "long-walk-d70": (140, 1000, 70, 30),    # every block walks 17 to 124 steps; hostile values in coordinates 1 .. 7 and 69
+    "groups-d512": (9, 500, 512, 31),        # the widest history the entry accepts: 8 coordinate groups of 64
+    "copies-d3": (300, 100, 3, 32),          # 21 histogram copies of 3 coordinates, the last thread of a block idle
+}
+LONG_WALK_NAN_COORDINATE = 69
+
+
+def plan_history(name):
+    """float32 (M, N, d), every coordinate with its own phi, mean and sd (diagnostics_case.spread).  "long-walk-d70" carries the
+    hostile coordinates of `adversarial` -- ties, a +-0 mix, +-inf, equal top 24 bits, denormals -- and one NaN in its LAST
+    coordinate, which belongs to the second coordinate group of the count passes."""
+    M, N, d, seed = PLAN_FIXTURES[name]
+    phi, mean, sd = dc.spread(d)
+    Y = dc.ar1(M, N, phi, seed, mean, sd)
+    if name == "long-walk-d70":
+        rng = np.random.RandomState(seed + 1000)
+        shape = Y.shape[:2]
+        Y[:, :, 1] = 2.5                                                # a constant
+        Y[:, :, 2] = np.round(Y[:, :, 2] * 2) / 2                       # multiples of 0.5: heavy ties
+        Y[:, :, 3] = np.where(rng.rand(*shape) < 0.5, np.float32(0.0), np.float32(-0.0))  # a +-0 mix
+        Y[3, 5, 4], Y[70, 20, 4], Y[139, 999, 4] = np.inf, -np.inf, np.inf                # the last draw of all among them
+        Y[:, :, 5] = (np.uint32(0x3FC00000) | rng.randint(0, 256, size=shape).astype(np.uint32)).view(np.float32)
+        Y[:, :, 6] = -np.abs(Y[:, :, 6]) - np.float32(0.125)            # all negative
+        Y[:, :, 7] = (rng.randint(1, 1 << 20, size=shape).astype(np.uint32)
+                      | (rng.randint(0, 2, size=shape).astype(np.uint32) << np.uint32(31))).view(np.float32)    # denormals
+        Y[137, 993, LONG_WALK_NAN_COORDINATE] = np.nan
+    return Y
+
+
 def draws(X):
     return np.ascontiguousarray(X, dtype=np.float32).reshape(-1, X.shape[-1])
 

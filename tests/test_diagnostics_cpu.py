@@ -30,6 +30,104 @@ def test_fixtures_keep_every_pair_sum_away_from_zero():
         assert int(ref["truncated"].sum()) == n_trunc, (name, ref["truncated"])
 
 
+_PLAN_REF = {}
+
+
+def _plan_case(name):
+    """(X, max_lag, split, the column restatement's summary), computed once"""
+    if name not in _PLAN_REF:
+        X, max_lag, split = dc.plan_fixture(name)
+        _PLAN_REF[name] = (X, max_lag, split, dc.reference_summary_columns(X, max_lag, split))
+    return _PLAN_REF[name]
+
+
+@pytest.mark.parametrize("split", [True, False])
+@pytest.mark.parametrize("name", ["F", "D"])
+def test_column_restatement_equals_the_chain_by_chain_one(name, split):
+    """`reference_sums_columns` is the reference of the large histories: it is itself held to the loop over chains, to 1e-12 of
+    G[k, 0] (both float64, another order of the additions), and its summary to the loop's."""
+    X, max_lag = dc.fixture(name)
+    mean, m2, G = dc.reference_sums(X, max_lag, split)
+    cmean, cm2, cG = dc.reference_sums_columns(X, max_lag, split)
+    g0 = G[:, 0]
+    assert cmean.shape == mean.shape and cm2.shape == m2.shape and cG.shape == G.shape
+    assert np.max(np.abs(cmean - mean) / (np.abs(mean) + np.sqrt(m2))) < 1e-12
+    assert np.max(np.abs(cm2 - m2) / g0) < 1e-12
+    assert np.max(np.abs(cG - G) / g0[:, None]) < 1e-12
+    a, b = dc.reference_summary(X, max_lag, split), dc.reference_summary_columns(X, max_lag, split)
+    assert np.array_equal(a["truncated"], b["truncated"]) and (a["n_steps"], a["n_chains"]) == (b["n_steps"], b["n_chains"])
+    for key in ("mean", "sd", "rhat", "ess", "tau"):
+        assert np.max(np.abs(a[key] - b[key]) / (np.abs(a[key]) + (a["sd"] if key == "mean" else 0.0))) < 1e-10, key
+
+
+@pytest.mark.parametrize("name", sorted(dc.PLAN_FIXTURES))
+def test_plan_fixtures_keep_every_pair_sum_away_from_zero(name):
+    """The condition of `test_fixtures_keep_every_pair_sum_away_from_zero` on the histories of PLAN_FIXTURES, from the
+    restatement alone: |P_j| >= 1e-4 up to and including the stopping pair, so `truncated` cannot flip on a rounding of rho
+    below 4e-5.  (The seeds were chosen for it: 14 and 15 left one pair of "period257-d257" / "period2-d512" at 1.6e-5 / 5e-5.)"""
+    X, max_lag, split, ref = _plan_case(name)
+    smallest = min(np.abs(p).min() for p in ref["pairs"])
+    print("fixture %s: smallest |P_j| %.3g, truncated %d of %d, max rhat %.4f" % (name, smallest, ref["truncated"].sum(),
+                                                                                  X.shape[2], ref["rhat"].max()))
+    assert all(len(p) >= 1 for p in ref["pairs"])                       # no degenerate coordinate
+    assert smallest >= 1e-4, (name, smallest)
+
+
+# name -> (column chunks, blocks along x): what tests/diagnostics_case.py states next to PLAN_FIXTURES
+PLANS = {"two-chunks-d3": (514, 513), "two-tiles-d3": (259, 258), "period15-d60": (516, 270), "period65-d130": (559, 520),
+         "period257-d257": (516, 514), "period2-d512": (600, 512), "one-chunk-d300": (528, 528), "tiny-d300": (24, 24)}
+
+
+def test_plan_fixtures_reach_their_branch():
+    """The workspace of `l2hmc_chain_stats` is nb halves min(d, 256) (max_lag + 1) doubles, so nb, the number of blocks along x,
+    is visible without a GPU: the multi-chunk fixtures have nb < ceil(N d / 256) (a block walks chunk b, b + nb, ...), with nb a
+    multiple of the period d / gcd(256, d); the one-chunk ones nb = the number of chunks; and "A" .. "F" stay one chunk per
+    block, which is why these fixtures exist.  A planner that moves a fixture off its branch fails here."""
+    from math import gcd
+    from l2hmc_amd import _ffi
+    ws = _ffi.lib().l2hmc_chain_stats_workspace_doubles
+
+    def blocks(M, N, d, max_lag, split):
+        total = ws(M, N, d, max_lag, int(split))
+        per = (2 if split else 1) * min(d, 256) * (max_lag + 1)
+        assert total > 0 and total % per == 0
+        return total // per, -(-N * d // 256)
+
+    assert set(PLANS) == set(dc.PLAN_FIXTURES)
+    for name, (M, N, d, _, max_lag, split) in dc.PLAN_FIXTURES.items():
+        nb, nchunks = blocks(M, N, d, max_lag, split)
+        assert (nchunks, nb) == PLANS[name], (name, nchunks, nb)
+        if nb < nchunks:
+            assert nb % (d // gcd(256, d)) == 0, name
+    multi = {n for n, (c, b) in PLANS.items() if b < c}
+    assert multi == set(PLANS) - {"one-chunk-d300", "tiny-d300"}
+    assert {n for n in PLANS if dc.PLAN_FIXTURES[n][2] > 256} == {"period257-d257", "period2-d512", "one-chunk-d300", "tiny-d300"}
+    for name in NAMES:
+        M, N, phis, _, _, _, max_lag = dc.FIXTURES[name]
+        for split in (True, False):
+            nb, nchunks = blocks(M, N, len(phis), max_lag, split)
+            assert nb == nchunks, (name, split)
+
+
+def test_numpy_path_holds_more_than_256_coordinates():
+    """"tiny-d300" on the numpy path against both restatements, as `test_numpy_path_matches_the_restatement` does."""
+    from l2hmc_amd import diagnostics
+    X, max_lag, split, ref = _plan_case("tiny-d300")
+    slow = dc.reference_summary(X, max_lag, split)
+    got = diagnostics.summarize(X, max_lag, split)
+    sums = diagnostics.chain_sums(X, max_lag, split)
+    for r in (ref, slow):
+        mean, m2, G = r["sums"]
+        assert np.max(np.abs(sums["mean"] - mean) / (np.abs(mean) + np.sqrt(m2 / (r["n_steps"] - 1)))) < 1e-10
+        assert np.max(np.abs(sums["m2"] - m2) / m2) < 1e-10
+        assert np.max(np.abs(sums["G"] - G) / G[:, :1]) < 1e-10
+        for key in ("mean", "sd", "rhat", "ess"):
+            scale = np.abs(r[key]) + (r["sd"] if key == "mean" else 0.0)
+            assert np.max(np.abs(got[key] - r[key]) / scale) < 1e-10, key
+        assert np.array_equal(got.truncated, r["truncated"])
+    assert (got.n_steps, got.n_chains, got.max_lag) == (8, 40, 7)
+
+
 def test_estimator_recovers_known_ar1_answers():
     """On the restatement alone: the ESS of an AR(1) chain is C Mh (1 - phi) / (1 + phi); chains from one distribution have
     R-hat near 1 and chains from two do not; too few lags are reported."""

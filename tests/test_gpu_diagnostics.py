@@ -7,7 +7,10 @@ of G[k, 0] -- a chunk of float32 FMAs of at most 64 steps is off by at most 64 *
 is at most G[k, 0] by Cauchy-Schwarz; rounding the centred values adds 2^-23 of the same; a factor 5 on top for the float64
 fold.  rhat: 2e-5 relative.  ess: the ceiling is (max_lag + 1) * 4e-5 / tau (every pair off by the bound, the same way), about
 1e-2 at max_lag = 255, tau = 1; the gate is ten times the worst deviation measured on the MI355X (profiles/
-diagnostics_accuracy.txt: 8.47e-8 over the six fixtures, split and unsplit) or the ceiling, whichever is smaller."""
+diagnostics_accuracy.txt: 8.47e-8 over the six fixtures, split and unsplit) or the ceiling, whichever is smaller.
+
+The six fixtures all get one column chunk per block and d <= 130; the histories of diagnostics_case.PLAN_FIXTURES reach the
+rest of the plan (several chunks per block, d > 256) under the same derived gates, ess under the ceiling alone."""
 import numpy as np
 import pytest
 import torch
@@ -76,6 +79,70 @@ def test_summarize_matches_the_restatement(name, split):
     assert np.all(e_ess < ess_gate(lag, ref["tau"]))
     assert np.max(np.abs(got.mean - ref["mean"]) / (np.abs(ref["mean"]) + ref["sd"])) < 1e-10
     assert (got.n_steps, got.n_chains, got.max_lag) == (ref["n_steps"], ref["n_chains"], lag)
+
+
+PLAN_NAMES = sorted(dc.PLAN_FIXTURES)
+_PLAN_REF = {}
+
+
+def _plan_case(name):
+    """(X, max_lag, split, the column restatement's summary) of a history of diagnostics_case.PLAN_FIXTURES, computed once"""
+    if name not in _PLAN_REF:
+        X, lag, split = dc.plan_fixture(name)
+        _PLAN_REF[name] = (X, lag, split, dc.reference_summary_columns(X, lag, split))
+    return _PLAN_REF[name]
+
+
+@pytest.mark.parametrize("name", PLAN_NAMES)
+def test_raw_sums_across_chunks_and_wide_histories(name):
+    """The branches of the plan "A" .. "F" never take (tests/diagnostics_case.py states each history's plan,
+    tests/test_diagnostics_cpu.py pins it): a block that walks two or three column chunks with its 32 float64 sums and its
+    coordinate in registers, in the first lag tile and in one that reloads x_t; a ragged last chunk as a block's SECOND chunk;
+    d > 256, where a block holds 256 of the coordinates and the reducer skips the blocks that do not hold coordinate k; d = 512.
+    Every coordinate has its own phi, mean and sd, so the gates of `test_raw_sums_match_the_restatement` -- unchanged --
+    catch a coordinate that slips (orders of magnitude) and a chunk dropped or added twice (>= 1 / 600 of G[k, 0])."""
+    from l2hmc_amd import diagnostics
+    X, lag, split, ref = _plan_case(name)
+    sums = diagnostics.chain_sums(torch.as_tensor(X).cuda(), lag, split)
+    assert tuple(sums["mean"].shape) == ref["sums"][0].shape and tuple(sums["G"].shape) == (X.shape[2], lag + 1)
+    assert (sums["n_steps"], sums["n_chains"]) == (ref["n_steps"], ref["n_chains"])
+    e_mean, e_m2, e_G = _sums_errors(sums, ref)
+    print("fixture %s max_lag %d split %d: mean %.3g of |mean| + sd, M2 %.3g and G %.3g of G[k, 0]" % (name, lag, split, e_mean,
+                                                                                                     e_m2, e_G))
+    assert e_mean < 1e-10
+    assert e_m2 < 2e-5 and e_G < 2e-5
+
+
+@pytest.mark.parametrize("name", PLAN_NAMES)
+def test_summarize_across_chunks_and_wide_histories(name):
+    """The finished numbers of the same histories.  ess: the derived ceiling (max_lag + 1) * 4e-5 / tau alone -- `ESS_MEASURED`
+    was measured on "A" .. "F" and says nothing here (profiles/diagnostics_accuracy.txt has these histories' own figures)."""
+    from l2hmc_amd import diagnostics
+    X, lag, split, ref = _plan_case(name)
+    got = diagnostics.summarize(torch.as_tensor(X).cuda(), lag, split)
+    assert np.array_equal(got.truncated, ref["truncated"])
+    e_rhat = np.max(np.abs(got.rhat - ref["rhat"]) / ref["rhat"])
+    e_ess = np.abs(got.ess - ref["ess"]) / np.abs(ref["ess"])
+    e_sd = np.max(np.abs(got.sd - ref["sd"]) / ref["sd"])
+    ceiling = (lag + 1) * 4e-5 / ref["tau"]
+    print("fixture %s split %d: rhat %.3g, sd %.3g, ess %.3g relative (smallest ceiling %.3g)" % (
+        name, split, e_rhat, e_sd, e_ess.max(), ceiling.min()))
+    assert e_rhat < 2e-5 and e_sd < 2e-5
+    assert np.all(e_ess < ceiling)
+    assert np.max(np.abs(got.mean - ref["mean"]) / (np.abs(ref["mean"]) + ref["sd"])) < 1e-10
+    assert (got.n_steps, got.n_chains, got.max_lag) == (ref["n_steps"], ref["n_chains"], lag)
+
+
+def test_two_calls_across_chunks_give_identical_bits():
+    """"period65-d130": 520 blocks over 559 chunks, the threads of a coordinate added through LDS after the last chunk."""
+    from l2hmc_amd import diagnostics
+    X, lag, split, _ = _plan_case("period65-d130")
+    Xd = torch.as_tensor(X).cuda()
+    a = diagnostics.chain_sums(Xd, lag, split)
+    torch.empty(1 << 24, device="cuda").normal_()                  # other work, another workspace address
+    b = diagnostics.chain_sums(Xd.clone(), lag, split)
+    for k in ("mean", "m2", "G"):
+        assert torch.equal(a[k].view(torch.int64), b[k].view(torch.int64)), k
 
 
 def test_two_calls_give_identical_bits():

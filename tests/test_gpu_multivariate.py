@@ -18,7 +18,10 @@ centred ones).
 
 Measured on the MI355X (profiles/multivariate_accuracy.txt, written by tools/multivariate_accuracy.py) -- the worst
 deviation of the sums as a fraction of their gate, and of multi_ess, relative:
-    E 1.6e-6, 6.6e-14;  B 5.6e-6, 7.2e-16;  F 7.8e-6, 1.5e-16;  C 2.3e-4, 9.8e-12;  G 7.4e-6, 1.3e-15;  A 4.1e-5, 1.5e-12."""
+    E 1.6e-6, 6.6e-14;  B 5.6e-6, 7.2e-16;  F 7.8e-6, 1.5e-16;  C 2.3e-4, 9.8e-12;  G 7.4e-6, 1.3e-15;  A 4.1e-5, 1.5e-12.
+
+Those fixtures have at most 1000 chains (63 chunks of 16: one chunk per block) and T = 1, 2 or 7 tiles; the histories of
+multivariate_case.PLAN_FIXTURES reach the rest of the plan under the same gates (their figures are in the same file)."""
 import numpy as np
 import pytest
 import torch
@@ -101,6 +104,54 @@ def test_multi_ess_matches_the_restatement(name):
     assert np.all(np.abs(got.corr - got.cov / np.outer(got.sd, got.sd)) <= 1e-15) and np.all(np.diag(got.corr) == 1.0)
     assert np.all(np.abs(got.sd - ref["sd"]) * (ref["n_draws"] - 1) * 2 * ref["sd"] <= 3 * np.diag(g) * (1 + 1e-6))
     assert np.array_equal(got.cov, got.cov.T) and np.array_equal(got.cov_asymptotic, got.cov_asymptotic.T)
+
+
+PLAN_NAMES = sorted(mc.PLAN_FIXTURES)
+
+
+@pytest.mark.parametrize("name", PLAN_NAMES)
+def test_sums_and_multi_ess_across_chunks_and_panels(name):
+    """The branches of the plan the fixtures above never take (tests/multivariate_case.py states each history's plan,
+    tests/test_multivariate_cpu.py pins it): more than 256 chunks of 16 chains, so that a block keeps its accumulators, column
+    sums and batch sums across two chunks while the batch in progress, and the leading rows that belong to no batch, start
+    again in the second; T = 3 and T = 4 tiles in one panel; the off-diagonal panels <4, 1>, <4, 2>, <4, 4> and second diagonal
+    panels of 1, 2 and 4 tiles; d = 64, 65, 128.  Every coordinate has its own phi, mean and sd.  The gates are those of
+    `test_sums_match_the_restatement` and `test_multi_ess_matches_the_restatement`, unchanged: every history has fewer than the
+    4e5 rows the sum gate allows for, and more batches than coordinates."""
+    from l2hmc_amd import multivariate
+    steps, chains, d, batch, _ = mc.PLAN_FIXTURES[name]
+    X = mc.history(name)
+    Xd = _device(name)
+    assert X.shape == (steps, chains, d) and steps * chains < 4e5 and (steps // batch) * chains > d
+    for b in (batch, 0):
+        got = multivariate.moment_sums(Xd, b)
+        ref = _reference(name, b)
+        assert got["n_draws"] == ref["n_draws"] and got["n_batches"] == ref.get("n_batches", 0)
+        worst = _check_sums(got, ref)
+        print("fixture %s batch %d: worst deviation %.3g of the gate" % (name, b, worst))
+    ref = _reference(name, batch)
+    got = multivariate.multi_ess(Xd, batch)
+    assert not got.degenerate.any()
+    assert (got.n_draws, got.n_batches, got.batch_size) == (ref["n_draws"], ref["n_batches"], batch)
+    B = mess_bound(ref)
+    e = abs(got.multi_ess - ref["multi_ess"]) / ref["multi_ess"]
+    print("fixture %s: multi_ess %.6g, relative deviation %.3g, bound 2 B = %.3g, cond(Sigma) %.3g" % (
+        name, got.multi_ess, e, 2 * B, np.linalg.cond(ref["cov_asymptotic"])))
+    assert e <= 2 * B
+    _, g = mc.sum_gates(np.diag(ref["cross"]), ref["n_draws"])
+    assert np.all(np.abs(got.cov - ref["cov"]) * (ref["n_draws"] - 1) <= 3 * g)
+    assert np.array_equal(got.cov, got.cov.T) and np.array_equal(got.cov_asymptotic, got.cov_asymptotic.T)
+
+
+def test_two_calls_across_chunks_give_identical_bits():
+    """"two-chunks-d17" (4113 chains, 258 chunks over 256 blocks), with batches."""
+    from l2hmc_amd import multivariate
+    Xd = _device("two-chunks-d17")
+    first = multivariate.moment_sums(Xd, 4)
+    torch.empty(1 << 24, device="cuda").normal_()                       # 64 MB of other work, another workspace address
+    second = multivariate.moment_sums(Xd.clone(), 4)
+    for key in ("sum", "cross", "batch_sum", "batch_cross"):
+        assert torch.equal(first[key].view(torch.int64), second[key].view(torch.int64)), key
 
 
 def test_batch_size_one_and_whole_chain():

@@ -1,10 +1,20 @@
 """GPU: exact order statistics on the device (csrc/order_stats.hip behind `l2hmc_order_stats`), the indicator form of the chain
 sums (`l2hmc_chain_stats_below`) and `quantiles.describe` on top of them, against the restatement of tests/quantiles_case.py.
 
-Shapes: the smallest at which the count pass's plan can go wrong -- "E" (d = 1, S = 250: less than one block, 64 histogram
-copies), "F" (N d odd, 17 coordinates: 15 rows per block step, idle lanes), "D" (d = 130: three coordinate groups in every pass),
-"B" (S = 51400: every block walks several steps), and per-coordinate tables of 32 ranks (rank groups: 32 x d pairs never fit one
-group).
+Shapes: the smallest at which the count pass's plan can go wrong.  The plan (csrc/order_stats.hip, `order_stats_plan`): a group
+is sg <= 64 / rg coordinates x rg ranks (rg = 1 in pass 0, otherwise the power of two with the fewest groups), ngk coordinate
+and ngr rank groups; a block step is rpc = 256 // sg rows, the LDS histogram has min(64 // (sg rg), rpc) copies; nb =
+max(1024 // (ngk ngr), 64) blocks along x, at most ceil(S / rpc), and a block walks ceil(S / rpc) / nb steps -- 8 or more enter
+the software-pipelined load loop.  By that plan, for 5 standard ranks / a table of 32:
+ - "E" (d = 1, S = 250): one block, one step, 64 copies; later passes rg 8 / 32, 8 / 2 copies;
+ - "F" and the adversarial history (d = 17, S = 7392, N d odd): sg 17, 15 rows per step with one idle thread, 3 copies, one
+   step; later passes rg 2 x 3 rank groups, 341 blocks and 1 or 2 steps / rg 32, 9 groups of 2 coordinates, one step;
+ - "D" (d = 130, S = 1024): 3 groups of 44 (2 idle coordinates), rpc 5, one step; later passes 3 x 5 groups, 68 blocks and 3 or
+   4 steps / rg 32, 65 groups of 2, one step;
+ - "B" (d = 2, S = 51 400): 32 copies, rpc 128, 402 chunks in 402 blocks -- ONE step per block in every pass (rg 8 / 32);
+ - "C" (d = 25, S = 400 000, through `describe` with 3 to 5 ranks only): 39 to 118 steps;
+so of these only "C" reaches the pipelined loop, never with a rank table, and none has d > 130.  The histories of
+quantiles_case.PLAN_FIXTURES close that; `test_order_statistics_are_exact_where_blocks_walk_far` derives their plans.
 
 Gates.  Order statistics and quantiles: exact / 1e-15.  The indicator sums carry the gates tests/test_gpu_diagnostics.py
 derives for the same arithmetic: mean 1e-10 of |mean| + sd, M2 and G 2e-5 of G[k, 0].  ess_quantile: the derived ceiling
@@ -49,6 +59,36 @@ def test_order_statistics_are_exact(name):
         ok = want_nan == 0
         assert np.array_equal(got[:, ok], want[:, ok]), np.argwhere(got != want)[:8]
         assert np.all(np.isnan(got[-1, ~ok]))                           # NaNs sort last: rank S - 1 of such a coordinate
+
+
+@pytest.mark.parametrize("name,table_rows", [("long-walk-d70", 32), ("groups-d512", 3), ("copies-d3", 20)])
+def test_order_statistics_are_exact_where_blocks_walk_far(name, table_rows):
+    """Bit-exact against np.sort, at the standard ranks (R = 5) and a per-coordinate table, where the plan (module docstring)
+    leaves what the other histories reach:
+     - "long-walk-d70" (S = 140 000, d = 70), hostile coordinates included.  Pass 0: 2 groups of sg 35, rpc 7, 1 copy, 20 000
+       chunks over nb = 512: 39 or 40 steps, four or five rounds of the pipelined loop and a tail.  Later passes, R = 5: rg 2,
+       ngk 3 (sg 24, two idle coordinates), ngr 3 (the last with one rank), rpc 10, nb = 113, 123 or 124 steps; R = 32: rg 32,
+       ngk 35 groups of sg 2, ngr 1, rpc 128, 1094 chunks over nb = 64, 17 or 18 steps.
+     - "groups-d512" (S = 4500, d = 512, the widest the entry accepts).  Pass 0: ngk 8 groups of sg 64, rpc 4, 1125 chunks over
+       nb = 128, 8 or 9 steps (one round of the pipelined loop, a tail of 0 or 1).  Later passes: rg 1, ngk 8, ngr 5 / 3, nb = 64,
+       17 or 18 steps.
+     - "copies-d3" (S = 30 000, d = 3).  Pass 0: sg 3, rpc 85 (thread 255 idle), 21 copies, 63 LDS columns, 353 blocks of one
+       step.  Later passes, R = 5: rg 8, 2 copies; R = 20: rg 16, ngr 2 (the second group with 4 of its 16 ranks), 1 copy."""
+    from l2hmc_amd import quantiles
+    X = qc.plan_history(name)
+    Xd = torch.as_tensor(X).cuda()
+    S, d = X.shape[0] * X.shape[1], X.shape[2]
+    for ranks in (qc.standard_ranks(S), qc.rank_table(S, d, seed=1, R=table_rows)):
+        want, want_nan = qc.reference_order_statistics(X, ranks)
+        got, got_nan = quantiles.order_statistics(Xd, ranks)
+        assert got.dtype == np.float32 and got.shape == want.shape
+        assert np.array_equal(got_nan, want_nan)
+        ok = want_nan == 0
+        assert np.array_equal(got[:, ok], want[:, ok]), np.argwhere(got != want)[:8]
+        assert np.all(np.isnan(got[-1, ~ok]))                           # NaNs sort last: rank S - 1 of such a coordinate
+        fin = ~np.isnan(want)
+        assert np.array_equal(got[fin], want[fin])                      # and every other rank of it is a value
+    assert want_nan.sum() == (1 if name == "long-walk-d70" else 0)
 
 
 def test_nan_coordinate_is_nan_alone():
@@ -160,6 +200,33 @@ def test_indicator_sums_match_the_restatement(name, split):
                                                                                                     e_m2, e_G))
         assert e_mean < 1e-10
         assert e_m2 < 2e-5 and e_G < 2e-5
+
+
+@pytest.mark.parametrize("name", ["two-chunks-d3", "period65-d130", "period257-d257"])
+def test_indicator_sums_across_chunks(name):
+    """`l2hmc_chain_stats_below` where a block walks more than one column chunk (diagnostics_case.PLAN_FIXTURES: d = 3 with the
+    ragged chunk as block 0's second, d = 130, and d = 257 where a block holds 256 of the coordinates): a thread's threshold is
+    that of its coordinate in EVERY chunk.  The thresholds are the coordinates' own means, -2 .. 2 at sd 0.05 .. 2: under a
+    neighbour's threshold an indicator series is another series.  Against the column restatement on the indicator history,
+    under the gates of `test_indicator_sums_match_the_restatement`."""
+    from l2hmc_amd import diagnostics
+    X, lag, split = dc.plan_fixture(name)
+    thresholds = dc.spread(X.shape[2])[1]
+    mean, m2, G = dc.reference_sums_columns(qc.indicator_history(X, thresholds), lag, split)
+    sums = diagnostics.chain_sums_below(torch.as_tensor(X).cuda(), thresholds, lag, split)
+    Mh = sums["n_steps"]
+    assert (Mh, sums["n_chains"]) == (X.shape[0] // 2, 2 * X.shape[1]) and split
+    sd = np.sqrt(m2 / (Mh - 1))
+    got_mean, got_m2, got_G = (sums[k].cpu().numpy() for k in ("mean", "m2", "G"))
+    g0 = G[:, 0]
+    assert np.all(g0 > 0)
+    scale = np.abs(mean) + sd                                           # 0 for a series that never reaches the threshold: exact 0
+    e_mean = np.max(np.abs(got_mean - mean) / np.where(scale > 0, scale, 1.0))
+    e_m2 = np.max(np.abs(got_m2 - m2).sum(axis=0) / g0)
+    e_G = np.max(np.abs(got_G - G) / g0[:, None])
+    print("fixture %s: mean %.3g of |mean| + sd, M2 %.3g and G %.3g of G[k, 0]" % (name, e_mean, e_m2, e_G))
+    assert e_mean < 1e-10
+    assert e_m2 < 2e-5 and e_G < 2e-5
 
 
 def ess_gate(max_lag, tau):

@@ -44,6 +44,74 @@ def test_numpy_path_matches_the_restatement(name):
     assert np.max(np.abs(flat.cov * (n - 1) - ref["P"]) / scale) < 1e-12
 
 
+# name -> (chunks of 16 chains, blocks along x, step segments): what tests/multivariate_case.py states next to PLAN_FIXTURES
+PLANS = {"two-chunks-d17": (258, 256, 1), "two-chunks-d70": (257, 256, 1)}
+PLANS.update({"panel-d%d" % d: (3, 3, 6) for d in (40, 64, 65, 96, 113, 128)})
+
+
+def test_plan_fixtures_reach_their_branch():
+    """The workspace of `l2hmc_moment_sums` is stride nbx nseg npanel doubles with, as csrc/moment_sums.hip's header says,
+    stride = (P 256 + 4 x 64) doubles per accumulator set (two sets with batches), P the pairs of the largest panel, so the
+    number of blocks per panel is visible without a GPU.  The two-chunk fixtures have nbx = 256 < ceil(chains / 16): block 0
+    (and 1) walks a second chunk; the panel fixtures 3 chunks in 3 blocks x 6 segments; and the older fixtures never more blocks
+    than chunks along x.  Both with batches and without."""
+    from l2hmc_amd import _ffi
+    ws = _ffi.lib().l2hmc_moment_sums_workspace_doubles
+
+    def blocks(steps, chains, d, batch):
+        T = -(-d // 16)
+        pairs, npanel = (T * (T + 1) // 2, 1) if T <= 4 else (max(10, 4 * (T - 4)), 3)
+        per = (pairs * 256 + 4 * 64) * (2 if batch else 1) * npanel
+        total = ws(steps, chains, d, batch)
+        assert total > 0 and total % per == 0
+        return total // per
+
+    assert set(PLANS) == set(mc.PLAN_FIXTURES)
+    for name, (steps, chains, d, batch, _) in mc.PLAN_FIXTURES.items():
+        nchunks, nbx, nseg = PLANS[name]
+        assert nchunks == -(-chains // 16)
+        assert blocks(steps, chains, d, batch) == nbx * nseg, name
+        if nbx < nchunks:
+            assert nbx == 256 and blocks(steps, chains, d, 0) == 256, name              # batch 0: the same walk
+        else:
+            assert blocks(steps, chains, d, 0) == nbx * min(-(-256 // nbx), steps), name  # segments of single rows
+    rem = {name: steps % batch for name, (steps, _, _, batch, _) in mc.PLAN_FIXTURES.items()}     # leading rows in no batch
+    assert rem["two-chunks-d17"] == 1 and rem["two-chunks-d70"] == 0 and rem["panel-d65"] == 4
+    for name in ("A", "B", "C", "E", "F", "G"):
+        steps, chains, d = mc.history(name).shape
+        nchunks = -(-chains // 16)
+        assert nchunks <= 256 and blocks(steps, chains, d, mc.default_batch(steps)) % nchunks == 0, name   # nbx = nchunks
+
+
+def test_numpy_path_matches_the_restatement_at_five_tiles():
+    """"panel-d65" (40 x 33 x 65, batch 6, four leading rows in no batch) on the numpy path, as
+    `test_numpy_path_matches_the_restatement` does."""
+    from l2hmc_amd import multivariate
+    X = mc.history("panel-d65")
+    ref = mc.reference(X, 6)
+    got = multivariate.multi_ess(X, 6)
+    n = ref["n_draws"]
+    scale = np.sqrt(np.outer(np.diag(ref["P"]), np.diag(ref["P"])))
+    qscale = np.sqrt(np.outer(np.diag(ref["Q"]), np.diag(ref["Q"])))
+    assert (got.n_draws, got.batch_size, got.n_batches) == (1320, 6, 198) and not got.degenerate.any()
+    assert np.max(np.abs(got.cov * (n - 1) - ref["P"]) / scale) < 1e-12
+    assert np.max(np.abs(got.cov_asymptotic * (198 - 1) / 6 - ref["Q"]) / qscale) < 1e-12
+    assert np.max(np.abs(got.mean - ref["mean"]) / ref["sd"]) < 1e-12
+    assert np.max(np.abs(got.ess_batch - ref["ess_batch"]) / ref["ess_batch"]) < 1e-10
+    assert abs(got.multi_ess - ref["multi_ess"]) / ref["multi_ess"] < 1e-10
+
+
+@pytest.mark.parametrize("name", sorted(mc.PLAN_FIXTURES))
+def test_both_covariances_are_symmetric_bit_for_bit(name):
+    """`finish` takes the raw moments apart entry by entry: (i, j) and (j, i) must go through the same additions in the same
+    order.  (Q = batch_cross - mu sb^T - sb mu^T + A mu mu^T subtracted one term after the other did not: "panel-d65" and
+    "panel-d128" had 4 and 2 entries of `cov_asymptotic` one ulp from their mirror image.)"""
+    from l2hmc_amd import multivariate
+    got = multivariate.multi_ess(mc.history(name), mc.PLAN_FIXTURES[name][3])
+    assert np.array_equal(got.cov, got.cov.T) and np.array_equal(got.cov_asymptotic, got.cov_asymptotic.T)
+    assert np.array_equal(got.corr, got.corr.T)
+
+
 def test_raw_sums_and_batch_edges():
     from l2hmc_amd import multivariate
     X = mc.history("B")                                                        # 257 steps: batch rows start at row 1

@@ -42,6 +42,31 @@ def test_order_statistics_and_quantiles_match_the_restatement(name):
         assert np.all(got[:, 1] == 2.5)
 
 
+def test_order_statistics_of_the_plan_fixtures_on_numpy():
+    """"copies-d3" (300 x 100 x 3) with its 20-row rank table, and the hostile coordinates of "long-walk-d70" at the standard
+    ranks: the numpy path equals the sort, so the fixtures the device tests rest on are what they are said to be."""
+    from l2hmc_amd import quantiles
+    X = qc.plan_history("copies-d3")
+    S, d = 300 * 100, 3
+    assert X.shape == (300, 100, 3) and X.dtype == np.float32
+    for ranks in (qc.standard_ranks(S), qc.rank_table(S, d, seed=1, R=20)):
+        want, want_nan = qc.reference_order_statistics(X, ranks)
+        got, got_nan = quantiles.order_statistics(X, ranks)
+        assert got.dtype == np.float32 and np.array_equal(got, want) and np.array_equal(got_nan, want_nan) and not got_nan.any()
+    probs = (0.05, 0.5, 0.95)
+    got, want = quantiles.quantiles(X, probs), qc.reference_quantiles(X, probs)
+    assert np.all(np.abs(got - want) <= 1e-15 * np.abs(want))
+    Y = qc.plan_history("long-walk-d70")
+    S = 140 * 1000
+    want, want_nan = qc.reference_order_statistics(Y, qc.standard_ranks(S))
+    got, got_nan = quantiles.order_statistics(Y, qc.standard_ranks(S))
+    assert np.array_equal(got, want, equal_nan=True) and np.array_equal(got_nan, want_nan)
+    assert want_nan[qc.LONG_WALK_NAN_COORDINATE] == 1 and want_nan.sum() == 1 and np.isnan(want[-1, qc.LONG_WALK_NAN_COORDINATE])
+    assert want[0, 4] == -np.inf and want[-1, 4] == want[-2, 4] == np.inf and np.all(want[:, 1] == 2.5)
+    assert np.all(want[:, 3] == 0) and np.signbit(Y[:, :, 3]).any() and not np.signbit(Y[:, :, 3]).all()      # a +-0 mix
+    assert len(np.unique(Y[:, :, 2])) < 64 and np.all(np.abs(Y[:, :, 7]) < 2.0 ** -126)               # ties; denormals
+
+
 def test_numpy_radix_select_equals_the_sort():
     """The select the sharded path runs on numpy shards (8-bit digits, four passes, the histograms added between count and
     advance) agrees with np.sort at every rank of the adversarial history, ranks past the end included."""
