@@ -9,8 +9,8 @@ with each other -- what a posterior whose mean is not 0 needs.
     s.max_rhat, s.min_ess, s.rhat, s.ess, s.mean, s.sd, s.truncated
 
 A ROCm tensor goes to the HIP kernels behind `l2hmc_chain_stats` (csrc/chain_stats.hip) where it lies -- a first-axis slice of a
-history is contiguous -- and only the per-coordinate sums (3 d + d (max_lag + 1) numbers) come back; a numpy history is computed in float64 numpy (the convention
-of `func_utils`: there is no CPU path for sampling, but diagnostics of a numpy history are host arithmetic).
+history is contiguous -- and only the per-coordinate sums (3 d + d (max_lag + 1) numbers) come back; a numpy history is computed in float64 numpy (`_history`
+has the rule and the host side of the launch).
 
 The estimator.  With `split` every chain becomes two, rows [0, Mh) and [M - Mh, M) with Mh = M // 2: C = 2 N series of length
 Mh per coordinate (first halves, then second halves); without it Mh = M, C = N.  Per series: mean m and M2 = sum (x - m)^2.  Per
@@ -21,16 +21,11 @@ minimum; tau = -1 + 2 sum P; ess = C Mh / tau.
 """
 import numpy as np
 
+from . import _ffi
+from ._history import as_numpy, history_shape, in_place, is_device_tensor, launch, workspace
+
 DEFAULT_MAX_LAG = 255
 MAX_DEVICE_DIM = 512          # l2hmc_chain_stats: d <= 512
-
-
-def _is_device_tensor(X):
-    try:
-        import torch
-        return isinstance(X, torch.Tensor) and X.is_cuda
-    except ImportError:
-        return False
 
 
 def _shape(M, N, split, max_lag):
@@ -50,25 +45,19 @@ def _shape(M, N, split, max_lag):
 def _device_sums(X, Mh, C, max_lag, split, thresholds=None):
     """`thresholds` (d float64): the sums of the indicator series [x <= thresholds[k]] (`l2hmc_chain_stats_below`)."""
     import torch
-    from . import _ffi
-    X = X.detach()
-    if X.dtype != torch.float32 or not X.is_contiguous():
-        X = X.to(torch.float32).contiguous()
+    X = in_place(X)
     M, N, d = X.shape
-    L = _ffi.lib()
-    ws = torch.empty(_ffi.check(L.l2hmc_chain_stats_workspace_doubles(M, N, d, max_lag, int(split))), dtype=torch.float64,
-                     device=X.device)
-    mean = torch.empty((C, d), dtype=torch.float64, device=X.device)
-    m2 = torch.empty((C, d), dtype=torch.float64, device=X.device)
-    G = torch.empty((d, max_lag + 1), dtype=torch.float64, device=X.device)
-    with torch.cuda.device(X.device):
-        if thresholds is None:
-            _ffi.check(L.l2hmc_chain_stats(X.data_ptr(), M, N, d, max_lag, int(split), mean.data_ptr(), m2.data_ptr(),
-                                           G.data_ptr(), ws.data_ptr(), _ffi.current_stream(X.device)))
-        else:
-            thr = torch.as_tensor(np.ascontiguousarray(thresholds, dtype=np.float64)).to(X.device)
-            _ffi.check(L.l2hmc_chain_stats_below(X.data_ptr(), M, N, d, max_lag, int(split), thr.data_ptr(), mean.data_ptr(),
-                                                 m2.data_ptr(), G.data_ptr(), ws.data_ptr(), _ffi.current_stream(X.device)))
+    L, dev = _ffi.lib(), X.device
+    ws = workspace(dev, torch.float64, L.l2hmc_chain_stats_workspace_doubles, M, N, d, max_lag, int(split))
+    mean = torch.empty((C, d), dtype=torch.float64, device=dev)
+    m2 = torch.empty((C, d), dtype=torch.float64, device=dev)
+    G = torch.empty((d, max_lag + 1), dtype=torch.float64, device=dev)
+    out = (mean.data_ptr(), m2.data_ptr(), G.data_ptr(), ws.data_ptr())
+    if thresholds is None:
+        launch(dev, L.l2hmc_chain_stats, X.data_ptr(), M, N, d, max_lag, int(split), *out)
+    else:
+        thr = torch.as_tensor(np.ascontiguousarray(thresholds, dtype=np.float64)).to(dev)
+        launch(dev, L.l2hmc_chain_stats_below, X.data_ptr(), M, N, d, max_lag, int(split), thr.data_ptr(), *out)
     return mean, m2, G
 
 
@@ -101,32 +90,21 @@ def chain_sums_below(X, thresholds, max_lag=None, split=True):
 def chain_sums(X, max_lag=None, split=True, _thresholds=None):
     """The raw sums of a (M, N, d) history: {'mean': (C, d), 'm2': (C, d), 'G': (d, max_lag + 1), 'n_steps': Mh, 'n_chains': C}.
     A ROCm tensor -> HIP kernels, float64 device tensors (bitwise reproducible); numpy -> float64 numpy."""
-    if len(X.shape) != 3:
-        raise ValueError("a history is (steps, chains, dim); got shape %s" % (tuple(X.shape),))
-    M, N, d = (int(v) for v in X.shape)
+    M, N, d = history_shape(X)
     Mh, C, max_lag = _shape(M, N, split, max_lag)
     if d < 1:
         raise ValueError("a history needs dim >= 1")
-    if _is_device_tensor(X):
+    if is_device_tensor(X):
         if d > MAX_DEVICE_DIM:
             raise ValueError("the diagnostic kernels hold dim <= %d (got %d)" % (MAX_DEVICE_DIM, d))
         mean, m2, G = _device_sums(X, Mh, C, max_lag, split, _thresholds)
     else:
-        try:
-            import torch
-            if isinstance(X, torch.Tensor):
-                X = X.detach().numpy()
-        except ImportError:
-            pass
+        X = as_numpy(X)
         if _thresholds is not None:
             with np.errstate(invalid="ignore"):
-                X = (np.asarray(X).astype(np.float64) <= _thresholds).astype(np.float64)
+                X = (X.astype(np.float64) <= _thresholds).astype(np.float64)
         mean, m2, G = _host_sums(X, Mh, max_lag, split)
     return {"mean": mean, "m2": m2, "G": G, "n_steps": Mh, "n_chains": C}
-
-
-def _np(a):
-    return a.detach().cpu().numpy() if hasattr(a, "detach") else np.asarray(a, dtype=np.float64)
 
 
 def reduce_sums(sums):
@@ -140,8 +118,8 @@ def reduce_sums(sums):
     else:
         mean, m2 = np.asarray(mean, dtype=np.float64), np.asarray(m2, dtype=np.float64)
         parts = (mean.sum(axis=0), (mean * mean).sum(axis=0), m2.sum(axis=0))
-    return {"count": float(mean.shape[0]), "sum_mean": _np(parts[0]), "sum_mean_sq": _np(parts[1]), "sum_m2": _np(parts[2]),
-            "G": _np(sums["G"]).astype(np.float64), "n_steps": int(sums["n_steps"])}
+    return {"count": float(mean.shape[0]), "sum_mean": as_numpy(parts[0]), "sum_mean_sq": as_numpy(parts[1]),
+            "sum_m2": as_numpy(parts[2]), "G": as_numpy(sums["G"], np.float64), "n_steps": int(sums["n_steps"])}
 
 
 class Summary(dict):

@@ -2,37 +2,27 @@
 (`accept` :33-42, `autocovariance` :45-54, `acl_spectrum` :114-116, `ESS` :118-120) on recorded
 chains of shape (steps, chains, dim).  numpy input -> numpy arithmetic exactly like the
 reference; a ROCm tensor (e.g. the `x_hist` of `sample_chain`) -> the HIP kernel `l2hmc_autocov`,
-the history never leaves the GPU.  Also the small host-side helpers the VAE programs import from that file (`binarize`,
+the history never leaves the GPU (`_history` has the host side of that call).  Also the small host-side helpers the VAE programs import from that file (`binarize`,
 `binarize_and_shuffle`, `normal_kl`, `get_log_likelihood`, `tf_accept`); `get_data` (MNIST download) is out of scope."""
 import numpy as np
 
-
-def _is_device_tensor(X):
-    try:
-        import torch
-        return isinstance(X, torch.Tensor) and X.is_cuda
-    except ImportError:
-        return False
+from . import _ffi
+from ._history import in_place, is_device_tensor, launch, workspace
 
 
 def device_autocov(X, scale=1.0, n_total=None):
-    """(raw sums S(tau), A(tau)) of a (steps, N, d) float32 device history via `l2hmc_autocov`;
-    both are float64 device tensors of length steps-1."""
+    """(raw sums S(tau), A(tau)) of a (steps, N, d) float32 device history via `l2hmc_autocov`, launched on the history's own
+    device; both are float64 device tensors of length steps-1."""
     import torch
-    from . import _ffi
-    X = X.detach()
-    if X.dtype != torch.float32 or not X.is_contiguous():
-        X = X.to(torch.float32).contiguous()
+    X = in_place(X)
     steps, N, d = X.shape
     S = torch.empty(steps - 1, dtype=torch.float64, device=X.device)
     A = torch.empty(steps - 1, dtype=torch.float64, device=X.device)
     L = _ffi.lib()
     # per-block partial sums, added in block order: S and the thresholded ESS are bitwise reproducible
-    ws = torch.empty(max(1, _ffi.check(L.l2hmc_autocov_workspace_doubles(steps, N, d))), dtype=torch.float64,
-                     device=X.device)
-    _ffi.check(L.l2hmc_autocov(X.data_ptr(), steps, N, d, float(scale),
-                               int(N if n_total is None else n_total), S.data_ptr(),
-                               A.data_ptr(), ws.data_ptr(), _ffi.current_stream(X.device)))
+    ws = workspace(X.device, torch.float64, L.l2hmc_autocov_workspace_doubles, steps, N, d, at_least=1)
+    launch(X.device, L.l2hmc_autocov, X.data_ptr(), steps, N, d, float(scale), int(N if n_total is None else n_total),
+           S.data_ptr(), A.data_ptr(), ws.data_ptr())
     return S, A
 
 
@@ -55,7 +45,7 @@ def autocovariance(X, tau=0):
 
 def acl_spectrum(X, scale):
     """A(tau) for tau = 0 .. steps-2 on X / scale."""
-    if _is_device_tensor(X):
+    if is_device_tensor(X):
         return device_autocov(X, scale)[1].cpu().numpy()
     Xs = np.asarray(X) / scale
     return np.array([autocovariance(Xs, tau=t) for t in range(Xs.shape[0] - 1)])

@@ -8,7 +8,7 @@ estimate of the asymptotic covariance -- one number that, unlike `min_ess`, no i
 
 A ROCm tensor goes to the HIP kernels behind `l2hmc_moment_sums` (csrc/moment_sums.hip: float64 on the matrix pipe, one read of
 the history for d <= 64) where it lies -- a first-axis slice of a history is contiguous -- and only 2 (d + d^2) numbers come
-back; a numpy history is float64 numpy, the convention of `diagnostics`.  The device holds dim <= 128; beyond it use numpy.
+back; a numpy history is float64 numpy (`_history` has that rule and the host side of the launch).  The device holds dim <= 128; beyond it use numpy.
 
 The estimator.  n = steps * chains draws; raw sums s = sum x, C = sum x x^T.  mu = s / n, P = C - n mu mu^T, Lambda = P / (n - 1).
 A batch is `batch_size` consecutive steps of one chain (default floor(sqrt(steps))): a = steps // batch_size per chain over
@@ -26,7 +26,8 @@ sqrt(P_ii P_jj); where it is float64 the path still works and loses what a float
 """
 import numpy as np
 
-from . import diagnostics as dg
+from . import _ffi, diagnostics as dg
+from ._history import as_numpy, history_shape, in_place, is_device_tensor, launch, workspace
 
 MAX_DEVICE_DIM = 128          # l2hmc_moment_sums: d <= 128
 MAX_FLAT_CHAINS = 4096        # (draws, d) is read as (draws / c, c, d), c <= this: one wave per SIMD on 256 CUs
@@ -38,14 +39,12 @@ def _layout(X, batch_size):
     Without batches any factorisation of the draws gives the same sums, and the kernels fill their lanes with adjacent
     "chains": (draws, d) is read as (draws / c, c, d) with c the largest divisor of draws up to 4096 (a prime number of
     draws stays one chain, a sixteenth of the lanes live)."""
-    shape = tuple(int(v) for v in X.shape)
     batch_size = int(batch_size)
-    if len(shape) == 2 and batch_size == 0:
+    shape = history_shape(X, flat_ok=batch_size == 0,
+                          says=None if batch_size == 0 else "a history is (steps, chains, dim) when batches are asked for")
+    if len(shape) == 2:
         c = max([k for k in range(1, min(shape[0], MAX_FLAT_CHAINS) + 1) if shape[0] % k == 0] or [1])
         shape = (shape[0] // c, c, shape[1])
-    elif len(shape) != 3:
-        raise ValueError("a history is (steps, chains, dim)%s; got shape %s" % (
-            " or (draws, dim)" if batch_size == 0 else " when batches are asked for", tuple(X.shape)))
     M, N, d = shape
     if M < 1 or N < 1 or d < 1:
         raise ValueError("a history needs at least one draw and dim >= 1; got shape %s" % (tuple(X.shape),))
@@ -56,20 +55,14 @@ def _layout(X, batch_size):
 
 def _device_sums(X, M, N, d, batch):
     import torch
-    from . import _ffi
-    X = X.detach()
-    if X.dtype != torch.float32 or not X.is_contiguous():
-        X = X.to(torch.float32).contiguous()
-    L = _ffi.lib()
-    dev = X.device
-    ws = torch.empty(_ffi.check(L.l2hmc_moment_sums_workspace_doubles(M, N, d, batch)), dtype=torch.float64, device=dev)
+    X = in_place(X)
+    L, dev = _ffi.lib(), X.device
+    ws = workspace(dev, torch.float64, L.l2hmc_moment_sums_workspace_doubles, M, N, d, batch)
     out = [torch.empty(d, dtype=torch.float64, device=dev), torch.empty((d, d), dtype=torch.float64, device=dev)]
     if batch:
         out += [torch.empty(d, dtype=torch.float64, device=dev), torch.empty((d, d), dtype=torch.float64, device=dev)]
-    with torch.cuda.device(dev):
-        _ffi.check(L.l2hmc_moment_sums(X.data_ptr(), M, N, d, batch, out[0].data_ptr(), out[1].data_ptr(),
-                                       out[2].data_ptr() if batch else None, out[3].data_ptr() if batch else None,
-                                       ws.data_ptr(), _ffi.current_stream(dev)))
+    launch(dev, L.l2hmc_moment_sums, X.data_ptr(), M, N, d, batch, out[0].data_ptr(), out[1].data_ptr(),
+           out[2].data_ptr() if batch else None, out[3].data_ptr() if batch else None, ws.data_ptr())
     return out + [None] * (4 - len(out))
 
 
@@ -107,23 +100,19 @@ def moment_sums(X, batch_size=0):
     chains simply add."""
     M, N, d = _layout(X, batch_size)
     batch = int(batch_size)
-    if dg._is_device_tensor(X):
+    if is_device_tensor(X):
         if d > MAX_DEVICE_DIM:
             raise ValueError("the moment kernels hold dim <= %d (got %d): pass the history as a numpy array" % (MAX_DEVICE_DIM, d))
         s, c, bs, bc = _device_sums(X, M, N, d, batch)
     else:
-        if hasattr(X, "detach"):
-            X = X.detach().numpy()
-        s, c, bs, bc = _host_sums(X, M, N, d, batch)
+        s, c, bs, bc = _host_sums(as_numpy(X), M, N, d, batch)
     return {"n_draws": M * N, "sum": s, "cross": c, "batch_size": batch, "n_batches": (M // batch) * N if batch else 0,
             "batch_sum": bs, "batch_cross": bc}
 
 
 def _wide(a):
     """A sum as a long double numpy array (device float64 tensors and float64 arrays widen exactly)."""
-    if hasattr(a, "detach"):
-        a = a.detach().cpu().numpy()
-    return np.asarray(a, dtype=np.longdouble)
+    return as_numpy(a, np.longdouble)
 
 
 def finish(sums):
@@ -190,9 +179,7 @@ def covariance(X):
 
 
 def _batch_size(X, batch_size):
-    if len(X.shape) != 3:
-        raise ValueError("multi_ess needs a history (steps, chains, dim); got shape %s" % (tuple(X.shape),))
-    M = int(X.shape[0])
+    M = history_shape(X, says="multi_ess needs a history (steps, chains, dim)")[0]
     if batch_size is None:
         return default_batch_size(M)
     if int(batch_size) != batch_size or not 1 <= int(batch_size) <= M:

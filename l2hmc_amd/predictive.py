@@ -16,10 +16,9 @@ Both are expectations over every draw s of a function of every data row i.  With
 
 A ROCm tensor of draws goes to the HIP kernel behind `l2hmc_logistic_predict` (csrc/predictive.hip) where it lies -- a first-axis
 slice of a history is contiguous -- the (S, n) log-likelihood matrix is never formed and only the (4, n) sums come back; the
-logits are float32 there and the sums float64, bitwise reproducible.  numpy or a CPU tensor is computed in float64 numpy (the
-convention of `diagnostics`: there is no CPU path for sampling, but arithmetic on host data is host arithmetic), with a
-two-pass variance and `logaddexp`; the host sums carry these as `m2_ll` and `log_sum_lik`, which `finish` prefers when they are
-there.  The four plain sums are what ranks that hold different draws add up (`sharding.predictive`).
+logits are float32 there and the sums float64, bitwise reproducible.  numpy or a CPU tensor is computed in float64 numpy
+(`_history` has that rule and the host side of the launches), with a two-pass variance and `logaddexp`; the host sums carry
+these as `m2_ll` and `log_sum_lik`, which `finish` prefers when they are there.  The four plain sums are what ranks that hold different draws add up (`sharding.predictive`).
 
 Summing lik itself needs no running maximum and is exact as long as one draw gives lik above the smallest float32; a row where
 every draw underflows has sum_lik = 0, lppd_i = -inf, and is counted in `n_underflow` -- reported, not hidden.
@@ -27,7 +26,9 @@ every draw underflows has sum_lik = 0, lppd_i = -inf, and is counted in `n_under
 """
 import numpy as np
 
-from .diagnostics import Summary, _is_device_tensor
+from . import _ffi
+from ._history import as_numpy, history_shape, in_place, is_device_tensor, launch, workspace
+from .diagnostics import Summary
 
 MAX_DEVICE_ROWS = 1 << 20     # l2hmc_pack_logistic
 MAX_DEVICE_DIM = 128
@@ -35,25 +36,9 @@ HIGH_VARIANCE = 0.4
 _HOST_CHUNK_ELEMS = 1 << 22   # (draws x rows) logits formed at a time on the host
 
 
-def _is_tensor(a):
-    try:
-        import torch
-        return isinstance(a, torch.Tensor)
-    except ImportError:
-        return False
-
-
-def _host_array(a):
-    if _is_tensor(a):
-        a = a.detach().cpu().numpy()
-    return np.asarray(a, dtype=np.float64)
-
-
 def _check(draws, X, y):
     """(S, d, n) of valid arguments, or ValueError (shapes only: the labels' values are checked where they lie)."""
-    shape = tuple(int(v) for v in draws.shape)
-    if len(shape) not in (2, 3):
-        raise ValueError("draws are a history (steps, chains, dim) or a matrix (n_draws, dim); got shape %s" % (shape,))
+    shape = history_shape(draws, flat_ok=True, says="draws are a history (steps, chains, dim) or a matrix (n_draws, dim)")
     d = shape[-1]
     S = shape[0] * shape[1] if len(shape) == 3 else shape[0]
     if d < 1:
@@ -72,14 +57,11 @@ def _check(draws, X, y):
 
 def _device_sums(draws, X, y, S, d, n):
     import torch
-    from . import _ffi
     if n > MAX_DEVICE_ROWS or d > MAX_DEVICE_DIM:
         raise ValueError("the predictive kernel holds n_rows <= %d and dim <= %d (got %d, %d)"
                          % (MAX_DEVICE_ROWS, MAX_DEVICE_DIM, n, d))
     dev = draws.device
-    W = draws.detach()
-    if W.dtype != torch.float32 or not W.is_contiguous():
-        W = W.to(torch.float32).contiguous()
+    W = in_place(draws)
     Xd = torch.as_tensor(X).detach().to(device=dev, dtype=torch.float32).contiguous()
     if y is None:
         yd = torch.zeros(n, dtype=torch.float32, device=dev)
@@ -88,23 +70,21 @@ def _device_sums(draws, X, y, S, d, n):
         if not bool(((yd == 0) | (yd == 1)).all()):
             raise ValueError("labels y must be 0 or 1")
     L = _ffi.lib()
-    with torch.cuda.device(dev):
-        stream = _ffi.current_stream(dev)
-        packed = torch.empty(_ffi.check(L.l2hmc_packed_logistic_floats(n, d)), dtype=torch.float32, device=dev)
-        _ffi.check(L.l2hmc_pack_logistic(Xd.data_ptr(), yd.data_ptr(), n, d, packed.data_ptr(), stream))
-        ws = torch.empty(_ffi.check(L.l2hmc_logistic_predict_workspace_doubles(S, n, d)), dtype=torch.float64, device=dev)
-        sums = torch.empty((4, n), dtype=torch.float64, device=dev)
-        _ffi.check(L.l2hmc_logistic_predict(W.data_ptr(), S, d, packed.data_ptr(), n, sums.data_ptr(), ws.data_ptr(), stream))
+    packed = workspace(dev, torch.float32, L.l2hmc_packed_logistic_floats, n, d)
+    launch(dev, L.l2hmc_pack_logistic, Xd.data_ptr(), yd.data_ptr(), n, d, packed.data_ptr())
+    ws = workspace(dev, torch.float64, L.l2hmc_logistic_predict_workspace_doubles, S, n, d)
+    sums = torch.empty((4, n), dtype=torch.float64, device=dev)
+    launch(dev, L.l2hmc_logistic_predict, W.data_ptr(), S, d, packed.data_ptr(), n, sums.data_ptr(), ws.data_ptr())
     return sums.cpu().numpy()
 
 
 def _host_sums(draws, X, y, S, d, n):
-    W = _host_array(draws).reshape(S, d)
-    X = _host_array(X)
+    W = as_numpy(draws, np.float64).reshape(S, d)
+    X = as_numpy(X, np.float64)
     if y is None:
         y = np.zeros(n)
     else:
-        y = _host_array(y)
+        y = as_numpy(y, np.float64)
         if not np.all((y == 0.0) | (y == 1.0)):
             raise ValueError("labels y must be 0 or 1")
     sign = 2.0 * y - 1.0
@@ -134,7 +114,7 @@ def pointwise_sums(draws, X, y=None):
     HIP kernel, read in place (bitwise reproducible); numpy or a CPU tensor -> float64 numpy, which adds 'm2_ll' (two-pass
     sum of squares about the mean) and 'log_sum_lik' (by logaddexp)."""
     S, d, n = _check(draws, X, y)
-    if _is_device_tensor(draws):
+    if is_device_tensor(draws):
         s = _device_sums(draws, X, y, S, d, n)
         out = {"sum_p": s[0], "sum_lik": s[1], "sum_ll": s[2], "sum_ll2": s[3]}
     else:

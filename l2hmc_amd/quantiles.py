@@ -10,7 +10,7 @@ names and definitions are those of Vehtari, Gelman, Simpson, Carpenter, Buerkner
 A ROCm tensor is read where it lies: `order_statistics` is a radix select on the device (csrc/order_stats.hip behind
 `l2hmc_order_stats`, a few reads of the history and R d numbers back; no sort, no second copy), `ess_quantile` is the
 split-chain ESS of the indicator series [x <= Q_p], formed by `l2hmc_chain_stats_below` as the values are loaded.  A numpy
-history is host arithmetic (`np.sort`), the convention of `diagnostics`.
+history is host arithmetic (`np.sort`); `_history` has that rule and the host side of every launch.
 
 Definitions.  Quantiles follow numpy's default ("linear"): h = (S - 1) p, lo = floor(h), hi = min(lo + 1, S - 1), and with
 a, b the order statistics at lo, hi the result is a when a == b (or h == lo), else a + (h - lo) (b - a), in float64.
@@ -22,7 +22,8 @@ i2 = min(ceil(a2 S), S) of the sorted draws, mcse = (x_(i2) - x_(i1)) / 2.  A co
 """
 import numpy as np
 
-from . import diagnostics as dg
+from . import _ffi, diagnostics as dg
+from ._history import as_numpy, history_shape, in_place, is_device_tensor, launch, workspace
 
 MAX_RANKS = 32                    # l2hmc_order_stats: n_ranks <= 32 per call; more go in chunks
 TAIL_PROBS = (0.05, 0.95)
@@ -31,24 +32,15 @@ HOST_BITS, HOST_PASSES = 8, 4     # the radix select restated in numpy (historie
 
 
 def _as_draws(X):
-    """The history as (S, d) float32: a device tensor under the rule of `diagnostics._device_sums` (a first-axis slice is
-    read in place), anything else as a numpy array."""
-    if len(X.shape) not in (2, 3):
-        raise ValueError("a history is (steps, chains, dim) or (draws, dim); got shape %s" % (tuple(X.shape),))
-    d = int(X.shape[-1])
+    """The history as (S, d) float32: a device tensor read in place (`_history.in_place`), anything else as a numpy array."""
+    d = history_shape(X, flat_ok=True)[-1]
     if d < 1 or int(np.prod([int(v) for v in X.shape[:-1]])) < 1:
         raise ValueError("a history needs at least one draw and dim >= 1; got shape %s" % (tuple(X.shape),))
-    if dg._is_device_tensor(X):
-        import torch
+    if is_device_tensor(X):
         if d > dg.MAX_DEVICE_DIM:
             raise ValueError("the order-statistics kernels hold dim <= %d (got %d)" % (dg.MAX_DEVICE_DIM, d))
-        X = X.detach()
-        if X.dtype != torch.float32 or not X.is_contiguous():
-            X = X.to(torch.float32).contiguous()
-        return X.view(-1, d)
-    if hasattr(X, "detach"):
-        X = X.detach().numpy()
-    return np.ascontiguousarray(np.asarray(X), dtype=np.float32).reshape(-1, d)
+        return in_place(X).view(-1, d)
+    return np.ascontiguousarray(as_numpy(X), dtype=np.float32).reshape(-1, d)
 
 
 def _rank_table(ranks, S, d):
@@ -78,21 +70,18 @@ def _check_probs(probs):
 def _device_select(X2, ranks):
     """One `l2hmc_order_stats` call per chunk of 32 ranks."""
     import torch
-    from . import _ffi
-    L = _ffi.lib()
+    L, dev = _ffi.lib(), X2.device
     S, d = (int(v) for v in X2.shape)
     out, n_nan = [], None
-    with torch.cuda.device(X2.device):
-        for a in range(0, ranks.shape[0], MAX_RANKS):
-            rk = torch.as_tensor(ranks[a:a + MAX_RANKS]).to(X2.device)
-            R = int(rk.shape[0])
-            ws = torch.empty(_ffi.check(L.l2hmc_order_stats_workspace_bytes(d, R)), dtype=torch.uint8, device=X2.device)
-            values = torch.empty((R, d), dtype=torch.float32, device=X2.device)
-            nn = torch.empty(d, dtype=torch.int64, device=X2.device)
-            _ffi.check(L.l2hmc_order_stats(X2.data_ptr(), S, d, rk.data_ptr(), R, values.data_ptr(), nn.data_ptr(),
-                                           ws.data_ptr(), _ffi.current_stream(X2.device)))
-            out.append(values.cpu().numpy())
-            n_nan = nn.cpu().numpy() if n_nan is None else n_nan
+    for a in range(0, ranks.shape[0], MAX_RANKS):
+        rk = torch.as_tensor(ranks[a:a + MAX_RANKS]).to(dev)
+        R = int(rk.shape[0])
+        ws = workspace(dev, torch.uint8, L.l2hmc_order_stats_workspace_bytes, d, R)
+        values = torch.empty((R, d), dtype=torch.float32, device=dev)
+        nn = torch.empty(d, dtype=torch.int64, device=dev)
+        launch(dev, L.l2hmc_order_stats, X2.data_ptr(), S, d, rk.data_ptr(), R, values.data_ptr(), nn.data_ptr(), ws.data_ptr())
+        out.append(values.cpu().numpy())
+        n_nan = nn.cpu().numpy() if n_nan is None else n_nan
     return np.concatenate(out, axis=0), n_nan
 
 
@@ -140,35 +129,33 @@ def _sharded_select(X2, ranks, allreduce):
     result on the concatenated draws (integer histograms add exactly)."""
     import torch
     S, d = (int(v) for v in X2.shape)
-    device = dg._is_device_tensor(X2)
+    device = is_device_tensor(X2)
     out, n_nan = [], None
     if device:
-        from . import _ffi
-        L = _ffi.lib()
-        passes, bins, stream = L.l2hmc_order_stats_passes(), L.l2hmc_order_stats_bins(), _ffi.current_stream(X2.device)
+        L, dev = _ffi.lib(), X2.device
+        passes, bins = L.l2hmc_order_stats_passes(), L.l2hmc_order_stats_bins()
     else:
         passes, bins, keys = HOST_PASSES, 1 << HOST_BITS, _host_keys(X2)
     for a in range(0, ranks.shape[0], MAX_RANKS):
         R = min(MAX_RANKS, ranks.shape[0] - a)
         if device:
-            remaining = torch.as_tensor(ranks[a:a + R]).to(X2.device)
-            prefix = torch.zeros((R, d), dtype=torch.int32, device=X2.device)           # uint32 bits
-            flat = torch.empty(R * d * bins + d, dtype=torch.int64, device=X2.device)   # hist | n_nan: one all-reduce
-            values = torch.empty((R, d), dtype=torch.float32, device=X2.device)
+            remaining = torch.as_tensor(ranks[a:a + R]).to(dev)
+            prefix = torch.zeros((R, d), dtype=torch.int32, device=dev)                  # uint32 bits
+            flat = torch.empty(R * d * bins + d, dtype=torch.int64, device=dev)          # hist | n_nan: one all-reduce
+            values = torch.empty((R, d), dtype=torch.float32, device=dev)
         else:
             remaining, prefix = ranks[a:a + R].copy(), np.zeros((R, d), dtype=np.uint32)
         for p in range(passes):
             if device:
-                with torch.cuda.device(X2.device):
-                    _ffi.check(L.l2hmc_order_stats_count(X2.data_ptr(), S, d, R, p, prefix.data_ptr(), flat.data_ptr(),
-                                                         flat[R * d * bins:].data_ptr() if p == 0 else None, stream))
-                    red = allreduce(flat if p == 0 else flat[:R * d * bins])
-                    if red.data_ptr() != flat.data_ptr():
-                        flat[:red.numel()] = red.to(flat.device)
-                    if p == 0 and n_nan is None:
-                        n_nan = flat[R * d * bins:].cpu().numpy().copy()
-                    _ffi.check(L.l2hmc_order_stats_advance(flat.data_ptr(), remaining.data_ptr(), prefix.data_ptr(), d, R, p,
-                                                           values.data_ptr() if p == passes - 1 else None, stream))
+                launch(dev, L.l2hmc_order_stats_count, X2.data_ptr(), S, d, R, p, prefix.data_ptr(), flat.data_ptr(),
+                       flat[R * d * bins:].data_ptr() if p == 0 else None)
+                red = allreduce(flat if p == 0 else flat[:R * d * bins])
+                if red.data_ptr() != flat.data_ptr():
+                    flat[:red.numel()] = red.to(dev)
+                if p == 0 and n_nan is None:
+                    n_nan = flat[R * d * bins:].cpu().numpy().copy()
+                launch(dev, L.l2hmc_order_stats_advance, flat.data_ptr(), remaining.data_ptr(), prefix.data_ptr(), d, R, p,
+                       values.data_ptr() if p == passes - 1 else None)
             else:
                 hist = _host_count(keys, prefix, p, R)
                 parts = [hist.ravel(), np.isnan(X2).sum(axis=0).astype(np.int64)] if p == 0 else [hist.ravel()]
@@ -183,7 +170,7 @@ def _sharded_select(X2, ranks, allreduce):
 def _select(X2, ranks, allreduce=None):
     if allreduce is not None:
         return _sharded_select(X2, ranks, allreduce)
-    if dg._is_device_tensor(X2):
+    if is_device_tensor(X2):
         return _device_select(X2, ranks)
     srt = np.sort(X2, axis=0)                                                  # NaNs last
     return np.take_along_axis(srt, ranks, axis=0), np.isnan(X2).sum(axis=0).astype(np.int64)
@@ -230,8 +217,6 @@ def _describe(X, probs, max_lag, split, allreduce=None, finish=dg.finish):
     """`describe`; with `allreduce` / `finish` of `sharding.describe` the same on chains sharded over ranks."""
     from scipy.special import betaincinv
     probs = _check_probs(probs)
-    if len(X.shape) != 3:
-        raise ValueError("a history is (steps, chains, dim); got shape %s" % (tuple(X.shape),))
     out = finish(dg.chain_sums(X, max_lag=max_lag, split=split))
     X2 = _as_draws(X)
     S, d, Q = int(X2.shape[0]), int(X2.shape[1]), probs.shape[0]

@@ -5,12 +5,14 @@ cross-chain term), so the chain batch is cut into contiguous blocks -- rank r ow
 [r*N/W, (r+1)*N/W) -- and the leapfrog kernels run with NO data-path collective.  The only
 exchanges are small statistics: the mean accept probability, the autocovariance partial
 sums behind ESS (utils/func_utils.py:45-54,114-120), the per-coordinate sums behind split R-hat /
-ESS (`diagnostics`), the integer digit histograms behind posterior quantiles (`describe`), the four per-row sums behind the posterior predictive and WAIC (`predictive`), the raw moments behind the posterior covariance and the multivariate ESS (`multivariate`) and the two doubles per window of the step-size warm-up (`warmup`), each ONE flat all-reduce.  Backend
+ESS (`diagnostics`), the integer digit histograms behind posterior quantiles (`describe`), the four per-row sums behind the posterior predictive and WAIC (`predictive`), the raw moments behind the posterior covariance and the multivariate ESS (`multivariate`) and the two doubles per window of the step-size warm-up (`warmup`), each ONE flat all-reduce (`_allreduce_pieces` says it once for the float64 sums; `_on_device_collective` decides where it runs).  Backend
 "nccl" is RCCL over xGMI on the GPU box; "gloo" is used by the CPU tests.
 """
 import numpy as np
 import torch
 import torch.distributed as dist
+
+from ._history import is_device_tensor
 
 
 def world():
@@ -59,7 +61,7 @@ def acl_spectrum(X_local, scale, n_total):
     """`acl_spectrum` of utils/func_utils.py:114-116 for chains sharded over ranks: one
     all-reduce of the (steps-1,) partial sums; equals the single-process value on the
     concatenated chains."""
-    if isinstance(X_local, torch.Tensor) and X_local.is_cuda:      # HIP kernel, history stays in HBM
+    if is_device_tensor(X_local):                                  # HIP kernel, history stays in HBM
         from .func_utils import device_autocov
         steps = X_local.shape[0]
         s = _allreduce_sum(device_autocov(X_local, 1.0)[0] / (scale * scale))
@@ -88,22 +90,37 @@ def diagnostics(X_local, max_lag=None, split=True):
 
 
 def _on_device_collective(X_local):
-    return isinstance(X_local, torch.Tensor) and X_local.is_cuda and world()[1] > 1 and dist.get_backend() != "gloo"
+    return is_device_tensor(X_local) and world()[1] > 1 and dist.get_backend() != "gloo"
+
+
+def _allreduce_where(t, X_local):
+    """`_allreduce_sum` of `t` where the backend of the local history reduces: on its device (`_on_device_collective`), else
+    on the host -- gloo does not reduce device tensors.  A tensor that had to move for it comes back on the host."""
+    on_device = _on_device_collective(X_local)
+    if t.is_cuda == on_device:
+        return _allreduce_sum(t)
+    return _allreduce_sum(t.to(X_local.device) if on_device else t.cpu()).cpu()
+
+
+def _cut(flat, like):
+    """The consecutive pieces of a flat vector in the shapes of `like`."""
+    ends = np.cumsum([p.size for p in like])
+    return [flat[e - p.size:e].reshape(p.shape) for e, p in zip(ends, like)]
+
+
+def _allreduce_pieces(pieces, X_local):
+    """ONE all-reduce of float64 numbers and arrays, concatenated in the order given; the reduced pieces in their shapes."""
+    pieces = [np.asarray(p, dtype=np.float64) for p in pieces]
+    flat = torch.from_numpy(np.concatenate([p.ravel() for p in pieces]))
+    return _cut(_allreduce_where(flat, X_local).numpy(), pieces)
 
 
 def _finish_chain_sums(sums, X_local):
     """`diagnostics.finish` of this rank's `chain_sums` after ONE all-reduce of their per-coordinate reductions."""
     from . import diagnostics as dg
     r = dg.reduce_sums(sums)
-    d, nlag = r["G"].shape
-    flat = torch.from_numpy(np.concatenate([[r["count"]], r["sum_mean"], r["sum_mean_sq"], r["sum_m2"], r["G"].ravel()]))
-    if _on_device_collective(X_local):
-        flat = _allreduce_sum(flat.to(X_local.device)).cpu()
-    else:
-        flat = _allreduce_sum(flat)
-    flat = flat.numpy()
-    return dg.finish({"count": float(flat[0]), "sum_mean": flat[1:1 + d], "sum_mean_sq": flat[1 + d:1 + 2 * d],
-                      "sum_m2": flat[1 + 2 * d:1 + 3 * d], "G": flat[1 + 3 * d:].reshape(d, nlag), "n_steps": r["n_steps"]})
+    keys = ("count", "sum_mean", "sum_mean_sq", "sum_m2", "G")
+    return dg.finish(dict(zip(keys, _allreduce_pieces([r[k] for k in keys], X_local)), n_steps=r["n_steps"]))
 
 
 def describe(X_local, probs=(0.05, 0.5, 0.95), max_lag=None, split=True):
@@ -115,15 +132,7 @@ def describe(X_local, probs=(0.05, 0.5, 0.95), max_lag=None, split=True):
     the single-process value on the concatenated chains; the `ess_*` agree to all-reduce rounding.  Ranks may hold different
     numbers of chains, but the same number of steps, and must pass the same `probs` and `max_lag`."""
     from . import quantiles as qt
-
-    def allreduce(t):
-        # integer counts: a backend that cannot reduce device tensors (gloo) gets them on the host
-        if t.is_cuda and not _on_device_collective(X_local):
-            return _allreduce_sum(t.cpu())
-        if not t.is_cuda and _on_device_collective(X_local):
-            return _allreduce_sum(t.to(X_local.device)).cpu()
-        return _allreduce_sum(t)
-    return qt._describe(X_local, probs, max_lag, split, allreduce=allreduce,
+    return qt._describe(X_local, probs, max_lag, split, allreduce=lambda t: _allreduce_where(t, X_local),
                         finish=lambda sums: _finish_chain_sums(sums, X_local))
 
 
@@ -134,15 +143,10 @@ def predictive(draws_local, X, y=None):
     concatenated draws.  Every rank passes the same rows X (and labels y); ranks may hold different numbers of draws."""
     from . import predictive as pd
     s = pd.pointwise_sums(draws_local, X, y)
-    n = s["sum_p"].shape[0]
-    flat = torch.from_numpy(np.concatenate([[float(s["n_draws"])], s["sum_p"], s["sum_lik"], s["sum_ll"], s["sum_ll2"]]))
-    if isinstance(draws_local, torch.Tensor) and draws_local.is_cuda and world()[1] > 1 and dist.get_backend() != "gloo":
-        flat = _allreduce_sum(flat.to(draws_local.device)).cpu()
-    else:
-        flat = _allreduce_sum(flat)
-    flat = flat.numpy()
-    return pd.finish({"n_draws": int(round(flat[0])), "sum_p": flat[1:1 + n], "sum_lik": flat[1 + n:1 + 2 * n],
-                      "sum_ll": flat[1 + 2 * n:1 + 3 * n], "sum_ll2": flat[1 + 3 * n:1 + 4 * n]})
+    keys = ("n_draws", "sum_p", "sum_lik", "sum_ll", "sum_ll2")
+    r = dict(zip(keys, _allreduce_pieces([s[k] for k in keys], draws_local)))
+    r["n_draws"] = int(round(float(r["n_draws"])))
+    return pd.finish(r)
 
 
 def multivariate(X_local, batch_size=None):
@@ -153,9 +157,9 @@ def multivariate(X_local, batch_size=None):
     number of steps, and must pass the same `batch_size`."""
     from . import multivariate as mv
     s = mv.moment_sums(X_local, mv._batch_size(X_local, batch_size))
-    d = int(X_local.shape[-1])
-    wide = np.concatenate([[s["n_draws"]], mv._wide(s["sum"]), mv._wide(s["cross"]).ravel(), [s["n_batches"]],
-                           mv._wide(s["batch_sum"]), mv._wide(s["batch_cross"]).ravel()]).astype(np.longdouble)
+    keys = ("n_draws", "sum", "cross", "n_batches", "batch_sum", "batch_cross")
+    like = [mv._wide(s[k]) for k in keys]
+    wide = np.concatenate([p.ravel() for p in like])
     # every number travels as two float64: a head of 24 significant bits, whose sums over ranks are exact, and the rest (for a
     # device sum, what float64 holds beyond the head; for a numpy sum, what long double holds) -- still ONE all-reduce.  The
     # head is cut by scaling, so it has the range of float64 and a finite moment stays finite
@@ -163,18 +167,10 @@ def multivariate(X_local, batch_size=None):
         frac, expo = np.frexp(wide)
         hi = np.ldexp(np.rint(frac * 2.0 ** 24) / 2.0 ** 24, expo).astype(np.float64)
         lo = np.where(np.isfinite(hi), wide - hi, 0.0).astype(np.float64)
-    flat = torch.from_numpy(np.concatenate([hi, lo]))
-    if _on_device_collective(X_local):
-        flat = _allreduce_sum(flat.to(X_local.device)).cpu()
-    else:
-        flat = _allreduce_sum(flat)
-    flat = flat.numpy()
-    m = wide.shape[0]
-    flat = flat[:m].astype(np.longdouble) + flat[m:].astype(np.longdouble)
-    o = 1 + d + d * d
-    return mv.finish({"n_draws": int(round(float(flat[0]))), "sum": flat[1:1 + d], "cross": flat[1 + d:o].reshape(d, d),
-                      "batch_size": s["batch_size"], "n_batches": int(round(float(flat[o]))), "batch_sum": flat[o + 1:o + 1 + d],
-                      "batch_cross": flat[o + 1 + d:].reshape(d, d)})
+    hi, lo = _allreduce_pieces([hi, lo], X_local)
+    r = dict(zip(keys, _cut(hi.astype(np.longdouble) + lo.astype(np.longdouble), like)), batch_size=s["batch_size"])
+    r["n_draws"], r["n_batches"] = int(round(float(r["n_draws"]))), int(round(float(r["n_batches"])))
+    return mv.finish(r)
 
 
 def warmup(x_local, dynamics, n_updates=100, *, n_total=None, **kwargs):

@@ -21,6 +21,7 @@ import math
 import torch
 
 from . import _ffi
+from ._history import launch
 from .distributions import as_device_f32
 from .sampler import sample_chain
 
@@ -82,10 +83,8 @@ def adapt_init(dynamics, search=True, target_accept=0.8, gamma=0.05, t0=10.0, ka
         raise ValueError("eps_bounds must be positive (got %r)" % (eps_bounds,))
     dev = dynamics.device
     state = torch.empty(STATE_DOUBLES, dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        _ffi.check(_ffi.lib().l2hmc_adapt_init(state.data_ptr(), dynamics.alpha.data_ptr(), int(bool(search)),
-                                               float(target_accept), float(gamma), float(t0), float(kappa), math.log(lo),
-                                               math.log(hi), _ffi.current_stream(dev)))
+    launch(dev, _ffi.lib().l2hmc_adapt_init, state.data_ptr(), dynamics.alpha.data_ptr(), int(bool(search)),
+           float(target_accept), float(gamma), float(t0), float(kappa), math.log(lo), math.log(hi))
     return state
 
 
@@ -99,17 +98,13 @@ def adapt_update(p, state, alpha, trace_row=None, *, mode=REDUCE | APPLY, sums2=
         need = _ffi.check(_ffi.lib().l2hmc_adapt_workspace_doubles(n))
         if need and (workspace is None or workspace.numel() < need):
             workspace = torch.empty(need, dtype=torch.float64, device=p.device)
-    dev = p.device if mode & REDUCE else state.device
-    with torch.cuda.device(dev):
-        _ffi.check(_ffi.lib().l2hmc_adapt_update(_ffi.ptr(p) if mode & REDUCE else None, n, int(mode), _ffi.ptr(sums2),
-                                                 _ffi.ptr(state), _ffi.ptr(alpha), _ffi.ptr(trace_row), _ffi.ptr(workspace),
-                                                 _ffi.current_stream(dev)))
+    launch(p.device if mode & REDUCE else state.device, _ffi.lib().l2hmc_adapt_update, _ffi.ptr(p) if mode & REDUCE else None,
+           n, int(mode), _ffi.ptr(sums2), _ffi.ptr(state), _ffi.ptr(alpha), _ffi.ptr(trace_row), _ffi.ptr(workspace))
     return workspace
 
 
 def adapt_finish(state, alpha):
-    with torch.cuda.device(state.device):
-        _ffi.check(_ffi.lib().l2hmc_adapt_finish(state.data_ptr(), alpha.data_ptr(), _ffi.current_stream(state.device)))
+    launch(state.device, _ffi.lib().l2hmc_adapt_finish, state.data_ptr(), alpha.data_ptr())
 
 
 def warmup(x, dynamics, n_updates=100, *, proposals_per_update=1, target_accept=0.8, search=True, gamma=0.05, t0=10.0,

@@ -251,3 +251,28 @@ def test_reads_the_cold_history_of_parallel_tempering():
     assert tuple(o["cold_hist"].shape) == (400, 512, 8)
     s = diagnostics.summarize(o["cold_hist"][100:])
     _check_known_gaussian(s, "cold rung")
+
+
+@pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs two visible devices")
+def test_history_on_another_device_is_read_there():
+    """Every statistic launches on the device its history lies on, whichever device is current, and leaves the current
+    device alone: the results for a history on cuda:1 equal those for the same history on cuda:0 bit for bit."""
+    from l2hmc_amd import diagnostics, func_utils, multivariate, predictive, quantiles
+    X = dc.ar1(16, 4, [0.5, 0.1, 0.8], 0).astype(np.float32)
+    rng = np.random.RandomState(1)
+    rows, y = 0.2 * rng.randn(5, 3), (rng.rand(5) < 0.5).astype(np.float64)
+    calls = (lambda H: diagnostics.summarize(H), lambda H: quantiles.order_statistics(H, np.arange(0, 64, 9)),
+             lambda H: multivariate.covariance(H), lambda H: predictive.waic(H, rows, y),
+             lambda H: func_utils.acl_spectrum(H, 1.7))
+
+    def raw(v):
+        if isinstance(v, dict):
+            return [(k, raw(v[k])) for k in sorted(v)]
+        if isinstance(v, tuple):
+            return [raw(e) for e in v]
+        return np.asarray(v).tobytes()
+    torch.cuda.set_device(0)
+    here, there = torch.as_tensor(X).to("cuda:0"), torch.as_tensor(X).to("cuda:1")
+    for i, call in enumerate(calls):
+        assert raw(call(there)) == raw(call(here)), i
+        assert torch.cuda.current_device() == 0, i

@@ -1,0 +1,186 @@
+#!/usr/bin/env python
+"""Bit-for-bit fingerprint of the host side of the history statistics (`diagnostics`, `quantiles`, `multivariate`, `predictive`,
+`func_utils.acl_spectrum` and their `sharding` forms): one SHA-256 per host code path, over the raw bytes of every array a call
+returns, each case at the smallest shape that still takes its path.  Public API only, so the same file runs against two
+versions of `l2hmc_amd/*.py` on ONE build of the library (`L2HMC_LIB=`): a host-side refactor must leave every line as it was.
+
+    python tools/stats_fingerprint.py                       # numpy, a CPU tensor and, with a GPU, four forms of a device tensor
+    python tools/stats_fingerprint.py --cpu                 # the host inputs only
+    python tools/stats_fingerprint.py --ranks 2 --backend gloo|nccl --input numpy|device      # chains sharded 2 | 4
+    python tools/stats_fingerprint.py --time                # median host time of `describe` on the tiny device history
+
+The history is a seeded AR(1) of 40 steps, 6 chains and 3 coordinates whose means and scales differ per coordinate."""
+import argparse
+import hashlib
+import os
+import socket
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import numpy as np
+import torch
+
+from l2hmc_amd import diagnostics, func_utils, multivariate, predictive, quantiles, sharding
+
+STEPS, CHAINS, DIM, ROWS, SCALE = 40, 6, 3, 5, 1.7
+SPLIT = 2                                 # --ranks 2: rank 0 holds chains [0, 2), rank 1 chains [2, 6)
+RANKS33 = np.arange(33) * 7               # 33 ranks: two chunks of at most 32
+PROBS = (0.1, 0.5, 0.9)
+
+
+def history():
+    rng = np.random.RandomState(17)
+    X = np.empty((STEPS, CHAINS, DIM))
+    X[0] = rng.randn(CHAINS, DIM)
+    for t in range(1, STEPS):
+        X[t] = 0.7 * X[t - 1] + rng.randn(CHAINS, DIM)
+    return X * np.array([0.5, 1.0, 3.0]) + np.array([-2.0, 0.25, 10.0])
+
+
+def rows():
+    rng = np.random.RandomState(18)
+    return 0.2 * rng.randn(ROWS, DIM), (rng.rand(ROWS) < 0.5).astype(np.float64)
+
+
+def sha(result):
+    h = hashlib.sha256()
+
+    def feed(v):
+        if isinstance(v, dict):
+            for k in sorted(v):
+                h.update(k.encode())
+                feed(v[k])
+        elif isinstance(v, (tuple, list)):
+            for e in v:
+                feed(e)
+        elif v is not None:
+            h.update(np.ascontiguousarray(v.detach().cpu().numpy() if torch.is_tensor(v) else v).tobytes())
+    feed(result)
+    return h.hexdigest()
+
+
+def cases(X):
+    """(name, call) of every single-process statistic on the history X (numpy or a tensor, anywhere)."""
+    rx, ry = rows()
+    thresholds = np.array([-2.0, 0.25, 10.0])
+    for split in (True, False):
+        for lag in (3, None):
+            yield "summarize split=%d max_lag=%s" % (split, lag), lambda s=split, g=lag: diagnostics.summarize(X, max_lag=g, split=s)
+    yield "chain_sums_below", lambda: diagnostics.chain_sums_below(X, thresholds)
+    yield "order_statistics 33 ranks", lambda: quantiles.order_statistics(X, RANKS33)
+    yield "quantiles", lambda: quantiles.quantiles(X, PROBS)
+    yield "describe", lambda: quantiles.describe(X)
+    yield "covariance (240, 3)", lambda: multivariate.covariance(X.reshape(STEPS * CHAINS, DIM))
+    yield "multi_ess", lambda: multivariate.multi_ess(X)
+    yield "waic", lambda: predictive.waic(X, rx, ry)
+    yield "predict_proba", lambda: predictive.predict_proba(X, rx)
+    yield "log_predictive_density", lambda: predictive.log_predictive_density(X, rx, ry)
+    yield "acl_spectrum", lambda: func_utils.acl_spectrum(X, SCALE)
+
+
+def device_inputs(X, dev):
+    """The history on the device, four ways: the first reads in place, so does the second, the last two are copied."""
+    x32 = torch.as_tensor(X.astype(np.float32)).to(dev)
+    longer = torch.zeros((STEPS + 10, CHAINS, DIM), dtype=torch.float32, device=dev)
+    longer[10:] = x32
+    wider = torch.zeros((STEPS, 2 * CHAINS, DIM), dtype=torch.float32, device=dev)
+    wider[:, ::2] = x32
+    assert longer[10:].is_contiguous() and not wider[:, ::2].is_contiguous()
+    return (("device float32", x32), ("device first-axis slice", longer[10:]), ("device float64", torch.as_tensor(X).to(dev)),
+            ("device X[:, ::2]", wider[:, ::2]))
+
+
+def single(cpu_only):
+    X = history()
+    inputs = [("numpy", X.astype(np.float32)), ("cpu tensor", torch.as_tensor(X.astype(np.float32)))]
+    if not cpu_only:
+        torch.cuda.set_device(0)
+        inputs += device_inputs(X, torch.device("cuda", 0))
+    for label, Xi in inputs:
+        for name, call in cases(Xi):
+            print("%s  %s: %s" % (sha(call()), label, name), flush=True)
+
+
+def _rank(rank, world, port, backend, on_device, out):
+    import torch.distributed as dist
+    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
+    X = history().astype(np.float32)
+    X = X[:, :SPLIT] if rank == 0 else X[:, SPLIT:]
+    if on_device:
+        dev = torch.device("cuda", rank % torch.cuda.device_count() if backend == "gloo" else rank)
+        torch.cuda.set_device(dev)
+        X = torch.as_tensor(X).to(dev)
+    dist.init_process_group(backend, rank=rank, world_size=world)
+    try:
+        rx, ry = rows()
+        res = [("sharding.diagnostics", sharding.diagnostics(X)),
+               ("sharding.describe", sharding.describe(X)),
+               ("sharding.predictive", sharding.predictive(X, rx, ry)),
+               ("sharding.multivariate", sharding.multivariate(X)),
+               ("sharding.acl_spectrum", sharding.acl_spectrum(X, SCALE, CHAINS)),
+               ("sharding.ess", np.float64(sharding.ess(X, SCALE, CHAINS)))]
+        out.put((rank, [(name, sha(r)) for name, r in res]))
+        dist.barrier()
+    finally:
+        dist.destroy_process_group()
+
+
+def sharded(world, backend, on_device):
+    import torch.multiprocessing as mp
+    if world != 2:
+        raise SystemExit("the sharded fingerprint is defined for --ranks 2 (chains %d | %d)" % (SPLIT, CHAINS - SPLIT))
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    port = s.getsockname()[1]
+    s.close()
+    ctx = mp.get_context("spawn")
+    out = ctx.SimpleQueue()
+    procs = [ctx.Process(target=_rank, args=(r, world, port, backend, on_device, out)) for r in range(world)]
+    for pr in procs:
+        pr.start()
+    for pr in procs:
+        pr.join(150)
+    if any(pr.exitcode != 0 for pr in procs):
+        for pr in procs:
+            if pr.is_alive():
+                pr.kill()
+        raise SystemExit("a rank failed or did not finish: exit codes %s" % [pr.exitcode for pr in procs])
+    label = "%s, %s" % (backend, "device" if on_device else "numpy")
+    for rank, lines in sorted(out.get() for _ in range(world)):
+        for name, digest in lines:
+            print("%s  %s, rank %d: %s" % (digest, label, rank, name), flush=True)
+
+
+def timed():
+    """The host side of a call is all there is to time on a history this small: median of 200 synchronised `describe`."""
+    torch.cuda.set_device(0)
+    X = torch.as_tensor(history().astype(np.float32)).cuda()
+    t = []
+    for i in range(220):
+        t0 = time.perf_counter()
+        quantiles.describe(X)
+        torch.cuda.synchronize()
+        t.append(time.perf_counter() - t0)
+    print("describe (40, 6, 3) on the device: median %.1f us over 200 calls after 20" % (1e6 * float(np.median(t[20:]))), flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--cpu", action="store_true", help="numpy and CPU-tensor inputs only (no GPU needed)")
+    ap.add_argument("--ranks", type=int, default=1)
+    ap.add_argument("--backend", default="gloo", choices=("gloo", "nccl"))
+    ap.add_argument("--input", default="numpy", choices=("numpy", "device"))
+    ap.add_argument("--time", action="store_true")
+    a = ap.parse_args()
+    if a.time:
+        timed()
+    elif a.ranks > 1:
+        sharded(a.ranks, a.backend, a.input == "device")
+    else:
+        single(a.cpu)
+
+
+if __name__ == "__main__":
+    main()
