@@ -1,4 +1,4 @@
-"""Which model predicts better?  WAIC and held-out predictive density on the device (needs a GPU).
+"""Which model predicts better?  WAIC, PSIS-LOO and held-out predictive density on the device (needs a GPU).
 
 One seeded synthetic data set (1200 rows, d = 12 features of which the last one is informative; 1000 rows to fit, 200 held
 out) and two Bayesian logistic regressions: every feature, and the informative last feature dropped.  Each is sampled with HMC
@@ -7,9 +7,11 @@ out) and two Bayesian logistic regressions: every feature, and the informative l
 
   * `model.waic(history)`: the expected log pointwise predictive density of the rows the model was fitted to, by WAIC, its
     effective number of parameters and standard error;
+  * `model.loo(history)`: the same quantity by Pareto-smoothed importance-sampling leave-one-out, with the number of rows whose
+    Pareto k-hat says the estimate cannot be trusted (`n_bad`);
   * `log_predictive_density(history, X_test, y_test)`: the same question answered with the 200 rows neither model has seen.
 
-Both should prefer the full model, by a margin of several standard errors of the difference.
+All three should prefer the full model, by a margin of several standard errors of the difference.
 
     python examples/model_comparison.py
 """
@@ -58,6 +60,9 @@ def main(chains=1024, updates=60, proposals=200, n_train=1000, seed=1):
         h = log_predictive_density(kept, X_test[:, cols], y_test)
         print("  WAIC %.1f: elpd_waic %.1f (se %.1f), p_waic %.2f, lppd %.1f; %d rows with p_waic_i > 0.4, %d underflowed" % (
             w.waic, w.elpd_waic, w.se, w.p_waic, w.lppd, w.n_high_variance, w.n_underflow))
+        o = model.loo(kept)
+        print("  LOO: elpd_loo %.1f (se %.1f), p_loo %.2f; %d rows with khat > 0.7 (n_bad), %d above the threshold %.2f, max khat %.2f" % (
+            o.elpd_loo, o.se, o.p_loo, o.n_bad, o.n_above_threshold, o.khat_threshold, float(np.max(o.khat))))
         print("  held-out lppd of %d rows: %.1f (se %.1f)" % (h.n_rows, h.lppd, h.se))
         results[name] = (w, h)
     (wa, ha), (wb, hb) = results["all features"], results["last feature dropped"]

@@ -734,6 +734,33 @@ int64_t l2hmc_logistic_predict_workspace_doubles(int64_t n_draws, int32_t n_data
 int l2hmc_logistic_predict(const float* draws, int64_t n_draws, int32_t d, const float* packed, int32_t n_data,
                            double* sums /* (4, n_data) */, double* workspace, void* stream);
 
+/* Bayesian logistic regression: the per-row raw material of PSIS-LOO (Pareto-smoothed importance-sampling leave-one-out;
+ * Vehtari, Gelman, Gabry 2017) over every recorded draw (csrc/loo.hip; l2hmc_amd/predictive.py `loo_finish` turns it into
+ * elpd_loo and the Pareto k-hat).  `draws` and `packed` are those of l2hmc_logistic_predict.  With t = (2 y_i - 1) x_i . w_s the
+ * signed logit of row i under draw s (float32, f32-input MFMA) and M = l2hmc_logistic_loo_tail_len(n_draws) =
+ * min(n_draws / 5, ceil(3 sqrt(n_draws))), per row i:
+ *   cutoff  (n_data) float32: the element of rank M (0-based) of an ascending order of {t_s}; the order is that of the monotone
+ *           key of l2hmc_order_stats (-0 before +0, every NaN after +inf).
+ *   n_tail  (n_data) int64: L = the number of t strictly before the cutoff in that order, L <= M (ties at the cutoff shorten it).
+ *   tail    (n_data, M) float32: those L values in ANY order in slots 0 .. L - 1, +inf in slots L .. M - 1 (may be NULL when M = 0).
+ *   sums    (2, n_data) float64: [0] body = the sum over the draws NOT in the tail of e^m + e^(m - t), m = min(cutoff, 0) (every
+ *           term in (0, 2]: log of the summed ratios 1 + e^-t is log(body) - m); [1] the sum over all draws of sigmoid(t).
+ *           Every term is float32 (hardware exp and reciprocal) and is converted to float64 BEFORE it is added.
+ * The cutoff is found by a radix select (4 passes of 8 bits: a fused contraction and histogram each, nothing is sorted and the
+ * (n_draws, n_data) matrix is never written) and one more pass gathers; every pass forms bit-identical t.  `workspace`:
+ * l2hmc_logistic_loo_workspace_bytes(...) bytes, 8-byte aligned, required: error word | histograms | ranks | prefixes | the
+ * waves' partial sums, which a last kernel adds in a fixed order.  No floating-point atomics: cutoff, n_tail, the tail as a set
+ * and the sums are bitwise reproducible, and the same whatever set of rows a call holds (the draws are cut into chunks by
+ * n_draws alone).  The first int64 of the workspace is non-zero after the call if a tail slot at or past M was asked for (never
+ * while the passes agree; the value is then not written and n_tail counts it).
+ * L2HMC_ERR_ARG (before any launch): n_draws < 2, n_data outside 1 .. 1048576, d outside 1 .. 128, n_draws > 2^40 / d, a tail
+ * the caller could not have sized (M n_data > 2^31: call with fewer rows), a NULL or misaligned pointer. */
+int64_t l2hmc_logistic_loo_tail_len(int64_t n_draws);
+int64_t l2hmc_logistic_loo_workspace_bytes(int64_t n_draws, int32_t n_data, int32_t d);
+int l2hmc_logistic_loo_tails(const float* draws, int64_t n_draws, int32_t d, const float* packed, int32_t n_data,
+                             float* cutoff /* (n_data) */, int64_t* n_tail /* (n_data) */, float* tail /* (n_data, M) */,
+                             double* sums /* (2, n_data): body, sum_lik */, void* workspace, void* stream);
+
 /* The raw first and second moments of a recorded history X (steps, N, d) kept on the device (csrc/moment_sums.hip): what the
  * posterior covariance and the multivariate effective sample size of Vats, Flegal & Jones (2019) are made of
  * (l2hmc_amd/multivariate.py `finish` turns them into numbers on the host, and ranks that hold different chains add them).

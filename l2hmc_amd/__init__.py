@@ -13,12 +13,12 @@ from .tempering import ParallelTempering, geometric_ladder  # noqa: F401
 from .distributions import LogisticRegression  # noqa: F401
 from .training import LogisticTrainer  # noqa: F401
 from .diagnostics import summarize  # noqa: F401
-from .predictive import waic  # noqa: F401
+from .predictive import loo, waic  # noqa: F401
 from .quantiles import describe  # noqa: F401
 from .multivariate import covariance, multi_ess  # noqa: F401
 from .warmup import warmup  # noqa: F401  (the function; its module stays importable as `from l2hmc_amd.warmup import ...`)
 
 __all__ = ["Dynamics", "propose", "tf_accept", "chain_operator", "sample_chain", "ParallelTempering", "geometric_ladder",
-           "LogisticRegression", "LogisticTrainer", "summarize", "diagnostics", "warmup", "predictive", "waic", "quantiles", "describe",
+           "LogisticRegression", "LogisticTrainer", "summarize", "diagnostics", "warmup", "predictive", "waic", "loo", "quantiles", "describe",
            "multivariate", "covariance", "multi_ess",
            "layers", "distributions", "func_utils", "losses", "tempering"]

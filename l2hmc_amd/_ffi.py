@@ -184,6 +184,9 @@ SYMBOLS = {
     "l2hmc_moment_sums": (C.c_int, [_fp, C.c_int64, C.c_int64, C.c_int32, C.c_int64, _fp, _fp, _fp, _fp, _fp, _fp]),
     "l2hmc_logistic_predict_workspace_doubles": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
     "l2hmc_logistic_predict": (C.c_int, [_fp, C.c_int64, C.c_int32, _fp, C.c_int32, _fp, _fp, _fp]),
+    "l2hmc_logistic_loo_tail_len": (C.c_int64, [C.c_int64]),
+    "l2hmc_logistic_loo_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
+    "l2hmc_logistic_loo_tails": (C.c_int, [_fp, C.c_int64, C.c_int32, _fp, C.c_int32, _fp, _fp, _fp, _fp, _fp, _fp]),
     "l2hmc_adapt_workspace_doubles": (C.c_int64, [C.c_int64]),
     "l2hmc_adapt_init": (C.c_int, [_fp, _fp, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
                                    C.c_double, _fp]),

@@ -1,0 +1,470 @@
+// l2hmc_logistic_loo_tails -- the per-row raw material of Pareto-smoothed importance-sampling leave-one-out (PSIS-LOO; Vehtari,
+// Gelman, Gabry 2017; Vehtari, Simpson, Gelman, Yao, Gabry 2024) of Bayesian logistic regression over every recorded draw, from a
+// history that stays where the sampler wrote it.  For draws W (S, d) and the data packed by l2hmc_pack_logistic, the log
+// importance ratio of row i under draw s is lambda = softplus(-t) with t = (2 y_i - 1) x_i . w_s the SIGNED logit; lambda
+// decreases in t, so the M largest ratios are the M smallest t.  Per row, with M = min(S / 5, ceil(3 sqrt S)):
+//     cutoff   c = the element of rank M (0-based) of an ascending order of {t_s}   (the total order of the monotone key of
+//              order_stats.hip: -0 before +0, every NaN last)
+//     tail     the t strictly before c in that order, L <= M of them in any order; slots L .. M - 1 hold +inf
+//     body     sum over the draws NOT in the tail of e^m + e^(m - t), m = min(c, 0): every term lies in (0, 2]
+//     sum_lik  sum over all draws of sigmoid(t)
+// l2hmc_amd/predictive.py `loo_finish` turns them into elpd_loo and the Pareto k-hat; include/l2hmc.h states the contract.  The
+// (S, n) matrix is never written and nothing is sorted: a most-significant-digit radix select, kLooPasses = 4 passes of 8 bits,
+// finds c per row, and one more pass gathers.  Every pass forms t again from W.
+//
+// THE INVARIANT THE SELECT AND THE GATHER RELY ON: every pass computes t by ONE device function, loo_logits (staged by
+// loo_stage), which adds the feature tiles tg = 0 .. NT - 1 in that order, four f32-input MFMAs each, onto a zero accumulator.
+// The bits of t_si therefore depend on (W, X, y) alone -- not on the pass, the chunk, the plan or the row grouping of the caller.
+// A key counted in one pass is the key compared in the next, and exactly the keys below the selected one reach the tail.
+//
+// The contraction is predict_kernel's (predictive.hip): the same f32-input MFMA and operand layouts, the same staging of
+// 16-draw tiles by coalesced scalar loads from a base that is only 4-byte aligned, one tile ahead, into the wave's own LDS
+// region, the same masks (a draw at or past S, a row at or past n never counts).  Work unit = one wave: NB = 2 consecutive 16-row
+// data blocks x a chunk of tpc 16-draw tiles.  tpc depends on S ALONE (about kLooChunks chunks), so the order in which float64
+// terms are added does not depend on how many rows a call holds.  A workgroup is four waves on the SAME data blocks and four
+// consecutive chunks; blockIdx.x = quad * ngroups + group.
+//
+//   count    loo_kernel<NTM, 0>: the workgroup keeps one LDS histogram [32 rows][256 bins] uint32 (32 KiB) of the next digit of
+//            the keys that share their row's prefix, added to with integer LDS atomics and flushed -- non-zero bins only -- to
+//            the global int64 histogram (n, 256) with integer atomics.  In pass 0 every key counts and the top digit (sign and
+//            high exponent) concentrates in a few bins: the 16 draw lanes of a row would add to one address.  There the 16 lanes
+//            compare their bin with the first lane's; those that agree are counted by a ballot and added by that lane in ONE
+//            atomic, the others add for themselves.  Later passes count only the keys on the prefix: few, plain atomics.
+//   advance  loo_advance_kernel: one wave per row scans the 256 bins for the digit in which the remaining rank falls, as
+//            order_advance_kernel does; after the last pass the prefix is the cutoff's key and the cutoff is written.
+//   gather   loo_kernel<NTM, 1>: a key below the cutoff's key takes slot atomicAdd(n_tail[row], 1) (an integer atomic) of the
+//            row's tail; a slot at or past M is not written and raises the error word of the workspace (it cannot happen while
+//            the invariant holds).  Every other live draw adds its body term, every live draw its sigmoid, converted to float64
+//            BEFORE the addition, to the lane's own sums; once per wave the 16 draw lanes are added in the order c = 0 .. 15 and
+//            the wave's partials go to workspace[chunk][2][n].
+//   reduce   loo_reduce_kernel: sums[k][i] = the chunks' partials added in chunk order, as predict_reduce_kernel does.
+// No floating-point atomics anywhere: integer counts do not depend on arrival order, the tail is a set, the sums have a fixed
+// tree.  Every outward write is an ordinary vector store or atomic from plain C++.
+//
+// TWIN: loo_load / loo_stage / loo_logits and the end reduction restate the tile loop of predict_kernel (predictive.hip), which
+// keeps its own copy; a fix to the staging walk or to its register trick belongs in both until they share a header.
+//
+// Counts: a bin of the LDS histogram is a uint32 and a workgroup adds at most 4 waves x tpc x 16 draws to one bin of a row.
+// tpc <= 2^40 / 16 / 1024 = 2^26 at the largest n_draws the entry accepts, i.e. at most 2^32 -- one more than a bin holds, and
+// only if every draw of a 2^40-draw, d = 1 history (4 TB) fell into one bin; any history that fits a device stays far below.
+//
+// Occupancy by design: 2 workgroups per CU (2 waves per SIMD) -- every geometry must stay within 256 registers (held by
+// tests/test_loo_cpu.py from the compiler's listing) and its LDS, 32 KiB of histogram plus at most 33 KiB of staging, within
+// 80 KiB: two resident workgroups use at most 130 KiB of the 160 KiB of a CU.  Geometries <NTM feature tiles compiled>: 1, 2, 4, 8.
+#include <math.h>
+
+#include "l2hmc_kernels.hpp"
+
+namespace l2hmc {
+
+constexpr int kLooThreads = 256;          // 4 waves on the same rows
+constexpr int kLooNB = 2;                 // 16-row data blocks per wave
+constexpr int kLooRows = 16 * kLooNB;     // rows of a workgroup's histogram
+constexpr int kLooBits = 8;
+constexpr int kLooBins = 1 << kLooBits;
+constexpr int kLooPasses = 32 / kLooBits;
+constexpr int kLooChunks = 1024;          // draw chunks aimed for, whatever n is
+constexpr int kLooMinTiles = 4;           // draw tiles per chunk at least
+
+struct LooPlan {
+  int NT, NTM, nblk, ngroups;
+  long long ntiles, tpc, nchunks, quads, M;
+};
+
+// M = min(floor(S / 5), ceil(3 sqrt S)) in integers
+static long long loo_tail_len(long long S) {
+  if (S < 1) return 0;
+  long long k = (long long)ceil(3.0 * sqrt((double)S));
+  while (k > 0 && (k - 1) * (k - 1) >= 9 * S) --k;
+  while (k * k < 9 * S) ++k;
+  const long long f = S / 5;
+  return f < k ? f : k;
+}
+
+static bool loo_plan(const char* who, int64_t n_draws, int32_t n_data, int32_t d, LooPlan& p) {
+  if (n_draws < 2) { fail(L2HMC_ERR_ARG, "%s: n_draws >= 2 (got %lld)", who, n_draws); return false; }
+  if (n_data < 1 || n_data > kLogisticMaxRows) {
+    fail(L2HMC_ERR_ARG, "%s: 1 <= n_data <= 1048576 (got %lld)", who, n_data);
+    return false;
+  }
+  if (d < 1 || d > kLogisticMaxDim) { fail(L2HMC_ERR_ARG, "%s: 1 <= d <= 128 (got %lld)", who, d); return false; }
+  if (n_draws > (1LL << 40) / d) { fail(L2HMC_ERR_ARG, "%s: draws too large (n_draws d > 2^40)", who); return false; }
+  p.M = loo_tail_len(n_draws);
+  if (p.M * n_data > (1LL << 31)) { fail(L2HMC_ERR_ARG, "%s: tail too large (tail_len n_data > 2^31): fewer rows per call", who); return false; }
+  p.NT = tiles_of(d);
+  p.NTM = p.NT <= 2 ? p.NT : p.NT <= 4 ? 4 : 8;
+  p.nblk = (n_data + 15) / 16;
+  p.ngroups = (p.nblk + kLooNB - 1) / kLooNB;
+  p.ntiles = (n_draws + 15) / 16;
+  p.tpc = (p.ntiles + kLooChunks - 1) / kLooChunks;          // a function of n_draws alone
+  if (p.tpc < kLooMinTiles) p.tpc = kLooMinTiles;
+  p.nchunks = (p.ntiles + p.tpc - 1) / p.tpc;                // no empty chunk
+  p.quads = (p.nchunks + 3) / 4;
+  return true;
+}
+
+// workspace: error word (8 B) | hist (n, 256) int64 | remaining (n) int64 | prefix (n) uint32, padded to 8 B | partials
+struct LooWorkspace {
+  unsigned long long* err;
+  unsigned long long* hist;
+  long long* remaining;
+  uint32_t* prefix;
+  double* part;
+  int64_t bytes;
+};
+
+static LooWorkspace loo_workspace(void* base, const LooPlan& p, int32_t n) {
+  LooWorkspace w;
+  char* b = (char*)base;
+  int64_t o = 0;
+  w.err = (unsigned long long*)(b + o); o += 8;
+  w.hist = (unsigned long long*)(b + o); o += (int64_t)n * kLooBins * 8;
+  w.remaining = (long long*)(b + o); o += (int64_t)n * 8;
+  w.prefix = (uint32_t*)(b + o); o += ((int64_t)n * 4 + 7) / 8 * 8;
+  w.part = (double*)(b + o); o += p.nchunks * 2 * (int64_t)n * 8;
+  w.bytes = o;
+  return w;
+}
+
+__device__ __forceinline__ void loo_lds_fence() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// the monotone key of order_stats.hip; every NaN takes the last key
+__device__ __forceinline__ uint32_t loo_key(float v) {
+  const uint32_t b = __float_as_uint(v);
+  const uint32_t k = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+  return v != v ? 0xFFFFFFFFu : k;
+}
+__device__ __forceinline__ float loo_unkey(uint32_t key) {
+  return __uint_as_float((key & 0x80000000u) ? (key & 0x7FFFFFFFu) : ~key);
+}
+
+// the loads of draw tile t: element e = lane + 64 i of a tile is W[16 t d + e], 0 past the end of W
+template <int NTM>
+__device__ __forceinline__ void loo_load(const float* __restrict__ W, long long t, int tile_elems, long long total, int lane,
+                                         float (&pre)[4 * NTM]) {
+#pragma unroll
+  for (int i = 0; i < 4 * NTM; ++i) {
+    const int e = lane + 64 * i;
+    const long long g = t * tile_elems + e;
+    pre[i] = (e < tile_elems && g < total) ? W[g] : 0.f;
+  }
+}
+
+// the loaded tile into the wave's LDS region as [16 draws][16 NTM + 4]; element e is (draw e / d, feature e % d)
+template <int NTM>
+__device__ __forceinline__ void loo_stage(float* lds, const float (&pre)[4 * NTM], int lane, int d, int tile_elems, int row0,
+                                          int col0, int dq, int dr) {
+  constexpr int STRIDE = 16 * NTM + 4;
+  int row = row0, col = col0;
+  asm volatile("" : "+v"(row), "+v"(col));               // (recomputed per tile, not held in 4 NTM registers across the loop)
+#pragma unroll
+  for (int i = 0; i < 4 * NTM; ++i) {
+    if (lane + 64 * i < tile_elems) lds[row * STRIDE + col] = pre[i];
+    row += dq;
+    col += dr;
+    if (col >= d) { col -= d; row += 1; }
+  }
+}
+
+// THE signed logits of the staged tile: T[j][r] = t of draw c, row 16 (b0 + j) + 4 q + r.  Feature tiles in the order
+// tg = 0 .. NT - 1, four MFMAs each, onto zero; then the label's sign (exact).  Every pass calls this and nothing else.
+template <int NTM>
+__device__ __forceinline__ void loo_logits(const float* lds, const f4 (&xa)[kLooNB][NTM], const f4 (&yv)[kLooNB], int c, int q,
+                                           int NT, int b0, int nblk, f4 (&T)[kLooNB]) {
+  constexpr int STRIDE = 16 * NTM + 4;
+#pragma unroll
+  for (int j = 0; j < kLooNB; ++j) T[j] = splat(0.f);
+#pragma unroll
+  for (int tg = 0; tg < NTM; ++tg) {
+    if (tg < NT) {
+      const f4 B = lds4(lds + c * STRIDE + 16 * tg + 4 * q);
+#pragma unroll
+      for (int j = 0; j < kLooNB; ++j) {
+        if (b0 + j < nblk) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) T[j] = MFMA16(xa[j][tg][r], B[r], T[j]);
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < kLooNB; ++j)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) T[j][r] = yv[j][r] > 0.5f ? T[j][r] : -T[j][r];
+}
+
+// MODE 0: count the digit at `shift` of the keys on their row's prefix (first: no prefix, every key).  MODE 1: gather.
+template <int NTM, int MODE>
+__global__ __launch_bounds__(kLooThreads) void loo_kernel(const float* __restrict__ W, long long S, int d,
+                                                          const float* __restrict__ P, int n, int NT, int ngroups,
+                                                          long long nchunks, long long tpc, const uint32_t* __restrict__ prefix,
+                                                          int shift, int first, unsigned long long* __restrict__ hist,
+                                                          unsigned long long* __restrict__ n_tail, float* __restrict__ tail,
+                                                          long long M, unsigned long long* __restrict__ err,
+                                                          double* __restrict__ part) {
+  constexpr int NB = kLooNB;
+  constexpr int STRIDE = 16 * NTM + 4;
+  constexpr int REGION = 16 * STRIDE > 512 ? 16 * STRIDE : 512;   // per wave; the end reduction needs 256 doubles
+  __shared__ __attribute__((aligned(16))) float lds_all[4 * REGION];
+  __shared__ uint32_t hl[MODE == 0 ? kLooRows * kLooBins : 1];
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, c = lane & 15, q = lane >> 4;
+  const int group = (int)(blockIdx.x % (unsigned)ngroups);
+  const long long chunk = (long long)(blockIdx.x / (unsigned)ngroups) * 4 + w;
+  const bool live_wave = chunk < nchunks;                    // (wave-uniform; a dead wave still meets the barriers below)
+  float* lds = lds_all + w * REGION;
+#pragma unroll
+  for (int i = 0; i < REGION / 64; ++i) lds[lane + 64 * i] = 0.f;
+  if (MODE == 0) {
+    for (int i = threadIdx.x; i < kLooRows * kLooBins; i += kLooThreads) hl[i] = 0u;
+    __syncthreads();
+  }
+
+  const int nblk = (n + 15) >> 4, b0 = group * NB, BS = logistic_block_floats(NT);
+  if (live_wave) {
+    f4 xa[NB][NTM], yv[NB];
+    uint32_t pre_key[NB][4];          // count: the row's prefix above the digit; gather: the cutoff's key
+    float em[NB][4], mm[NB][4];       // gather: e^m and m = min(cutoff, 0)
+    bool row_ok[NB][4];
+#pragma unroll
+    for (int j = 0; j < NB; ++j) {
+      const bool live = b0 + j < nblk;
+      const float* blk = P + (size_t)(live ? b0 + j : nblk - 1) * BS;
+#pragma unroll
+      for (int tg = 0; tg < NTM; ++tg) xa[j][tg] = (live && tg < NT) ? lds4(blk + (tg * 64 + lane) * 4) : splat(0.f);
+      yv[j] = lds4(blk + 512 * NT + 4 * q);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = 16 * (b0 + j) + 4 * q + r;
+        row_ok[j][r] = live && row < n;
+        const uint32_t key = (row_ok[j][r] && !(MODE == 0 && first)) ? prefix[row] : 0u;
+        if (MODE == 0) {
+          pre_key[j][r] = first ? 0u : key >> (shift + kLooBits);
+          em[j][r] = mm[j][r] = 0.f;
+        } else {
+          pre_key[j][r] = key;
+          mm[j][r] = fminf(loo_unkey(key), 0.f);             // (a NaN cutoff gives 0)
+          em[j][r] = (float)exp((double)mm[j][r]);
+        }
+      }
+    }
+    double acc[NB][2][4];
+#pragma unroll
+    for (int j = 0; j < NB; ++j)
+#pragma unroll
+      for (int k = 0; k < 2; ++k)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[j][k][r] = 0.0;
+
+    const long long ntiles = (S + 15) >> 4, total = S * d;
+    const long long t0 = chunk * tpc, t1 = t0 + tpc < ntiles ? t0 + tpc : ntiles;
+    const int tile_elems = 16 * d;
+    const int row0 = lane / d, col0 = lane - row0 * d, dq = 64 / d, dr = 64 - dq * d;
+    float pre[4 * NTM];
+    loo_load<NTM>(W, t0, tile_elems, total, lane, pre);
+
+    for (long long t = t0; t < t1; ++t) {
+      loo_stage<NTM>(lds, pre, lane, d, tile_elems, row0, col0, dq, dr);
+      loo_lds_fence();
+      f4 T[NB];
+      loo_logits<NTM>(lds, xa, yv, c, q, NT, b0, nblk, T);
+      loo_lds_fence();
+      if (t + 1 < t1) loo_load<NTM>(W, t + 1, tile_elems, total, lane, pre);   // in flight during this tile's arithmetic
+      const bool valid = 16 * t + c < S;
+#pragma unroll
+      for (int j = 0; j < NB; ++j) {
+        if (b0 + j < nblk) {                                 // wave-uniform
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            const float tv = T[j][r];
+            const uint32_t key = loo_key(tv);
+            const bool ok = valid && row_ok[j][r];
+            if (MODE == 0) {
+              uint32_t* hrow = hl + (16 * j + 4 * q + r) * kLooBins;
+              if (first) {
+                // the 16 draw lanes of this row: those in the first lane's bin are added by it in one atomic
+                const int bin = (int)(key >> 24);
+                const int lead = __shfl(bin, lane & 48, 64);
+                const bool same = ok && bin == lead;
+                const unsigned long long bal = __ballot(same);
+                const int cnt = __popc((unsigned)((bal >> (lane & 48)) & 0xFFFFull));
+                if (c == 0) { if (cnt) atomicAdd(&hrow[lead], (uint32_t)cnt); }
+                else if (ok && !same) atomicAdd(&hrow[bin], 1u);
+              } else {
+                if (ok && (key >> (shift + kLooBits)) == pre_key[j][r]) atomicAdd(&hrow[(key >> shift) & (kLooBins - 1)], 1u);
+              }
+            } else {
+              const bool in_tail = ok && key < pre_key[j][r];
+              if (in_tail) {
+                const int row = 16 * (b0 + j) + 4 * q + r;
+                const unsigned long long slot = atomicAdd(&n_tail[row], 1ull);
+                if (slot < (unsigned long long)M) tail[(long long)row * M + (long long)slot] = tv;
+                else atomicOr(err, 1ull);
+              }
+              const float e = fexp(-fabsf(tv));
+              const float inv = __builtin_amdgcn_rcpf(1.f + e);
+              const float lik = tv >= 0.f ? inv : e * inv;
+              const float body = em[j][r] + fexp(mm[j][r] - tv);
+              acc[j][0][r] += (double)((ok && !in_tail) ? body : 0.f);
+              acc[j][1][r] += (double)(ok ? lik : 0.f);
+            }
+          }
+        }
+      }
+    }
+
+    if (MODE == 1) {
+      // the 16 draw lanes of every (data block, sum, row), added in the order c = 0 .. 15
+      double* red = reinterpret_cast<double*>(lds);
+#pragma unroll
+      for (int j = 0; j < NB; ++j) {
+        if (b0 + j < nblk) {
+#pragma unroll
+          for (int k = 0; k < 2; ++k) {
+            loo_lds_fence();
+#pragma unroll
+            for (int r = 0; r < 4; ++r) red[c * 16 + 4 * q + r] = acc[j][k][r];
+            loo_lds_fence();
+            if (lane < 16) {
+              double a = red[lane];
+#pragma unroll
+              for (int cc = 1; cc < 16; ++cc) a += red[cc * 16 + lane];
+              const int row = 16 * (b0 + j) + lane;
+              if (row < n) part[(chunk * 2 + k) * (long long)n + row] = a;
+            }
+          }
+        }
+      }
+    }
+  }
+
+  if (MODE == 0) {
+    __syncthreads();
+    for (int i = threadIdx.x; i < kLooRows * kLooBins; i += kLooThreads) {
+      const uint32_t cnt = hl[i];
+      const int row = 16 * b0 + (i >> kLooBits);
+      if (cnt && row < n) atomicAdd(&hist[(long long)row * kLooBins + (i & (kLooBins - 1))], (unsigned long long)cnt);
+    }
+  }
+}
+
+// one wave per row: lane l holds bins 4 l .. 4 l + 3, a wave scan finds the lane and that lane the digit (order_advance_kernel)
+__global__ __launch_bounds__(64) void loo_advance_kernel(const long long* __restrict__ hist, long long* __restrict__ remaining,
+                                                         uint32_t* __restrict__ prefix, int n, int shift,
+                                                         float* __restrict__ cutoff) {
+  static_assert(kLooBins == 4 * 64, "four bins per lane");
+  const int i = blockIdx.x, lane = threadIdx.x;
+  if (i >= n) return;
+  const long long* h = hist + (long long)i * kLooBins + 4 * lane;
+  long long c[4];
+#pragma unroll
+  for (int b = 0; b < 4; ++b) c[b] = h[b];
+  const long long mine = c[0] + c[1] + c[2] + c[3];
+  long long incl = mine;
+#pragma unroll
+  for (int o = 1; o < 64; o *= 2) {
+    const long long up = __shfl_up(incl, o, 64);
+    if (lane >= o) incl += up;
+  }
+  const long long total = __shfl(incl, 63, 64);
+  long long rem = remaining[i];
+  if (total <= 0) {                                   // nothing on the prefix (cannot happen: the rank is below n_draws)
+    if (lane == 0 && cutoff) cutoff[i] = loo_unkey(prefix[i]);
+    return;
+  }
+  if (rem < 0) rem = 0;
+  if (rem >= total) rem = total - 1;
+  long long below = incl - mine;
+  if (rem < below || rem >= incl) return;             // exactly one lane holds the rank
+  int digit = 4 * lane;
+#pragma unroll
+  for (int b = 0; b < 3; ++b)
+    if (rem >= below + c[b] && digit == 4 * lane + b) { below += c[b]; ++digit; }
+  const uint32_t key = prefix[i] | ((uint32_t)digit << shift);
+  prefix[i] = key;
+  remaining[i] = rem - below;
+  if (cutoff) cutoff[i] = loo_unkey(key);
+}
+
+__global__ void loo_init_kernel(long long* __restrict__ remaining, uint32_t* __restrict__ prefix,
+                                unsigned long long* __restrict__ n_tail, float* __restrict__ tail, int n, long long M,
+                                unsigned long long* __restrict__ err) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i == 0) *err = 0ull;
+  if (i < n) { remaining[i] = M; prefix[i] = 0u; n_tail[i] = 0ull; }
+  if (i < (long long)n * M) tail[i] = __builtin_inff();
+}
+
+// sums[i] = the chunks' partials of entry i = k n + row, added in chunk order
+__global__ void loo_reduce_kernel(const double* __restrict__ part, long long nchunks, long long m, double* __restrict__ sums) {
+  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= m) return;
+  double a = 0.0;
+  for (long long ch = 0; ch < nchunks; ++ch) a += part[ch * m + i];
+  sums[i] = a;
+}
+
+}  // namespace l2hmc
+
+using namespace l2hmc;
+
+extern "C" {
+
+int64_t l2hmc_logistic_loo_tail_len(int64_t n_draws) { return loo_tail_len(n_draws); }
+
+int64_t l2hmc_logistic_loo_workspace_bytes(int64_t n_draws, int32_t n_data, int32_t d) {
+  LooPlan p;
+  if (!loo_plan("l2hmc_logistic_loo_workspace_bytes", n_draws, n_data, d, p)) return L2HMC_ERR_ARG;
+  return loo_workspace(nullptr, p, n_data).bytes;
+}
+
+int l2hmc_logistic_loo_tails(const float* draws, int64_t n_draws, int32_t d, const float* packed, int32_t n_data, float* cutoff,
+                             int64_t* n_tail, float* tail, double* sums, void* workspace, void* stream) {
+  LooPlan p;
+  if (!loo_plan("l2hmc_logistic_loo_tails", n_draws, n_data, d, p)) return L2HMC_ERR_ARG;
+  if (!draws || !packed || !cutoff || !n_tail || (!tail && p.M > 0) || !sums || !workspace)
+    return fail(L2HMC_ERR_ARG, "l2hmc_logistic_loo_tails: draws, packed, cutoff, n_tail, tail, sums and workspace are required%s");
+  if (((uintptr_t)draws & 3) || ((uintptr_t)packed & 15) || ((uintptr_t)cutoff & 3) || ((uintptr_t)n_tail & 7) ||
+      ((uintptr_t)tail & 3) || ((uintptr_t)sums & 7) || ((uintptr_t)workspace & 7))
+    return fail(L2HMC_ERR_ARG, "l2hmc_logistic_loo_tails: draws, cutoff and tail must be 4-byte, packed 16-byte, n_tail, sums and "
+                               "workspace 8-byte aligned%s");
+  hipStream_t s = (hipStream_t)stream;
+  const LooWorkspace ws = loo_workspace(workspace, p, n_data);
+  const long long n = n_data, cells = n * p.M > n ? n * p.M : n;
+  hipLaunchKernelGGL(loo_init_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s, ws.remaining, ws.prefix,
+                     (unsigned long long*)n_tail, tail, (int)n_data, p.M, ws.err);
+  const dim3 grid((unsigned)(p.quads * p.ngroups)), block(kLooThreads);
+#define L2HMC_LOO_LAUNCH(NTM, MODE, shift, first)                                                                          \
+  hipLaunchKernelGGL((loo_kernel<NTM, MODE>), grid, block, 0, s, draws, (long long)n_draws, (int)d, packed, (int)n_data, p.NT, \
+                     p.ngroups, p.nchunks, p.tpc, (const uint32_t*)ws.prefix, (int)(shift), (int)(first), ws.hist,             \
+                     (unsigned long long*)n_tail, tail, p.M, ws.err, ws.part)
+#define L2HMC_LOO_PASS(MODE, shift, first)                 \
+  switch (p.NTM) {                                         \
+    case 1: L2HMC_LOO_LAUNCH(1, MODE, shift, first); break; \
+    case 2: L2HMC_LOO_LAUNCH(2, MODE, shift, first); break; \
+    case 4: L2HMC_LOO_LAUNCH(4, MODE, shift, first); break; \
+    default: L2HMC_LOO_LAUNCH(8, MODE, shift, first); break; \
+  }
+  for (int pass = 0; pass < kLooPasses; ++pass) {
+    const int shift = 32 - kLooBits * (pass + 1);
+    hipError_t e = hipMemsetAsync(ws.hist, 0, (size_t)n * kLooBins * sizeof(long long), s);
+    if (e != hipSuccess) return fail(L2HMC_ERR_HIP, "hipMemsetAsync: %s", hipGetErrorString(e));
+    L2HMC_LOO_PASS(0, shift, pass == 0)
+    hipLaunchKernelGGL(loo_advance_kernel, dim3((unsigned)n_data), dim3(64), 0, s, (const long long*)ws.hist, ws.remaining,
+                       ws.prefix, (int)n_data, shift, pass == kLooPasses - 1 ? cutoff : (float*)nullptr);
+  }
+  L2HMC_LOO_PASS(1, 0, 0)
+#undef L2HMC_LOO_PASS
+#undef L2HMC_LOO_LAUNCH
+  const long long m = 2LL * n_data;
+  hipLaunchKernelGGL(loo_reduce_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, (const double*)ws.part, p.nchunks, m,
+                     sums);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(L2HMC_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
+  return L2HMC_OK;
+}
+
+}  // extern "C"

@@ -28,6 +28,9 @@
 // Units are ordered (chunk, group) with the group fastest, so the waves of a workgroup read the same draws.  The planner aims
 // for kPredictUnits waves: at S large / n small the chunks supply them, at n large / S small the data-block groups do.
 //
+// TWIN: loo.hip (loo_load / loo_stage / loo_logits and its end reduction) restates this tile loop for the PSIS-LOO passes; a
+// fix to the staging walk or to its register trick belongs in both until they share a header.
+//
 // Occupancy by design: 2 waves per SIMD (8 per CU) -- the main kernel must stay within 256 registers (held by
 // tests/test_predictive_cpu.py from the compiler's listing); its LDS (at most 4 x 8448 bytes per workgroup) never limits that.
 // Geometries <NTM feature tiles compiled, NB data blocks per wave>: <1, 4>, <2, 4>, <4, 2>, <8, 2> -- 32 NB registers of

@@ -244,6 +244,12 @@ class LogisticRegression(object):
         from . import predictive
         return predictive.waic(draws, self.X, self.y)
 
+    def loo(self, draws):
+        """PSIS-LOO of this model's own data under the draws (`predictive.loo`): a `Summary` with elpd_loo, p_loo, looic, se,
+        the per-row Pareto `khat` and `n_bad`, the number of rows where it exceeds 0.7."""
+        from . import predictive
+        return predictive.loo(draws, self.X, self.y)
+
 
 def as_device_f32(x, device=None):
     """numpy / torch input -> contiguous float32 tensor on the GPU."""

@@ -23,6 +23,22 @@ these as `m2_ll` and `log_sum_lik`, which `finish` prefers when they are there. 
 Summing lik itself needs no running maximum and is exact as long as one draw gives lik above the smallest float32; a row where
 every draw underflows has sum_lik = 0, lppd_i = -inf, and is counted in `n_underflow` -- reported, not hidden.
 `n_high_variance` counts the rows with p_waic_i > 0.4, the usual warning threshold: WAIC is unreliable there.
+
+The standard answer to those rows is PSIS-LOO (Vehtari, Gelman, Gabry 2017; Vehtari, Simpson, Gelman, Yao, Gabry 2024) with its
+per-row diagnostic, the Pareto k-hat:
+
+    s = loo(x_hist[burn_in:], X, y)                  # = loo_finish(loo_tails(...))
+    s.elpd_loo, s.p_loo, s.looic, s.se, s.khat, s.n_bad, s.khat_threshold, s.n_above_threshold, s.elpd_loo_i, ...
+
+The log importance ratio of row i under draw s is softplus(-t) with t = (2 y_i - 1) x_i . w_s the signed logit, and it decreases
+in t.  PSIS needs per row only the M = min(S // 5, ceil(3 sqrt S)) smallest t -- the tail, cut strictly before the element of
+rank M so that ties shorten it, the rule of the `loo` package -- and one sum over the other draws: `loo_tails` returns
+{'cutoff', 'n_tail', 'tail' (n, M; +inf past n_tail), 'body', 'sum_lik', 'tail_len', 'n_draws'}, where body = the sum over the
+draws outside the tail of e^m + e^(m - t), m = min(cutoff, 0).  A ROCm tensor of draws goes to the kernels behind
+`l2hmc_logistic_loo_tails` (csrc/loo.hip: a fused contraction and per-row radix select, nothing is sorted, float32 t, bitwise
+reproducible) and the dict holds device tensors; numpy or a CPU tensor is float64 numpy.  `loo_finish` fits the generalised
+Pareto distribution to every tail (Zhang & Stephens 2009 with the prior of `loo`), smooths the tail weights and forms elpd_loo_i
+in float64 where the tails lie: torch on the device in row chunks of bounded memory, numpy on the host.
 """
 import numpy as np
 
@@ -34,6 +50,10 @@ MAX_DEVICE_ROWS = 1 << 20     # l2hmc_pack_logistic
 MAX_DEVICE_DIM = 128
 HIGH_VARIANCE = 0.4
 _HOST_CHUNK_ELEMS = 1 << 22   # (draws x rows) logits formed at a time on the host
+KHAT_BAD = 0.7                # PSIS is unreliable above it whatever S is
+MIN_TAIL_FIT = 5              # a shorter tail is not fitted: khat = +inf
+_FINISH_CHUNK_BYTES = 1 << 26  # the (rows, theta grid, tail) block of the Pareto profile formed at a time by `loo_finish`
+_NEG_ZERO_KEY = -5e-324       # stands for -0.0 on the host so that a float64 sort puts it before +0.0, as the device order does
 
 
 def _check(draws, X, y):
@@ -170,3 +190,284 @@ def log_predictive_density(draws, X_new, y_new):
     with np.errstate(all="ignore"):
         se = float(np.sqrt(n * f.lppd_i.var(ddof=1))) if n > 1 else float("nan")
     return Summary(lppd=f.lppd, lppd_i=f.lppd_i, se=se, n_draws=f.n_draws, n_rows=n, n_underflow=f.n_underflow)
+
+
+def loo_tail_len(S):
+    """M = min(S // 5, ceil(3 sqrt S)): how many of the largest importance ratios PSIS may fit and smooth."""
+    import math
+    S = int(S)
+    return min(S // 5, math.isqrt(9 * S - 1) + 1) if S >= 1 else 0
+
+
+def _device_labels(X, y, dev):
+    import torch
+    Xd = torch.as_tensor(X).detach().to(device=dev, dtype=torch.float32).contiguous()
+    yd = torch.as_tensor(y).detach().to(device=dev, dtype=torch.float32).contiguous()
+    if not bool(((yd == 0) | (yd == 1)).all()):
+        raise ValueError("labels y must be 0 or 1")
+    return Xd, yd
+
+
+def _device_tail_groups(draws, X, y, S, d, n, max_tail_bytes):
+    """The raw dict of one group of consecutive rows at a time, on the device; a group's tail stays under `max_tail_bytes`."""
+    import torch
+    if n > MAX_DEVICE_ROWS or d > MAX_DEVICE_DIM:
+        raise ValueError("the LOO kernels hold n_rows <= %d and dim <= %d (got %d, %d)" % (MAX_DEVICE_ROWS, MAX_DEVICE_DIM, n, d))
+    dev = draws.device
+    W = in_place(draws)
+    Xd, yd = _device_labels(X, y, dev)
+    L = _ffi.lib()
+    M = _ffi.check(L.l2hmc_logistic_loo_tail_len(S))
+    rows = max(1, min(n, int(max_tail_bytes) // max(1, 4 * M), (1 << 31) // max(1, M)))
+    flags = []                                               # every group's error word, read once after the last group
+    for a in range(0, n, rows):
+        m = min(rows, n - a)
+        packed = workspace(dev, torch.float32, L.l2hmc_packed_logistic_floats, m, d)
+        launch(dev, L.l2hmc_pack_logistic, Xd[a:a + m].data_ptr(), yd[a:a + m].data_ptr(), m, d, packed.data_ptr())
+        ws = workspace(dev, torch.uint8, L.l2hmc_logistic_loo_workspace_bytes, S, m, d)
+        cutoff = torch.empty(m, dtype=torch.float32, device=dev)
+        n_tail = torch.empty(m, dtype=torch.int64, device=dev)
+        tail = torch.empty((m, M), dtype=torch.float32, device=dev)
+        sums = torch.empty((2, m), dtype=torch.float64, device=dev)
+        launch(dev, L.l2hmc_logistic_loo_tails, W.data_ptr(), S, d, packed.data_ptr(), m, cutoff.data_ptr(), n_tail.data_ptr(),
+               tail.data_ptr() if M else None, sums.data_ptr(), ws.data_ptr())
+        flags.append(ws[:8].view(torch.int64).clone())
+        yield {"cutoff": cutoff, "n_tail": n_tail, "tail": tail, "body": sums[0], "sum_lik": sums[1], "tail_len": M, "n_draws": S}
+    if bool(torch.cat(flags).any()):
+        raise RuntimeError("l2hmc_logistic_loo_tails: a tail outgrew its %d slots: the passes disagree" % M)
+
+
+def _host_tails(draws, X, y, S, d, n):
+    """The same raw dict in float64 numpy: per row the M + 1 smallest signed logits are kept while the draws pass in chunks
+    (a partition, not a sort), then one more pass over the draws adds the body and the likelihoods."""
+    W = as_numpy(draws, np.float64).reshape(S, d)
+    X = as_numpy(X, np.float64)
+    y = as_numpy(y, np.float64)
+    if not np.all((y == 0.0) | (y == 1.0)):
+        raise ValueError("labels y must be 0 or 1")
+    sign = 2.0 * y - 1.0
+    M = loo_tail_len(S)
+    step = max(1, _HOST_CHUNK_ELEMS // n)
+
+    def logits(a):
+        t = (W[a:a + step] @ X.T) * sign
+        return np.where((t == 0.0) & np.signbit(t), _NEG_ZERO_KEY, t)             # the device order: -0 before +0
+
+    with np.errstate(all="ignore"):
+        low = np.empty((0, n))
+        for a in range(0, S, step):
+            low = np.concatenate([low, logits(a)])
+            if low.shape[0] > M + 1:
+                low = np.partition(low, M, axis=0)[:M + 1]                         # NaN sorts last, as on the device
+        low = np.sort(low, axis=0)
+        c = low[M]
+        keep = low[:M] < c                                                         # strictly before the cutoff
+        n_tail = keep.sum(axis=0).astype(np.int64)
+        tail = np.where(keep, low[:M], np.inf).T.copy()                            # (n, M): sorted, +inf past n_tail
+        m = np.minimum(np.where(c != c, 0.0, c), 0.0)
+        body, sum_lik = np.zeros(n), np.zeros(n)
+        for a in range(0, S, step):
+            t = logits(a)
+            body += np.where(t < c, 0.0, np.exp(m) + np.exp(m - t)).sum(axis=0)
+            sum_lik += np.exp(-np.logaddexp(0.0, -t)).sum(axis=0)
+    unkey = lambda v: np.where(v == _NEG_ZERO_KEY, -0.0, v)  # noqa: E731
+    return {"cutoff": unkey(c), "n_tail": n_tail, "tail": unkey(tail), "body": body, "sum_lik": sum_lik, "tail_len": M, "n_draws": S}
+
+
+def _check_loo(draws, X, y):
+    if y is None:
+        raise ValueError("loo needs the labels y")
+    return _check(draws, X, y)
+
+
+def loo_tails(draws, X, y, max_tail_bytes=256 << 20):
+    """The raw material of PSIS-LOO per row of X (module docstring): {'cutoff' (n,), 'n_tail' (n,) int64, 'tail' (n, M) with
+    +inf past n_tail, 'body' (n,), 'sum_lik' (n,), 'tail_len': M, 'n_draws': S}.  A ROCm tensor of draws -> the HIP kernels,
+    read in place, device tensors back (float32 cutoff and tail in any order, float64 sums; bitwise reproducible); the rows go
+    in groups whose tail buffer stays under `max_tail_bytes`, and the bits do not depend on the grouping.  numpy or a CPU
+    tensor -> float64 numpy arrays, the tail sorted."""
+    S, d, n = _check_loo(draws, X, y)
+    if not is_device_tensor(draws):
+        return _host_tails(draws, X, y, S, d, n)
+    import torch
+    groups = list(_device_tail_groups(draws, X, y, S, d, n, max_tail_bytes))
+    out = {k: torch.cat([g[k] for g in groups]) for k in ("cutoff", "n_tail", "tail", "body", "sum_lik")}
+    out["tail_len"], out["n_draws"] = groups[0]["tail_len"], S
+    return out
+
+
+class _Numpy:
+    """The few array operations `_loo_rows` needs, over numpy ..."""
+    def __init__(self):
+        for k in ("exp", "log", "log1p", "expm1", "sqrt", "floor", "where", "isfinite", "minimum", "maximum", "isnan"):
+            setattr(self, k, getattr(np, k))
+
+    def f64(self, a):
+        return np.asarray(a, dtype=np.float64)
+
+    def arange(self, n, like):
+        return np.arange(n, dtype=np.float64)
+
+    def sort(self, a):
+        return np.sort(a, axis=-1)
+
+    def sum(self, a):
+        return a.sum(axis=-1)
+
+    def max(self, a):
+        return a.max(axis=-1) if a.shape[-1] else np.full(a.shape[:-1], -np.inf)
+
+    def take(self, a, idx):
+        return np.take_along_axis(a, idx.astype(np.int64)[..., None], axis=-1)[..., 0]
+
+    def host(self, a):
+        return np.asarray(a)
+
+
+class _Torch:
+    """... and over torch, on the device of the tails."""
+    def __init__(self):
+        import torch
+        self.t = torch
+        for k in ("exp", "log", "log1p", "expm1", "sqrt", "floor", "where", "isfinite", "minimum", "maximum", "isnan"):
+            setattr(self, k, getattr(torch, k))
+
+    def f64(self, a):
+        return a.to(self.t.float64)
+
+    def arange(self, n, like):
+        return self.t.arange(n, dtype=self.t.float64, device=like.device)
+
+    def sort(self, a):
+        return self.t.sort(a, dim=-1).values
+
+    def sum(self, a):
+        return a.sum(dim=-1)
+
+    def max(self, a):
+        return a.amax(dim=-1) if a.shape[-1] else self.t.full(a.shape[:-1], -float("inf"), dtype=a.dtype, device=a.device)
+
+    def take(self, a, idx):
+        return self.t.gather(a, -1, idx.to(self.t.int64).unsqueeze(-1)).squeeze(-1)
+
+    def host(self, a):
+        return a.cpu().numpy()
+
+
+def _loo_rows(xp, cutoff, n_tail, tail, body, sum_lik, S, M):
+    """(khat, elpd_loo_i, lppd_i) of a chunk of rows, float64, over the operations of `xp` alone.  The tail is sorted so that
+    t ascends: slot s < L holds the ratio of ascending rank j = L - s, and slot 0 the largest."""
+    c, Lf = xp.f64(cutoff), xp.f64(n_tail)
+    t = xp.sort(xp.f64(tail))                                                      # the +inf pads last
+    zero = Lf * 0.0
+    slot = xp.arange(M, c)
+    zeros = zero[:, None] + slot[None, :] * 0.0                                    # (rows, M)
+    minus_inf = zeros - float("inf")
+
+    def softplus_neg(v):                                                           # softplus(-v) = log(1 + e^-v)
+        return xp.maximum(-v, v * 0.0) + xp.log1p(xp.exp(-xp.maximum(v, -v)))
+
+    def lse(a):                                                                    # logsumexp over the last axis; -inf when empty
+        mx = xp.max(a)
+        mx = xp.where(xp.isfinite(mx), mx, xp.where(xp.isnan(mx), mx, zero))          # centre: 0 for an empty (-inf) row
+        return mx + xp.log(xp.sum(xp.exp(a - mx[..., None])))
+
+    def add(a, b):                                                                 # logaddexp of two (rows,) arrays
+        mx = xp.maximum(a, b)
+        mx = xp.where(xp.isfinite(mx), mx, xp.where(xp.isnan(mx), mx, zero))
+        return mx + xp.log(xp.exp(a - mx) + xp.exp(b - mx))
+
+    live = slot[None, :] < Lf[:, None]
+    j = Lf[:, None] - slot[None, :]                                                # ascending rank of the ratio, 1 .. L
+    lam_c = softplus_neg(c)
+    lam = softplus_neg(t)                                                          # 0 in the pads
+    lam_max = xp.where(Lf > 0, lam[:, 0], lam_c) if M else lam_c
+    floor_c = xp.exp(lam_c - lam_max)                                              # the cutoff's ratio over the largest one
+    x = xp.where(live, xp.exp(lam - lam_max[:, None]) - floor_c[:, None], zeros)
+    fit = Lf >= MIN_TAIL_FIT
+    Ls = xp.where(fit, Lf, zero + MIN_TAIL_FIT)                                    # (a placeholder length where nothing is fitted)
+    # Zhang & Stephens (2009) with the prior of `loo`: the profile likelihood on a grid of theta, theta's posterior mean
+    jt = xp.arange(30 + int(np.floor(np.sqrt(max(M, 1)))), c) + 1.0
+    m_theta = 30.0 + xp.floor(xp.sqrt(Ls))
+    on_grid = jt[None, :] <= m_theta[:, None]
+    if M:
+        x_star = xp.take(x, xp.minimum(xp.maximum(Ls - xp.floor(Ls / 4.0 + 0.5), zero), zero + (M - 1)))   # rank floor(L/4 + 0.5)
+        x_top = x[:, 0]
+    else:
+        x_star = x_top = zero
+    theta = 1.0 / x_top[:, None] + (1.0 - xp.sqrt(m_theta[:, None] / (jt[None, :] - 0.5))) / (3.0 * x_star[:, None])
+    kj = xp.sum(xp.where(live[:, None, :], xp.log1p(-theta[:, :, None] * x[:, None, :]), zeros[:, None, :])) / Ls[:, None]
+    ell = xp.where(on_grid, Ls[:, None] * (xp.log(-theta / kj) - kj - 1.0), theta * 0.0 - float("inf"))
+    wj = xp.exp(ell - lse(ell)[:, None])                                           # = 1 / sum_j' exp(ell_j' - ell_j)
+    theta_hat = xp.sum(xp.where(on_grid, theta * wj, theta * 0.0))
+    k = xp.sum(xp.where(live, xp.log1p(-theta_hat[:, None] * x), zeros)) / Ls
+    sigma = -k / theta_hat
+    k = (k * Ls + 5.0) / (Ls + 10.0)
+    smooth = fit & xp.isfinite(k) & xp.isfinite(sigma)
+    lp = xp.log1p(-xp.where(live, (j - 0.5) / Ls[:, None], zeros))                 # log(1 - p_j)
+    ks = xp.where(smooth & (k != 0.0), k, zero + 1.0)[:, None]
+    qj = xp.where((k == 0.0)[:, None], -sigma[:, None] * lp, sigma[:, None] * xp.expm1(-ks * lp) / ks)
+    omega = xp.where(smooth[:, None], xp.minimum(xp.log(qj + floor_c[:, None]), zeros), lam - lam_max[:, None])
+    m = xp.minimum(xp.where(xp.isnan(c), zero, c), zero)
+    num = add(xp.log(S - Lf) - lam_max, lse(xp.where(live, omega - lam, minus_inf)))
+    den = add(xp.log(xp.f64(body)) - m - lam_max, lse(xp.where(live, omega, minus_inf)))
+    elpd = num - den
+    khat = xp.where(smooth, k, zero + float("inf"))
+    khat = xp.where(xp.isnan(elpd), elpd, khat)                                    # a NaN draw makes the row NaN, quietly
+    return khat, elpd, xp.log(xp.f64(sum_lik) / S)
+
+
+def _loo_summary(khat, elpd_i, lppd_i, n_tail, S, M):
+    n = elpd_i.shape[0]
+    with np.errstate(all="ignore"):
+        p_loo_i = lppd_i - elpd_i
+        elpd, p_loo, lppd = float(elpd_i.sum()), float(p_loo_i.sum()), float(lppd_i.sum())
+        se = float(np.sqrt(n * elpd_i.var(ddof=1))) if n > 1 else float("nan")
+        threshold = min(1.0 - 1.0 / np.log10(S), KHAT_BAD)
+    return Summary(elpd_loo_i=elpd_i, p_loo_i=p_loo_i, lppd_i=lppd_i, khat=khat, n_tail=n_tail, elpd_loo=elpd, p_loo=p_loo,
+                   lppd=lppd, looic=-2.0 * elpd, se=se, khat_threshold=threshold, n_bad=int(np.sum(khat > KHAT_BAD)),
+                   n_above_threshold=int(np.sum(khat > threshold)), tail_len=M, n_draws=S, n_rows=n,
+                   n_underflow=int(np.sum(np.isneginf(lppd_i))))
+
+
+def _finish_rows(tails):
+    """(khat, elpd_loo_i, lppd_i, n_tail) as float64 / int64 numpy of one raw dict, in row chunks of bounded memory, computed
+    where the tails lie; only these O(n) numbers come to the host."""
+    S, M = int(tails["n_draws"]), int(tails["tail_len"])
+    if S < 2:
+        raise ValueError("PSIS-LOO needs >= 2 draws (got %d)" % S)
+    xp = _Torch() if is_device_tensor(tails["tail"]) else _Numpy()
+    keys = ("cutoff", "n_tail", "tail", "body", "sum_lik")
+    arrays = [tails[k] if isinstance(xp, _Torch) else np.asarray(tails[k]) for k in keys]
+    n = int(arrays[0].shape[0])
+    n_theta = 30 + int(np.floor(np.sqrt(max(M, 1))))
+    rows = max(1, _FINISH_CHUNK_BYTES // (8 * n_theta * max(M, 1)))
+    out = [[], [], []]
+    with np.errstate(all="ignore"):
+        for a in range(0, n, rows):
+            res = _loo_rows(xp, *(v[a:a + rows] for v in arrays), S, M)
+            for o, r in zip(out, res):
+                o.append(xp.host(r))
+    return tuple(np.concatenate(o) for o in out) + (np.asarray(xp.host(arrays[1]), dtype=np.int64),)
+
+
+def loo_finish(tails):
+    """The `Summary` of `loo_tails`' result: per row `elpd_loo_i`, `p_loo_i`, `lppd_i`, `khat`, `n_tail`; the totals `elpd_loo`,
+    `p_loo`, `lppd`, `looic` = -2 elpd_loo, `se` = sqrt(n var_i elpd_loo_i) (NaN for one row); `khat_threshold` =
+    min(1 - 1 / log10 S, 0.7), `n_bad` = #{khat > 0.7}, `n_above_threshold`; `tail_len`, `n_draws`, `n_rows`, `n_underflow`.
+    A tail shorter than 5 (or a fit that is not finite) is not smoothed and has khat = +inf."""
+    khat, elpd_i, lppd_i, n_tail = _finish_rows(tails)
+    return _loo_summary(khat, elpd_i, lppd_i, n_tail, int(tails["n_draws"]), int(tails["tail_len"]))
+
+
+def loo(draws, X, y, max_tail_bytes=256 << 20):
+    """PSIS-LOO of the logistic regression (X, y) under the posterior draws: `loo_finish(loo_tails(draws, X, y))`, except that
+    on the device every group of rows is finished before the next one's tails are formed, so that no more than
+    `max_tail_bytes` of tails exist at a time.  Compare two models on the same rows by `elpd_loo` (higher is better) against
+    `se`; rows with khat > 0.7 (`n_bad`) are where the estimate cannot be trusted."""
+    S, d, n = _check_loo(draws, X, y)
+    if not is_device_tensor(draws):
+        return loo_finish(_host_tails(draws, X, y, S, d, n))
+    parts = [_finish_rows(g) for g in _device_tail_groups(draws, X, y, S, d, n, max_tail_bytes)]
+    khat, elpd_i, lppd_i, n_tail = (np.concatenate([p[k] for p in parts]) for k in range(4))
+    return _loo_summary(khat, elpd_i, lppd_i, n_tail, S, loo_tail_len(S))
