@@ -761,6 +761,35 @@ int l2hmc_logistic_loo_tails(const float* draws, int64_t n_draws, int32_t d, con
                              float* cutoff /* (n_data) */, int64_t* n_tail /* (n_data) */, float* tail /* (n_data, M) */,
                              double* sums /* (2, n_data): body, sum_lik */, void* workspace, void* stream);
 
+/* Pareto-smoothed importance sampling of the tails of ANY log importance ratios, float64 throughout (csrc/psis.hip;
+ * l2hmc_amd/psis.py `smooth_tails`, `psis`, `loo_from_log_lik`; `predictive.loo(finish="kernel")`).  Per row i:
+ *   lam         (n_rows, tail_len) the L_i = n_tail[i] <= tail_len largest log ratios, descending, in slots 0 .. L_i - 1; a slot
+ *               at or past L_i is never read
+ *   n_tail      (n_rows) int64
+ *   lam_cutoff  (n_rows) the log ratio of the cutoff (below every tail member)
+ *   out         (3, n_rows): khat | lse_w = logsumexp_s omega_s | lse_wl = logsumexp_s (omega_s - lam_s), where omega_s is the
+ *               smoothed log weight of slot s relative to the row's largest ratio.  L_i >= 5 and a finite fit (Zhang & Stephens
+ *               2009 with the prior of `loo`; the formulas stand at the head of csrc/psis.hip): omega = the log of the
+ *               generalised-Pareto quantile at (rank - 0.5) / L_i, capped at 0, and khat the fitted shape.  Otherwise
+ *               omega_s = lam_s - lam_max and khat = +inf.  L_i = 0: -inf, -inf.  A NaN among a row's live slots makes that
+ *               row's three outputs NaN and touches no other row.
+ *   weights     (n_rows, tail_len) or NULL: omega in the input's slot order, -inf in the slots at or past L_i.
+ * `workspace`: l2hmc_psis_workspace_bytes(n_rows, tail_len) bytes, 8-byte aligned, required: error word | x | the profile's
+ * sums.  The first int64 of the workspace is non-zero after the call if an n_tail entry lay outside 0 .. tail_len (the row is
+ * then computed with the entry clamped).  Every sum has a fixed order that depends on L_i alone and there are no floating-point
+ * atomics: two calls give identical bits, and a row gives the same bits whichever other rows share the call.
+ * l2hmc_psis_plan(n_rows, tail_len, what) reports the launch plan: what = 0 the theta blocks per row, 1 the workgroups along
+ * the rows (further rows are taken in a loop), 2 the theta accumulators per thread, 3 the threads of a workgroup, 4 the
+ * theta grid's length at tail_len.
+ * L2HMC_ERR_ARG (before any launch): n_rows < 1, tail_len < 0, a tail the caller could not have sized (n_rows > 2^31 or
+ * tail_len n_rows > 2^31: call with fewer rows), a NULL required pointer (lam may be NULL when tail_len = 0), a pointer that is
+ * not 8-byte aligned.  tail_len = 0 is valid: every row has L = 0. */
+int64_t l2hmc_psis_plan(int64_t n_rows, int64_t tail_len, int32_t what);
+int64_t l2hmc_psis_workspace_bytes(int64_t n_rows, int64_t tail_len);
+int l2hmc_psis_smooth(const double* lam, const int64_t* n_tail, const double* lam_cutoff, int64_t n_rows, int64_t tail_len,
+                      double* out /* (3, n_rows) */, double* weights /* (n_rows, tail_len) or NULL */, void* workspace,
+                      void* stream);
+
 /* The raw first and second moments of a recorded history X (steps, N, d) kept on the device (csrc/moment_sums.hip): what the
  * posterior covariance and the multivariate effective sample size of Vats, Flegal & Jones (2019) are made of
  * (l2hmc_amd/multivariate.py `finish` turns them into numbers on the host, and ranks that hold different chains add them).

@@ -244,11 +244,12 @@ class LogisticRegression(object):
         from . import predictive
         return predictive.waic(draws, self.X, self.y)
 
-    def loo(self, draws):
+    def loo(self, draws, finish="torch"):
         """PSIS-LOO of this model's own data under the draws (`predictive.loo`): a `Summary` with elpd_loo, p_loo, looic, se,
-        the per-row Pareto `khat` and `n_bad`, the number of rows where it exceeds 0.7."""
+        the per-row Pareto `khat` and `n_bad`, the number of rows where it exceeds 0.7.  `finish="kernel"`: the Pareto fit on
+        the fused kernels of csrc/psis.hip (device draws only)."""
         from . import predictive
-        return predictive.loo(draws, self.X, self.y)
+        return predictive.loo(draws, self.X, self.y, finish=finish)
 
 
 def as_device_f32(x, device=None):

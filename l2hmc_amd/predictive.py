@@ -39,6 +39,7 @@ draws outside the tail of e^m + e^(m - t), m = min(cutoff, 0).  A ROCm tensor of
 reproducible) and the dict holds device tensors; numpy or a CPU tensor is float64 numpy.  `loo_finish` fits the generalised
 Pareto distribution to every tail (Zhang & Stephens 2009 with the prior of `loo`), smooths the tail weights and forms elpd_loo_i
 in float64 where the tails lie: torch on the device in row chunks of bounded memory, numpy on the host.
+`finish="kernel"` (opt-in, device tails only) fits and smooths on the fused float64 kernels of csrc/psis.hip instead (`psis.py`).
 """
 import numpy as np
 
@@ -354,40 +355,51 @@ class _Torch:
         return a.cpu().numpy()
 
 
-def _loo_rows(xp, cutoff, n_tail, tail, body, sum_lik, S, M):
-    """(khat, elpd_loo_i, lppd_i) of a chunk of rows, float64, over the operations of `xp` alone.  The tail is sorted so that
-    t ascends: slot s < L holds the ratio of ascending rank j = L - s, and slot 0 the largest."""
+def _softplus_neg(xp, v):
+    """softplus(-v) = log(1 + e^-v)"""
+    return xp.maximum(-v, v * 0.0) + xp.log1p(xp.exp(-xp.maximum(v, -v)))
+
+
+def _lse(xp, a, zero):
+    """logsumexp over the last axis; -inf when empty"""
+    mx = xp.max(a)
+    mx = xp.where(xp.isfinite(mx), mx, xp.where(xp.isnan(mx), mx, zero))              # centre: 0 for an empty (-inf) row
+    return mx + xp.log(xp.sum(xp.exp(a - mx[..., None])))
+
+
+def _logaddexp(xp, a, b, zero):
+    """logaddexp of two (rows,) arrays"""
+    mx = xp.maximum(a, b)
+    mx = xp.where(xp.isfinite(mx), mx, xp.where(xp.isnan(mx), mx, zero))
+    return mx + xp.log(xp.exp(a - mx) + xp.exp(b - mx))
+
+
+def _loo_prepare(xp, cutoff, n_tail, tail):
+    """The first seam of `_loo_rows`: (c, L, lam_c, lam) float64 of a chunk of rows -- the tail sorted so that t ascends (the
+    +inf pads last), lam = softplus(-t) descending with 0 in the pads."""
     c, Lf = xp.f64(cutoff), xp.f64(n_tail)
     t = xp.sort(xp.f64(tail))                                                      # the +inf pads last
+    return c, Lf, _softplus_neg(xp, c), _softplus_neg(xp, t)
+
+
+def _psis_rows(xp, lam, Lf, lam_c, M):
+    """The middle of `_loo_rows`, and the host form of `psis.smooth_tails` (csrc/psis.hip restates it formula for formula):
+    (khat, lam_max, lse_w, lse_wl, omega, live) of a chunk of rows whose (rows, M) log ratios `lam` descend over the L live
+    slots; slot s < L holds the ratio of ascending rank j = L - s.  khat is the fitted shape or +inf where nothing was
+    smoothed; omega (rows, M) is meaningful in the live slots only."""
     zero = Lf * 0.0
-    slot = xp.arange(M, c)
+    slot = xp.arange(M, Lf)
     zeros = zero[:, None] + slot[None, :] * 0.0                                    # (rows, M)
     minus_inf = zeros - float("inf")
-
-    def softplus_neg(v):                                                           # softplus(-v) = log(1 + e^-v)
-        return xp.maximum(-v, v * 0.0) + xp.log1p(xp.exp(-xp.maximum(v, -v)))
-
-    def lse(a):                                                                    # logsumexp over the last axis; -inf when empty
-        mx = xp.max(a)
-        mx = xp.where(xp.isfinite(mx), mx, xp.where(xp.isnan(mx), mx, zero))          # centre: 0 for an empty (-inf) row
-        return mx + xp.log(xp.sum(xp.exp(a - mx[..., None])))
-
-    def add(a, b):                                                                 # logaddexp of two (rows,) arrays
-        mx = xp.maximum(a, b)
-        mx = xp.where(xp.isfinite(mx), mx, xp.where(xp.isnan(mx), mx, zero))
-        return mx + xp.log(xp.exp(a - mx) + xp.exp(b - mx))
-
     live = slot[None, :] < Lf[:, None]
     j = Lf[:, None] - slot[None, :]                                                # ascending rank of the ratio, 1 .. L
-    lam_c = softplus_neg(c)
-    lam = softplus_neg(t)                                                          # 0 in the pads
     lam_max = xp.where(Lf > 0, lam[:, 0], lam_c) if M else lam_c
     floor_c = xp.exp(lam_c - lam_max)                                              # the cutoff's ratio over the largest one
     x = xp.where(live, xp.exp(lam - lam_max[:, None]) - floor_c[:, None], zeros)
     fit = Lf >= MIN_TAIL_FIT
     Ls = xp.where(fit, Lf, zero + MIN_TAIL_FIT)                                    # (a placeholder length where nothing is fitted)
     # Zhang & Stephens (2009) with the prior of `loo`: the profile likelihood on a grid of theta, theta's posterior mean
-    jt = xp.arange(30 + int(np.floor(np.sqrt(max(M, 1)))), c) + 1.0
+    jt = xp.arange(30 + int(np.floor(np.sqrt(max(M, 1)))), Lf) + 1.0
     m_theta = 30.0 + xp.floor(xp.sqrt(Ls))
     on_grid = jt[None, :] <= m_theta[:, None]
     if M:
@@ -398,7 +410,7 @@ def _loo_rows(xp, cutoff, n_tail, tail, body, sum_lik, S, M):
     theta = 1.0 / x_top[:, None] + (1.0 - xp.sqrt(m_theta[:, None] / (jt[None, :] - 0.5))) / (3.0 * x_star[:, None])
     kj = xp.sum(xp.where(live[:, None, :], xp.log1p(-theta[:, :, None] * x[:, None, :]), zeros[:, None, :])) / Ls[:, None]
     ell = xp.where(on_grid, Ls[:, None] * (xp.log(-theta / kj) - kj - 1.0), theta * 0.0 - float("inf"))
-    wj = xp.exp(ell - lse(ell)[:, None])                                           # = 1 / sum_j' exp(ell_j' - ell_j)
+    wj = xp.exp(ell - _lse(xp, ell, zero)[:, None])                                # = 1 / sum_j' exp(ell_j' - ell_j)
     theta_hat = xp.sum(xp.where(on_grid, theta * wj, theta * 0.0))
     k = xp.sum(xp.where(live, xp.log1p(-theta_hat[:, None] * x), zeros)) / Ls
     sigma = -k / theta_hat
@@ -408,13 +420,30 @@ def _loo_rows(xp, cutoff, n_tail, tail, body, sum_lik, S, M):
     ks = xp.where(smooth & (k != 0.0), k, zero + 1.0)[:, None]
     qj = xp.where((k == 0.0)[:, None], -sigma[:, None] * lp, sigma[:, None] * xp.expm1(-ks * lp) / ks)
     omega = xp.where(smooth[:, None], xp.minimum(xp.log(qj + floor_c[:, None]), zeros), lam - lam_max[:, None])
-    m = xp.minimum(xp.where(xp.isnan(c), zero, c), zero)
-    num = add(xp.log(S - Lf) - lam_max, lse(xp.where(live, omega - lam, minus_inf)))
-    den = add(xp.log(xp.f64(body)) - m - lam_max, lse(xp.where(live, omega, minus_inf)))
-    elpd = num - den
+    lse_wl = _lse(xp, xp.where(live, omega - lam, minus_inf), zero)
+    lse_w = _lse(xp, xp.where(live, omega, minus_inf), zero)
     khat = xp.where(smooth, k, zero + float("inf"))
+    return khat, lam_max, lse_w, lse_wl, omega, live
+
+
+def _loo_combine(xp, khat, lam_max, lse_w, lse_wl, c, Lf, body, sum_lik, S):
+    """The last seam of `_loo_rows`: the O(rows) numbers into (khat, elpd_loo_i, lppd_i)."""
+    zero = Lf * 0.0
+    m = xp.minimum(xp.where(xp.isnan(c), zero, c), zero)
+    num = _logaddexp(xp, xp.log(S - Lf) - lam_max, lse_wl, zero)
+    den = _logaddexp(xp, xp.log(xp.f64(body)) - m - lam_max, lse_w, zero)
+    elpd = num - den
     khat = xp.where(xp.isnan(elpd), elpd, khat)                                    # a NaN draw makes the row NaN, quietly
     return khat, elpd, xp.log(xp.f64(sum_lik) / S)
+
+
+def _loo_rows(xp, cutoff, n_tail, tail, body, sum_lik, S, M):
+    """(khat, elpd_loo_i, lppd_i) of a chunk of rows, float64, over the operations of `xp` alone: prepare lam / fit and smooth
+    / combine.  The tail is sorted so that t ascends: slot s < L holds the ratio of ascending rank j = L - s, and slot 0 the
+    largest."""
+    c, Lf, lam_c, lam = _loo_prepare(xp, cutoff, n_tail, tail)
+    khat, lam_max, lse_w, lse_wl, _, _ = _psis_rows(xp, lam, Lf, lam_c, M)
+    return _loo_combine(xp, khat, lam_max, lse_w, lse_wl, c, Lf, body, sum_lik, S)
 
 
 def _loo_summary(khat, elpd_i, lppd_i, n_tail, S, M):
@@ -451,23 +480,62 @@ def _finish_rows(tails):
     return tuple(np.concatenate(o) for o in out) + (np.asarray(xp.host(arrays[1]), dtype=np.int64),)
 
 
-def loo_finish(tails):
+def _check_finish(finish, on_device):
+    if finish not in ("torch", "kernel"):
+        raise ValueError('finish is "torch" or "kernel" (got %r)' % (finish,))
+    if finish == "kernel" and not on_device:
+        raise ValueError('finish="kernel" runs the Pareto fit of csrc/psis.hip where the tails lie, on a ROCm device; these are '
+                         'host data (numpy or a CPU tensor), which float64 numpy finishes: leave finish="torch"')
+
+
+_KERNEL_FINISH_BYTES = 1 << 28  # the float64 (rows, M) log ratios formed at a time by the kernel finish
+
+
+def _finish_rows_kernel(tails):
+    """`_finish_rows` of device tails with the middle on csrc/psis.hip: `torch.sort` of the float32 tail, lam = softplus(-t) in
+    float64 torch, `psis.smooth_tails`, and the O(n) combine of `_loo_rows` -- in row chunks of bounded memory, whose bits do
+    not depend on the chunking."""
+    from .psis import smooth_tails
+    S, M = int(tails["n_draws"]), int(tails["tail_len"])
+    if S < 2:
+        raise ValueError("PSIS-LOO needs >= 2 draws (got %d)" % S)
+    xp = _Torch()
+    arrays = [tails[k] for k in ("cutoff", "n_tail", "tail", "body", "sum_lik")]
+    n = int(arrays[0].shape[0])
+    rows = max(1, _KERNEL_FINISH_BYTES // (8 * max(M, 1)))
+    out = [[], [], []]
+    for a in range(0, n, rows):
+        cutoff, n_tail, tail, body, sum_lik = (v[a:a + rows] for v in arrays)
+        c, Lf, lam_c, lam = _loo_prepare(xp, cutoff, n_tail, tail)
+        khat, lse_w, lse_wl = smooth_tails(lam, n_tail, lam_c)
+        lam_max = xp.where(Lf > 0, lam[:, 0], lam_c) if M else lam_c
+        for o, r in zip(out, _loo_combine(xp, khat, lam_max, lse_w, lse_wl, c, Lf, body, sum_lik, S)):
+            o.append(xp.host(r))
+    return tuple(np.concatenate(o) for o in out) + (np.asarray(xp.host(arrays[1]), dtype=np.int64),)
+
+
+def loo_finish(tails, finish="torch"):
     """The `Summary` of `loo_tails`' result: per row `elpd_loo_i`, `p_loo_i`, `lppd_i`, `khat`, `n_tail`; the totals `elpd_loo`,
     `p_loo`, `lppd`, `looic` = -2 elpd_loo, `se` = sqrt(n var_i elpd_loo_i) (NaN for one row); `khat_threshold` =
     min(1 - 1 / log10 S, 0.7), `n_bad` = #{khat > 0.7}, `n_above_threshold`; `tail_len`, `n_draws`, `n_rows`, `n_underflow`.
-    A tail shorter than 5 (or a fit that is not finite) is not smoothed and has khat = +inf."""
-    khat, elpd_i, lppd_i, n_tail = _finish_rows(tails)
+    A tail shorter than 5 (or a fit that is not finite) is not smoothed and has khat = +inf.  `finish="kernel"` (device tails
+    only; opt-in) fits and smooths on the fused float64 kernels of csrc/psis.hip instead of chunked torch: the same formulas,
+    another summation order."""
+    _check_finish(finish, is_device_tensor(tails["tail"]))
+    khat, elpd_i, lppd_i, n_tail = (_finish_rows_kernel if finish == "kernel" else _finish_rows)(tails)
     return _loo_summary(khat, elpd_i, lppd_i, n_tail, int(tails["n_draws"]), int(tails["tail_len"]))
 
 
-def loo(draws, X, y, max_tail_bytes=256 << 20):
+def loo(draws, X, y, max_tail_bytes=256 << 20, finish="torch"):
     """PSIS-LOO of the logistic regression (X, y) under the posterior draws: `loo_finish(loo_tails(draws, X, y))`, except that
     on the device every group of rows is finished before the next one's tails are formed, so that no more than
     `max_tail_bytes` of tails exist at a time.  Compare two models on the same rows by `elpd_loo` (higher is better) against
-    `se`; rows with khat > 0.7 (`n_bad`) are where the estimate cannot be trusted."""
+    `se`; rows with khat > 0.7 (`n_bad`) are where the estimate cannot be trusted.  `finish`: see `loo_finish`."""
     S, d, n = _check_loo(draws, X, y)
+    _check_finish(finish, is_device_tensor(draws))
     if not is_device_tensor(draws):
         return loo_finish(_host_tails(draws, X, y, S, d, n))
-    parts = [_finish_rows(g) for g in _device_tail_groups(draws, X, y, S, d, n, max_tail_bytes)]
+    rows_of = _finish_rows_kernel if finish == "kernel" else _finish_rows
+    parts = [rows_of(g) for g in _device_tail_groups(draws, X, y, S, d, n, max_tail_bytes)]
     khat, elpd_i, lppd_i, n_tail = (np.concatenate([p[k] for p in parts]) for k in range(4))
     return _loo_summary(khat, elpd_i, lppd_i, n_tail, S, loo_tail_len(S))
