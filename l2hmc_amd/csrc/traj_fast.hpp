@@ -83,18 +83,20 @@ __device__ __forceinline__ h2v lo_pair16(h2v h, float a0, float a1) {
 // float4 instead of eight, but no instruction waits for its neighbour's half of a register: measured faster where one wave owns
 // its SIMD (traj_fast_kernel: 20.4 against 20.7 us per proposal at 4096 chains, 31.5 against 32.3 at 8192;
 // profiles/r06_f16x2.txt).  LAT = false: v_fma_mixlo_f16 + v_fma_mixhi_f16 write the two halves of the pair in place.
-template <bool LAT>
+// W0 = true: the caller's a.w is a literal +0 (the dead fourth hidden unit of a KH = 3 tail).  Its residual f16(0 - 64 * 0) is
+// +0 as well, but the compiler cannot see through the asm: it is written as the constant, one instruction less per split.
+template <bool LAT, bool W0 = false>
 __device__ __forceinline__ h8v split16(f4 a) {
   const f4 ad = a * (1.f / L2HMC_F16_SCALE);
   const h2v h01 = cvt_pk16(ad.x, ad.y), h23 = cvt_pk16(ad.z, ad.w);
   h2v l01, l23;
   if constexpr (LAT) {
-    float r0, r1, r2, r3;
+    float r0, r1, r2, r3 = 0.f;
     const float ns = -L2HMC_F16_SCALE;
     asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(r0) : "v"(h01), "s"(ns), "v"(a.x));
     asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r1) : "v"(h01), "s"(ns), "v"(a.y));
     asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(r2) : "v"(h23), "s"(ns), "v"(a.z));
-    asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r3) : "v"(h23), "s"(ns), "v"(a.w));
+    if constexpr (!W0) asm("v_fma_mix_f32 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(r3) : "v"(h23), "s"(ns), "v"(a.w));
     l01 = cvt_pk16(r0, r1);
     l23 = cvt_pk16(r2, r3);
   } else {
@@ -257,11 +259,11 @@ __device__ __forceinline__ void tail_fast(const TailK<DT, true>& tk, f4 hs_, F&&
 #pragma unroll
   for (int r = 0; r < KH; ++r) h[r] = relu_i(hs_[r]);
   {
-    const f4 acc = mfma16x2(tk.w2, split16<L2HMC_FAST_SPLIT_LAT_TAIL>(h), splat(0.f));
+    const f4 acc = mfma16x2(tk.w2, split16<L2HMC_FAST_SPLIT_LAT_TAIL, KH == 3>(h), splat(0.f));
 #pragma unroll
     for (int r = 0; r < KH; ++r) h[r] = relu_i(acc[r]);
   }
-  const h8v b = split16<L2HMC_FAST_SPLIT_LAT_TAIL>(h);
+  const h8v b = split16<L2HMC_FAST_SPLIT_LAT_TAIL, KH == 3>(h);
 #pragma unroll
   for (int t = 0; t < DT; ++t) {
     f4 zs = __builtin_amdgcn_mfma_f32_16x16x32_f16(tk.hs[t].a1, b, splat(0.f), 0, 0, 0);
@@ -289,7 +291,7 @@ __device__ __forceinline__ void tail_fast2(const TailK<DT, true>& tk, f4 hsa, f4
 #pragma unroll
   for (int r = 0; r < KH; ++r) { ha[r] = relu_i(hsa[r]); hb[r] = relu_i(hsb[r]); }
   {
-    const h8v sa = split16<L2HMC_FAST_SPLIT_LAT_PAIR>(ha), sb = split16<L2HMC_FAST_SPLIT_LAT_PAIR>(hb);
+    const h8v sa = split16<L2HMC_FAST_SPLIT_LAT_PAIR, KH == 3>(ha), sb = split16<L2HMC_FAST_SPLIT_LAT_PAIR, KH == 3>(hb);
     f4 acca = __builtin_amdgcn_mfma_f32_16x16x32_f16(tk.w2.a1, sa, splat(0.f), 0, 0, 0);
     f4 accb = __builtin_amdgcn_mfma_f32_16x16x32_f16(tk.w2.a1, sb, splat(0.f), 0, 0, 0);
     acca = __builtin_amdgcn_mfma_f32_16x16x32_f16(tk.w2.a2, sa, acca, 0, 0, 0);
@@ -297,7 +299,7 @@ __device__ __forceinline__ void tail_fast2(const TailK<DT, true>& tk, f4 hsa, f4
 #pragma unroll
     for (int r = 0; r < KH; ++r) { ha[r] = relu_i(acca[r]); hb[r] = relu_i(accb[r]); }
   }
-  const h8v ba = split16<L2HMC_FAST_SPLIT_LAT_PAIR>(ha), bb = split16<L2HMC_FAST_SPLIT_LAT_PAIR>(hb);
+  const h8v ba = split16<L2HMC_FAST_SPLIT_LAT_PAIR, KH == 3>(ha), bb = split16<L2HMC_FAST_SPLIT_LAT_PAIR, KH == 3>(hb);
 #pragma unroll
   for (int t = 0; t < DT; ++t) {
     f4 zsa = __builtin_amdgcn_mfma_f32_16x16x32_f16(tk.hs[t].a1, ba, splat(0.f), 0, 0, 0);
@@ -338,6 +340,13 @@ __device__ __forceinline__ f4 l1_part16(const f4 (&z)[DT], f4 acc, const WF16* W
 }
 
 // PK: 0 = f32-input MFMA (v_mfma_f32_16x16x4_f32), 1 = f16x2 (above)
+// CC: the body compiled for the sampler's common launch -- all three draws in-kernel, p_out + x_next and no other output.  What
+// a launch draws and writes is launch-uniform, but the general body tests it lane by lane at every proposal boundary; with CC
+// those tests are constants (traj_fast_kernel below picks the body by one uniform branch at entry).  The same statements either
+// way: the same bits.
+template <int EK, int DT, int NW, int KH, int PK, bool CC>
+__device__ __forceinline__ void traj_fast_body(const KArgs& A);
+
 template <int EK, int DT, int NW, int KH, int PK = 0>
 #ifndef L2HMC_FAST_WAVES
 #define L2HMC_FAST_WAVES 2
@@ -353,6 +362,21 @@ template <int EK, int DT, int NW, int KH, int PK = 0>
 #define L2HMC_FAST_WAVES_DT2 1
 #endif
 __global__ __launch_bounds__(64 * NW, (DT >= 2 && PK == 1) ? L2HMC_FAST_WAVES_DT2 : L2HMC_FAST_WAVES) void traj_fast_kernel(const KArgs A) {
+  // (the diagonal Gaussian's one-tile f16x2 kernels: the bench workload and its relatives.  Not Rough Well's: its body spills
+  //  under the two-wave bound as it is, and a second copy raised that)
+  if constexpr (EK == L2HMC_ENERGY_GAUSS_DIAG && DT == 1 && PK == 1) {
+    const bool common = (A.rng_flags & (L2HMC_RNG_V | L2HMC_RNG_DIR | L2HMC_RNG_U)) == (L2HMC_RNG_V | L2HMC_RNG_DIR | L2HMC_RNG_U) &&
+                        A.p_out != nullptr && A.x_next != nullptr && A.x_hist == nullptr && A.logjac_out == nullptr &&
+                        A.x_out == nullptr && A.v_out == nullptr;
+    if (common) traj_fast_body<EK, DT, NW, KH, PK, true>(A);
+    else traj_fast_body<EK, DT, NW, KH, PK, false>(A);
+  } else {
+    traj_fast_body<EK, DT, NW, KH, PK, false>(A);
+  }
+}
+
+template <int EK, int DT, int NW, int KH, int PK, bool CC>
+__device__ __forceinline__ void traj_fast_body(const KArgs& A) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   lds_poison(smem);
   static_assert(DT <= 2, "the fast kernel keeps layer-1 and tail fragments in registers");
@@ -371,6 +395,12 @@ __global__ __launch_bounds__(64 * NW, (DT >= 2 && PK == 1) ? L2HMC_FAST_WAVES_DT
             RECD = fast_rec_dir(NTp, A.T);
 
   // ---- prologue: stage the tail fragments (scaled), the constant tables and the schedule records ----
+  // (the state and the register-resident layer-1 fragments are asked for first: global loads that nothing below depends on, in flight
+  //  beside the staging instead of a round trip of their own behind the barrier)
+  f4 x[DT], v[DT], g[DT];
+  load_state<DT, NW>(A.x, A, chain, live, w, q, x);
+  L1W<DT> l1w;
+  load_l1w<DT, NW>(l1w, A.packed, A.packed + NF, A, w, lane);
   {
     // (eight loads in flight per thread: one element per trip, each waited for before the next, made the prologue ~7 us)
     constexpr int GN = 3 * NTp + 1;                 // groups per net: W4, then (S, T, Q) per dimension tile
@@ -415,23 +445,55 @@ __global__ __launch_bounds__(64 * NW, (DT >= 2 && PK == 1) ? L2HMC_FAST_WAVES_DT
     fc[2 * DPp + dim] = cq;
     fc[3 * DPp + dim] = cq + log2f(epn);
   }
-#pragma unroll 4
-  for (int i = tid; i < 2 * A.T * R; i += nthr) {      // (branch-free body: clamped loads, so that unrolled trips overlap)
-    const int dr = i / (A.T * R), r = (i / R) % A.T, j = i % R;
-    const bool tb = j < 32;
-    const int net = tb ? j >> 4 : 0, u = j & 15, dim = tb ? 0 : j - 32;
-    const float* tf = A.packed + (size_t)net * NF + (2 * NT * 64) * 4;
-    const float a0 = tf[u * 4], a1 = tf[(16 + u) * 4], a2 = tf[(32 + u) * 4], c0 = A.trig[2 * r], c1 = A.trig[2 * r + 1];
-    const float mk = A.masks[r * A.d + (dim < A.d ? dim : 0)];
-    const float m = dim < A.d ? mk : 0.f;
-    // time / bias row, or the mask row: forward keeps m first, backward keeps 1 - m first
-    smem[A.o_rec + dr * RECD + (r + 1) * R + j] = tb ? fmaf(a0, c0, fmaf(a1, c1, a2)) : (dr ? m : 1.f - m);
+  // The schedule records, both directions' tables from one evaluation, four elements' loads in flight per thread before the first
+  // is waited for.  (One loop over all 2 T R elements with a select between the two kinds became a divergent branch with a
+  // load-and-wait on either side in every trip: some sixteen dependent global round trips, most of the prologue's time.)
+  constexpr int SU = 4;
+  {      // time / bias rows: the same for both directions
+    const int nA = A.T * 32;
+    for (int i0 = tid; i0 < nA; i0 += SU * nthr) {
+      float a0[SU], a1[SU], a2[SU], c0[SU], c1[SU];
+#pragma unroll
+      for (int s = 0; s < SU; ++s) {
+        const int i = min(i0 + s * nthr, nA - 1), r = i >> 5, net = (i >> 4) & 1, u = i & 15;
+        const float* tf = A.packed + (size_t)net * NF + (2 * NT * 64) * 4;
+        a0[s] = tf[u * 4], a1[s] = tf[(16 + u) * 4], a2[s] = tf[(32 + u) * 4], c0[s] = A.trig[2 * r], c1[s] = A.trig[2 * r + 1];
+      }
+#pragma unroll
+      for (int s = 0; s < SU; ++s) {
+        const int i = i0 + s * nthr, r = i >> 5, j = i & 31;
+        if (i < nA) {
+          const float tbr = fmaf(a0[s], c0[s], fmaf(a1[s], c1[s], a2[s]));
+          smem[A.o_rec + (r + 1) * R + j] = tbr;
+          smem[A.o_rec + RECD + (r + 1) * R + j] = tbr;
+        }
+      }
+    }
+  }
+  {      // mask rows: forward keeps m first, backward keeps 1 - m first
+    constexpr int W16 = 16 * NTp;
+    const int nB = A.T * W16;
+    for (int i0 = tid; i0 < nB; i0 += SU * nthr) {
+      float mk[SU];
+#pragma unroll
+      for (int s = 0; s < SU; ++s) {
+        const int i = min(i0 + s * nthr, nB - 1), r = i / W16, dim = i % W16;
+        mk[s] = A.masks[r * A.d + (dim < A.d ? dim : 0)];
+      }
+#pragma unroll
+      for (int s = 0; s < SU; ++s) {
+        const int i = i0 + s * nthr, r = i / W16, dim = i % W16;
+        if (i < nB) {
+          const float m = dim < A.d ? mk[s] : 0.f;
+          smem[A.o_rec + (r + 1) * R + 32 + dim] = 1.f - m;
+          smem[A.o_rec + RECD + (r + 1) * R + 32 + dim] = m;
+        }
+      }
+    }
   }
   stage_energy<EK, false>(A, smem, tid, nthr);
 
-  f4 x[DT], v[DT], g[DT];
-  load_state<DT, NW>(A.x, A, chain, live, w, q, x);
-  const bool need_p = A.p_out != nullptr || A.x_next != nullptr || A.u != nullptr ||
+  const bool need_p = CC || A.p_out != nullptr || A.x_next != nullptr || A.u != nullptr ||
                       (A.rng_flags & L2HMC_RNG_U) != 0;
   __syncthreads();
 
@@ -464,8 +526,6 @@ __global__ __launch_bounds__(64 * NW, (DT >= 2 && PK == 1) ? L2HMC_FAST_WAVES_DT
   grad(x, g, U_start, need_p);
   if constexpr (EK == L2HMC_ENERGY_GAUSS_DIAG) U_start = diag_U(x, g);
 
-  L1W<DT> l1w;
-  load_l1w<DT, NW>(l1w, A.packed, A.packed + NF, A, w, lane);
   TailK<DT, F16> tk;
   f4 pv[1];
   // VNet layer 1 at (x, grad U(x)).  Diagonal Gaussian: grad U = P (x - mu) is linear in x, so
@@ -493,8 +553,10 @@ __global__ __launch_bounds__(64 * NW, (DT >= 2 && PK == 1) ? L2HMC_FAST_WAVES_DT
     }
     cv[0] = l1_part<DT, NW>(nullptr, NT, A, w, lane, pm, Z, l1w.vb);
     xchg<NW, 1>(cv, A, smem, w, lane, pb);
-    if (w == 0 && c == 0) {
-      for (int i = 0; i < 2 * A.T; ++i) {
+    // (every column of the tile holds the same cv: lane (c, q) of wave 0 folds it into rows c, c + 16, ... -- one addition per
+    //  row as before, two trips instead of 2 T)
+    if (w == 0) {
+      for (int i = c; i < 2 * A.T; i += 16) {
         float* tb = smem + A.o_rec + (i / A.T) * RECD + (i % A.T + 1) * R + 16 + 4 * q;
         *reinterpret_cast<f4*>(tb) = lds4(tb) + cv[0];
       }
@@ -519,13 +581,13 @@ __global__ __launch_bounds__(64 * NW, (DT >= 2 && PK == 1) ? L2HMC_FAST_WAVES_DT
 
   // ---- persistent sampler loop (as traj_kernel) ------------------------------------------------------
   const long long gchain = A.chain_off + chain;
-  const bool rng_v = (A.rng_flags & L2HMC_RNG_V) != 0, rng_d = (A.rng_flags & L2HMC_RNG_DIR) != 0;
-  const bool rng_u = (A.rng_flags & L2HMC_RNG_U) != 0;
+  const bool rng_v = CC || (A.rng_flags & L2HMC_RNG_V) != 0, rng_d = CC || (A.rng_flags & L2HMC_RNG_DIR) != 0;
+  const bool rng_u = CC || (A.rng_flags & L2HMC_RNG_U) != 0;
   f4 vn[DT];
   if (!rng_v) load_state<DT, NW>(A.v, A, chain, live, w, q, vn);
   bool fwd_n = (A.dir != nullptr && !rng_d) ? (live ? A.dir[chain] != 0 : true) : (A.dir_all != 0);
   float u_n = (A.u != nullptr && !rng_u && live) ? A.u[chain] : 0.f;
-  const bool have_u = A.u != nullptr || rng_u;
+  const bool have_u = CC || A.u != nullptr || rng_u;
   for (int m = 0; m < A.M; ++m) {
     const long long moff = (long long)m * A.N;
     const unsigned long long prop = A.rng_prop0 + (unsigned long long)m;
@@ -585,6 +647,9 @@ __global__ __launch_bounds__(64 * NW, (DT >= 2 && PK == 1) ? L2HMC_FAST_WAVES_DT
     // proposal beside VNet's (44 VGPRs per net as f16x2) instead of being re-read from LDS twice per step -- 22 of a step's 37
     // ds_read_b128: ICG-50 20.4 -> 19.4-19.6 us per proposal at 4096 chains, 31.3 -> 30.0 at 8192 (251 VGPRs, no scratch).  Not for
     // the f32-input form of DT = 2, which spills under the two-wave bound already.  Same values, same arithmetic: same bits.
+    // (Measured and not kept, profiles/sampler_invariant_work.txt: loading everything but the direction's cS row once per launch, in
+    //  front of the proposal loop -- 20 ds_read_b128 fewer per proposal, and 0.7 % SLOWER at 4096 chains: the registers stay live
+    //  through the epilogue and the allocator's choices in the step loop change.)
     constexpr bool RT = DT == 1 || PK == 1;
     TailK<DT, F16> tkx;
     if constexpr (RT) load_tailk<DT>(tkx, fwx, fcx, dofs, NTp, w, lane);
@@ -604,7 +669,9 @@ __global__ __launch_bounds__(64 * NW, (DT >= 2 && PK == 1) ? L2HMC_FAST_WAVES_DT
     if constexpr (PAIR) {
       tail_fast<DT, KH>(tk, pv[0] + tbv, [&](int t, f4 aS, f4 T, f4 EQ) { aS_n[t] = aS; T_n[t] = T; EQ_n[t] = EQ; });
     }
-    for (int it = 0; it < A.n_steps; ++it) {
+    // one leapfrog step.  LAST (paired tails only): a proposal's last step, which has no next step to look ahead to
+    auto step = [&](auto LASTC, bool wantU) {
+      constexpr bool LAST = decltype(LASTC)::value;
       f4 k1[DT], vh[DT], y[DT], xin[DT];
       const f4 tbx = lds4(rec);
 #pragma unroll
@@ -670,7 +737,7 @@ __global__ __launch_bounds__(64 * NW, (DT >= 2 && PK == 1) ? L2HMC_FAST_WAVES_DT
 
       // ---- momentum half-update #2 at the new position  (:147-153 / :192-199)
       if constexpr (!RT) load_tailk<DT>(tk, fwv, fcv, dofs, NTp, w, lane);
-      grad(x, g, red[2], need_p && it == A.n_steps - 1);
+      grad(x, g, red[2], wantU);
       pv[0] = vnet_l1(x, g);
       PT_MARK(9);  // grad U + VNet layer-1 partials
       xchg<NW, 1>(pv, A, smem, w, lane, pb);
@@ -682,12 +749,25 @@ __global__ __launch_bounds__(64 * NW, (DT >= 2 && PK == 1) ? L2HMC_FAST_WAVES_DT
         v[t] = ES * (nf * tr + vh[t]) + ff * tr;
       };
       if constexpr (PAIR) {
-        tail_fast2<DT, KH>(tk, pv[0] + tbv, pv[0] + tbv_n, vhalf2, [&](int t, f4 aS, f4 T, f4 EQ) { aS_n[t] = aS; T_n[t] = T; EQ_n[t] = EQ; });
+        // (the last step takes the single tail: the same operations on the evaluation that is kept, none on one that is dropped)
+        if constexpr (!LAST) {
+          tail_fast2<DT, KH>(tk, pv[0] + tbv, pv[0] + tbv_n, vhalf2, [&](int t, f4 aS, f4 T, f4 EQ) { aS_n[t] = aS; T_n[t] = T; EQ_n[t] = EQ; });
+        } else {
+          tail_fast<DT, KH>(tk, pv[0] + tbv, vhalf2);
+        }
       } else {
         tail_fast<DT, KH>(tk, pv[0] + tbv, vhalf2);
       }
       PT_MARK(11); // VNet tail #2
       tbv = tbv_n;
+    };
+    // the last step peeled: no test inside the step loop.  (Diagonal Gaussian only: Rough Well's kernels spill under the two-wave
+    // bound as they are -- they hold the start point's gradient -- and the second copy of the step raised that by 24 bytes per lane.)
+    if constexpr (PAIR && EK == L2HMC_ENERGY_GAUSS_DIAG) {
+      for (int it = 0; it + 1 < A.n_steps; ++it) step(std::false_type{}, false);
+      if (A.n_steps > 0) step(std::true_type{}, need_p);
+    } else {
+      for (int it = 0; it < A.n_steps; ++it) step(std::false_type{}, need_p && it == A.n_steps - 1);
     }
     if constexpr (EK == L2HMC_ENERGY_GAUSS_DIAG) red[2] = diag_U(x, g);
     const float ld = hsum(ldv) * 0.6931471805599453f;   // the log-det was accumulated in log2 units
@@ -713,16 +793,16 @@ __global__ __launch_bounds__(64 * NW, (DT >= 2 && PK == 1) ? L2HMC_FAST_WAVES_DT
         red[4] = qnan;
       }
     }
-    if (last) {
+    if (!CC && last) {
       store_state<DT, NW>(A.x_out, A, chain, live, w, q, x);
       store_state<DT, NW>(A.v_out, A, chain, live, w, q, v);
     }
     const bool writer = live && w == 0 && lane < 16;
-    if (A.logjac_out != nullptr && writer) A.logjac_out[moff + chain] = red[4];
+    if (!CC && A.logjac_out != nullptr && writer) A.logjac_out[moff + chain] = red[4];
     if (need_p) {
       const float val = (red[0] + red[1]) - (red[2] + red[3]) + red[4];       // dynamics.py:302-309
       const float p = accept_prob(val);
-      if (A.p_out != nullptr && writer) A.p_out[moff + chain] = p;
+      if ((CC || A.p_out != nullptr) && writer) A.p_out[moff + chain] = p;
       if (have_u) {
         const bool acc = live && (p - u_m) >= 0.f;                            // sampler.py:53-55
 #pragma unroll
@@ -739,7 +819,7 @@ __global__ __launch_bounds__(64 * NW, (DT >= 2 && PK == 1) ? L2HMC_FAST_WAVES_DT
     } else {
       U_start = U_end;
     }
-    if (A.x_hist != nullptr) store_state<DT, NW>(A.x_hist + moff * A.d, A, chain, live, w, q, x);
+    if (!CC && A.x_hist != nullptr) store_state<DT, NW>(A.x_hist + moff * A.d, A, chain, live, w, q, x);
   }  // proposals
   PT_FLUSH(w, lane);
   store_state<DT, NW>(A.x_next, A, chain, live, w, q, x);
