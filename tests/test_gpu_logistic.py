@@ -209,22 +209,11 @@ def test_swap_counters_and_round_trips_match_the_reference():
     x0 = to_dev((0.3 * np.random.RandomState(2).randn(K * nl, d)).astype(np.float32))
     o = pt.run(x0, R, M, record_rungs=True, record_states=True)
     x_hist = o["x_hist"]
-    rh = to_np(o["rung_hist"]).astype(np.int64)
     t32 = np.asarray(temps, np.float32).astype(np.float64)
-    prev, trip = np.tile(np.arange(K), (nl, 1)), np.zeros((nl, K), np.int64)
-    acc, att, trips, compared = np.zeros(K - 1, np.int64), np.zeros(K - 1, np.int64), np.zeros(nl, np.int64), 0
-    for j in range(R):
-        U = to_np(dyn.energy(x_hist[j * M + M - 1])).astype(np.float64).reshape(nl, K)
-        new, a, t, near = ref.sweep(prev, U, t32, j, ref.swap_uniforms(21, nl, K, j), tol=1e-5)
-        got = rh[j].reshape(nl, K)
-        ok = ~near.any(axis=1)
-        assert np.array_equal(new[ok], got[ok]), j
-        compared += int(ok.sum())
-        acc += a
-        att += t
-        prev = got
-        trip, done = ref.update_trips(got, trip, K)
-        trips += done
+
+    def U_of(xs):
+        return to_np(dyn.energy(xs)).astype(np.float64)
+    compared, acc, att, trips = ref.replay(pt, o, x_hist, U_of, t32, R, M, None, 21, np.tile(np.arange(K), (nl, 1)), tol=1e-5)
     assert compared >= 0.95 * R * nl
     assert np.array_equal(att, to_np(o["swaps_attempted"]))
     assert np.abs(acc - to_np(o["swaps_accepted"])).sum() <= R * nl - compared

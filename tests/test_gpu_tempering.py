@@ -73,28 +73,6 @@ def test_each_rung_matches_the_oracle_at_its_temperature(case):
         helpers.check_x_next(xn[rows], x[rows], rLx, rpx, u[rows], 1e-4)
 
 
-def _replay(pt, o, x_hist, U_of, temps, R, M, u_inj, seed, labels0):
-    """Replay the sweeps on the kernel's own states: returns (decisions compared, accepted, attempted, trips per ladder)."""
-    K, nl = pt.K, pt.n_ladders
-    rh = helpers.to_np(o["rung_hist"]).astype(np.int64)
-    prev, trip = labels0.copy(), np.zeros((nl, K), np.int64)
-    acc, att, trips, compared = np.zeros(K - 1, np.int64), np.zeros(K - 1, np.int64), np.zeros(nl, np.int64), 0
-    for j in range(R):
-        U = U_of(x_hist[j * M + M - 1]).reshape(nl, K)
-        uj = u_inj[j] if u_inj is not None else ref.swap_uniforms(seed, nl, K, j)
-        new, a, t, near = ref.sweep(prev, U, temps, j, uj, tol=1e-5)
-        got = rh[j].reshape(nl, K)
-        ok = ~near.any(axis=1)
-        assert np.array_equal(new[ok], got[ok]), (j, np.nonzero(~np.all(new == got, axis=1) & ok))
-        compared += int(ok.sum())
-        acc += a
-        att += t
-        prev = got
-        trip, done = ref.update_trips(got, trip, K)
-        trips += done
-    return compared, acc, att, trips
-
-
 @pytest.mark.parametrize("injected", [True, False])
 def test_swap_decisions_counters_and_round_trips_match_the_reference(injected):
     g = helpers.load("mog2d")
@@ -110,7 +88,7 @@ def test_swap_decisions_counters_and_round_trips_match_the_reference(injected):
     def U_of(xs):
         return helpers.to_np(dyn.energy(xs)).astype(np.float64)        # T = 1 (use_temperature off)
     t32 = np.asarray(temps, np.float32).astype(np.float64)
-    compared, acc, att, trips = _replay(pt, o, x_hist, U_of, t32, R, M, u_inj, 21, np.tile(np.arange(K), (nl, 1)))
+    compared, acc, att, trips = ref.replay(pt, o, x_hist, U_of, t32, R, M, u_inj, 21, np.tile(np.arange(K), (nl, 1)), tol=1e-5)
     assert compared >= 0.95 * R * nl
     assert np.array_equal(att, helpers.to_np(o["swaps_attempted"]))
     assert np.abs(acc - helpers.to_np(o["swaps_accepted"])).sum() <= R * nl - compared

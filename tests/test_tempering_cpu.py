@@ -10,6 +10,7 @@ import pytest
 
 from l2hmc_amd import _ffi
 from l2hmc_amd import distributions as D
+from tests import ladder_cases as LC
 from tests import pt_reference as ref
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -157,6 +158,74 @@ def test_deo_sweep_rule_and_nan():
     u = np.array([[np.exp(0.99)], [np.exp(1.01)], [0.5]])
     new, acc, att, _ = ref.sweep(labels, U, temps, 0, u)
     assert new.tolist() == [[1, 0], [1, 0], [0, 1]] and acc.tolist() == [1] and att.tolist() == [3]
+
+
+def test_sweep_takes_the_near_tie_margin_as_a_scalar_or_per_ladder_and_pair():
+    rng = np.random.RandomState(1)
+    nl, K, temps = 500, 4, [1.0, 1.5, 2.5, 4.0]
+    labels = np.stack([rng.permutation(K) for _ in range(nl)])
+    U = rng.randn(nl, K) * 3.0
+    u = rng.uniform(size=(nl, K // 2))
+    for rnd in (0, 1):
+        s = ref.sweep(labels, U, temps, rnd, u, tol=0.2)
+        assert 0 < s[3].sum() < s[3].size
+        for tol in (np.full((nl, K - 1), 0.2), np.full((1, K - 1), 0.2), np.full((nl, 1), 0.2), np.float32(0.2)):
+            a = ref.sweep(labels, U, temps, rnd, u, tol=tol)
+            assert all(np.array_equal(p, q) for p, q in zip(a, s))
+        # a margin of its own per ladder and pair: near exactly where the scalar form of that entry's margin says so
+        tol = rng.uniform(0.0, 0.5, size=(nl, K - 1))
+        a = ref.sweep(labels, U, temps, rnd, u, tol=tol)
+        assert all(np.array_equal(p, q) for p, q in zip(a[:3], s[:3]))                      # (decisions do not depend on it)
+        for l, k in [(0, rnd), (7, rnd), (nl - 1, K - 2 if rnd == 0 else 1)]:
+            assert a[3][l, k] == ref.sweep(labels, U, temps, rnd, u, tol=tol[l, k])[3][l, k]
+        wide = np.where(np.arange(nl)[:, None] < nl // 2, np.inf, 0.0) * np.ones((1, K - 1))
+        near = ref.sweep(labels, U, temps, rnd, u, tol=wide)[3]
+        assert near[:nl // 2, rnd::2].all() and not near[nl // 2:].any() and not near[:, 1 - rnd::2].any()
+
+
+def test_replay_follows_the_labels_it_is_given_and_skips_near_ties():
+    """`replay` on a rung history made by `sweep` itself: everything is compared and the counters are the sweeps'; with the
+    margin of one ladder set to infinity that ladder is left out; a wrong label in the history is reported."""
+    import torch
+
+    class Ladder(object):
+        K, n_ladders = 4, 6
+    rng = np.random.RandomState(2)
+    K, nl, R, M, temps = 4, 6, 5, 2, [1.0, 1.5, 2.5, 4.0]
+    x_hist = rng.randn(R * M, nl * K, 1) * 3.0
+    u = rng.uniform(size=(R, nl, K // 2))
+    labels0 = np.tile(np.arange(K), (nl, 1))
+    lab, rh, acc, att = labels0, [], 0, 0
+    trip, trips = np.zeros((nl, K), np.int64), np.zeros(nl, np.int64)
+    for j in range(R):
+        lab, a, t, _ = ref.sweep(lab, x_hist[j * M + M - 1, :, 0].reshape(nl, K), temps, j, u[j])
+        rh.append(lab.reshape(-1))
+        acc, att = acc + a, att + t
+        trip, done = ref.update_trips(lab, trip, K)
+        trips += done
+    o = {"rung_hist": torch.as_tensor(np.asarray(rh, np.int8))}
+
+    def U_of(xs):
+        return xs[:, 0]
+    got = ref.replay(Ladder, o, x_hist, U_of, temps, R, M, u, 0, labels0, tol=0.0)
+    assert got[0] == R * nl and np.array_equal(got[1], acc) and np.array_equal(got[2], att) and np.array_equal(got[3], trips)
+    got = ref.replay(Ladder, o, x_hist, U_of, temps, R, M, u, 0, labels0,
+                     tol=lambda labels, U: np.where(np.arange(nl)[:, None] == 2, np.inf, 0.0) * np.ones((1, K - 1)))
+    assert got[0] == R * nl - R
+    bad = np.asarray(rh, np.int8)
+    bad[1, [4, 5]] = bad[1, [5, 4]]
+    with pytest.raises(AssertionError):
+        ref.replay(Ladder, {"rung_hist": torch.as_tensor(bad)}, x_hist, U_of, temps, R, M, u, 0, labels0, tol=0.0)
+
+
+@pytest.mark.parametrize("name", list(LC.CASES))
+def test_ladder_case_inputs_accept_and_reject_swaps_away_from_the_near_tie_margin(name):
+    """The conditions tests/test_gpu_ladder_geometries.py puts on its inputs, from the float64 oracle energy of x0 alone."""
+    c = LC.case(name)
+    acc0, att0, near = c.check_inputs()
+    assert 0 < acc0 < att0 and near < 0.01
+    assert c.N % c.K == 0 and c.N <= 48 and (c.N % 16 != 0 or c.K == 16)        # a half-live last tile wherever K allows one
+    assert LC.R * LC.M == 8 and LC.T == 5
 
 
 def test_round_trip_counting_matches_a_hand_worked_sequence():
