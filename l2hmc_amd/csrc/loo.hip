@@ -9,20 +9,20 @@
 //     body     sum over the draws NOT in the tail of e^m + e^(m - t), m = min(c, 0): every term lies in (0, 2]
 //     sum_lik  sum over all draws of sigmoid(t)
 // l2hmc_amd/predictive.py `loo_finish` turns them into elpd_loo and the Pareto k-hat; include/l2hmc.h states the contract.  The
-// (S, n) matrix is never written and nothing is sorted: a most-significant-digit radix select, kLooPasses = 4 passes of 8 bits,
-// finds c per row, and one more pass gathers.  Every pass forms t again from W.
+// (S, n) matrix is never written and nothing is sorted: a most-significant-digit radix select (radix_select.hpp), kRadixPasses =
+// 4 passes of 8 bits, finds c per row, and one more pass gathers.  Every pass forms t again from W.
 //
-// THE INVARIANT THE SELECT AND THE GATHER RELY ON: every pass computes t by ONE device function, loo_logits (staged by
-// loo_stage), which adds the feature tiles tg = 0 .. NT - 1 in that order, four f32-input MFMAs each, onto a zero accumulator.
-// The bits of t_si therefore depend on (W, X, y) alone -- not on the pass, the chunk, the plan or the row grouping of the caller.
-// A key counted in one pass is the key compared in the next, and exactly the keys below the selected one reach the tail.
+// THE INVARIANT THE SELECT AND THE GATHER RELY ON: every pass computes t by ONE device function, tile_logits of draw_tiles.hpp
+// (staged by tile_stage), which adds the feature tiles tg = 0 .. NT - 1 in that order, four f32-input MFMAs each, onto a zero
+// accumulator; the label's sign is applied afterwards (exact).  The bits of t_si therefore depend on (W, X, y) alone -- not on
+// the pass, the chunk, the plan or the row grouping of the caller.  A key counted in one pass is the key compared in the next,
+// and exactly the keys below the selected one reach the tail.
 //
-// The contraction is predict_kernel's (predictive.hip): the same f32-input MFMA and operand layouts, the same staging of
-// 16-draw tiles by coalesced scalar loads from a base that is only 4-byte aligned, one tile ahead, into the wave's own LDS
-// region, the same masks (a draw at or past S, a row at or past n never counts).  Work unit = one wave: NB = 2 consecutive 16-row
-// data blocks x a chunk of tpc 16-draw tiles.  tpc depends on S ALONE (about kLooChunks chunks), so the order in which float64
-// terms are added does not depend on how many rows a call holds.  A workgroup is four waves on the SAME data blocks and four
-// consecutive chunks; blockIdx.x = quad * ngroups + group.
+// The tile loop is draw_tiles.hpp's, shared with predict_kernel (predictive.hip), with the same masks (a draw at or past S, a
+// row at or past n never counts).  Work unit = one wave: NB = 2 consecutive 16-row data blocks x a chunk of tpc 16-draw tiles.
+// tpc depends on S ALONE (about kLooChunks chunks), so the order in which float64 terms are added does not depend on how many
+// rows a call holds.  A workgroup is four waves on the SAME data blocks and four consecutive chunks; blockIdx.x = quad * ngroups
+// + group.
 //
 //   count    loo_kernel<NTM, 0>: the workgroup keeps one LDS histogram [32 rows][256 bins] uint32 (32 KiB) of the next digit of
 //            the keys that share their row's prefix, added to with integer LDS atomics and flushed -- non-zero bins only -- to
@@ -30,19 +30,16 @@
 //            high exponent) concentrates in a few bins: the 16 draw lanes of a row would add to one address.  There the 16 lanes
 //            compare their bin with the first lane's; those that agree are counted by a ballot and added by that lane in ONE
 //            atomic, the others add for themselves.  Later passes count only the keys on the prefix: few, plain atomics.
-//   advance  loo_advance_kernel: one wave per row scans the 256 bins for the digit in which the remaining rank falls, as
-//            order_advance_kernel does; after the last pass the prefix is the cutoff's key and the cutoff is written.
+//   advance  radix_advance_kernel: one wave per row scans the 256 bins for the digit in which the remaining rank falls; after
+//            the last pass the prefix is the cutoff's key and the cutoff is written.
 //   gather   loo_kernel<NTM, 1>: a key below the cutoff's key takes slot atomicAdd(n_tail[row], 1) (an integer atomic) of the
 //            row's tail; a slot at or past M is not written and raises the error word of the workspace (it cannot happen while
 //            the invariant holds).  Every other live draw adds its body term, every live draw its sigmoid, converted to float64
 //            BEFORE the addition, to the lane's own sums; once per wave the 16 draw lanes are added in the order c = 0 .. 15 and
 //            the wave's partials go to workspace[chunk][2][n].
-//   reduce   loo_reduce_kernel: sums[k][i] = the chunks' partials added in chunk order, as predict_reduce_kernel does.
+//   reduce   chunk_reduce_kernel: sums[k][i] = the chunks' partials added in chunk order.
 // No floating-point atomics anywhere: integer counts do not depend on arrival order, the tail is a set, the sums have a fixed
 // tree.  Every outward write is an ordinary vector store or atomic from plain C++.
-//
-// TWIN: loo_load / loo_stage / loo_logits and the end reduction restate the tile loop of predict_kernel (predictive.hip), which
-// keeps its own copy; a fix to the staging walk or to its register trick belongs in both until they share a header.
 //
 // Counts: a bin of the LDS histogram is a uint32 and a workgroup adds at most 4 waves x tpc x 16 draws to one bin of a row.
 // tpc <= 2^40 / 16 / 1024 = 2^26 at the largest n_draws the entry accepts, i.e. at most 2^32 -- one more than a bin holds, and
@@ -53,16 +50,14 @@
 // 80 KiB: two resident workgroups use at most 130 KiB of the 160 KiB of a CU.  Geometries <NTM feature tiles compiled>: 1, 2, 4, 8.
 #include <math.h>
 
-#include "l2hmc_kernels.hpp"
+#include "draw_tiles.hpp"
+#include "radix_select.hpp"
 
 namespace l2hmc {
 
 constexpr int kLooThreads = 256;          // 4 waves on the same rows
 constexpr int kLooNB = 2;                 // 16-row data blocks per wave
 constexpr int kLooRows = 16 * kLooNB;     // rows of a workgroup's histogram
-constexpr int kLooBits = 8;
-constexpr int kLooBins = 1 << kLooBits;
-constexpr int kLooPasses = 32 / kLooBits;
 constexpr int kLooChunks = 1024;          // draw chunks aimed for, whatever n is
 constexpr int kLooMinTiles = 4;           // draw tiles per chunk at least
 
@@ -82,13 +77,7 @@ static long long loo_tail_len(long long S) {
 }
 
 static bool loo_plan(const char* who, int64_t n_draws, int32_t n_data, int32_t d, LooPlan& p) {
-  if (n_draws < 2) { fail(L2HMC_ERR_ARG, "%s: n_draws >= 2 (got %lld)", who, n_draws); return false; }
-  if (n_data < 1 || n_data > kLogisticMaxRows) {
-    fail(L2HMC_ERR_ARG, "%s: 1 <= n_data <= 1048576 (got %lld)", who, n_data);
-    return false;
-  }
-  if (d < 1 || d > kLogisticMaxDim) { fail(L2HMC_ERR_ARG, "%s: 1 <= d <= 128 (got %lld)", who, d); return false; }
-  if (n_draws > (1LL << 40) / d) { fail(L2HMC_ERR_ARG, "%s: draws too large (n_draws d > 2^40)", who); return false; }
+  if (!logistic_history_args_ok(who, n_draws, n_data, d)) return false;
   p.M = loo_tail_len(n_draws);
   if (p.M * n_data > (1LL << 31)) { fail(L2HMC_ERR_ARG, "%s: tail too large (tail_len n_data > 2^31): fewer rows per call", who); return false; }
   p.NT = tiles_of(d);
@@ -118,83 +107,12 @@ static LooWorkspace loo_workspace(void* base, const LooPlan& p, int32_t n) {
   char* b = (char*)base;
   int64_t o = 0;
   w.err = (unsigned long long*)(b + o); o += 8;
-  w.hist = (unsigned long long*)(b + o); o += (int64_t)n * kLooBins * 8;
+  w.hist = (unsigned long long*)(b + o); o += (int64_t)n * kRadixBins * 8;
   w.remaining = (long long*)(b + o); o += (int64_t)n * 8;
   w.prefix = (uint32_t*)(b + o); o += ((int64_t)n * 4 + 7) / 8 * 8;
   w.part = (double*)(b + o); o += p.nchunks * 2 * (int64_t)n * 8;
   w.bytes = o;
   return w;
-}
-
-__device__ __forceinline__ void loo_lds_fence() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// the monotone key of order_stats.hip; every NaN takes the last key
-__device__ __forceinline__ uint32_t loo_key(float v) {
-  const uint32_t b = __float_as_uint(v);
-  const uint32_t k = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-  return v != v ? 0xFFFFFFFFu : k;
-}
-__device__ __forceinline__ float loo_unkey(uint32_t key) {
-  return __uint_as_float((key & 0x80000000u) ? (key & 0x7FFFFFFFu) : ~key);
-}
-
-// the loads of draw tile t: element e = lane + 64 i of a tile is W[16 t d + e], 0 past the end of W
-template <int NTM>
-__device__ __forceinline__ void loo_load(const float* __restrict__ W, long long t, int tile_elems, long long total, int lane,
-                                         float (&pre)[4 * NTM]) {
-#pragma unroll
-  for (int i = 0; i < 4 * NTM; ++i) {
-    const int e = lane + 64 * i;
-    const long long g = t * tile_elems + e;
-    pre[i] = (e < tile_elems && g < total) ? W[g] : 0.f;
-  }
-}
-
-// the loaded tile into the wave's LDS region as [16 draws][16 NTM + 4]; element e is (draw e / d, feature e % d)
-template <int NTM>
-__device__ __forceinline__ void loo_stage(float* lds, const float (&pre)[4 * NTM], int lane, int d, int tile_elems, int row0,
-                                          int col0, int dq, int dr) {
-  constexpr int STRIDE = 16 * NTM + 4;
-  int row = row0, col = col0;
-  asm volatile("" : "+v"(row), "+v"(col));               // (recomputed per tile, not held in 4 NTM registers across the loop)
-#pragma unroll
-  for (int i = 0; i < 4 * NTM; ++i) {
-    if (lane + 64 * i < tile_elems) lds[row * STRIDE + col] = pre[i];
-    row += dq;
-    col += dr;
-    if (col >= d) { col -= d; row += 1; }
-  }
-}
-
-// THE signed logits of the staged tile: T[j][r] = t of draw c, row 16 (b0 + j) + 4 q + r.  Feature tiles in the order
-// tg = 0 .. NT - 1, four MFMAs each, onto zero; then the label's sign (exact).  Every pass calls this and nothing else.
-template <int NTM>
-__device__ __forceinline__ void loo_logits(const float* lds, const f4 (&xa)[kLooNB][NTM], const f4 (&yv)[kLooNB], int c, int q,
-                                           int NT, int b0, int nblk, f4 (&T)[kLooNB]) {
-  constexpr int STRIDE = 16 * NTM + 4;
-#pragma unroll
-  for (int j = 0; j < kLooNB; ++j) T[j] = splat(0.f);
-#pragma unroll
-  for (int tg = 0; tg < NTM; ++tg) {
-    if (tg < NT) {
-      const f4 B = lds4(lds + c * STRIDE + 16 * tg + 4 * q);
-#pragma unroll
-      for (int j = 0; j < kLooNB; ++j) {
-        if (b0 + j < nblk) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) T[j] = MFMA16(xa[j][tg][r], B[r], T[j]);
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int j = 0; j < kLooNB; ++j)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) T[j][r] = yv[j][r] > 0.5f ? T[j][r] : -T[j][r];
 }
 
 // MODE 0: count the digit at `shift` of the keys on their row's prefix (first: no prefix, every key).  MODE 1: gather.
@@ -207,46 +125,40 @@ __global__ __launch_bounds__(kLooThreads) void loo_kernel(const float* __restric
                                                           long long M, unsigned long long* __restrict__ err,
                                                           double* __restrict__ part) {
   constexpr int NB = kLooNB;
-  constexpr int STRIDE = 16 * NTM + 4;
-  constexpr int REGION = 16 * STRIDE > 512 ? 16 * STRIDE : 512;   // per wave; the end reduction needs 256 doubles
+  constexpr int REGION = tile_region(NTM);
   __shared__ __attribute__((aligned(16))) float lds_all[4 * REGION];
-  __shared__ uint32_t hl[MODE == 0 ? kLooRows * kLooBins : 1];
+  __shared__ uint32_t hl[MODE == 0 ? kLooRows * kRadixBins : 1];
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, c = lane & 15, q = lane >> 4;
   const int group = (int)(blockIdx.x % (unsigned)ngroups);
   const long long chunk = (long long)(blockIdx.x / (unsigned)ngroups) * 4 + w;
   const bool live_wave = chunk < nchunks;                    // (wave-uniform; a dead wave still meets the barriers below)
   float* lds = lds_all + w * REGION;
-#pragma unroll
-  for (int i = 0; i < REGION / 64; ++i) lds[lane + 64 * i] = 0.f;
+  tile_region_clear<NTM>(lds, lane);
   if (MODE == 0) {
-    for (int i = threadIdx.x; i < kLooRows * kLooBins; i += kLooThreads) hl[i] = 0u;
+    for (int i = threadIdx.x; i < kLooRows * kRadixBins; i += kLooThreads) hl[i] = 0u;
     __syncthreads();
   }
 
-  const int nblk = (n + 15) >> 4, b0 = group * NB, BS = logistic_block_floats(NT);
+  const int nblk = (n + 15) >> 4, b0 = group * NB;
   if (live_wave) {
     f4 xa[NB][NTM], yv[NB];
+    block_fragments<NTM, NB>(P, NT, b0, nblk, lane, xa, yv);
     uint32_t pre_key[NB][4];          // count: the row's prefix above the digit; gather: the cutoff's key
     float em[NB][4], mm[NB][4];       // gather: e^m and m = min(cutoff, 0)
     bool row_ok[NB][4];
 #pragma unroll
     for (int j = 0; j < NB; ++j) {
-      const bool live = b0 + j < nblk;
-      const float* blk = P + (size_t)(live ? b0 + j : nblk - 1) * BS;
-#pragma unroll
-      for (int tg = 0; tg < NTM; ++tg) xa[j][tg] = (live && tg < NT) ? lds4(blk + (tg * 64 + lane) * 4) : splat(0.f);
-      yv[j] = lds4(blk + 512 * NT + 4 * q);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int row = 16 * (b0 + j) + 4 * q + r;
-        row_ok[j][r] = live && row < n;
+        row_ok[j][r] = b0 + j < nblk && row < n;
         const uint32_t key = (row_ok[j][r] && !(MODE == 0 && first)) ? prefix[row] : 0u;
         if (MODE == 0) {
-          pre_key[j][r] = first ? 0u : key >> (shift + kLooBits);
+          pre_key[j][r] = first ? 0u : key >> (shift + kRadixBits);
           em[j][r] = mm[j][r] = 0.f;
         } else {
           pre_key[j][r] = key;
-          mm[j][r] = fminf(loo_unkey(key), 0.f);             // (a NaN cutoff gives 0)
+          mm[j][r] = fminf(radix_unkey(key), 0.f);             // (a NaN cutoff gives 0)
           em[j][r] = (float)exp((double)mm[j][r]);
         }
       }
@@ -259,31 +171,30 @@ __global__ __launch_bounds__(kLooThreads) void loo_kernel(const float* __restric
 #pragma unroll
         for (int r = 0; r < 4; ++r) acc[j][k][r] = 0.0;
 
-    const long long ntiles = (S + 15) >> 4, total = S * d;
+    const long long ntiles = (S + 15) >> 4;
     const long long t0 = chunk * tpc, t1 = t0 + tpc < ntiles ? t0 + tpc : ntiles;
-    const int tile_elems = 16 * d;
-    const int row0 = lane / d, col0 = lane - row0 * d, dq = 64 / d, dr = 64 - dq * d;
+    const TileWalk walk = tile_walk(lane, d, S);
     float pre[4 * NTM];
-    loo_load<NTM>(W, t0, tile_elems, total, lane, pre);
+    tile_load<NTM>(W, t0, walk, lane, pre);
 
     for (long long t = t0; t < t1; ++t) {
-      loo_stage<NTM>(lds, pre, lane, d, tile_elems, row0, col0, dq, dr);
-      loo_lds_fence();
+      tile_stage<NTM>(lds, pre, walk, lane);
+      wave_lds_fence();
       f4 T[NB];
-      loo_logits<NTM>(lds, xa, yv, c, q, NT, b0, nblk, T);
-      loo_lds_fence();
-      if (t + 1 < t1) loo_load<NTM>(W, t + 1, tile_elems, total, lane, pre);   // in flight during this tile's arithmetic
+      tile_logits<NTM, NB>(lds, xa, c, q, NT, b0, nblk, T);
+      wave_lds_fence();
+      if (t + 1 < t1) tile_load<NTM>(W, t + 1, walk, lane, pre);         // in flight during this tile's arithmetic
       const bool valid = 16 * t + c < S;
 #pragma unroll
       for (int j = 0; j < NB; ++j) {
         if (b0 + j < nblk) {                                 // wave-uniform
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            const float tv = T[j][r];
-            const uint32_t key = loo_key(tv);
+            const float tv = yv[j][r] > 0.5f ? T[j][r] : -T[j][r];        // the signed logit (the sign is exact)
+            const uint32_t key = radix_key(tv);
             const bool ok = valid && row_ok[j][r];
             if (MODE == 0) {
-              uint32_t* hrow = hl + (16 * j + 4 * q + r) * kLooBins;
+              uint32_t* hrow = hl + (16 * j + 4 * q + r) * kRadixBins;
               if (first) {
                 // the 16 draw lanes of this row: those in the first lane's bin are added by it in one atomic
                 const int bin = (int)(key >> 24);
@@ -294,7 +205,7 @@ __global__ __launch_bounds__(kLooThreads) void loo_kernel(const float* __restric
                 if (c == 0) { if (cnt) atomicAdd(&hrow[lead], (uint32_t)cnt); }
                 else if (ok && !same) atomicAdd(&hrow[bin], 1u);
               } else {
-                if (ok && (key >> (shift + kLooBits)) == pre_key[j][r]) atomicAdd(&hrow[(key >> shift) & (kLooBins - 1)], 1u);
+                if (ok && (key >> (shift + kRadixBits)) == pre_key[j][r]) atomicAdd(&hrow[(key >> shift) & (kRadixBins - 1)], 1u);
               }
             } else {
               const bool in_tail = ok && key < pre_key[j][r];
@@ -316,77 +227,17 @@ __global__ __launch_bounds__(kLooThreads) void loo_kernel(const float* __restric
       }
     }
 
-    if (MODE == 1) {
-      // the 16 draw lanes of every (data block, sum, row), added in the order c = 0 .. 15
-      double* red = reinterpret_cast<double*>(lds);
-#pragma unroll
-      for (int j = 0; j < NB; ++j) {
-        if (b0 + j < nblk) {
-#pragma unroll
-          for (int k = 0; k < 2; ++k) {
-            loo_lds_fence();
-#pragma unroll
-            for (int r = 0; r < 4; ++r) red[c * 16 + 4 * q + r] = acc[j][k][r];
-            loo_lds_fence();
-            if (lane < 16) {
-              double a = red[lane];
-#pragma unroll
-              for (int cc = 1; cc < 16; ++cc) a += red[cc * 16 + lane];
-              const int row = 16 * (b0 + j) + lane;
-              if (row < n) part[(chunk * 2 + k) * (long long)n + row] = a;
-            }
-          }
-        }
-      }
-    }
+    if (MODE == 1) tile_sums_out<NB, 2>(lds, acc, lane, b0, nblk, n, chunk, part);
   }
 
   if (MODE == 0) {
     __syncthreads();
-    for (int i = threadIdx.x; i < kLooRows * kLooBins; i += kLooThreads) {
+    for (int i = threadIdx.x; i < kLooRows * kRadixBins; i += kLooThreads) {
       const uint32_t cnt = hl[i];
-      const int row = 16 * b0 + (i >> kLooBits);
-      if (cnt && row < n) atomicAdd(&hist[(long long)row * kLooBins + (i & (kLooBins - 1))], (unsigned long long)cnt);
+      const int row = 16 * b0 + (i >> kRadixBits);
+      if (cnt && row < n) atomicAdd(&hist[(long long)row * kRadixBins + (i & (kRadixBins - 1))], (unsigned long long)cnt);
     }
   }
-}
-
-// one wave per row: lane l holds bins 4 l .. 4 l + 3, a wave scan finds the lane and that lane the digit (order_advance_kernel)
-__global__ __launch_bounds__(64) void loo_advance_kernel(const long long* __restrict__ hist, long long* __restrict__ remaining,
-                                                         uint32_t* __restrict__ prefix, int n, int shift,
-                                                         float* __restrict__ cutoff) {
-  static_assert(kLooBins == 4 * 64, "four bins per lane");
-  const int i = blockIdx.x, lane = threadIdx.x;
-  if (i >= n) return;
-  const long long* h = hist + (long long)i * kLooBins + 4 * lane;
-  long long c[4];
-#pragma unroll
-  for (int b = 0; b < 4; ++b) c[b] = h[b];
-  const long long mine = c[0] + c[1] + c[2] + c[3];
-  long long incl = mine;
-#pragma unroll
-  for (int o = 1; o < 64; o *= 2) {
-    const long long up = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += up;
-  }
-  const long long total = __shfl(incl, 63, 64);
-  long long rem = remaining[i];
-  if (total <= 0) {                                   // nothing on the prefix (cannot happen: the rank is below n_draws)
-    if (lane == 0 && cutoff) cutoff[i] = loo_unkey(prefix[i]);
-    return;
-  }
-  if (rem < 0) rem = 0;
-  if (rem >= total) rem = total - 1;
-  long long below = incl - mine;
-  if (rem < below || rem >= incl) return;             // exactly one lane holds the rank
-  int digit = 4 * lane;
-#pragma unroll
-  for (int b = 0; b < 3; ++b)
-    if (rem >= below + c[b] && digit == 4 * lane + b) { below += c[b]; ++digit; }
-  const uint32_t key = prefix[i] | ((uint32_t)digit << shift);
-  prefix[i] = key;
-  remaining[i] = rem - below;
-  if (cutoff) cutoff[i] = loo_unkey(key);
 }
 
 __global__ void loo_init_kernel(long long* __restrict__ remaining, uint32_t* __restrict__ prefix,
@@ -396,15 +247,6 @@ __global__ void loo_init_kernel(long long* __restrict__ remaining, uint32_t* __r
   if (i == 0) *err = 0ull;
   if (i < n) { remaining[i] = M; prefix[i] = 0u; n_tail[i] = 0ull; }
   if (i < (long long)n * M) tail[i] = __builtin_inff();
-}
-
-// sums[i] = the chunks' partials of entry i = k n + row, added in chunk order
-__global__ void loo_reduce_kernel(const double* __restrict__ part, long long nchunks, long long m, double* __restrict__ sums) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= m) return;
-  double a = 0.0;
-  for (long long ch = 0; ch < nchunks; ++ch) a += part[ch * m + i];
-  sums[i] = a;
 }
 
 }  // namespace l2hmc
@@ -448,20 +290,18 @@ int l2hmc_logistic_loo_tails(const float* draws, int64_t n_draws, int32_t d, con
     case 4: L2HMC_LOO_LAUNCH(4, MODE, shift, first); break; \
     default: L2HMC_LOO_LAUNCH(8, MODE, shift, first); break; \
   }
-  for (int pass = 0; pass < kLooPasses; ++pass) {
-    const int shift = 32 - kLooBits * (pass + 1);
-    hipError_t e = hipMemsetAsync(ws.hist, 0, (size_t)n * kLooBins * sizeof(long long), s);
+  for (int pass = 0; pass < kRadixPasses; ++pass) {
+    const int shift = 32 - kRadixBits * (pass + 1);
+    hipError_t e = hipMemsetAsync(ws.hist, 0, (size_t)n * kRadixBins * sizeof(long long), s);
     if (e != hipSuccess) return fail(L2HMC_ERR_HIP, "hipMemsetAsync: %s", hipGetErrorString(e));
     L2HMC_LOO_PASS(0, shift, pass == 0)
-    hipLaunchKernelGGL(loo_advance_kernel, dim3((unsigned)n_data), dim3(64), 0, s, (const long long*)ws.hist, ws.remaining,
-                       ws.prefix, (int)n_data, shift, pass == kLooPasses - 1 ? cutoff : (float*)nullptr);
+    hipLaunchKernelGGL(radix_advance_kernel, dim3((unsigned)n_data), dim3(64), 0, s, (const long long*)ws.hist, ws.remaining,
+                       ws.prefix, (int)n_data, shift, pass == kRadixPasses - 1 ? cutoff : (float*)nullptr);
   }
   L2HMC_LOO_PASS(1, 0, 0)
 #undef L2HMC_LOO_PASS
 #undef L2HMC_LOO_LAUNCH
-  const long long m = 2LL * n_data;
-  hipLaunchKernelGGL(loo_reduce_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, (const double*)ws.part, p.nchunks, m,
-                     sums);
+  chunk_reduce_launch(ws.part, p.nchunks, 2LL * n_data, sums, s);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(L2HMC_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
   return L2HMC_OK;

@@ -3,7 +3,8 @@
 // l2hmc_amd/quantiles.py turns them into quantiles, tail-ESS and quantile MCSE; include/l2hmc.h states the contract.
 //
 // Most-significant-digit radix select on the monotone key of a float32 (bits ^ 0xFFFFFFFF for a negative value, bits | 0x80000000
-// otherwise; every NaN takes the key 0xFFFFFFFF and sorts last, like numpy), kOsPasses = 4 passes of kOsBits = 8 bits.  A pass:
+// otherwise; every NaN takes the key 0xFFFFFFFF and sorts last, like numpy), kRadixPasses = 4 passes of kRadixBits = 8 bits; the
+// key and the advance step are radix_select.hpp's, shared with loo.hip.  A pass:
 //
 //   count    order_count_kernel: for every (r, k) the histogram of the next digit of the keys whose higher digits equal the
 //            pair's prefix.  In pass 0 the prefix is empty and the R histograms of a coordinate are equal: one is counted and
@@ -21,20 +22,16 @@
 //            Integer addition does not depend on arrival order: the histogram is bitwise reproducible and the same however
 //            the draws are sharded.  When a group cannot hold every coordinate and rank (sg RG <= 64), blockIdx.y / z walk the
 //            coordinate / rank groups and the history is read once per group.
-//   advance  order_advance_kernel: one wave per (r, k) scans the 256 bins (four per lane, a wave prefix sum) for the digit in
-//            which the remaining rank falls, extends the prefix, subtracts the counts below that digit and, after the last pass,
-//            writes the value the prefix encodes.  A rank at or past the number of draws takes the maximum.
+//   advance  radix_advance_kernel (radix_select.hpp), one wave per (r, k); after the last pass it writes the value the prefix
+//            encodes.  A rank at or past the number of draws takes the maximum.
 // Nothing returns to the host between passes, and the library allocates nothing.
 #include <stdlib.h>
 
-#include "l2hmc_kernels.hpp"
+#include "radix_select.hpp"
 
 namespace l2hmc {
 
 constexpr int kOsThreads = 256;
-constexpr int kOsBits = 8;
-constexpr int kOsBins = 1 << kOsBits;
-constexpr int kOsPasses = 32 / kOsBits;
 constexpr int kOsCols = 64;        // columns of the LDS histogram: 256 bins x 64 x 4 B = 64 KiB, two blocks per CU
 constexpr int kOsMaxRanks = 32;
 constexpr int kOsBlocks = 1024;    // blocks the planner aims for over all groups
@@ -51,7 +48,7 @@ static bool order_stats_plan(const char* who, int64_t n_draws, int32_t d, int32_
   if (n_draws < 1 || d < 1) { fail(L2HMC_ERR_ARG, "%s: n_draws and d must be >= 1", who); return false; }
   if (d > 512) { fail(L2HMC_ERR_ARG, "%s: d <= 512 (got %lld)", who, d); return false; }
   if (n_ranks < 1 || n_ranks > kOsMaxRanks) { fail(L2HMC_ERR_ARG, "%s: 1 <= n_ranks <= 32 (got %lld)", who, n_ranks); return false; }
-  if (pass < 0 || pass >= kOsPasses) { fail(L2HMC_ERR_ARG, "%s: 0 <= pass <= 3 (got %lld)", who, pass); return false; }
+  if (pass < 0 || pass >= kRadixPasses) { fail(L2HMC_ERR_ARG, "%s: 0 <= pass <= 3 (got %lld)", who, pass); return false; }
   if (n_draws > (1LL << 40) / d) { fail(L2HMC_ERR_ARG, "%s: history too large (n_draws d > 2^40)", who); return false; }
   // fewest groups = fewest reads of the history; among equals the widest coordinate group (the longest contiguous runs)
   int best_rg = 1;
@@ -81,11 +78,6 @@ static bool order_stats_plan(const char* who, int64_t n_draws, int32_t d, int32_
   return true;
 }
 
-__device__ __forceinline__ uint32_t os_key(float v) {
-  const uint32_t b = __float_as_uint(v);
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-
 // RG: rank slots per thread (compile-time register indices); kPass0: empty prefix, one histogram per coordinate, NaNs counted;
 // kRuns (pass 0 only): runs of equal bins are counted in a register and cost one atomic per run
 template <int RG, bool kPass0, bool kRuns>
@@ -93,7 +85,7 @@ __global__ __launch_bounds__(kOsThreads) void order_count_kernel(const float* __
                                                                  int shift, const uint32_t* __restrict__ prefix,
                                                                  unsigned long long* __restrict__ hist,
                                                                  unsigned long long* __restrict__ n_nan, int sg, int copies) {
-  extern __shared__ uint32_t os_h[];                  // [kOsBins][ns]
+  extern __shared__ uint32_t os_h[];                  // [kRadixBins][ns]
   const int tid = threadIdx.x;
   const int rpc = kOsThreads / sg, ns = copies * sg * RG;
   const int kk = tid % sg, rowin = tid / sg;
@@ -103,18 +95,18 @@ __global__ __launch_bounds__(kOsThreads) void order_count_kernel(const float* __
   const bool active = rowin < rpc && k < d;
   const int col0 = ((rowin % copies) * sg + kk) * RG;
 
-  for (int i = tid; i < kOsBins * ns; i += kOsThreads) os_h[i] = 0u;
+  for (int i = tid; i < kRadixBins * ns; i += kOsThreads) os_h[i] = 0u;
   uint32_t pre[RG];
 #pragma unroll
-  for (int r = 0; r < RG; ++r) pre[r] = (!kPass0 && active && r < nr) ? prefix[(long long)(r0 + r) * d + k] >> (shift + kOsBits) : 0u;
+  for (int r = 0; r < RG; ++r) pre[r] = (!kPass0 && active && r < nr) ? prefix[(long long)(r0 + r) * d + k] >> (shift + kRadixBits) : 0u;
   __syncthreads();
 
   unsigned nan_count = 0u;
   int run_bin = 0;
   unsigned run_len = 0u;
   auto count = [&](float v) {
-    uint32_t key = os_key(v);
-    if (v != v) { key = 0xFFFFFFFFu; ++nan_count; }
+    const uint32_t key = radix_key(v);
+    if (v != v) ++nan_count;
     if (kPass0) {
       const int bin = (int)(key >> 24);
       if (kRuns) {
@@ -125,8 +117,8 @@ __global__ __launch_bounds__(kOsThreads) void order_count_kernel(const float* __
         atomicAdd(&os_h[bin * ns + col0], 1u);
       }
     } else {
-      const uint32_t hi = key >> (shift + kOsBits);
-      const int at = (int)((key >> shift) & (kOsBins - 1)) * ns + col0;
+      const uint32_t hi = key >> (shift + kRadixBits);
+      const int at = (int)((key >> shift) & (kRadixBins - 1)) * ns + col0;
 #pragma unroll
       for (int r = 0; r < RG; ++r)
         if (r < nr && hi == pre[r]) atomicAdd(&os_h[at + r], 1u);
@@ -165,9 +157,9 @@ __global__ __launch_bounds__(kOsThreads) void order_count_kernel(const float* __
   }
   __syncthreads();
 
-  // the copies added, non-zero bins only to the global histogram (n_ranks, d, kOsBins)
+  // the copies added, non-zero bins only to the global histogram (n_ranks, d, kRadixBins)
   const int per_bin = sg * RG;
-  for (int i = tid; i < kOsBins * per_bin; i += kOsThreads) {
+  for (int i = tid; i < kRadixBins * per_bin; i += kOsThreads) {
     const int bin = i / per_bin, rem = i - bin * per_bin;
     const int fk = rem / RG, r = rem - fk * RG;
     const int gk = blockIdx.y * sg + fk;
@@ -176,57 +168,19 @@ __global__ __launch_bounds__(kOsThreads) void order_count_kernel(const float* __
     for (int cp = 0; cp < copies; ++cp) c += os_h[bin * ns + (cp * sg + fk) * RG + r];
     if (!c) continue;
     if (kPass0) {
-      for (int q = 0; q < n_ranks; ++q) atomicAdd(&hist[((long long)q * d + gk) * kOsBins + bin], c);
+      for (int q = 0; q < n_ranks; ++q) atomicAdd(&hist[((long long)q * d + gk) * kRadixBins + bin], c);
     } else {
-      atomicAdd(&hist[((long long)(r0 + r) * d + gk) * kOsBins + bin], c);
+      atomicAdd(&hist[((long long)(r0 + r) * d + gk) * kRadixBins + bin], c);
     }
   }
-}
-
-// one wave per (r, k): lane l holds bins 4 l .. 4 l + 3, a wave scan finds the lane and that lane the digit
-__global__ __launch_bounds__(64) void order_advance_kernel(const long long* __restrict__ hist, long long* __restrict__ remaining,
-                                                           uint32_t* __restrict__ prefix, int n, int shift,
-                                                           float* __restrict__ values) {
-  static_assert(kOsBins == 4 * 64, "four bins per lane");
-  const int i = blockIdx.x, lane = threadIdx.x;
-  if (i >= n) return;
-  const long long* h = hist + (long long)i * kOsBins + 4 * lane;
-  long long c[4];
-#pragma unroll
-  for (int b = 0; b < 4; ++b) c[b] = h[b];
-  const long long mine = c[0] + c[1] + c[2] + c[3];
-  long long incl = mine;
-#pragma unroll
-  for (int o = 1; o < 64; o *= 2) {
-    const long long up = __shfl_up(incl, o, 64);
-    if (lane >= o) incl += up;
-  }
-  const long long total = __shfl(incl, 63, 64);
-  long long rem = remaining[i];
-  if (rem < 0) rem = 0;
-  if (rem >= total) rem = total - 1;                  // a rank at or past the end: the maximum
-  if (total <= 0) {                                   // no draws counted (cannot happen with n_draws >= 1)
-    if (lane == 0) { remaining[i] = 0; if (values) values[i] = __uint_as_float(~prefix[i]); }
-    return;
-  }
-  long long below = incl - mine;
-  if (rem < below || rem >= incl) return;             // exactly one lane holds the rank
-  int digit = 4 * lane;
-#pragma unroll
-  for (int b = 0; b < 3; ++b)
-    if (rem >= below + c[b] && digit == 4 * lane + b) { below += c[b]; ++digit; }
-  const uint32_t key = prefix[i] | ((uint32_t)digit << shift);
-  prefix[i] = key;
-  remaining[i] = rem - below;
-  if (values) values[i] = __uint_as_float((key & 0x80000000u) ? (key & 0x7FFFFFFFu) : ~key);
 }
 
 template <int RG>
 static void order_count_launch(const OrderStatsPlan& p, bool runs, hipStream_t s, const float* X, int64_t S, int32_t d,
                                int32_t n_ranks, int32_t pass, const uint32_t* prefix, int64_t* hist, int64_t* n_nan) {
   const dim3 grid((unsigned)p.nb, (unsigned)p.ngk, (unsigned)p.ngr), block(kOsThreads);
-  const size_t lds = (size_t)kOsBins * p.ns * sizeof(uint32_t);
-  const int shift = 32 - kOsBits * (pass + 1);
+  const size_t lds = (size_t)kRadixBins * p.ns * sizeof(uint32_t);
+  const int shift = 32 - kRadixBits * (pass + 1);
   unsigned long long* h = (unsigned long long*)hist;
   unsigned long long* nn = (unsigned long long*)n_nan;
   if (pass == 0) {
@@ -245,15 +199,15 @@ using namespace l2hmc;
 
 extern "C" {
 
-int32_t l2hmc_order_stats_passes(void) { return kOsPasses; }
-int32_t l2hmc_order_stats_bins(void) { return kOsBins; }
+int32_t l2hmc_order_stats_passes(void) { return kRadixPasses; }
+int32_t l2hmc_order_stats_bins(void) { return kRadixBins; }
 
 int64_t l2hmc_order_stats_workspace_bytes(int32_t d, int32_t n_ranks) {
   OrderStatsPlan p;
   if (!order_stats_plan("l2hmc_order_stats_workspace_bytes", 1, d, n_ranks, 0, p)) return L2HMC_ERR_ARG;
   // histogram (n_ranks, d, bins) int64 | remaining (n_ranks, d) int64 | prefix (n_ranks, d) uint32, rounded to 16 bytes
   const int64_t n = (int64_t)n_ranks * d;
-  return (n * (kOsBins * 8 + 8 + 4) + 15) / 16 * 16;
+  return (n * (kRadixBins * 8 + 8 + 4) + 15) / 16 * 16;
 }
 
 int l2hmc_order_stats_count(const float* X, int64_t n_draws, int32_t d, int32_t n_ranks, int32_t pass, const uint32_t* prefix,
@@ -264,7 +218,7 @@ int l2hmc_order_stats_count(const float* X, int64_t n_draws, int32_t d, int32_t 
     return fail(L2HMC_ERR_ARG, "l2hmc_order_stats_count: X, hist, prefix (pass > 0) and n_nan (pass 0) are required%s");
   static const bool runs = [] { const char* e = getenv("L2HMC_ORDER_STATS_RUNS"); return e && e[0] && e[0] != '0'; }();
   hipStream_t s = (hipStream_t)stream;
-  hipError_t e = hipMemsetAsync(hist, 0, (size_t)n_ranks * d * kOsBins * sizeof(int64_t), s);
+  hipError_t e = hipMemsetAsync(hist, 0, (size_t)n_ranks * d * kRadixBins * sizeof(int64_t), s);
   if (e == hipSuccess && pass == 0) e = hipMemsetAsync(n_nan, 0, (size_t)d * sizeof(int64_t), s);
   if (e != hipSuccess) return fail(L2HMC_ERR_HIP, "hipMemsetAsync: %s", hipGetErrorString(e));
   switch (p.rg) {
@@ -284,12 +238,12 @@ int l2hmc_order_stats_advance(const int64_t* hist, int64_t* remaining, uint32_t*
                               int32_t pass, float* values, void* stream) {
   OrderStatsPlan p;
   if (!order_stats_plan("l2hmc_order_stats_advance", 1, d, n_ranks, pass, p)) return L2HMC_ERR_ARG;
-  if (!hist || !remaining || !prefix || (pass == kOsPasses - 1 && !values))
+  if (!hist || !remaining || !prefix || (pass == kRadixPasses - 1 && !values))
     return fail(L2HMC_ERR_ARG, "l2hmc_order_stats_advance: hist, remaining, prefix and values (last pass) are required%s");
   const int n = n_ranks * d;
-  hipLaunchKernelGGL(order_advance_kernel, dim3((unsigned)n), dim3(64), 0, (hipStream_t)stream,
-                     (const long long*)hist, (long long*)remaining, prefix, n, 32 - kOsBits * (pass + 1),
-                     pass == kOsPasses - 1 ? values : (float*)nullptr);
+  hipLaunchKernelGGL(radix_advance_kernel, dim3((unsigned)n), dim3(64), 0, (hipStream_t)stream,
+                     (const long long*)hist, (long long*)remaining, prefix, n, 32 - kRadixBits * (pass + 1),
+                     pass == kRadixPasses - 1 ? values : (float*)nullptr);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(L2HMC_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
   return L2HMC_OK;
@@ -303,16 +257,16 @@ int l2hmc_order_stats(const float* X, int64_t n_draws, int32_t d, const int64_t*
     return fail(L2HMC_ERR_ARG, "l2hmc_order_stats: X, ranks, values, n_nan and workspace are required%s");
   const int64_t n = (int64_t)n_ranks * d;
   int64_t* hist = (int64_t*)workspace;
-  int64_t* remaining = hist + n * kOsBins;
+  int64_t* remaining = hist + n * kRadixBins;
   uint32_t* prefix = (uint32_t*)(remaining + n);
   hipStream_t s = (hipStream_t)stream;
   hipError_t e = hipMemcpyAsync(remaining, ranks, (size_t)n * sizeof(int64_t), hipMemcpyDeviceToDevice, s);
   if (e == hipSuccess) e = hipMemsetAsync(prefix, 0, (size_t)n * sizeof(uint32_t), s);
   if (e != hipSuccess) return fail(L2HMC_ERR_HIP, "l2hmc_order_stats: %s", hipGetErrorString(e));
-  for (int pass = 0; pass < kOsPasses; ++pass) {
+  for (int pass = 0; pass < kRadixPasses; ++pass) {
     int rc = l2hmc_order_stats_count(X, n_draws, d, n_ranks, pass, prefix, hist, pass == 0 ? n_nan : nullptr, stream);
     if (rc != L2HMC_OK) return rc;
-    rc = l2hmc_order_stats_advance(hist, remaining, prefix, d, n_ranks, pass, pass == kOsPasses - 1 ? values : nullptr, stream);
+    rc = l2hmc_order_stats_advance(hist, remaining, prefix, d, n_ranks, pass, pass == kRadixPasses - 1 ? values : nullptr, stream);
     if (rc != L2HMC_OK) return rc;
   }
   return L2HMC_OK;

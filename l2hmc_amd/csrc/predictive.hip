@@ -8,34 +8,24 @@
 // with the reduction over draws.
 //
 // Work unit = one WAVE: a group of NB consecutive 16-row data blocks x a chunk of consecutive 16-draw tiles.  The wave keeps the
-// XA fragments and labels of its data blocks in registers for the whole launch and streams the draw tiles past them:
-//   stage    a tile is 16 d contiguous floats of W whatever d is.  The lanes load it with coalesced SCALAR loads (the base of a
-//            history slice is only 4-byte aligned) -- element e of the tile is (draw e / d, feature e % d), walked without a
-//            division -- one tile ahead of its use, and write it to the wave's own LDS region as [16 draws][16 NTM + 4];
-//            elements past the end of W are written as 0 (their draws are masked below), feature columns d .. 16 NTM - 1 are
-//            zeroed once and never written: they contribute nothing to the contraction;
-//   contract lane (c, q) reads the B operand {w[16 t + c][16 tg + 4 q + r]} with one 16-byte LDS read per feature tile and gets
-//            L^T[i, c] in C/D layout: logits of draw c, rows 4 q + r of each of its data blocks;
+// XA fragments and labels of its data blocks in registers for the whole launch and streams the draw tiles past them; the tile
+// loop -- load one tile ahead, stage into the wave's own LDS region, contract, and the end-of-wave reduction -- is the one of
+// draw_tiles.hpp, shared with loo.hip.  Here, per tile:
 //   sum      each of p1, lik, ll is converted to float64 and added to the lane's own sum of (draw lane c, row 4 q + r); ll^2 is
 //            formed and added in float64 (one fma).  A draw at or past S is EXCLUDED by a select on the lane (a zero draw would
 //            add p1 = 0.5 and ll = -log 2).  No float32 partial sums anywhere.
-// The LDS region is private to the wave (LDS operations of a wave execute in order; wavefront fences keep the compiler from
-// moving them), so the main loop has no workgroup barrier and the four waves of a workgroup are independent units.
-//   end      once per wave the 16 draw lanes are added through LDS in the order c = 0 .. 15 and the 16 NB rows x 4 sums go to
-//            workspace[chunk][4][n]; rows at or past n are never written.
-//   pass 2   predict_reduce_kernel: sums[k][i] = the chunks' partials added in chunk order.  No floating-point atomics: two
+// The main loop has no workgroup barrier and the four waves of a workgroup are independent units.
+//   end      the 16 NB rows x 4 sums go to workspace[chunk][4][n]; rows at or past n are never written.
+//   pass 2   chunk_reduce_kernel: sums[k][i] = the chunks' partials added in chunk order.  No floating-point atomics: two
 //            calls give identical bits.
 // Units are ordered (chunk, group) with the group fastest, so the waves of a workgroup read the same draws.  The planner aims
 // for kPredictUnits waves: at S large / n small the chunks supply them, at n large / S small the data-block groups do.
-//
-// TWIN: loo.hip (loo_load / loo_stage / loo_logits and its end reduction) restates this tile loop for the PSIS-LOO passes; a
-// fix to the staging walk or to its register trick belongs in both until they share a header.
 //
 // Occupancy by design: 2 waves per SIMD (8 per CU) -- the main kernel must stay within 256 registers (held by
 // tests/test_predictive_cpu.py from the compiler's listing); its LDS (at most 4 x 8448 bytes per workgroup) never limits that.
 // Geometries <NTM feature tiles compiled, NB data blocks per wave>: <1, 4>, <2, 4>, <4, 2>, <8, 2> -- 32 NB registers of
 // float64 sums and 4 NTM NB of fragments per lane.
-#include "l2hmc_kernels.hpp"
+#include "draw_tiles.hpp"
 
 namespace l2hmc {
 
@@ -49,13 +39,7 @@ struct PredictPlan {
 };
 
 static bool predict_plan(const char* who, int64_t n_draws, int32_t n_data, int32_t d, PredictPlan& p) {
-  if (n_draws < 2) { fail(L2HMC_ERR_ARG, "%s: n_draws >= 2 (got %lld)", who, n_draws); return false; }
-  if (n_data < 1 || n_data > kLogisticMaxRows) {
-    fail(L2HMC_ERR_ARG, "%s: 1 <= n_data <= 1048576 (got %lld)", who, n_data);
-    return false;
-  }
-  if (d < 1 || d > kLogisticMaxDim) { fail(L2HMC_ERR_ARG, "%s: 1 <= d <= 128 (got %lld)", who, d); return false; }
-  if (n_draws > (1LL << 40) / d) { fail(L2HMC_ERR_ARG, "%s: draws too large (n_draws d > 2^40)", who); return false; }
+  if (!logistic_history_args_ok(who, n_draws, n_data, d)) return false;
   p.NT = tiles_of(d);
   p.NTM = p.NT <= 2 ? p.NT : p.NT <= 4 ? 4 : 8;
   p.NB = p.NTM <= 2 ? 4 : 2;
@@ -70,41 +54,25 @@ static bool predict_plan(const char* who, int64_t n_draws, int32_t n_data, int32
   return true;
 }
 
-__device__ __forceinline__ void wave_lds_fence() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 template <int NTM, int NB>
 __global__ __launch_bounds__(kPredictThreads) void predict_kernel(const float* __restrict__ W, long long S, int d,
                                                                   const float* __restrict__ P, int n, int NT, int ngroups,
                                                                   long long nchunks, long long tpc,
                                                                   double* __restrict__ part) {
-  constexpr int STRIDE = 16 * NTM + 4;                       // floats per staged draw (a multiple of 4: 16-byte reads)
-  constexpr int REGION = 16 * STRIDE > 512 ? 16 * STRIDE : 512;   // per wave; the end reduction needs 256 doubles
-  constexpr int NLD = 4 * NTM;                               // loads per lane and tile: 64 NLD >= 16 d
+  constexpr int REGION = tile_region(NTM);
   __shared__ __attribute__((aligned(16))) float lds_all[4 * REGION];
   // (the wave index through readfirstlane: the unit, its group and chunk and every test on them are then scalar)
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, c = lane & 15, q = lane >> 4;
   const long long u = (long long)blockIdx.x * 4 + w;
   if (u >= (long long)ngroups * nchunks) return;             // (no workgroup barrier anywhere: a wave may leave alone)
   float* lds = lds_all + w * REGION;
-#pragma unroll
-  for (int i = 0; i < REGION / 64; ++i) lds[lane + 64 * i] = 0.f;      // (REGION is a multiple of 64)
+  tile_region_clear<NTM>(lds, lane);
 
   const int group = (int)(u % ngroups);
   const long long chunk = u / ngroups;
-  const int nblk = (n + 15) >> 4, b0 = group * NB, BS = logistic_block_floats(NT);
+  const int nblk = (n + 15) >> 4, b0 = group * NB;
   f4 xa[NB][NTM], yv[NB];
-#pragma unroll
-  for (int j = 0; j < NB; ++j) {
-    const bool live = b0 + j < nblk;
-    const float* blk = P + (size_t)(live ? b0 + j : nblk - 1) * BS;
-#pragma unroll
-    for (int tg = 0; tg < NTM; ++tg) xa[j][tg] = (live && tg < NT) ? lds4(blk + (tg * 64 + lane) * 4) : splat(0.f);
-    yv[j] = lds4(blk + 512 * NT + 4 * q);
-  }
+  block_fragments<NTM, NB>(P, NT, b0, nblk, lane, xa, yv);
   double acc[NB][4][4];
 #pragma unroll
   for (int j = 0; j < NB; ++j)
@@ -113,60 +81,19 @@ __global__ __launch_bounds__(kPredictThreads) void predict_kernel(const float* _
 #pragma unroll
       for (int r = 0; r < 4; ++r) acc[j][k][r] = 0.0;
 
-  const long long ntiles = (S + 15) >> 4, total = S * d;
+  const long long ntiles = (S + 15) >> 4;
   const long long t0 = chunk * tpc, t1 = t0 + tpc < ntiles ? t0 + tpc : ntiles;
-  const int tile_elems = 16 * d;
-  // element e = lane + 64 i of a tile is (draw e / d, feature e % d): the lane's walk over i, without a division per element
-  const int row0 = lane / d, col0 = lane - row0 * d, dq = 64 / d, dr = 64 - dq * d;
-  float pre[NLD];
-#pragma unroll
-  for (int i = 0; i < NLD; ++i) {
-    const int e = lane + 64 * i;
-    const long long g = t0 * tile_elems + e;
-    pre[i] = (e < tile_elems && g < total) ? W[g] : 0.f;
-  }
+  const TileWalk walk = tile_walk(lane, d, S);
+  float pre[4 * NTM];
+  tile_load<NTM>(W, t0, walk, lane, pre);
 
   for (long long t = t0; t < t1; ++t) {
-    {
-      // the walk's LDS addresses depend on the lane alone; seen as loop invariants they are hoisted out of the tile loop and
-      // held in NLD vector registers across it.  They cost three integer operations each: recompute them per tile.
-      int row = row0, col = col0;
-      asm volatile("" : "+v"(row), "+v"(col));
-#pragma unroll
-      for (int i = 0; i < NLD; ++i) {
-        if (lane + 64 * i < tile_elems) lds[row * STRIDE + col] = pre[i];
-        row += dq;
-        col += dr;
-        if (col >= d) { col -= d; row += 1; }
-      }
-    }
+    tile_stage<NTM>(lds, pre, walk, lane);
     wave_lds_fence();
-    // the logits of every data block of the wave, one feature tile of the draws (one 16-byte LDS read) at a time
     f4 Lg[NB];
-#pragma unroll
-    for (int j = 0; j < NB; ++j) Lg[j] = splat(0.f);
-#pragma unroll
-    for (int tg = 0; tg < NTM; ++tg) {
-      if (tg < NT) {                                         // wave-uniform, like the block test: the MFMAs run with every lane
-        const f4 B = lds4(lds + c * STRIDE + 16 * tg + 4 * q);
-#pragma unroll
-        for (int j = 0; j < NB; ++j) {
-          if (b0 + j < nblk) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) Lg[j] = MFMA16(xa[j][tg][r], B[r], Lg[j]);
-          }
-        }
-      }
-    }
+    tile_logits<NTM, NB>(lds, xa, c, q, NT, b0, nblk, Lg);
     wave_lds_fence();
-    if (t + 1 < t1) {                                        // the next tile's loads fly during this tile's arithmetic
-#pragma unroll
-      for (int i = 0; i < NLD; ++i) {
-        const int e = lane + 64 * i;
-        const long long g = (t + 1) * tile_elems + e;
-        pre[i] = (e < tile_elems && g < total) ? W[g] : 0.f;
-      }
-    }
+    if (t + 1 < t1) tile_load<NTM>(W, t + 1, walk, lane, pre);           // in flight during this tile's arithmetic
     const bool valid = 16 * t + c < S;
 #pragma unroll
     for (int j = 0; j < NB; ++j) {
@@ -193,37 +120,7 @@ __global__ __launch_bounds__(kPredictThreads) void predict_kernel(const float* _
     }
   }
 
-  // the 16 draw lanes of every (data block, sum, row), added in the order c = 0 .. 15
-  double* red = reinterpret_cast<double*>(lds);
-#pragma unroll
-  for (int j = 0; j < NB; ++j) {
-    if (b0 + j < nblk) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        wave_lds_fence();
-#pragma unroll
-        for (int r = 0; r < 4; ++r) red[c * 16 + 4 * q + r] = acc[j][k][r];
-        wave_lds_fence();
-        if (lane < 16) {
-          double a = red[lane];
-#pragma unroll
-          for (int cc = 1; cc < 16; ++cc) a += red[cc * 16 + lane];
-          const int row = 16 * (b0 + j) + lane;
-          if (row < n) part[(chunk * 4 + k) * (long long)n + row] = a;
-        }
-      }
-    }
-  }
-}
-
-// sums[i] = the chunks' partials of entry i = k n + row, added in chunk order
-__global__ void predict_reduce_kernel(const double* __restrict__ part, long long nchunks, long long m,
-                                      double* __restrict__ sums) {
-  const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= m) return;
-  double a = 0.0;
-  for (long long ch = 0; ch < nchunks; ++ch) a += part[ch * m + i];
-  sums[i] = a;
+  tile_sums_out<NB, 4>(lds, acc, lane, b0, nblk, n, chunk, part);
 }
 
 }  // namespace l2hmc
@@ -259,9 +156,7 @@ int l2hmc_logistic_predict(const float* draws, int64_t n_draws, int32_t d, const
     default: L2HMC_PREDICT_LAUNCH(8, 2); break;
   }
 #undef L2HMC_PREDICT_LAUNCH
-  const long long m = 4LL * n_data;
-  hipLaunchKernelGGL(predict_reduce_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, (const double*)workspace,
-                     p.nchunks, m, sums);
+  chunk_reduce_launch(workspace, p.nchunks, 4LL * n_data, sums, s);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(L2HMC_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
   return L2HMC_OK;

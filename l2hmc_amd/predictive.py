@@ -76,13 +76,12 @@ def _check(draws, X, y):
     return S, d, xs[0]
 
 
-def _device_sums(draws, X, y, S, d, n):
+def _device_packer(dev, X, y, n, d, who):
+    """`pack(a, m)`: rows [a, a + m) of (X, y) on `dev` as `l2hmc_pack_logistic` packs them.  The limits are checked, the data
+    moved and the labels validated once, here (y=None: zeros, which need no look and so no device synchronisation)."""
     import torch
     if n > MAX_DEVICE_ROWS or d > MAX_DEVICE_DIM:
-        raise ValueError("the predictive kernel holds n_rows <= %d and dim <= %d (got %d, %d)"
-                         % (MAX_DEVICE_ROWS, MAX_DEVICE_DIM, n, d))
-    dev = draws.device
-    W = in_place(draws)
+        raise ValueError("%s n_rows <= %d and dim <= %d (got %d, %d)" % (who, MAX_DEVICE_ROWS, MAX_DEVICE_DIM, n, d))
     Xd = torch.as_tensor(X).detach().to(device=dev, dtype=torch.float32).contiguous()
     if y is None:
         yd = torch.zeros(n, dtype=torch.float32, device=dev)
@@ -91,8 +90,20 @@ def _device_sums(draws, X, y, S, d, n):
         if not bool(((yd == 0) | (yd == 1)).all()):
             raise ValueError("labels y must be 0 or 1")
     L = _ffi.lib()
-    packed = workspace(dev, torch.float32, L.l2hmc_packed_logistic_floats, n, d)
-    launch(dev, L.l2hmc_pack_logistic, Xd.data_ptr(), yd.data_ptr(), n, d, packed.data_ptr())
+
+    def pack(a, m):
+        packed = workspace(dev, torch.float32, L.l2hmc_packed_logistic_floats, m, d)
+        launch(dev, L.l2hmc_pack_logistic, Xd[a:a + m].data_ptr(), yd[a:a + m].data_ptr(), m, d, packed.data_ptr())
+        return packed
+    return pack
+
+
+def _device_sums(draws, X, y, S, d, n):
+    import torch
+    dev = draws.device
+    packed = _device_packer(dev, X, y, n, d, "the predictive kernel holds")(0, n)
+    W = in_place(draws)
+    L = _ffi.lib()
     ws = workspace(dev, torch.float64, L.l2hmc_logistic_predict_workspace_doubles, S, n, d)
     sums = torch.empty((4, n), dtype=torch.float64, device=dev)
     launch(dev, L.l2hmc_logistic_predict, W.data_ptr(), S, d, packed.data_ptr(), n, sums.data_ptr(), ws.data_ptr())
@@ -200,31 +211,19 @@ def loo_tail_len(S):
     return min(S // 5, math.isqrt(9 * S - 1) + 1) if S >= 1 else 0
 
 
-def _device_labels(X, y, dev):
-    import torch
-    Xd = torch.as_tensor(X).detach().to(device=dev, dtype=torch.float32).contiguous()
-    yd = torch.as_tensor(y).detach().to(device=dev, dtype=torch.float32).contiguous()
-    if not bool(((yd == 0) | (yd == 1)).all()):
-        raise ValueError("labels y must be 0 or 1")
-    return Xd, yd
-
-
 def _device_tail_groups(draws, X, y, S, d, n, max_tail_bytes):
     """The raw dict of one group of consecutive rows at a time, on the device; a group's tail stays under `max_tail_bytes`."""
     import torch
-    if n > MAX_DEVICE_ROWS or d > MAX_DEVICE_DIM:
-        raise ValueError("the LOO kernels hold n_rows <= %d and dim <= %d (got %d, %d)" % (MAX_DEVICE_ROWS, MAX_DEVICE_DIM, n, d))
     dev = draws.device
+    pack = _device_packer(dev, X, y, n, d, "the LOO kernels hold")
     W = in_place(draws)
-    Xd, yd = _device_labels(X, y, dev)
     L = _ffi.lib()
     M = _ffi.check(L.l2hmc_logistic_loo_tail_len(S))
     rows = max(1, min(n, int(max_tail_bytes) // max(1, 4 * M), (1 << 31) // max(1, M)))
     flags = []                                               # every group's error word, read once after the last group
     for a in range(0, n, rows):
         m = min(rows, n - a)
-        packed = workspace(dev, torch.float32, L.l2hmc_packed_logistic_floats, m, d)
-        launch(dev, L.l2hmc_pack_logistic, Xd[a:a + m].data_ptr(), yd[a:a + m].data_ptr(), m, d, packed.data_ptr())
+        packed = pack(a, m)
         ws = workspace(dev, torch.uint8, L.l2hmc_logistic_loo_workspace_bytes, S, m, d)
         cutoff = torch.empty(m, dtype=torch.float32, device=dev)
         n_tail = torch.empty(m, dtype=torch.int64, device=dev)
@@ -459,25 +458,28 @@ def _loo_summary(khat, elpd_i, lppd_i, n_tail, S, M):
                    n_underflow=int(np.sum(np.isneginf(lppd_i))))
 
 
-def _finish_rows(tails):
-    """(khat, elpd_loo_i, lppd_i, n_tail) as float64 / int64 numpy of one raw dict, in row chunks of bounded memory, computed
-    where the tails lie; only these O(n) numbers come to the host."""
+def _row_chunks(tails, rows_for, middle):
+    """(khat, elpd_loo_i, lppd_i, n_tail) as float64 / int64 numpy of one raw dict: `middle(xp, cutoff, n_tail, tail, body,
+    sum_lik, S, M)` on chunks of `rows_for(M)` rows, computed where the tails lie; only these O(n) numbers come to the host."""
     S, M = int(tails["n_draws"]), int(tails["tail_len"])
     if S < 2:
         raise ValueError("PSIS-LOO needs >= 2 draws (got %d)" % S)
     xp = _Torch() if is_device_tensor(tails["tail"]) else _Numpy()
     keys = ("cutoff", "n_tail", "tail", "body", "sum_lik")
     arrays = [tails[k] if isinstance(xp, _Torch) else np.asarray(tails[k]) for k in keys]
-    n = int(arrays[0].shape[0])
-    n_theta = 30 + int(np.floor(np.sqrt(max(M, 1))))
-    rows = max(1, _FINISH_CHUNK_BYTES // (8 * n_theta * max(M, 1)))
+    n, rows = int(arrays[0].shape[0]), max(1, rows_for(M))
     out = [[], [], []]
     with np.errstate(all="ignore"):
         for a in range(0, n, rows):
-            res = _loo_rows(xp, *(v[a:a + rows] for v in arrays), S, M)
-            for o, r in zip(out, res):
+            for o, r in zip(out, middle(xp, *(v[a:a + rows] for v in arrays), S, M)):
                 o.append(xp.host(r))
     return tuple(np.concatenate(o) for o in out) + (np.asarray(xp.host(arrays[1]), dtype=np.int64),)
+
+
+def _finish_rows(tails):
+    """`_loo_rows` in row chunks of bounded memory: the (rows, theta grid, tail) block of the Pareto profile."""
+    n_theta = lambda M: 30 + int(np.floor(np.sqrt(max(M, 1))))  # noqa: E731
+    return _row_chunks(tails, lambda M: _FINISH_CHUNK_BYTES // (8 * n_theta(M) * max(M, 1)), _loo_rows)
 
 
 def _check_finish(finish, on_device):
@@ -491,27 +493,20 @@ def _check_finish(finish, on_device):
 _KERNEL_FINISH_BYTES = 1 << 28  # the float64 (rows, M) log ratios formed at a time by the kernel finish
 
 
-def _finish_rows_kernel(tails):
-    """`_finish_rows` of device tails with the middle on csrc/psis.hip: `torch.sort` of the float32 tail, lam = softplus(-t) in
-    float64 torch, `psis.smooth_tails`, and the O(n) combine of `_loo_rows` -- in row chunks of bounded memory, whose bits do
-    not depend on the chunking."""
+def _loo_rows_kernel(xp, cutoff, n_tail, tail, body, sum_lik, S, M):
+    """`_loo_rows` with the middle on csrc/psis.hip: `torch.sort` of the float32 tail, lam = softplus(-t) in float64 torch,
+    `psis.smooth_tails`, and the O(n) combine."""
     from .psis import smooth_tails
-    S, M = int(tails["n_draws"]), int(tails["tail_len"])
-    if S < 2:
-        raise ValueError("PSIS-LOO needs >= 2 draws (got %d)" % S)
-    xp = _Torch()
-    arrays = [tails[k] for k in ("cutoff", "n_tail", "tail", "body", "sum_lik")]
-    n = int(arrays[0].shape[0])
-    rows = max(1, _KERNEL_FINISH_BYTES // (8 * max(M, 1)))
-    out = [[], [], []]
-    for a in range(0, n, rows):
-        cutoff, n_tail, tail, body, sum_lik = (v[a:a + rows] for v in arrays)
-        c, Lf, lam_c, lam = _loo_prepare(xp, cutoff, n_tail, tail)
-        khat, lse_w, lse_wl = smooth_tails(lam, n_tail, lam_c)
-        lam_max = xp.where(Lf > 0, lam[:, 0], lam_c) if M else lam_c
-        for o, r in zip(out, _loo_combine(xp, khat, lam_max, lse_w, lse_wl, c, Lf, body, sum_lik, S)):
-            o.append(xp.host(r))
-    return tuple(np.concatenate(o) for o in out) + (np.asarray(xp.host(arrays[1]), dtype=np.int64),)
+    c, Lf, lam_c, lam = _loo_prepare(xp, cutoff, n_tail, tail)
+    khat, lse_w, lse_wl = smooth_tails(lam, n_tail, lam_c)
+    lam_max = xp.where(Lf > 0, lam[:, 0], lam_c) if M else lam_c
+    return _loo_combine(xp, khat, lam_max, lse_w, lse_wl, c, Lf, body, sum_lik, S)
+
+
+def _finish_rows_kernel(tails):
+    """`_finish_rows` of device tails by `_loo_rows_kernel`, in row chunks of bounded memory (the float64 (rows, M) log ratios),
+    whose bits do not depend on the chunking."""
+    return _row_chunks(tails, lambda M: _KERNEL_FINISH_BYTES // (8 * max(M, 1)), _loo_rows_kernel)
 
 
 def loo_finish(tails, finish="torch"):

@@ -216,7 +216,7 @@ def test_new_kernels_use_no_scratch_and_keep_their_occupancy():
         pytest.skip("no compiler listings under l2hmc_amd/csrc/build/asm (library built elsewhere)")
     names = {k for k, _, _, _ in rows}
     want = {"loo_kernel<%d, %d>" % (g, m) for g in (1, 2, 4, 8) for m in (0, 1)}
-    want |= {"loo_advance_kernel", "loo_init_kernel", "loo_reduce_kernel"}
+    want |= {"radix_advance_kernel", "loo_init_kernel", "chunk_reduce_kernel"}
     assert want <= names, names
     header = open(os.path.join(ROOT, "l2hmc_amd", "csrc", "loo.hip")).read()
     assert "2 waves per SIMD" in header and "ONE device function" in header

@@ -159,7 +159,7 @@ def test_new_kernels_use_no_scratch_and_keep_their_occupancy():
     if not rows:
         pytest.skip("no compiler listings under l2hmc_amd/csrc/build/asm (library built elsewhere)")
     names = {k for k, _, _, _ in rows}
-    want = {"predict_kernel<%d, %d>" % g for g in ((1, 4), (2, 4), (4, 2), (8, 2))} | {"predict_reduce_kernel"}
+    want = {"predict_kernel<%d, %d>" % g for g in ((1, 4), (2, 4), (4, 2), (8, 2))} | {"chunk_reduce_kernel"}
     assert want <= names, names
     header = open(os.path.join(ROOT, "l2hmc_amd", "csrc", "predictive.hip")).read()
     assert "2 waves per SIMD" in header

@@ -206,7 +206,7 @@ def test_order_statistics_kernels_use_no_scratch():
     if not rows:
         pytest.skip("no compiler listings under l2hmc_amd/csrc/build/asm (library built elsewhere)")
     names = {k for k, _, _, _ in rows}
-    assert "order_advance_kernel" in names and any(k.startswith("order_count_kernel<") for k in names), names
+    assert "radix_advance_kernel" in names and any(k.startswith("order_count_kernel<") for k in names), names
     for k, vg, sc, _ in rows:
         assert sc == 0 and vg <= 256, (k, vg, sc)
     assert {"chain_moments_below_kernel", "chain_lagsum_below_kernel"} <= {k for k, _, _, _ in res["chain_stats.s"]}

@@ -19,7 +19,7 @@ ASM = os.path.join(ROOT, "l2hmc_amd", "csrc", "build", "asm")
 def demangle_short(name):
     m = re.match(r"_ZN5l2hmc\d+([A-Za-z_0-9]+?)I(.*)EEv", name)
     if not m:
-        m2 = re.match(r"_ZN5l2hmc\d+([A-Za-z_0-9]+?)E", name)
+        m2 = re.match(r"_ZN5l2hmcL?\d+([A-Za-z_0-9]+?)E", name)       # (L: internal linkage, a kernel defined in a shared header)
         return m2.group(1) if m2 else name
     args = re.findall(r"L([ib])(\d+)E", m.group(2))
     return "%s<%s>" % (m.group(1), ", ".join(("true" if v == "1" else "false") if t == "b" else v for t, v in args))

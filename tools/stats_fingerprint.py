@@ -6,10 +6,13 @@ versions of `l2hmc_amd/*.py` on ONE build of the library (`L2HMC_LIB=`): a host-
 
     python tools/stats_fingerprint.py                       # numpy, a CPU tensor and, with a GPU, four forms of a device tensor
     python tools/stats_fingerprint.py --cpu                 # the host inputs only
+    python tools/stats_fingerprint.py --kernels             # the device kernels that share csrc/draw_tiles.hpp and radix_select.hpp
     python tools/stats_fingerprint.py --ranks 2 --backend gloo|nccl --input numpy|device      # chains sharded 2 | 4
     python tools/stats_fingerprint.py --time                # median host time of `describe` on the tiny device history
 
-The history is a seeded AR(1) of 40 steps, 6 chains and 3 coordinates whose means and scales differ per coordinate."""
+The history is a seeded AR(1) of 40 steps, 6 chains and 3 coordinates whose means and scales differ per coordinate.  `--kernels`
+runs ONE version of the Python against two builds of the library instead: `pointwise_sums`, `loo_tails` and `order_statistics`
+are declared bitwise reproducible, so a refactor of their kernels must leave every line as it was too."""
 import argparse
 import hashlib
 import os
@@ -28,6 +31,10 @@ STEPS, CHAINS, DIM, ROWS, SCALE = 40, 6, 3, 5, 1.7
 SPLIT = 2                                 # --ranks 2: rank 0 holds chains [0, 2), rank 1 chains [2, 6)
 RANKS33 = np.arange(33) * 7               # 33 ranks: two chunks of at most 32
 PROBS = (0.1, 0.5, 0.9)
+# (S, n, d) of tests/loo_case.case, the smallest shapes that reach every branch of the shared tile loop: 1, 2, 4, 8 compiled
+# feature tiles; two row groups of the predict plan at four blocks per wave; five tiles per chunk with a last tile of 9 draws, a
+# last chunk of one tile and dead waves; no tail at all (M = 0)
+KERNEL_SHAPES = ((70, 35, 5), (523, 33, 17), (70, 35, 40), (300, 50, 128), (4099, 100, 25), (65609, 33, 1), (4, 3, 2))
 
 
 def history():
@@ -77,7 +84,29 @@ def cases(X):
     yield "waic", lambda: predictive.waic(X, rx, ry)
     yield "predict_proba", lambda: predictive.predict_proba(X, rx)
     yield "log_predictive_density", lambda: predictive.log_predictive_density(X, rx, ry)
+    yield "loo", lambda: predictive.loo(X, rx, ry)
     yield "acl_spectrum", lambda: func_utils.acl_spectrum(X, SCALE)
+
+
+def kernels():
+    """One line per (statistic, shape) of the kernels behind `pointwise_sums`, `loo_tails` and `order_statistics`."""
+    from tests import loo_case
+    torch.cuda.set_device(0)
+    inputs = []
+    for S, n, d in KERNEL_SHAPES:
+        inputs.append(("(%d, %d, %d)" % (S, n, d),) + tuple(torch.as_tensor(a).cuda() for a in loo_case.case(S, n, d)))
+    W, X, y = (torch.as_tensor(a).cuda() for a in loo_case.case(40 * 13, 33, 17))
+    hist = W.reshape(40, 13, 17)[3:]                          # a base that is not 16-byte aligned
+    assert hist.is_contiguous() and hist.data_ptr() % 16
+    inputs.append(("(40, 13, 17)[3:], 33 rows", hist, X, y))
+    for label, W, X, y in inputs:
+        S = W.numel() // W.shape[-1]
+        ranks = np.unique([0, 1, S // 3, S // 2, S - 2, S - 1])
+        tails = predictive.loo_tails(W, X, y)
+        tails["tail"] = torch.sort(tails["tail"], dim=-1).values                    # its slot order is arrival order
+        for name, res in (("pointwise_sums", predictive.pointwise_sums(W, X, y)), ("loo_tails", tails),
+                          ("order_statistics", quantiles.order_statistics(W, ranks))):
+            print("%s  %s %s" % (sha(res), name, label), flush=True)
 
 
 def device_inputs(X, dev):
@@ -169,6 +198,7 @@ def timed():
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--cpu", action="store_true", help="numpy and CPU-tensor inputs only (no GPU needed)")
+    ap.add_argument("--kernels", action="store_true", help="the device kernels of predictive and quantiles, shape by shape")
     ap.add_argument("--ranks", type=int, default=1)
     ap.add_argument("--backend", default="gloo", choices=("gloo", "nccl"))
     ap.add_argument("--input", default="numpy", choices=("numpy", "device"))
@@ -176,6 +206,8 @@ def main():
     a = ap.parse_args()
     if a.time:
         timed()
+    elif a.kernels:
+        kernels()
     elif a.ranks > 1:
         sharded(a.ranks, a.backend, a.input == "device")
     else:
