@@ -79,6 +79,7 @@ __device__ __forceinline__ void lds_poison(float* smem) {
 #endif
 }
 int check_energy(const L2hmcEnergy* e, int d);
+int device_cus();      // l2hmc_abi.hip: compute units of the current device (256 when the query fails)
 struct KArgs;
 // traj_wide.hip: the LDS plan of the LDS-resident-state kernel for d > 256 (elementwise energies) and its waves per workgroup
 long long plan_lds_wide(KArgs& k, int& NW);

@@ -281,7 +281,7 @@ struct Mlp3Ws {
   // pre-split bf16 planes (gemm_pl_kernel), NULL = the fp32 path: the weights of the two decoder-sized layers in both
   // orientations, and the activations that only ever feed the next product (a1, a2, the BCE gradient, d a2)
   unsigned short *pw2t, *pw3t, *pw2, *pw3, *pa1, *pa2, *plg, *pda2;
-  // the trainer's forward evaluations (vae_energy_keep): the same four weight matrices once more as f16x2 planes (two planes each),
+  // the trainer's forward evaluations (vae_energy with a DecPoint): the same four weight matrices once more as f16x2 planes (two planes each),
   // NULL = the forward pass uses the bf16x3 planes above like the reverse sweep
   unsigned short *pw2t_h, *pw3t_h, *pw2_h, *pw3_h;
 };
@@ -333,42 +333,65 @@ inline int bce_tiles_max(int n_pix) { return (n_pix + 63) / 64; }
 inline int pld(int K) { return ceil_to(K, 32); }
 inline long long prows(int N) { return ceil_to(N, XLP_TN); }
 
+// The decoder's share of one trajectory point, kept for the trainer's reverse sweep (train_split.hpp): s1, s2 (sigmoids =
+// softplus'), sigma' of the logits, and the raw reverse products b2 = r W3^T, b1 = c2 W2^T (r = sigmoid(logit) - aux, c2 = s2 b2)
+struct DecPoint { float *s1, *s2, *rd, *b2, *b1; };
+__global__ void k_sigd(const float* r, const float* t, float* out, long long n);     // train_split.hpp
+
 // U (N) and grad (N x d, row stride ldg) of the VAE latent posterior at z (row stride ldz) (mnist_vae.py:122-126):
 // six GEMMs, every bias / softplus / sigmoid / BCE / chain-rule product fused into their epilogues; lg (N x n_pix)
 // and rowsum (N x 2 tiles) are scratch.  The transposed decoder weights must already be in ws (mlp3_transposes).
+// With `pt` the point's DecPoint is left behind: the sigmoids go to pt, lg is written in fp32 on the planes path too (k_sigd
+// reads it) and the two reverse products leave their raw form through C2; the weight planes are the f16x2 ones where ws has them.
 // Returns the first error of the pre-split launches (their LDS-size request can be refused by a device), L2HMC_OK otherwise.
 int vae_energy(hipStream_t s, const L2hmcMlp3& dec, const float* aux, const float* z, int ldz, long long N, int d,
-               const Mlp3Ws& ws, float* lg, float* rowsum, float* U, double* Ud, float* grad, int ldg, float beta = 1.f) {
+               const Mlp3Ws& ws0, float* lg, float* rowsum, float* U, double* Ud, float* grad, int ldg, float beta = 1.f,
+               const DecPoint* pt = nullptr) {
+  Mlp3Ws ws = ws0;
+  if (pt != nullptr) { ws.s1 = pt->s1; ws.s2 = pt->s2; }
+  const long long npix = N * dec.n_out;
   if (ws.pa1 != nullptr) {
     int rc = L2HMC_OK, r1;
-    // ---- pre-split form (gemm_mode 1 at decoder sizes, gemm_xl.hpp): every activation that only feeds the next product is
-    //      written as bf16 planes by its producer's epilogue; the four decoder-sized products read planes on both sides.
-    //      Plane row strides are whole k-tiles (pld) and the weight planes whole tiles of rows (prows), zero-padded.
+    // ---- pre-split form (gemm_mode 1 / 3 at decoder sizes, gemm_xl.hpp): every activation that only feeds the next product is
+    //      written as planes by its producer's epilogue; the four decoder-sized products read planes on both sides
+    //      (gemm_xlp_kernel: bit-identical per product to the in-loop split).  Plane row strides are whole k-tiles (pld) and
+    //      the weight planes whole tiles of rows (prows), zero-padded.
     const int l1 = pld(dec.n_h1), l2 = pld(dec.n_h2), lo = pld(dec.n_out);
     const long long n1 = N * l1, n2 = N * l2, no = N * lo;
+    // (the trainer's gemm_mode 3: this evaluation is the SAMPLER's -- activations, logits, BCE gradients of O(1) -- and runs on
+    //  f16x2 planes like it, with the weights' f16 planes; the reverse sweep's tangents and adjoints keep bf16x3: t_plane_mode)
+    const int pm_keep = t_plane_mode;
+    const bool h16 = ws.pw2t_h != nullptr;
+    if (h16) t_plane_mode = 1;
+    const unsigned short *qw2t = h16 ? ws.pw2t_h : ws.pw2t, *qw3t = h16 ? ws.pw3t_h : ws.pw3t, *qw2 = h16 ? ws.pw2_h : ws.pw2,
+                         *qw3 = h16 ? ws.pw3_h : ws.pw3;
     GemmArgs g = gemm_args(z, ldz, ws.w1t, dec.n_in, nullptr, dec.n_h1, N, dec.n_h1, dec.n_in);
     g.bias = dec.b1; g.C2 = ws.s1; g.ldc2 = dec.n_h1; g.Cp = ws.pa1; g.cp_plane = n1; g.ldcp = l1;
     launch_gemm<EPI_BIAS_SOFTPLUS>(g, s, dec.n_in <= 64 ? SHAPE_MID : SHAPE_AUTO);                 // a1 (planes), s1
     g = gemm_args(nullptr, 0, nullptr, 0, nullptr, dec.n_h2, N, dec.n_h2, dec.n_h1);
-    g.Ap = ws.pa1; g.ap_plane = n1; g.ldap = l1; g.Bp = ws.pw2t; g.bp_plane = prows(dec.n_h2) * l1; g.ldbp = l1;
+    g.Ap = ws.pa1; g.ap_plane = n1; g.ldap = l1; g.Bp = qw2t; g.bp_plane = prows(dec.n_h2) * l1; g.ldbp = l1;
     g.bias = dec.b2; g.C2 = ws.s2; g.ldc2 = dec.n_h2; g.Cp = ws.pa2; g.cp_plane = n2; g.ldcp = l2;
-    if ((r1 = launch_gemm_planes<EPI_BIAS_SOFTPLUS>(g, s)) != L2HMC_OK) rc = rc ? rc : r1;                                                     // a2 (planes), s2
-    g = gemm_args(nullptr, 0, nullptr, 0, nullptr, dec.n_out, N, dec.n_out, dec.n_h2);
-    g.Ap = ws.pa2; g.ap_plane = n2; g.ldap = l2; g.Bp = ws.pw3t; g.bp_plane = prows(dec.n_out) * l2; g.ldbp = l2;
+    if ((r1 = launch_gemm_planes<EPI_BIAS_SOFTPLUS>(g, s)) != L2HMC_OK) rc = rc ? rc : r1;          // a2 (planes), s2
+    g = gemm_args(nullptr, 0, nullptr, 0, pt != nullptr ? lg : nullptr, dec.n_out, N, dec.n_out, dec.n_h2);
+    g.Ap = ws.pa2; g.ap_plane = n2; g.ldap = l2; g.Bp = qw3t; g.bp_plane = prows(dec.n_out) * l2; g.ldbp = l2;
     g.bias = dec.b3; g.E = aux; g.lde = dec.n_out; g.rowsum = rowsum; g.n_tiles = bce_tiles_planes(dec.n_out); g.beta = beta;
     g.Cp = ws.plg; g.cp_plane = no; g.ldcp = lo;
-    if ((r1 = launch_gemm_planes<EPI_BCE>(g, s)) != L2HMC_OK) rc = rc ? rc : r1;                                                               // beta (sigmoid(logit) - aux) (planes)
+    if ((r1 = launch_gemm_planes<EPI_BCE>(g, s)) != L2HMC_OK) rc = rc ? rc : r1;                    // beta (sigmoid(logit) - aux) (planes)
     if (U != nullptr || Ud != nullptr)
       launch_vae_U(s, rowsum, 2 * bce_tiles_planes(dec.n_out), z, ldz, d, U, Ud, N);
-    if (grad == nullptr) return rc;
+    if (pt != nullptr) hipLaunchKernelGGL(k_sigd, dim3(nblk(npix)), dim3(256), 0, s, lg, aux, pt->rd, npix);
+    if (grad == nullptr) { t_plane_mode = pm_keep; return rc; }
     g = gemm_args(nullptr, 0, nullptr, 0, nullptr, dec.n_h2, N, dec.n_h2, dec.n_out);
-    g.Ap = ws.plg; g.ap_plane = no; g.ldap = lo; g.Bp = ws.pw3; g.bp_plane = prows(dec.n_h2) * lo; g.ldbp = lo;
+    g.Ap = ws.plg; g.ap_plane = no; g.ldap = lo; g.Bp = qw3; g.bp_plane = prows(dec.n_h2) * lo; g.ldbp = lo;
     g.E = ws.s2; g.lde = dec.n_h2; g.Cp = ws.pda2; g.cp_plane = n2; g.ldcp = l2;
-    if ((r1 = launch_gemm_planes<EPI_MUL>(g, s)) != L2HMC_OK) rc = rc ? rc : r1;                                                               // d a2 (planes)
+    if (pt != nullptr) { g.C2 = pt->b2; g.ldc2 = dec.n_h2; }
+    if ((r1 = launch_gemm_planes<EPI_MUL>(g, s)) != L2HMC_OK) rc = rc ? rc : r1;                    // d a2 = s2 b2 (planes), b2
     g = gemm_args(nullptr, 0, nullptr, 0, ws.a1, dec.n_h1, N, dec.n_h1, dec.n_h2);
-    g.Ap = ws.pda2; g.ap_plane = n2; g.ldap = l2; g.Bp = ws.pw2; g.bp_plane = prows(dec.n_h1) * l2; g.ldbp = l2;
+    g.Ap = ws.pda2; g.ap_plane = n2; g.ldap = l2; g.Bp = qw2; g.bp_plane = prows(dec.n_h1) * l2; g.ldbp = l2;
     g.E = ws.s1; g.lde = dec.n_h1;
-    if ((r1 = launch_gemm_planes<EPI_MUL>(g, s)) != L2HMC_OK) rc = rc ? rc : r1;                                                               // d a1 (fp32: the K = 1024, N = d product reads it)
+    if (pt != nullptr) { g.C2 = pt->b1; g.ldc2 = dec.n_h1; }
+    if ((r1 = launch_gemm_planes<EPI_MUL>(g, s)) != L2HMC_OK) rc = rc ? rc : r1;                    // d a1 = s1 b1 (fp32: the K = 1024, N = d product reads it), b1
+    t_plane_mode = pm_keep;
     g = gemm_args(ws.a1, dec.n_h1, dec.W1, dec.n_h1, grad, ldg, N, d, dec.n_h1);
     g.E = z; g.lde = ldz;
     launch_gemm<EPI_ADD>(g, s, d <= 64 ? SHAPE_SKINNY : SHAPE_MID);
@@ -380,13 +403,16 @@ int vae_energy(hipStream_t s, const L2hmcMlp3& dec, const float* aux, const floa
   launch_gemm<EPI_BCE>(g, s);                                     // lg := beta (sigmoid(logit) - aux)
   if (U != nullptr || Ud != nullptr)
     launch_vae_U(s, rowsum, bce_partials(N, dec.n_out), z, ldz, d, U, Ud, N);
+  if (pt != nullptr) hipLaunchKernelGGL(k_sigd, dim3(nblk(npix)), dim3(256), 0, s, lg, aux, pt->rd, npix);
   if (grad == nullptr) return L2HMC_OK;
   // d a2 = dl W3^T (.) sigmoid(p2);  d a1 = d a2 W2^T (.) sigmoid(p1);  d z = d a1 W1^T + z
   g = gemm_args(lg, dec.n_out, dec.W3, dec.n_out, ws.a2, dec.n_h2, N, dec.n_h2, dec.n_out);
   g.E = ws.s2; g.lde = dec.n_h2;
+  if (pt != nullptr) { g.C2 = pt->b2; g.ldc2 = dec.n_h2; }
   launch_gemm<EPI_MUL>(g, s);
   g = gemm_args(ws.a2, dec.n_h2, dec.W2, dec.n_h2, ws.a1, dec.n_h1, N, dec.n_h1, dec.n_h2);
   g.E = ws.s1; g.lde = dec.n_h1;
+  if (pt != nullptr) { g.C2 = pt->b1; g.ldc2 = dec.n_h1; }
   launch_gemm<EPI_MUL>(g, s);
   g = gemm_args(ws.a1, dec.n_h1, dec.W1, dec.n_h1, grad, ldg, N, d, dec.n_h1);
   g.E = z; g.lde = ldz;
@@ -450,6 +476,285 @@ int check_mlp(const L2hmcMlp3* m, const char* what) {
   return L2HMC_OK;
 }
 
+// ---- the host path of the engine: what l2hmc_trajectory_split (below) and l2hmc_train_split_grad (train_split.hpp) share -----
+// the launch form of the S/T/Q net evaluations of a call (plan_nets)
+struct NetPlan {
+  int cb;                    // chain blocks of 16 per workgroup
+  unsigned blocks;
+  size_t ne_lds, nb_lds;     // dynamic LDS of net_eval_kernel / net_bwd_kernel (nb_lds = 0: no reverse in this call)
+  bool fused;                // one launch per evaluation (and per reverse); else three products each
+};
+// where an evaluation's hidden activations and raw head products go when the caller keeps them (the trainer's stash)
+struct NetKeep { float *h1, *h2, *out3; };
+
+// Everything both entry points derive from their argument block.  engine_target fills the upper half from the block alone
+// (nothing is dereferenced: the checks come after it), engine_bind the workspace views once the block has passed them.
+struct EngineCtx {
+  long long N;
+  int d, H, T, L;                                   // L = 2 d: row stride of [x | grad U] and [v_h | masked x]
+  hipStream_t s;
+  void* stream;                                     // the same stream as the callbacks and l2hmc_energy take it
+  bool user, builtin, vae, unets, hmc;              // energy by callback / built-in target / decoder posterior; nets by callback; HMC mode
+  const unsigned char* dir;
+  int dall;
+  const float *masks, *trig, *alpha, *aux;
+  float eps_host, beta, temp;                       // beta: bce_scale of the decoder posterior; temp: the decoder posterior is tempered behind
+  const L2hmcEnergy* energy;
+  L2hmcEnergyCallback energy_cb;
+  void* energy_cb_user;
+  L2hmcNetCallback net_cb;
+  void* net_cb_user;
+  const L2hmcMlp3 *dec, *enc;
+  const L2hmcNet* nets[2];                          // [X, V]; an empty net (lam_s == NULL) in HMC mode and with net_cb
+  // ---- engine_bind
+  float* w;
+  SplitPlan p;
+  bool use_planes;                                  // the decoder-sized products take the pre-split form in this call
+  Mlp3Ws dws, ews;                                  // decoder (with its plane views) and image branch
+  float *w12t[2], *w4t[2], *wht[2];                 // per net: [W1; W2]^T (H x 2d), W4^T (H x H), [Ws | Wt | Wq]^T (3d x H)
+  float *ld, *tb, *aux_h, *h1, *h2, *out3;          // h1 / h2 / out3: scratch of an evaluation nobody keeps
+  NetPlan np;                                       // plan_nets
+};
+
+// `temperature_only`: the block's `energy` only carries a temperature (the trainer's kind 0), the target is one of the others
+template <class A>
+EngineCtx engine_target(const A& a, void* stream, bool hmc, bool temperature_only) {
+  static const L2hmcNet no_net = {};
+  EngineCtx c = {};
+  c.user = a.energy_cb != nullptr;
+  c.builtin = a.energy != nullptr && !temperature_only;
+  c.vae = !c.user && !c.builtin;
+  c.unets = a.net_cb != nullptr;
+  c.hmc = hmc;
+  c.N = a.n_chains; c.d = a.d; c.H = c.unets ? 4 : a.H; c.T = a.T; c.L = 2 * a.d;    // (caller-supplied nets: no hidden activations are planned for)
+  c.s = (hipStream_t)stream; c.stream = stream;
+  c.dir = a.direction; c.dall = a.direction_all; c.masks = a.masks; c.trig = a.trig; c.alpha = a.alpha; c.eps_host = a.eps_host;
+  c.aux = a.aux; c.beta = 1.f; c.temp = 1.f;
+  c.energy = a.energy; c.energy_cb = a.energy_cb; c.energy_cb_user = a.energy_cb_user;
+  c.net_cb = a.net_cb; c.net_cb_user = a.net_cb_user;
+  c.dec = a.decoder; c.enc = a.aux_encoder;
+  c.nets[0] = (hmc || c.unets) ? &no_net : a.xnet;
+  c.nets[1] = (hmc || c.unets) ? &no_net : a.vnet;
+  return c;
+}
+
+// The refusals both entry points make in the same words.  Each entry point calls them where it has always made them, between
+// the checks that are its own: the first complaint about a block with several faults stays what it was.
+inline int check_dims(const EngineCtx& c) {
+  return (c.N < 0 || c.d < 1 || c.H < 1 || c.T < 1) ? fail(L2HMC_ERR_ARG, "bad n_chains / d / H / T%s") : L2HMC_OK;
+}
+inline int check_decoder_width(const EngineCtx& c) {
+  return (c.vae && c.dec->n_in != c.d) ? fail(L2HMC_ERR_ARG, "decoder input width != d%s") : L2HMC_OK;
+}
+inline int check_image_branch(const EngineCtx& c) {
+  return (c.enc && (c.enc->n_out != c.H || (c.vae && c.enc->n_in != c.dec->n_out)))
+             ? fail(L2HMC_ERR_ARG, "aux_encoder must map (N, n_pix) -> (N, H)%s") : L2HMC_OK;
+}
+inline int check_eps(const EngineCtx& c) {
+  return (!c.alpha && !(c.eps_host > 0.f)) ? fail(L2HMC_ERR_ARG, "eps must be > 0%s") : L2HMC_OK;
+}
+inline int check_workspace(long long have, long long need) {
+  return have < need ? fail(L2HMC_ERR_ARG, "workspace too small: need %s%lld floats", "", need) : L2HMC_OK;
+}
+
+// the workspace views of a block that passed its checks; gemm_mode 1 / 3 take the planes where the plan has them
+inline void engine_bind(EngineCtx& c, float* w, const SplitPlan& p, int gemm_mode) {
+  static const L2hmcMlp3 no_dec = {};
+  if (!c.vae) c.dec = &no_dec;
+  c.w = w; c.p = p;
+  c.use_planes = c.vae && p.planes && (gemm_mode == 1 || gemm_mode == 3);
+  c.dws = Mlp3Ws{w + p.dw1t, w + p.dw2t, w + p.dw3t, w + p.a1, w + p.s1, w + p.a2, w + p.s2};
+  if (c.use_planes) {
+    auto us = [&](long long off) { return reinterpret_cast<unsigned short*>(w + off); };
+    c.dws.pw2t = us(p.pw2t); c.dws.pw3t = us(p.pw3t); c.dws.pw2 = us(p.pw2); c.dws.pw3 = us(p.pw3);
+    c.dws.pa1 = us(p.pa1); c.dws.pa2 = us(p.pa2); c.dws.plg = us(p.plg); c.dws.pda2 = us(p.pda2);
+  }
+  c.ews = Mlp3Ws{w + p.ew1t, w + p.ew2t, w + p.ew3t, w + p.e1, nullptr, w + p.e2, nullptr};
+  c.w12t[0] = w + p.nx12t; c.w12t[1] = w + p.nv12t; c.w4t[0] = w + p.nx4t; c.w4t[1] = w + p.nv4t;
+  c.wht[0] = w + p.nxht; c.wht[1] = w + p.nvht;
+  c.ld = w + p.ld; c.tb = w + p.tb; c.aux_h = c.enc ? w + p.aux_h : nullptr;
+  c.h1 = w + p.h1; c.h2 = w + p.h2; c.out3 = w + p.out3;
+}
+
+// the LDS-size requests of the three epilogues the decoder posterior launches on planes, up front: a device that refuses
+// them refuses the call before anything is enqueued
+inline int planes_prepare() {
+  int rc;
+  if (t_plane_mode) {
+    if ((rc = gemm_planes_prepare<EPI_BIAS_SOFTPLUS, 1>()) != L2HMC_OK || (rc = gemm_planes_prepare<EPI_BCE, 1>()) != L2HMC_OK ||
+        (rc = gemm_planes_prepare<EPI_MUL, 1>()) != L2HMC_OK)
+      return rc;
+  } else if ((rc = gemm_planes_prepare<EPI_BIAS_SOFTPLUS>()) != L2HMC_OK || (rc = gemm_planes_prepare<EPI_BCE>()) != L2HMC_OK ||
+             (rc = gemm_planes_prepare<EPI_MUL>()) != L2HMC_OK)
+    return rc;
+  return L2HMC_OK;
+}
+
+// One net evaluation is out3 = relu(relu([a | b] [W1; W2] + time + aux_h) W4 + b4) [Ws|Wt|Wq] (the head biases are added by
+// the update).  H % 4 == 0, d even, K <= 256 and tiles that fit the LDS: ONE launch of net_eval_kernel (activations resident in
+// LDS, the half-update fused behind the heads) -- and of net_bwd_kernel for its reverse; otherwise three GEMMs with fused
+// epilogues on 64 x 64 tiles.  The widest K is 2 d forward (the first layer's inputs) and 3 d once the reverse runs (the head
+// cotangents): `with_reverse` is the trainer's.  net_mode 1 asks for the three products (A/B measurements and tests).
+// (32 chains per workgroup -- every weight fragment streamed from L2 feeding two MFMAs, net_eval_kernel<2> -- was
+//  measured twice at 8192 chains: with one workgroup per CU (88 KB of LDS) the evaluation is 25 % slower than with 16
+//  chains, with two per CU (69 KB after the head products moved into the dead first activation) still 8 % slower:
+//  occupancy, not L2 traffic, is what this kernel lives on)
+// 32 chains on 8 waves (one workgroup per CU, half the L2 weight traffic) once that still fills the chip
+// (Round 5: at config 5's shapes the 120 launches of 64 x 64-tile products these replace were 2.5 ms of a 10.5 ms step.)
+inline int plan_nets(EngineCtx& c, bool with_reverse, int net_mode) {
+  const int d = c.d, H = c.H;
+  NetPlan& n = c.np;
+  n.cb = c.N >= 32LL * device_cus() ? 2 : 1;        // (32 chains per CU = one 8-wave workgroup each; 8192 on 256 CUs)
+  n.blocks = (unsigned)((c.N + 16 * n.cb - 1) / (16 * n.cb));
+  n.ne_lds = net_eval_lds_bytes(d, H, n.cb);
+  n.nb_lds = with_reverse ? net_bwd_lds_bytes(d, H, n.cb) : 0;
+  n.fused = !c.unets && (H % 4 == 0) && (d % 2 == 0) && ceil16(H) <= 16 * NE_MAXKT && ceil16((with_reverse ? 3 : 2) * d) <= 16 * NE_MAXKT &&
+            n.ne_lds <= 160 * 1024 && n.nb_lds <= 160 * 1024 && net_mode == 0;
+  if (!n.fused || c.hmc) return L2HMC_OK;
+  hipError_t e = hipSuccess;
+  if (n.ne_lds > 48 * 1024)
+    e = hipFuncSetAttribute(net_eval_fn(n.cb, d, H), hipFuncAttributeMaxDynamicSharedMemorySize, (int)n.ne_lds);
+  if (e == hipSuccess && n.nb_lds > 48 * 1024)
+    e = hipFuncSetAttribute(net_bwd_fn(n.cb, d, H), hipFuncAttributeMaxDynamicSharedMemorySize, (int)n.nb_lds);
+  return e != hipSuccess ? fail(L2HMC_ERR_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(e)) : L2HMC_OK;
+}
+
+// ---- preparation, once per call; `kept`: still in the workspace from the previous call (L2hmcSplitArgs.reuse: the caller vouches)
+// decoder: transposed copies; on the planes path the two decoder-sized layers in both orientations as planes of the call's
+// arithmetic (t_plane_mode) -- and once more as f16x2 planes where dws has room for them (the trainer's gemm_mode 3) --, and the
+// activations' padding up to a whole k-tile zeroed (the epilogues write the columns of an activation only)
+inline void prepare_decoder(const EngineCtx& c, bool kept) {
+  if (!c.vae || kept) return;
+  const L2hmcMlp3& dec = *c.dec;
+  const Mlp3Ws& ws = c.dws;
+  mlp3_transposes(c.s, dec, ws);
+  if (!c.use_planes) return;
+  auto weight_planes = [&](unsigned short* p2t, unsigned short* p3t, unsigned short* p2, unsigned short* p3, int pm) {
+    to_planes(c.s, ws.w2t, dec.n_h1, dec.n_h2, dec.n_h1, p2t, prows(dec.n_h2), pld(dec.n_h1), pm);
+    to_planes(c.s, ws.w3t, dec.n_h2, dec.n_out, dec.n_h2, p3t, prows(dec.n_out), pld(dec.n_h2), pm);
+    to_planes(c.s, dec.W2, dec.n_h2, dec.n_h1, dec.n_h2, p2, prows(dec.n_h1), pld(dec.n_h2), pm);
+    to_planes(c.s, dec.W3, dec.n_out, dec.n_h2, dec.n_out, p3, prows(dec.n_h2), pld(dec.n_out), pm);
+  };
+  weight_planes(ws.pw2t, ws.pw3t, ws.pw2, ws.pw3, t_plane_mode);
+  if (ws.pw2t_h != nullptr) weight_planes(ws.pw2t_h, ws.pw3t_h, ws.pw2_h, ws.pw3_h, 1);
+  planes_zero_pad(c.s, ws.pa1, c.N, dec.n_h1, pld(dec.n_h1));
+  planes_zero_pad(c.s, ws.pa2, c.N, dec.n_h2, pld(dec.n_h2));
+  planes_zero_pad(c.s, ws.plg, c.N, dec.n_out, pld(dec.n_out));
+  planes_zero_pad(c.s, ws.pda2, c.N, dec.n_h2, pld(dec.n_h2));
+}
+// the image branch is step-invariant: once per trajectory, not 4T times
+inline void prepare_image_branch(const EngineCtx& c, bool kept_weights, bool kept_aux_h) {
+  if (!c.enc || c.hmc) return;
+  if (!kept_weights) mlp3_transposes(c.s, *c.enc, c.ews);
+  if (!kept_aux_h) mlp3_forward(c.s, *c.enc, c.aux, c.N, c.ews, c.aux_h);
+}
+// S/T/Q nets: the time table and the zero-padded transposed copies; after_net(i) follows net i's copies on the stream
+template <class F>
+inline void prepare_nets(const EngineCtx& c, bool kept, F&& after_net) {
+  if (c.hmc || c.unets || kept) return;
+  const int d = c.d, H = c.H, K1p = ceil16(c.L), Hp = ceil16(H);
+  hipLaunchKernelGGL(k_time_table, dim3(nblk(2LL * c.T * H)), dim3(256), 0, c.s, *c.nets[0], *c.nets[1], c.trig, c.T, H, c.tb);
+  (void)hipMemsetAsync(c.w12t[0], 0, sizeof(float) * (size_t)(c.p.nvht + (long long)ceil16(3 * d) * Hp - c.p.nx12t), c.s);
+  for (int i = 0; i < 2; ++i) {
+    transpose_into(c.s, c.nets[i]->W1, d, H, c.w12t[i], K1p, 0);
+    transpose_into(c.s, c.nets[i]->W2, d, H, c.w12t[i], K1p, d);
+    transpose_into(c.s, c.nets[i]->W4, H, H, c.w4t[i], Hp, 0);
+    transpose_into(c.s, c.nets[i]->Ws, H, d, c.wht[i], Hp, 0);
+    transpose_into(c.s, c.nets[i]->Wt, H, d, c.wht[i] + (long long)d * Hp, Hp, 0);
+    transpose_into(c.s, c.nets[i]->Wq, H, d, c.wht[i] + 2LL * d * Hp, Hp, 0);
+    after_net(i);
+  }
+}
+
+// U (double, optional) and grad U at the point held in columns [0, d) of `ab` (row stride L) -> columns [d, 2 d): the caller's
+// callback, the decoder posterior (six GEMMs; `keep`: the point's DecPoint stays behind) or one of the built-in targets (the
+// fused kernels' own energy kernel on a contiguous copy of x)
+__global__ void k_temper(float* g, int ldg, double* U, float it, double itd, long long N, int d);     // train_split.hpp
+inline int energy_at(const EngineCtx& c, float* ab, double* Ud, const DecPoint* keep = nullptr) {
+  const long long N = c.N;
+  const int d = c.d, L = c.L;
+  float* w = c.w;
+  if (c.user) {      // the caller enqueues U / grad U of the (N, d) block at ab (row stride L) on this stream
+    const int r = c.energy_cb(c.energy_cb_user, ab, L, N, d, Ud, ab + d, L, c.stream);
+    return r ? fail(L2HMC_ERR_ARG, "the energy callback failed (returned %s%lld)", "", (long long)r) : L2HMC_OK;
+  }
+  if (c.vae) {
+    const int r = vae_energy(c.s, *c.dec, c.aux, ab, L, N, d, c.dws, w + c.p.lg, w + c.p.rowsum, nullptr, Ud, ab + d, L, c.beta, keep);
+    if (r) return r;
+    if (c.temp != 1.f)     // evaluated plain and tempered behind; the built-in energies and the callbacks return U / temperature themselves
+      hipLaunchKernelGGL(k_temper, dim3(nblk(N * d)), dim3(256), 0, c.s, ab + d, L, Ud, 1.f / c.temp, 1.0 / (double)c.temp, N, d);
+    return L2HMC_OK;
+  }
+  (void)hipMemcpy2DAsync(w + c.p.xp, sizeof(float) * d, ab, sizeof(float) * L, sizeof(float) * d, (size_t)N, hipMemcpyDeviceToDevice, c.s);
+  const int r = l2hmc_energy(c.energy, w + c.p.xp, N, d, Ud ? w + c.p.uf : nullptr, w + c.p.gp, c.stream);
+  if (r) return r;
+  (void)hipMemcpy2DAsync(ab + d, sizeof(float) * L, w + c.p.gp, sizeof(float) * d, sizeof(float) * d, (size_t)N, hipMemcpyDeviceToDevice, c.s);
+  if (Ud) hipLaunchKernelGGL(k_f2d, dim3(nblk(N)), dim3(256), 0, c.s, w + c.p.uf, Ud, N);
+  return L2HMC_OK;
+}
+
+// the half-update that consumes a net evaluation: momentum (optionally with xin = k1 x for the X-net evaluation that
+// follows) and masked position (optionally with the masked input of the next evaluation)
+inline NetEvalArgs::Update v_update(int L, const float* vin, int ldvi, const float* g, float* vout, int ldvo, const float* x, float* xin) {
+  NetEvalArgs::Update u = {};
+  u.mode = 1; u.vin = vin; u.ldvi = ldvi; u.g = g; u.ldg = L; u.vout = vout; u.ldvo = ldvo;
+  if (xin != nullptr) { u.x = x; u.ldx = L; u.xin = xin; u.ldxi = L; }
+  return u;
+}
+inline NetEvalArgs::Update x_update(int L, const float* zin, int ldzi, const float* vh, float* zout, int ldzo, float* xin_next, int second) {
+  NetEvalArgs::Update u = {};
+  u.mode = 2; u.zin = zin; u.ldzi = ldzi; u.vh = vh; u.ldvh = L; u.zout = zout; u.ldzo = ldzo;
+  u.xin_next = xin_next; u.ldxn = L; u.second = second;
+  return u;
+}
+
+// One evaluation of net `net` (0 = X, 1 = V) on the inputs `ab` at leapfrog step `it`, and the half-update `upd` that consumes
+// it: fused into net_eval_kernel when that kernel runs (plan_nets), else the stand-alone update kernel(s) follow the three
+// GEMMs or the caller's net.  `keep`: both hidden activations and the raw head products also go to HBM (the trainer's stash).
+inline int net_eval(const EngineCtx& c, int net, const float* ab, int it, NetEvalArgs::Update upd, const NetKeep* keep = nullptr) {
+  const long long N = c.N;
+  const int d = c.d, H = c.H, L = c.L, T = c.T;
+  const L2hmcNet& nw = *c.nets[net];
+  float *h1 = keep ? keep->h1 : c.h1, *h2 = keep ? keep->h2 : c.h2, *out3 = keep ? keep->out3 : c.out3;
+  const float* tb = c.tb + (long long)net * T * H;
+  upd.bs = nw.bs; upd.bt = nw.bt; upd.bq = nw.bq; upd.lam_s = nw.lam_s; upd.lam_q = nw.lam_q;
+  upd.alpha = c.alpha; upd.eps_host = c.eps_host; upd.ld = c.ld; upd.masks = c.masks;
+  if (c.np.fused) {
+    NetEvalArgs na = {};
+    na.AB = ab; na.ldab = L; na.W12t = c.w12t[net]; na.W4t = c.w4t[net]; na.Wht = c.wht[net]; na.b4 = nw.b4; na.tb = tb; na.auxh = c.aux_h;
+    na.dir = c.dir; na.dir_all = c.dall; na.it = it; na.T = T; na.out3 = out3; na.M = (int)N; na.d = d; na.H = H;
+    if (keep) { na.keep_h1 = h1; na.keep_h2 = h2; na.keep_out3 = out3; }
+    na.upd = upd;
+    launch_net_eval(c.np.cb, c.np.blocks, c.np.ne_lds, c.s, na);
+    return L2HMC_OK;
+  }
+  if (c.unets) {     // the caller's net writes the final S | T | Q into out3 (nw is empty: the update kernels take them as they are)
+    const int r = c.net_cb(c.net_cb_user, net, ab, L, N, d, it, c.dir, c.dall, out3, c.stream);
+    if (r) return fail(L2HMC_ERR_ARG, "the net callback failed (returned %s%lld)", "", (long long)r);
+  } else {
+    GemmArgs ga = gemm_args(ab, L, c.w12t[net], ceil16(L), h1, H, N, H, L);
+    ga.E = c.aux_h; ga.lde = H; ga.tb = tb; ga.dir = c.dir; ga.dir_all = c.dall; ga.it = it; ga.T = T;
+    launch_gemm<EPI_NET1>(ga, c.s, SHAPE_MID);
+    ga = gemm_args(h1, H, c.w4t[net], ceil16(H), h2, H, N, H, H);
+    ga.bias = nw.b4;
+    launch_gemm<EPI_BIAS_RELU>(ga, c.s, SHAPE_MID);
+    ga = gemm_args(h2, H, c.wht[net], ceil16(H), out3, 3 * d, N, 3 * d, H);
+    launch_gemm<EPI_BIAS>(ga, c.s, SHAPE_MID);
+  }
+  const unsigned nw4 = (unsigned)((N + 3) / 4);                  // one wave per chain, 4 per workgroup
+  if (upd.mode == 1) {
+    hipLaunchKernelGGL(k_v_half, dim3(nw4), dim3(256), 0, c.s, out3, nw, upd.vin, upd.ldvi, upd.g, upd.ldg, upd.vout, upd.ldvo, c.ld,
+                       c.dir, c.dall, c.alpha, c.eps_host, N, d);
+    if (upd.xin != nullptr)
+      hipLaunchKernelGGL(k_mask_first, dim3(nblk(N * d)), dim3(256), 0, c.s, upd.x, upd.ldx, upd.xin, upd.ldxi, c.masks, c.dir, c.dall,
+                         it, T, N, d);
+  } else {
+    hipLaunchKernelGGL(k_x_half, dim3(nw4), dim3(256), 0, c.s, out3, nw, upd.zin, upd.ldzi, upd.vh, upd.ldvh, upd.zout, upd.ldzo,
+                       upd.xin_next, upd.ldxn, c.ld, c.masks, c.dir, c.dall, it, T, upd.second, c.alpha, c.eps_host, N, d);
+  }
+  return L2HMC_OK;
+}
+
 }  // namespace l2hmc
 
 using namespace l2hmc;
@@ -509,19 +814,17 @@ int l2hmc_trajectory_split(const L2hmcSplitArgs* a, void* stream) {
   if (a->gemm_mode < 0 || a->gemm_mode > 3) return fail(L2HMC_ERR_ARG, "gemm_mode must be 0 (f32 MFMA), 1 (bf16x3), 2 (bf16x3, split in the loop) or 3 (f16x2 planes)%s");
   t_gemm_bf3 = a->gemm_mode != 0;
   t_plane_mode = a->gemm_mode == 3;
-  const bool user = a->energy_cb != nullptr;        // the caller's own energy, evaluated on the host between launches
-  const bool builtin = a->energy != nullptr;        // a target of utils/distributions.py instead of the decoder posterior
-  const bool unets = a->net_cb != nullptr;          // the caller's own S/T/Q nets (any callable, dynamics.py:69-79)
+  EngineCtx c = engine_target(*a, stream, a->hmc != 0, false);
   int rc;
   // (round 6: also with the decoder posterior -- the caller's nets then receive the images themselves, e.g. two nets with
   //  SEPARATE image branches, which the fused form does not have)
-  if (unets && (a->xnet || a->vnet || a->aux_encoder || a->hmc))
+  if (c.unets && (a->xnet || a->vnet || a->aux_encoder || a->hmc))
     return fail(L2HMC_ERR_ARG, "net_cb excludes xnet / vnet / aux_encoder / hmc%s");
-  if (user) {
+  if (c.user) {
     if (a->decoder || a->energy) return fail(L2HMC_ERR_ARG, "energy_cb excludes decoder and energy%s");
     if (a->bce_scale != 0.f) return fail(L2HMC_ERR_UNSUPPORTED, "bce_scale with a caller-supplied energy (anneal it in the callback)%s");
     if (a->aux_encoder && !a->aux) return fail(L2HMC_ERR_ARG, "aux_encoder needs aux%s");
-  } else if (builtin) {
+  } else if (c.builtin) {
     if (a->decoder || a->aux_encoder || a->hmc)
       return fail(L2HMC_ERR_UNSUPPORTED, "a built-in energy excludes decoder / aux_encoder / hmc (HMC mode runs on l2hmc_trajectory)%s");
     if ((rc = check_energy(a->energy, a->d))) return rc;       // (a tempered target: l2hmc_energy divides U and grad U, dynamics.py:203-212)
@@ -529,210 +832,60 @@ int l2hmc_trajectory_split(const L2hmcSplitArgs* a, void* stream) {
     return rc;
   }
   if (a->aux_encoder && (rc = check_mlp(a->aux_encoder, "aux_encoder"))) return rc;
-  const long long N = a->n_chains;
-  const int d = a->d, H = unets ? 4 : a->H, T = a->T;      // (caller-supplied nets: no hidden activations are planned for)
-  if (N < 0 || d < 1 || H < 1 || T < 1) return fail(L2HMC_ERR_ARG, "bad n_chains / d / H / T%s");
+  if ((rc = check_dims(c))) return rc;
+  const long long N = c.N;
+  const int d = c.d, L = c.L;
   if (N == 0) return L2HMC_OK;
-  const bool hmc = a->hmc != 0;
-  if ((!hmc && ((!unets && (!a->xnet || !a->vnet)) || !a->masks || !a->trig)) || (!builtin && !user && !a->aux) || !a->x || !a->v || !a->workspace)
+  if ((!c.hmc && ((!c.unets && (!a->xnet || !a->vnet)) || !a->masks || !a->trig)) || (c.vae && !a->aux) || !a->x || !a->v || !a->workspace)
     return fail(L2HMC_ERR_ARG, "l2hmc_trajectory_split: NULL pointer%s");
   if (!(a->bce_scale >= 0.f && a->bce_scale <= 1.f)) return fail(L2HMC_ERR_ARG, "bce_scale must be in [0, 1] (0 = off)%s");
-  const float beta = a->bce_scale > 0.f ? a->bce_scale : 1.f;
-  if (!builtin && !user && a->decoder->n_in != d) return fail(L2HMC_ERR_ARG, "decoder input width != d%s");
-  if (a->aux_encoder && (a->aux_encoder->n_out != H || (!user && a->aux_encoder->n_in != a->decoder->n_out)))
-    return fail(L2HMC_ERR_ARG, "aux_encoder must map (N, n_pix) -> (N, H)%s");
-  if (a->step_begin < 0 || a->n_steps < 0 || a->step_begin + a->n_steps > T) return fail(L2HMC_ERR_ARG, "steps outside the schedule%s");
+  c.beta = a->bce_scale > 0.f ? a->bce_scale : 1.f;
+  if ((rc = check_decoder_width(c)) || (rc = check_image_branch(c))) return rc;
+  if (a->step_begin < 0 || a->n_steps < 0 || a->step_begin + a->n_steps > c.T) return fail(L2HMC_ERR_ARG, "steps outside the schedule%s");
   if (a->x_next && !a->u) return fail(L2HMC_ERR_ARG, "x_next needs u%s");
-  if (!a->alpha && !(a->eps_host > 0.f)) return fail(L2HMC_ERR_ARG, "eps must be > 0%s");
-  const SplitPlan p = plan_split(N, d, H, T, a->aux_encoder, a->decoder);
-  if (a->workspace_floats < p.total) return fail(L2HMC_ERR_ARG, "workspace too small: need %s%lld floats", "", p.total);
-  hipStream_t s = (hipStream_t)stream;
-  float* w = a->workspace;
-  static const L2hmcMlp3 no_dec = {};
-  const L2hmcMlp3& dec = (builtin || user) ? no_dec : *a->decoder;
-  Mlp3Ws dws = {w + p.dw1t, w + p.dw2t, w + p.dw3t, w + p.a1, w + p.s1, w + p.a2, w + p.s2};
-  const bool use_planes = p.planes && (a->gemm_mode == 1 || a->gemm_mode == 3) && !builtin && !user;
+  if ((rc = check_eps(c))) return rc;
+  const SplitPlan p = plan_split(N, d, c.H, c.T, a->aux_encoder, a->decoder);
+  if ((rc = check_workspace(a->workspace_floats, p.total))) return rc;
+  engine_bind(c, a->workspace, p, a->gemm_mode);
   // (what l2hmc_last_kernel reports for this engine: the kernel of the decoder-sized products, or the net evaluation)
-  note_kernel(builtin || user ? "net_eval_kernel" : use_planes ? "gemm_xlp_kernel" : "gemm_nt_kernel");
-  if (use_planes) {     // the three epilogues vae_energy launches on planes
-    if (t_plane_mode) {
-      if ((rc = gemm_planes_prepare<EPI_BIAS_SOFTPLUS, 1>()) != L2HMC_OK || (rc = gemm_planes_prepare<EPI_BCE, 1>()) != L2HMC_OK ||
-          (rc = gemm_planes_prepare<EPI_MUL, 1>()) != L2HMC_OK)
-        return rc;
-    } else if ((rc = gemm_planes_prepare<EPI_BIAS_SOFTPLUS>()) != L2HMC_OK || (rc = gemm_planes_prepare<EPI_BCE>()) != L2HMC_OK ||
-               (rc = gemm_planes_prepare<EPI_MUL>()) != L2HMC_OK)
-      return rc;
-  }
-  if (use_planes) {
-    auto us = [&](long long off) { return reinterpret_cast<unsigned short*>(w + off); };
-    dws.pw2t = us(p.pw2t); dws.pw3t = us(p.pw3t); dws.pw2 = us(p.pw2); dws.pw3 = us(p.pw3);
-    dws.pa1 = us(p.pa1); dws.pa2 = us(p.pa2); dws.plg = us(p.plg); dws.pda2 = us(p.pda2);
-  }
+  note_kernel(!c.vae ? "net_eval_kernel" : c.use_planes ? "gemm_xlp_kernel" : "gemm_nt_kernel");
+  if (c.use_planes && (rc = planes_prepare())) return rc;
+  hipStream_t s = c.s;
+  float* w = c.w;
   // [x | grad U] and [v_h | masked x] live side by side (row stride L = 2 d): they are the first-layer inputs
-  const int L = 2 * d;
-  float *xc = w + p.abv, *g = w + p.abv + d, *vh = w + p.abx, *xin = w + p.abx + d, *vc = w + p.vc, *y = w + p.y;
-  float *h1 = w + p.h1, *h2 = w + p.h2, *out3 = w + p.out3, *tb = w + p.tb, *ld = w + p.ld;
-  float* aux_h = a->aux_encoder ? w + p.aux_h : nullptr;
-  static const L2hmcNet no_net = {};
-  const L2hmcNet &xn = (hmc || unets) ? no_net : *a->xnet, &vn = (hmc || unets) ? no_net : *a->vnet;
-  const unsigned char* dir = a->direction;
-  const int dall = a->direction_all;
-  const unsigned nw4 = (unsigned)((N + 3) / 4);                  // one wave per chain, 4 per workgroup
+  float *xc = w + p.abv, *g = xc + d, *vh = w + p.abx, *xin = vh + d, *vc = w + p.vc, *y = w + p.y;
 
   (void)hipMemcpy2DAsync(xc, sizeof(float) * L, a->x, sizeof(float) * d, sizeof(float) * d, (size_t)N, hipMemcpyDeviceToDevice, s);
   (void)hipMemcpyAsync(vc, a->v, sizeof(float) * N * d, hipMemcpyDeviceToDevice, s);
   const bool have_w = (a->reuse & 1) != 0, have_auxh = (a->reuse & 2) != 0;    // still in the workspace (caller vouches)
-  if (!builtin && !user && !have_w) {
-    mlp3_transposes(s, dec, dws);
-    if (use_planes) {       // the two decoder-sized layers, both orientations, as bf16 planes: once per parameter update
-      to_planes(s, dws.w2t, dec.n_h1, dec.n_h2, dec.n_h1, dws.pw2t, prows(dec.n_h2), pld(dec.n_h1), t_plane_mode);
-      to_planes(s, dws.w3t, dec.n_h2, dec.n_out, dec.n_h2, dws.pw3t, prows(dec.n_out), pld(dec.n_h2), t_plane_mode);
-      to_planes(s, dec.W2, dec.n_h2, dec.n_h1, dec.n_h2, dws.pw2, prows(dec.n_h1), pld(dec.n_h2), t_plane_mode);
-      to_planes(s, dec.W3, dec.n_out, dec.n_h2, dec.n_out, dws.pw3, prows(dec.n_h2), pld(dec.n_out), t_plane_mode);
-      // the epilogues write the columns of an activation only: its padding up to a whole k-tile is zeroed here
-      planes_zero_pad(s, dws.pa1, N, dec.n_h1, pld(dec.n_h1));
-      planes_zero_pad(s, dws.pa2, N, dec.n_h2, pld(dec.n_h2));
-      planes_zero_pad(s, dws.plg, N, dec.n_out, pld(dec.n_out));
-      planes_zero_pad(s, dws.pda2, N, dec.n_h2, pld(dec.n_h2));
-    }
-  }
-  if (a->aux_encoder && !hmc) {      // the image branch is step-invariant: once per trajectory, not 4T times
-    const L2hmcMlp3& enc = *a->aux_encoder;
-    const Mlp3Ws ews = {w + p.ew1t, w + p.ew2t, w + p.ew3t, w + p.e1, nullptr, w + p.e2, nullptr};
-    if (!have_w) mlp3_transposes(s, enc, ews);
-    if (!have_auxh) mlp3_forward(s, enc, a->aux, N, ews, aux_h);
-  }
-  if (!hmc && !unets && !have_w) {
-    hipLaunchKernelGGL(k_time_table, dim3(nblk(2LL * T * H)), dim3(256), 0, s, xn, vn, a->trig, T, H, tb);
-    // per net: [W1; W2]^T (H x 2d), W4^T (H x H), [Ws | Wt | Wq]^T (3d x H)
-    const L2hmcNet* nets[2] = {&xn, &vn};
-    float* w12t[2] = {w + p.nx12t, w + p.nv12t};
-    float* w4t[2] = {w + p.nx4t, w + p.nv4t};
-    float* wht[2] = {w + p.nxht, w + p.nvht};
-    const int K1p = ceil16(L), Hp = ceil16(H);
-    (void)hipMemsetAsync(w + p.nx12t, 0, sizeof(float) * (size_t)(p.nvht + (long long)ceil16(3 * d) * Hp - p.nx12t), s);
-    for (int i = 0; i < 2; ++i) {
-      transpose_into(s, nets[i]->W1, d, H, w12t[i], K1p, 0);
-      transpose_into(s, nets[i]->W2, d, H, w12t[i], K1p, d);
-      transpose_into(s, nets[i]->W4, H, H, w4t[i], Hp, 0);
-      transpose_into(s, nets[i]->Ws, H, d, wht[i], Hp, 0);
-      transpose_into(s, nets[i]->Wt, H, d, wht[i] + (long long)d * Hp, Hp, 0);
-      transpose_into(s, nets[i]->Wq, H, d, wht[i] + 2LL * d * Hp, Hp, 0);
-    }
-  }
-  launch_kinetic(s, vc, w + p.K0, ld, N, d);
+  prepare_decoder(c, have_w);
+  prepare_image_branch(c, have_w, have_auxh);
+  prepare_nets(c, have_w, [](int) {});
+  launch_kinetic(s, vc, w + p.K0, c.ld, N, d);
   double *U0d = reinterpret_cast<double*>(w + p.U0), *U1d = reinterpret_cast<double*>(w + p.U1);
-  // U (double, optional) and grad U at the current x: the decoder posterior (six GEMMs) or one of the built-in
-  // targets (the fused kernels' own energy kernel on a contiguous copy of x)
-  auto energy_eval = [&](double* Ud) -> int {
-    if (user) {      // the caller enqueues U / grad U of the (N, d) block at xc (row stride L) on this stream
-      const int r = a->energy_cb(a->energy_cb_user, xc, L, N, d, Ud, g, L, stream);
-      return r ? fail(L2HMC_ERR_ARG, "the energy callback failed (returned %s%lld)", "", (long long)r) : L2HMC_OK;
-    }
-    if (!builtin) {
-      return vae_energy(s, dec, a->aux, xc, L, N, d, dws, w + p.lg, w + p.rowsum, nullptr, Ud, g, L, beta);
-    }
-    (void)hipMemcpy2DAsync(w + p.xp, sizeof(float) * d, xc, sizeof(float) * L, sizeof(float) * d, (size_t)N, hipMemcpyDeviceToDevice, s);
-    const int r = l2hmc_energy(a->energy, w + p.xp, N, d, Ud ? w + p.uf : nullptr, w + p.gp, stream);
-    if (r) return r;
-    (void)hipMemcpy2DAsync(g, sizeof(float) * L, w + p.gp, sizeof(float) * d, sizeof(float) * d, (size_t)N, hipMemcpyDeviceToDevice, s);
-    if (Ud) hipLaunchKernelGGL(k_f2d, dim3(nblk(N)), dim3(256), 0, s, w + p.uf, Ud, N);
-    return L2HMC_OK;
-  };
-  if ((rc = energy_eval(U0d))) return rc;
+  if ((rc = energy_at(c, xc, U0d))) return rc;
   if (a->n_steps == 0) (void)hipMemcpyAsync(U1d, U0d, sizeof(double) * N, hipMemcpyDeviceToDevice, s);
-
-  // one net evaluation: out3 = relu(relu([a | b] [W1; W2] + time + aux_h) W4 + b4) [Ws|Wt|Wq]   (the head biases are
-  // added by the update kernels).  H % 4 == 0 and d even: ONE launch of net_eval_kernel (activations resident in
-  // LDS); otherwise three GEMMs with fused epilogues on 64 x 64 tiles.
-  // (32 chains per workgroup -- every weight fragment streamed from L2 feeding two MFMAs, net_eval_kernel<2> -- was
-  //  measured twice at 8192 chains: with one workgroup per CU (88 KB of LDS) the evaluation is 25 % slower than with 16
-  //  chains, with two per CU (69 KB after the head products moved into the dead first activation) still 8 % slower:
-  //  occupancy, not L2 traffic, is what this kernel lives on)
-  // 32 chains on 8 waves (one workgroup per CU, half the L2 weight traffic) once that still fills the chip
-  int ne_dev = 0, ne_cus = 256;
-  if (hipGetDevice(&ne_dev) != hipSuccess || hipDeviceGetAttribute(&ne_cus, hipDeviceAttributeMultiprocessorCount, ne_dev) != hipSuccess ||
-      ne_cus <= 0)
-    ne_cus = 256;
-  const int ne_cb = N >= 32LL * ne_cus ? 2 : 1;            // (32 chains per CU = one 8-wave workgroup each; 8192 on 256 CUs)
-  const size_t ne_lds = net_eval_lds_bytes(d, H, ne_cb);
-  const bool ne_ok = !unets && (H % 4 == 0) && (d % 2 == 0) && ceil16(H) <= 16 * NE_MAXKT && ceil16(2 * d) <= 16 * NE_MAXKT && ne_lds <= 160 * 1024;
-  if (ne_ok && !hmc && ne_lds > 48 * 1024) {
-    hipError_t e = hipFuncSetAttribute(net_eval_fn(ne_cb, d, H), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ne_lds);
-    if (e != hipSuccess) return fail(L2HMC_ERR_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-  }
-  // `upd`: the half-update that consumes the evaluation; fused into net_eval_kernel when that kernel runs, else the
-  // stand-alone update kernel(s) follow the three GEMMs
-  auto net_eval = [&](const L2hmcNet& nw, int net, const float* ab, int it, NetEvalArgs::Update upd) -> int {
-    upd.bs = nw.bs; upd.bt = nw.bt; upd.bq = nw.bq; upd.lam_s = nw.lam_s; upd.lam_q = nw.lam_q;
-    upd.alpha = a->alpha; upd.eps_host = a->eps_host; upd.ld = ld; upd.masks = a->masks;
-    if (ne_ok) {
-      NetEvalArgs na = {};
-      na.AB = ab; na.ldab = L; na.W12t = w + (net == 0 ? p.nx12t : p.nv12t); na.W4t = w + (net == 0 ? p.nx4t : p.nv4t);
-      na.Wht = w + (net == 0 ? p.nxht : p.nvht); na.b4 = nw.b4; na.tb = tb + (long long)net * T * H; na.auxh = aux_h;
-      na.dir = dir; na.dir_all = dall; na.it = it; na.T = T; na.out3 = out3; na.M = (int)N; na.d = d; na.H = H;
-      na.upd = upd;
-      const unsigned blocks = (unsigned)((N + 16 * ne_cb - 1) / (16 * ne_cb));
-      launch_net_eval(ne_cb, blocks, ne_lds, s, na);
-      return L2HMC_OK;
-    }
-    if (unets) {     // the caller's net writes the final S | T | Q into out3 (nw = no_net: the update kernels take them as they are)
-      const int r = a->net_cb(a->net_cb_user, net, ab, L, N, d, it, dir, dall, out3, stream);
-      if (r) return fail(L2HMC_ERR_ARG, "the net callback failed (returned %s%lld)", "", (long long)r);
-    } else {
-    GemmArgs ga = gemm_args(ab, L, w + (net == 0 ? p.nx12t : p.nv12t), ceil16(L), h1, H, N, H, L);
-    ga.E = aux_h; ga.lde = H; ga.tb = tb + (long long)net * T * H; ga.dir = dir; ga.dir_all = dall; ga.it = it; ga.T = T;
-    launch_gemm<EPI_NET1>(ga, s, SHAPE_MID);
-    ga = gemm_args(h1, H, w + (net == 0 ? p.nx4t : p.nv4t), ceil16(H), h2, H, N, H, H);
-    ga.bias = nw.b4;
-    launch_gemm<EPI_BIAS_RELU>(ga, s, SHAPE_MID);
-    ga = gemm_args(h2, H, w + (net == 0 ? p.nxht : p.nvht), ceil16(H), out3, 3 * d, N, 3 * d, H);
-    launch_gemm<EPI_BIAS>(ga, s, SHAPE_MID);
-    }
-    if (upd.mode == 1) {
-      hipLaunchKernelGGL(k_v_half, dim3(nw4), dim3(256), 0, s, out3, nw, upd.vin, upd.ldvi, upd.g, upd.ldg, upd.vout, upd.ldvo, ld,
-                         dir, dall, a->alpha, a->eps_host, N, d);
-      if (upd.xin != nullptr)
-        hipLaunchKernelGGL(k_mask_first, dim3(nblk(N * d)), dim3(256), 0, s, upd.x, upd.ldx, upd.xin, upd.ldxi, a->masks, dir, dall,
-                           it, T, N, d);
-    } else {
-      hipLaunchKernelGGL(k_x_half, dim3(nw4), dim3(256), 0, s, out3, nw, upd.zin, upd.ldzi, upd.vh, upd.ldvh, upd.zout, upd.ldzo,
-                         upd.xin_next, upd.ldxn, ld, a->masks, dir, dall, it, T, upd.second, a->alpha, a->eps_host, N, d);
-    }
-    return L2HMC_OK;
-  };
-  auto v_update = [&](const float* vin, int ldvi, float* vout, int ldvo, bool with_mask) {
-    NetEvalArgs::Update u = {};
-    u.mode = 1; u.vin = vin; u.ldvi = ldvi; u.g = g; u.ldg = L; u.vout = vout; u.ldvo = ldvo;
-    if (with_mask) { u.x = xc; u.ldx = L; u.xin = xin; u.ldxi = L; }
-    return u;
-  };
-  auto x_update = [&](const float* zin, int ldzi, float* zout, int ldzo, float* xin_next, int second) {
-    NetEvalArgs::Update u = {};
-    u.mode = 2; u.zin = zin; u.ldzi = ldzi; u.vh = vh; u.ldvh = L; u.zout = zout; u.ldzo = ldzo;
-    u.xin_next = xin_next; u.ldxn = L; u.second = second;
-    return u;
-  };
+  if ((rc = plan_nets(c, false, 0))) return rc;
 
   for (int k = 0; k < a->n_steps; ++k) {
     const int it = a->step_begin + k;
     const bool last = k == a->n_steps - 1;
-    if (hmc) {
-      hipLaunchKernelGGL(k_hmc_drift, dim3(nblk(N * d)), dim3(256), 0, s, xc, L, vc, g, L, y, a->alpha, a->eps_host, dir, dall, N, d);
-      if ((rc = energy_eval(last ? U1d : nullptr))) return rc;
-      hipLaunchKernelGGL(k_hmc_kick, dim3(nblk(N * d)), dim3(256), 0, s, vc, y, g, L, a->alpha, a->eps_host, dir, dall, N, d);
+    if (c.hmc) {
+      hipLaunchKernelGGL(k_hmc_drift, dim3(nblk(N * d)), dim3(256), 0, s, xc, L, vc, g, L, y, c.alpha, c.eps_host, c.dir, c.dall, N, d);
+      if ((rc = energy_at(c, xc, last ? U1d : nullptr))) return rc;
+      hipLaunchKernelGGL(k_hmc_kick, dim3(nblk(N * d)), dim3(256), 0, s, vc, y, g, L, c.alpha, c.eps_host, c.dir, c.dall, N, d);
       continue;
     }
-    if ((rc = net_eval(vn, 1, xc, it, v_update(vc, d, vh, L, true)))) return rc;      // v_h, and xin = k1 x for the next evaluation
-    if ((rc = net_eval(xn, 0, vh, it, x_update(xc, L, y, d, xin, 0)))) return rc;      // y, xin = (1 - k1) y
-    if ((rc = net_eval(xn, 0, vh, it, x_update(y, d, xc, L, nullptr, 1)))) return rc;  // x'
-    if ((rc = energy_eval(last ? U1d : nullptr))) return rc;
-    if ((rc = net_eval(vn, 1, xc, it, v_update(vh, L, vc, d, false)))) return rc;      // v'
+    if ((rc = net_eval(c, 1, xc, it, v_update(L, vc, d, g, vh, L, xc, xin)))) return rc;          // v_h, and xin = k1 x for the next evaluation
+    if ((rc = net_eval(c, 0, vh, it, x_update(L, xc, L, vh, y, d, xin, 0)))) return rc;           // y, xin = (1 - k1) y
+    if ((rc = net_eval(c, 0, vh, it, x_update(L, y, d, vh, xc, L, nullptr, 1)))) return rc;       // x'
+    if ((rc = energy_at(c, xc, last ? U1d : nullptr))) return rc;
+    if ((rc = net_eval(c, 1, xc, it, v_update(L, vh, L, g, vc, d, nullptr, nullptr)))) return rc; // v'
   }
   launch_kinetic(s, vc, w + p.K1, (float*)nullptr, N, d);
   if (a->x_out) (void)hipMemcpy2DAsync(a->x_out, sizeof(float) * d, xc, sizeof(float) * L, sizeof(float) * d, (size_t)N, hipMemcpyDeviceToDevice, s);
   if (a->v_out) (void)hipMemcpyAsync(a->v_out, vc, sizeof(float) * N * d, hipMemcpyDeviceToDevice, s);
-  hipLaunchKernelGGL(k_finish, dim3(nblk(N * d)), dim3(256), 0, s, U0d, w + p.K0, U1d, w + p.K1, ld, a->u, a->x,
+  hipLaunchKernelGGL(k_finish, dim3(nblk(N * d)), dim3(256), 0, s, U0d, w + p.K0, U1d, w + p.K1, c.ld, a->u, a->x,
                      xc, L, a->p_out, a->logjac_out, a->x_next, N, d);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(L2HMC_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));

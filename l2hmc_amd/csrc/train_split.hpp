@@ -615,77 +615,6 @@ inline TrainSplitPlan plan_train_split(long long N, int d, int H, int T, const L
   return p;
 }
 
-// The decoder's share of one trajectory point, kept for the reverse sweep: s1, s2 (sigmoids = softplus'), sigma' of the
-// logits, and the raw reverse products b2 = r W3^T, b1 = c2 W2^T (r = sigmoid(logit) - aux, c2 = s2 b2)
-struct DecPoint { float *s1, *s2, *rd, *b2, *b1; };
-
-// vae_energy (U, grad U at z) that leaves the point's DecPoint behind
-void vae_energy_keep(hipStream_t s, const L2hmcMlp3& dec, const float* aux, const float* z, int ldz, long long N, int d,
-                     const Mlp3Ws& ws0, float* lg, float* rowsum, double* Ud, float* grad, int ldg, const DecPoint& pt) {
-  Mlp3Ws ws = ws0;
-  ws.s1 = pt.s1; ws.s2 = pt.s2;
-  if (ws.pa1 != nullptr) {
-    // ---- pre-split form (round 5; vae_energy's chain of split.hip with the point's DecPoint kept): activations that only feed the
-    //      next product are written as bf16 planes by their producer's epilogue, the four decoder-sized products read planes on both
-    //      sides (gemm_xlp_kernel: bit-identical per product to the in-loop split, x1.37)
-    const int l1 = pld(dec.n_h1), l2 = pld(dec.n_h2), lo = pld(dec.n_out);
-    const long long n1 = N * l1, n2 = N * l2, no = N * lo;
-    // (gemm_mode 3: this evaluation is the SAMPLER's -- activations, logits, BCE gradients of O(1) -- and runs on f16x2 planes
-    //  like it, with the weights' f16 planes; the reverse sweep's tangents and adjoints keep bf16x3: split.hip t_plane_mode)
-    const int pm_keep = t_plane_mode;
-    const bool h16 = ws.pw2t_h != nullptr;
-    if (h16) t_plane_mode = 1;
-    const unsigned short *qw2t = h16 ? ws.pw2t_h : ws.pw2t, *qw3t = h16 ? ws.pw3t_h : ws.pw3t, *qw2 = h16 ? ws.pw2_h : ws.pw2,
-                         *qw3 = h16 ? ws.pw3_h : ws.pw3;
-    GemmArgs g = gemm_args(z, ldz, ws.w1t, dec.n_in, nullptr, dec.n_h1, N, dec.n_h1, dec.n_in);
-    g.bias = dec.b1; g.C2 = pt.s1; g.ldc2 = dec.n_h1; g.Cp = ws.pa1; g.cp_plane = n1; g.ldcp = l1;
-    launch_gemm<EPI_BIAS_SOFTPLUS>(g, s, dec.n_in <= 64 ? SHAPE_MID : SHAPE_AUTO);                 // a1 (planes), s1
-    g = gemm_args(nullptr, 0, nullptr, 0, nullptr, dec.n_h2, N, dec.n_h2, dec.n_h1);
-    g.Ap = ws.pa1; g.ap_plane = n1; g.ldap = l1; g.Bp = qw2t; g.bp_plane = prows(dec.n_h2) * l1; g.ldbp = l1;
-    g.bias = dec.b2; g.C2 = pt.s2; g.ldc2 = dec.n_h2; g.Cp = ws.pa2; g.cp_plane = n2; g.ldcp = l2;
-    launch_gemm_planes<EPI_BIAS_SOFTPLUS>(g, s);                                                     // a2 (planes), s2
-    g = gemm_args(nullptr, 0, nullptr, 0, lg, dec.n_out, N, dec.n_out, dec.n_h2);                    // (lg in fp32 too: k_sigd reads it)
-    g.Ap = ws.pa2; g.ap_plane = n2; g.ldap = l2; g.Bp = qw3t; g.bp_plane = prows(dec.n_out) * l2; g.ldbp = l2;
-    g.bias = dec.b3; g.E = aux; g.lde = dec.n_out; g.rowsum = rowsum; g.n_tiles = bce_tiles_planes(dec.n_out); g.beta = 1.f;
-    g.Cp = ws.plg; g.cp_plane = no; g.ldcp = lo;
-    launch_gemm_planes<EPI_BCE>(g, s);
-    if (Ud != nullptr)
-      launch_vae_U(s, rowsum, 2 * bce_tiles_planes(dec.n_out), z, ldz, d, (float*)nullptr, Ud, N);
-    const long long npix_ = N * dec.n_out;
-    hipLaunchKernelGGL(k_sigd, dim3(nblk(npix_)), dim3(256), 0, s, lg, aux, pt.rd, npix_);
-    g = gemm_args(nullptr, 0, nullptr, 0, nullptr, dec.n_h2, N, dec.n_h2, dec.n_out);
-    g.Ap = ws.plg; g.ap_plane = no; g.ldap = lo; g.Bp = qw3; g.bp_plane = prows(dec.n_h2) * lo; g.ldbp = lo;
-    g.E = pt.s2; g.lde = dec.n_h2; g.C2 = pt.b2; g.ldc2 = dec.n_h2; g.Cp = ws.pda2; g.cp_plane = n2; g.ldcp = l2;
-    launch_gemm_planes<EPI_MUL>(g, s);                                                               // c2 = s2 b2 (planes), b2
-    g = gemm_args(nullptr, 0, nullptr, 0, ws.a1, dec.n_h1, N, dec.n_h1, dec.n_h2);
-    g.Ap = ws.pda2; g.ap_plane = n2; g.ldap = l2; g.Bp = qw2; g.bp_plane = prows(dec.n_h1) * l2; g.ldbp = l2;
-    g.E = pt.s1; g.lde = dec.n_h1; g.C2 = pt.b1; g.ldc2 = dec.n_h1;
-    launch_gemm_planes<EPI_MUL>(g, s);                                                               // c1 = s1 b1 (fp32), b1
-    t_plane_mode = pm_keep;
-    g = gemm_args(ws.a1, dec.n_h1, dec.W1, dec.n_h1, grad, ldg, N, d, dec.n_h1);
-    g.E = z; g.lde = ldz;
-    launch_gemm<EPI_ADD>(g, s, d <= 64 ? SHAPE_SKINNY : SHAPE_MID);
-    return;
-  }
-  mlp3_hidden(s, dec, z, ldz, N, ws);
-  GemmArgs g = gemm_args(ws.a2, dec.n_h2, ws.w3t, dec.n_h2, lg, dec.n_out, N, dec.n_out, dec.n_h2);
-  g.bias = dec.b3; g.E = aux; g.lde = dec.n_out; g.rowsum = rowsum; g.n_tiles = bce_tiles(N, dec.n_out); g.beta = 1.f;
-  launch_gemm<EPI_BCE>(g, s);
-  if (Ud != nullptr)
-    launch_vae_U(s, rowsum, bce_partials(N, dec.n_out), z, ldz, d, (float*)nullptr, Ud, N);
-  const long long npix = N * dec.n_out;
-  hipLaunchKernelGGL(k_sigd, dim3(nblk(npix)), dim3(256), 0, s, lg, aux, pt.rd, npix);
-  g = gemm_args(lg, dec.n_out, dec.W3, dec.n_out, ws.a2, dec.n_h2, N, dec.n_h2, dec.n_out);
-  g.E = pt.s2; g.lde = dec.n_h2; g.C2 = pt.b2; g.ldc2 = dec.n_h2;
-  launch_gemm<EPI_MUL>(g, s);
-  g = gemm_args(ws.a2, dec.n_h2, dec.W2, dec.n_h2, ws.a1, dec.n_h1, N, dec.n_h1, dec.n_h2);
-  g.E = pt.s1; g.lde = dec.n_h1; g.C2 = pt.b1; g.ldc2 = dec.n_h1;
-  launch_gemm<EPI_MUL>(g, s);
-  g = gemm_args(ws.a1, dec.n_h1, dec.W1, dec.n_h1, grad, ldg, N, d, dec.n_h1);
-  g.E = z; g.lde = ldz;
-  launch_gemm<EPI_ADD>(g, s, d <= 64 ? SHAPE_SKINNY : SHAPE_MID);
-}
-
 // hv = Hessian(z) u of the decoder posterior U(z) = sum_pix BCE(aux, dec(z)) + |z|^2 / 2 (mnist_vae.py:122-126) from the
 // point's DecPoint.  Forward-over-reverse: with the reverse pass b2 = r W3^T, c2 = s2 b2, b1 = c2 W2^T, c1 = s1 b1,
 // grad = c1 W1^T + z, the directional derivative along u is
@@ -770,20 +699,18 @@ int l2hmc_train_split_grad(const L2hmcTrainSplitArgs* a, void* stream) {
   // `energy` of kind 0 next to the decoder posterior or energy_cb: only its temperature is read (the target's own form is the
   // decoder / the callbacks)
   const bool tcarrier = a->energy != nullptr && a->energy->kind == 0;
-  const bool builtin = a->energy != nullptr && !tcarrier;
-  const bool user = a->energy_cb != nullptr;       // the caller's energy: U / grad U and Hessian-vector products by callback
-  const bool vae = !builtin && !user;              // the decoder posterior
-  // (ABI 6) the caller's own S/T/Q nets (any callable, dynamics.py:69-79): forward by net_cb, reverse by net_vjp_cb
-  const bool unets = a->net_cb != nullptr || a->net_vjp_cb != nullptr;
+  EngineCtx c = engine_target(*a, stream, false, tcarrier);
+  const bool user = c.user, builtin = c.builtin, vae = c.vae, unets = c.unets;
   int rc;
-  if (unets) {
+  // (ABI 6) the caller's own S/T/Q nets (any callable, dynamics.py:69-79): forward by net_cb, reverse by net_vjp_cb
+  if (a->net_cb || a->net_vjp_cb) {
     if (!a->net_cb || !a->net_vjp_cb) return fail(L2HMC_ERR_ARG, "training caller-supplied nets needs BOTH net_cb and net_vjp_cb%s");
     if (a->xnet || a->vnet || a->aux_encoder)
       return fail(L2HMC_ERR_ARG, "net_cb excludes xnet / vnet / aux_encoder (an image branch is the caller's net's own business)%s");
   }
-  const long long N = a->n_chains;
-  const int d = a->d, H = unets ? 4 : a->H, T = a->T;     // (caller-supplied nets: no hidden activations are planned for)
-  if (N < 0 || d < 1 || H < 1 || T < 1) return fail(L2HMC_ERR_ARG, "bad n_chains / d / H / T%s");
+  if ((rc = check_dims(c))) return rc;
+  const long long N = c.N;
+  const int d = c.d, H = c.H, T = c.T, L = c.L;
   if (N == 0) return L2HMC_OK;
   if (tcarrier && (a->energy->anneal_beta != 0.f || !(a->energy->temperature > 0.f && a->energy->temperature < INFINITY)))
     return fail(L2HMC_ERR_ARG, "an energy of kind 0 (the temperature of the decoder posterior / energy_cb) needs a finite "
@@ -811,56 +738,46 @@ int l2hmc_train_split_grad(const L2hmcTrainSplitArgs* a, void* stream) {
   } else {
     if ((rc = check_mlp(a->decoder, "decoder"))) return rc;
     if (!a->aux) return fail(L2HMC_ERR_ARG, "the decoder posterior needs aux%s");
-    if (a->decoder->n_in != d) return fail(L2HMC_ERR_ARG, "decoder input width != d%s");
+    if ((rc = check_decoder_width(c))) return rc;
   }
-  if (a->aux_encoder) {
-    if ((rc = check_mlp(a->aux_encoder, "aux_encoder"))) return rc;
-    if (a->aux_encoder->n_out != H || (vae && a->aux_encoder->n_in != a->decoder->n_out))
-      return fail(L2HMC_ERR_ARG, "aux_encoder must map (N, n_pix) -> (N, H)%s");
-  }
+  if (a->aux_encoder && ((rc = check_mlp(a->aux_encoder, "aux_encoder")) || (rc = check_image_branch(c)))) return rc;
   if ((!unets && (!a->xnet || !a->vnet)) || !a->masks || !a->trig || !a->x || !a->v || !a->Lx || (!a->no_accept && (!a->p || !a->v1)) ||
       !a->grad || !a->workspace)
     return fail(L2HMC_ERR_ARG, "l2hmc_train_split_grad: NULL pointer%s");
-  if (!a->alpha && !(a->eps_host > 0.f)) return fail(L2HMC_ERR_ARG, "eps must be > 0%s");
+  if ((rc = check_eps(c))) return rc;
   if (!(a->scale > 0.f) || !(a->inv_n >= 0.f)) return fail(L2HMC_ERR_ARG, "scale must be > 0 and inv_n >= 0%s");
   if (a->inv_n == 0.f && !a->dLx_in) return fail(L2HMC_ERR_ARG, "inv_n = 0 (no loss term of its own) needs dLx_in%s");
   if (a->no_accept && !a->dLx_in) return fail(L2HMC_ERR_ARG, "no_accept (a link of chain_operator) needs dLx_in%s");
   if (!(a->energy_scale >= 0.f)) return fail(L2HMC_ERR_ARG, "energy_scale must be >= 0%s");
   const TrainSplitPlan p = plan_train_split(N, d, H, T, a->aux_encoder, a->decoder);
-  if (a->workspace_floats < p.total) return fail(L2HMC_ERR_ARG, "workspace too small: need %s%lld floats", "", p.total);
-  hipStream_t s = (hipStream_t)stream;
-  float* w = a->workspace;
+  if ((rc = check_workspace(a->workspace_floats, p.total))) return rc;
   const SplitPlan& f = p.fwd;
-  static const L2hmcMlp3 no_dec = {};
-  const L2hmcMlp3& dec = vae ? *a->decoder : no_dec;
-  Mlp3Ws dws = {w + f.dw1t, w + f.dw2t, w + f.dw3t, w + f.a1, w + f.s1, w + f.a2, w + f.s2};
-  // the decoder-sized products of the forward pass and of the Hessian-vector products on pre-split planes (round 5), when the
-  // sampler's own planes rule says so (gemm_mode 1, >= 84 tiles: 3072 chains at config 5's widths)
-  const bool use_planes = vae && f.planes && (a->gemm_mode == 1 || a->gemm_mode == 3);
-  if (use_planes) {
-    if ((rc = gemm_planes_prepare<EPI_BIAS_SOFTPLUS>()) != L2HMC_OK || (rc = gemm_planes_prepare<EPI_BCE>()) != L2HMC_OK ||
-        (rc = gemm_planes_prepare<EPI_MUL>()) != L2HMC_OK || (rc = gemm_planes_prepare<EPI_TAN>()) != L2HMC_OK)
-      return rc;
-    auto us = [&](long long off) { return reinterpret_cast<unsigned short*>(w + off); };
-    dws.pw2t = us(f.pw2t); dws.pw3t = us(f.pw3t); dws.pw2 = us(f.pw2); dws.pw3 = us(f.pw3);
-    dws.pa1 = us(f.pa1); dws.pa2 = us(f.pa2); dws.plg = us(f.plg); dws.pda2 = us(f.pda2);
-    if (a->gemm_mode == 3) { dws.pw2t_h = us(p.pw2t_h); dws.pw3t_h = us(p.pw3t_h); dws.pw2_h = us(p.pw2_h); dws.pw3_h = us(p.pw3_h); }
-  }
-  const int L = 2 * d;
-  static const L2hmcNet no_net = {};              // lam_s == NULL: the update kernels and their adjoints take S | T | Q as they are
-  const L2hmcNet &xn = unets ? no_net : *a->xnet, &vn = unets ? no_net : *a->vnet;
-  const L2hmcNet* nets[2] = {&xn, &vn};
-  const unsigned char* dir = a->direction;
-  const int dall = a->direction_all;
-  const unsigned nw4 = (unsigned)((N + 3) / 4);
-  float *tb = w + f.tb, *ld = w + f.ld;
-  float* aux_h = a->aux_encoder ? w + f.aux_h : nullptr;
-  double *U0d = reinterpret_cast<double*>(w + f.U0), *U1d = reinterpret_cast<double*>(w + f.U1);
+  engine_bind(c, a->workspace, f, a->gemm_mode);
+  hipStream_t s = c.s;
+  float* w = c.w;
   // training on U / temperature: the built-in energies (l2hmc_energy) and the callbacks return it tempered; the decoder
   // posterior is evaluated plain and tempered behind (k_temper), only when temperature != 1
   const float temp = a->energy != nullptr ? a->energy->temperature : 1.f;
   const float itemp = 1.f / temp;
   const bool temper_dec = vae && temp != 1.f;
+  c.temp = temp;
+  auto us = [&](long long off) { return reinterpret_cast<unsigned short*>(w + off); };
+  // the decoder-sized products of the forward pass and of the Hessian-vector products on pre-split planes (round 5), when the
+  // sampler's own planes rule says so (gemm_mode 1, >= 84 tiles: 3072 chains at config 5's widths)
+  if (c.use_planes) {
+    if ((rc = planes_prepare()) || (rc = gemm_planes_prepare<EPI_TAN>())) return rc;      // ... and the Hessian-vector products' own
+    if (a->gemm_mode == 3) { c.dws.pw2t_h = us(p.pw2t_h); c.dws.pw3t_h = us(p.pw3t_h); c.dws.pw2_h = us(p.pw2_h); c.dws.pw3_h = us(p.pw3_h); }
+  }
+  c.ews.s1 = w + p.es1; c.ews.s2 = w + p.es2;        // the image branch's sigmoids stay for its reverse pass
+  const L2hmcMlp3& dec = *c.dec;
+  const Mlp3Ws &dws = c.dws, &ews = c.ews;
+  const L2hmcNet &xn = *c.nets[0], &vn = *c.nets[1];
+  const L2hmcNet* const* nets = c.nets;
+  const unsigned char* dir = c.dir;
+  const int dall = c.dall;
+  const unsigned nw4 = (unsigned)((N + 3) / 4);
+  float* ld = c.ld;
+  double *U0d = reinterpret_cast<double*>(w + f.U0), *U1d = reinterpret_cast<double*>(w + f.U1);
   const long long NL = N * L, NH = N * H, N3 = N * 3 * d, Nd = N * d;
   // stash slices of evaluation `ne` (= 2 it + which) of net `net` (0 = X, 1 = V)
   auto AB = [&](int net, int ne) { return w + p.AB[net] + ne * NL; };
@@ -874,68 +791,21 @@ int l2hmc_train_split_grad(const L2hmcTrainSplitArgs* a, void* stream) {
   auto YS = [&](int it) { return w + p.YS + it * Nd; };
 
   // One net evaluation -- and its reverse -- in ONE launch each (net_eval_kernel with both hidden activations kept,
-  // net_bwd_kernel) under the sampler's own rule for the fused form: H % 4 == 0, d even, K <= 256, the tiles fit the LDS.
-  // (Round 5: at config 5's shapes the 120 launches of 64 x 64-tile products these replace were 2.5 ms of a 10.5 ms step.)
-  int ne_dev = 0, ne_cus = 256;
-  if (hipGetDevice(&ne_dev) != hipSuccess || hipDeviceGetAttribute(&ne_cus, hipDeviceAttributeMultiprocessorCount, ne_dev) != hipSuccess ||
-      ne_cus <= 0)
-    ne_cus = 256;
-  const int ne_cb = N >= 32LL * ne_cus ? 2 : 1;
-  const size_t ne_lds = net_eval_lds_bytes(d, H, ne_cb), nb_lds = net_bwd_lds_bytes(d, H, ne_cb);
-  const bool fused_nets = !unets && (H % 4 == 0) && (d % 2 == 0) && ceil16(H) <= 16 * NE_MAXKT && ceil16(3 * d) <= 16 * NE_MAXKT &&
-                          ne_lds <= 160 * 1024 && nb_lds <= 160 * 1024 && a->net_mode == 0;
-  if (fused_nets) {
-    hipError_t e = hipSuccess;
-    if (ne_lds > 48 * 1024)
-      e = hipFuncSetAttribute(net_eval_fn(ne_cb, d, H), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ne_lds);
-    if (e == hipSuccess && nb_lds > 48 * 1024)
-      e = hipFuncSetAttribute(net_bwd_fn(ne_cb, d, H), hipFuncAttributeMaxDynamicSharedMemorySize, (int)nb_lds);
-    if (e != hipSuccess) return fail(L2HMC_ERR_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(e));
-  }
-  const unsigned ne_blocks = (unsigned)((N + 16 * ne_cb - 1) / (16 * ne_cb));
-  // ---- weights: transposed copies for the forward products, stacked copies for the input-gradient products ------
-  if (vae) mlp3_transposes(s, dec, dws);
-  if (use_planes) {           // weights split once per call; the activations' padding up to whole k-tiles zeroed once
-    auto us = [&](long long off) { return reinterpret_cast<unsigned short*>(w + off); };
-    to_planes(s, dws.w2t, dec.n_h1, dec.n_h2, dec.n_h1, dws.pw2t, prows(dec.n_h2), pld(dec.n_h1));
-    to_planes(s, dws.w3t, dec.n_h2, dec.n_out, dec.n_h2, dws.pw3t, prows(dec.n_out), pld(dec.n_h2));
-    to_planes(s, dec.W2, dec.n_h2, dec.n_h1, dec.n_h2, dws.pw2, prows(dec.n_h1), pld(dec.n_h2));
-    to_planes(s, dec.W3, dec.n_out, dec.n_h2, dec.n_out, dws.pw3, prows(dec.n_h2), pld(dec.n_out));
-    if (dws.pw2t_h != nullptr) {                     // ... and for the forward evaluations as f16x2 planes (gemm_mode 3)
-      to_planes(s, dws.w2t, dec.n_h1, dec.n_h2, dec.n_h1, dws.pw2t_h, prows(dec.n_h2), pld(dec.n_h1), 1);
-      to_planes(s, dws.w3t, dec.n_h2, dec.n_out, dec.n_h2, dws.pw3t_h, prows(dec.n_out), pld(dec.n_h2), 1);
-      to_planes(s, dec.W2, dec.n_h2, dec.n_h1, dec.n_h2, dws.pw2_h, prows(dec.n_h1), pld(dec.n_h2), 1);
-      to_planes(s, dec.W3, dec.n_out, dec.n_h2, dec.n_out, dws.pw3_h, prows(dec.n_h2), pld(dec.n_out), 1);
-    }
-    planes_zero_pad(s, dws.pa1, N, dec.n_h1, pld(dec.n_h1));
-    planes_zero_pad(s, dws.pa2, N, dec.n_h2, pld(dec.n_h2));
-    planes_zero_pad(s, dws.plg, N, dec.n_out, pld(dec.n_out));
-    planes_zero_pad(s, dws.pda2, N, dec.n_h2, pld(dec.n_h2));
+  // net_bwd_kernel) under the sampler's own rule for the fused form, with the reverse's wider K (plan_nets)
+  if ((rc = plan_nets(c, true, a->net_mode))) return rc;
+  const bool fused_nets = c.np.fused;
+  // ---- weights: the engine's preparation (nothing is kept from an earlier call: a `reuse` of the trainer's own would go
+  //      here), then what the reverse sweep needs on top of it -------------------------------------------------------
+  prepare_decoder(c, false);
+  if (c.use_planes) {          // the padding of the four tangent planes up to whole k-tiles, zeroed once
     planes_zero_pad(s, us(p.pHD1), N, dec.n_h1, pld(dec.n_h1));
     planes_zero_pad(s, us(p.pHD2), N, dec.n_h2, pld(dec.n_h2));
     planes_zero_pad(s, us(p.pRD), N, dec.n_out, pld(dec.n_out));
     planes_zero_pad(s, us(p.pM2), N, dec.n_h2, pld(dec.n_h2));
   }
-  Mlp3Ws ews = {};
-  if (a->aux_encoder) {
-    const L2hmcMlp3& enc = *a->aux_encoder;
-    ews = Mlp3Ws{w + f.ew1t, w + f.ew2t, w + f.ew3t, w + f.e1, w + p.es1, w + f.e2, w + p.es2};
-    mlp3_transposes(s, enc, ews);
-    mlp3_forward(s, enc, a->aux, N, ews, aux_h);
-  }
-  if (!unets) hipLaunchKernelGGL(k_time_table, dim3(nblk(2LL * T * H)), dim3(256), 0, s, xn, vn, a->trig, T, H, tb);
-  float* w12t[2] = {w + f.nx12t, w + f.nv12t};
-  float* w4t[2] = {w + f.nx4t, w + f.nv4t};
-  float* wht[2] = {w + f.nxht, w + f.nvht};
-  const int K1p = ceil16(L), Hp = ceil16(H);
-  if (!unets) (void)hipMemsetAsync(w + f.nx12t, 0, sizeof(float) * (size_t)(f.nvht + (long long)ceil16(3 * d) * Hp - f.nx12t), s);
-  for (int i = 0; i < 2 && !unets; ++i) {
-    transpose_into(s, nets[i]->W1, d, H, w12t[i], K1p, 0);
-    transpose_into(s, nets[i]->W2, d, H, w12t[i], K1p, d);
-    transpose_into(s, nets[i]->W4, H, H, w4t[i], Hp, 0);
-    transpose_into(s, nets[i]->Ws, H, d, wht[i], Hp, 0);
-    transpose_into(s, nets[i]->Wt, H, d, wht[i] + (long long)d * Hp, Hp, 0);
-    transpose_into(s, nets[i]->Wq, H, d, wht[i] + 2LL * d * Hp, Hp, 0);
+  prepare_image_branch(c, false, false);
+  const int Hp = ceil16(H);
+  prepare_nets(c, false, [&](int i) {       // stacked copies for the input-gradient products
     hipLaunchKernelGGL(k_stack_rows, dim3(nblk(2LL * d * H)), dim3(256), 0, s, nets[i]->W1, nets[i]->W2, (long long)d * H,
                        (long long)d * H, w + p.w12c[i]);
     hipLaunchKernelGGL(k_heads_side, dim3(nblk(3LL * d * H)), dim3(256), 0, s, nets[i]->Ws, nets[i]->Wt, nets[i]->Wq, H, d,
@@ -950,7 +820,7 @@ int l2hmc_train_split_grad(const L2hmcTrainSplitArgs* a, void* stream) {
       (void)hipMemcpy2DAsync(w + p.whp[i], sizeof(float) * K3p, w + p.whc[i], sizeof(float) * 3 * d, sizeof(float) * 3 * d, (size_t)H,
                              hipMemcpyDeviceToDevice, s);
     }
-  }
+  });
 
   // trajectory point j = 0 .. T (the start point and the position after each leapfrog step)
   auto dec_point = [&](int j) {
@@ -962,69 +832,18 @@ int l2hmc_train_split_grad(const L2hmcTrainSplitArgs* a, void* stream) {
     }
     return pt;
   };
-  // U (double, optional) and grad U at point j, held in columns [0, d) of `ab` -> columns [d, 2 d)
+  // U (double, optional) and grad U at point j, held in columns [0, d) of `ab` -> columns [d, 2 d), its DecPoint kept
   auto energy_eval = [&](float* ab, int j, double* Ud) -> int {
-    if (user) {      // the caller enqueues U / grad U of the (N, d) block at ab (row stride L) on this stream
-      const int r = a->energy_cb(a->energy_cb_user, ab, L, N, d, Ud, ab + d, L, stream);
-      return r ? fail(L2HMC_ERR_ARG, "the energy callback failed (returned %s%lld)", "", (long long)r) : L2HMC_OK;
-    }
-    if (vae) {
-      vae_energy_keep(s, dec, a->aux, ab, L, N, d, dws, w + f.lg, w + f.rowsum, Ud, ab + d, L, dec_point(j));
-      if (temper_dec)
-        hipLaunchKernelGGL(k_temper, dim3(nblk(Nd)), dim3(256), 0, s, ab + d, L, Ud, itemp, 1.0 / (double)temp, N, d);
-      return L2HMC_OK;
-    }
-    (void)hipMemcpy2DAsync(w + f.xp, sizeof(float) * d, ab, sizeof(float) * L, sizeof(float) * d, (size_t)N, hipMemcpyDeviceToDevice, s);
-    const int r = l2hmc_energy(a->energy, w + f.xp, N, d, Ud ? w + f.uf : nullptr, w + f.gp, stream);
-    if (r) return r;
-    (void)hipMemcpy2DAsync(ab + d, sizeof(float) * L, w + f.gp, sizeof(float) * d, sizeof(float) * d, (size_t)N, hipMemcpyDeviceToDevice, s);
-    if (Ud) hipLaunchKernelGGL(k_f2d, dim3(nblk(N)), dim3(256), 0, s, w + f.uf, Ud, N);
-    return L2HMC_OK;
+    const DecPoint pt = dec_point(j);
+    return energy_at(c, ab, Ud, &pt);
   };
-  // one net evaluation with everything kept: h1, h2 and the head products of evaluation (net, ne)
-  // `upd`: the half-update that consumes the evaluation (fused behind the heads when the fused kernel runs: the raw head
-  // products still go to O3 for the reverse sweep); returns false when the caller has to launch the stand-alone update kernel
-  int cb_rc = 0;                                   // first nonzero return of a net callback (checked after each phase)
-  auto net_fwd = [&](int net, int ne, int it, NetEvalArgs::Update upd = NetEvalArgs::Update{}) -> bool {
-    if (unets) {       // the caller's net writes the final S | T | Q of evaluation (net, ne) into the stash
-      if (!cb_rc) cb_rc = a->net_cb(a->net_cb_user, net, AB(net, ne), L, N, d, it, dir, dall, O3(net, ne), stream);
-      return false;
-    }
-    if (fused_nets) {
-      NetEvalArgs na = {};
-      const L2hmcNet& nw = *nets[net];
-      upd.bs = nw.bs; upd.bt = nw.bt; upd.bq = nw.bq; upd.lam_s = nw.lam_s; upd.lam_q = nw.lam_q;
-      upd.alpha = a->alpha; upd.eps_host = a->eps_host; upd.ld = ld; upd.masks = a->masks;
-      na.upd = upd;
-      na.keep_out3 = O3(net, ne);
-      na.AB = AB(net, ne); na.ldab = L; na.W12t = w12t[net]; na.W4t = w4t[net]; na.Wht = wht[net]; na.b4 = nets[net]->b4;
-      na.tb = tb + (long long)net * T * H; na.auxh = aux_h; na.dir = dir; na.dir_all = dall; na.it = it; na.T = T;
-      na.out3 = O3(net, ne); na.M = (int)N; na.d = d; na.H = H; na.keep_h1 = H1(net, ne); na.keep_h2 = H2(net, ne);
-      launch_net_eval(ne_cb, ne_blocks, ne_lds, s, na);
-      return upd.mode != 0;
-    }
-    GemmArgs ga = gemm_args(AB(net, ne), L, w12t[net], K1p, H1(net, ne), H, N, H, L);
-    ga.E = aux_h; ga.lde = H; ga.tb = tb + (long long)net * T * H; ga.dir = dir; ga.dir_all = dall; ga.it = it; ga.T = T;
-    launch_gemm<EPI_NET1>(ga, s, SHAPE_MID);
-    ga = gemm_args(H1(net, ne), H, w4t[net], Hp, H2(net, ne), H, N, H, H);
-    ga.bias = nets[net]->b4;
-    launch_gemm<EPI_BIAS_RELU>(ga, s, SHAPE_MID);
-    ga = gemm_args(H2(net, ne), H, wht[net], Hp, O3(net, ne), 3 * d, N, 3 * d, H);
-    launch_gemm<EPI_BIAS>(ga, s, SHAPE_MID);
-    return false;
+  // one net evaluation with everything kept: h1, h2 and the head products of evaluation (net, ne) (with the fused kernel the
+  // raw head products still go to O3 for the reverse sweep), and the half-update that consumes it
+  auto net_fwd = [&](int net, int ne, int it, const NetEvalArgs::Update& upd) -> int {
+    const NetKeep keep = {H1(net, ne), H2(net, ne), O3(net, ne)};
+    return net_eval(c, net, AB(net, ne), it, upd, &keep);
   };
-  auto v_upd = [&](const float* vin, int ldvi, const float* g, float* vout, int ldvo, const float* x, float* xin) {
-    NetEvalArgs::Update u = {};
-    u.mode = 1; u.vin = vin; u.ldvi = ldvi; u.g = g; u.ldg = L; u.vout = vout; u.ldvo = ldvo;
-    if (xin != nullptr) { u.x = x; u.ldx = L; u.xin = xin; u.ldxi = L; }
-    return u;
-  };
-  auto x_upd = [&](const float* zin, int ldzi, const float* vh, float* zout, int ldzo, float* xin_next, int second) {
-    NetEvalArgs::Update u = {};
-    u.mode = 2; u.zin = zin; u.ldzi = ldzi; u.vh = vh; u.ldvh = L; u.zout = zout; u.ldzo = ldzo;
-    u.xin_next = xin_next; u.ldxn = L; u.second = second;
-    return u;
-  };
+  int cb_rc = 0;                                   // first nonzero return of a net reverse callback (checked after the sweep)
   // reverse of net_fwd for the data path: O3 holds (d zs | d zt | d zq) -> DA2, DA1 (kept for the weight gradients), dAB
   auto net_bwd = [&](int net, int ne) {
     if (unets) {       // (d S | d T | d Q) of evaluation (net, ne) -> (d a | d b); the caller accumulates its parameters' gradients
@@ -1036,7 +855,7 @@ int l2hmc_train_split_grad(const L2hmcTrainSplitArgs* a, void* stream) {
       nb.dO3 = O3(net, ne); nb.ldo = 3 * d; nb.Whc = w + p.whp[net]; nb.W4 = w + p.w4p[net]; nb.W12 = w + p.w12p[net];
       nb.h2 = H2(net, ne); nb.h1 = H1(net, ne); nb.da2 = DA2(net, ne); nb.da1 = DA1(net, ne); nb.dAB = w + p.dAB; nb.ldab = L;
       nb.M = (int)N; nb.d = d; nb.H = H;
-      launch_net_bwd(ne_cb, ne_blocks, nb_lds, s, nb);
+      launch_net_bwd(c.np.cb, c.np.blocks, c.np.nb_lds, s, nb);
       return;
     }
     GemmArgs ga = gemm_args(O3(net, ne), 3 * d, w + p.whc[net], 3 * d, DA2(net, ne), H, N, H, 3 * d);
@@ -1057,26 +876,15 @@ int l2hmc_train_split_grad(const L2hmcTrainSplitArgs* a, void* stream) {
   for (int it = 0; it < T; ++it) {
     const bool last = it == T - 1;
     float *abv0 = AB(1, 2 * it), *abv1 = AB(1, 2 * it + 1), *abx0 = AB(0, 2 * it), *abx1 = AB(0, 2 * it + 1);
-    if (!net_fwd(1, 2 * it, it, v_upd(VS(it), d, abv0 + d, abx0, L, abv0, abx0 + d))) {
-      hipLaunchKernelGGL(k_v_half, dim3(nw4), dim3(256), 0, s, O3(1, 2 * it), vn, VS(it), d, abv0 + d, L, abx0, L, ld, dir, dall,
-                         a->alpha, a->eps_host, N, d);
-      hipLaunchKernelGGL(k_mask_first, dim3(nblk(Nd)), dim3(256), 0, s, abv0, L, abx0 + d, L, a->masks, dir, dall, it, T, N, d);
-    }
-    if (!net_fwd(0, 2 * it, it, x_upd(abv0, L, abx0, YS(it), d, abx1 + d, 0)))
-      hipLaunchKernelGGL(k_x_half, dim3(nw4), dim3(256), 0, s, O3(0, 2 * it), xn, abv0, L, abx0, L, YS(it), d, abx1 + d, L, ld,
-                         a->masks, dir, dall, it, T, 0, a->alpha, a->eps_host, N, d);
+    if ((rc = net_fwd(1, 2 * it, it, v_update(L, VS(it), d, abv0 + d, abx0, L, abv0, abx0 + d)))) return rc;     // v_h, xin = k1 x
+    if ((rc = net_fwd(0, 2 * it, it, x_update(L, abv0, L, abx0, YS(it), d, abx1 + d, 0)))) return rc;          // y, xin = (1 - k1) y
     (void)hipMemcpy2DAsync(abx1, sizeof(float) * L, abx0, sizeof(float) * L, sizeof(float) * d, (size_t)N, hipMemcpyDeviceToDevice, s);
-    if (!net_fwd(0, 2 * it + 1, it, x_upd(YS(it), d, abx0, abv1, L, nullptr, 1)))
-      hipLaunchKernelGGL(k_x_half, dim3(nw4), dim3(256), 0, s, O3(0, 2 * it + 1), xn, YS(it), d, abx0, L, abv1, L, (float*)nullptr, 0,
-                         ld, a->masks, dir, dall, it, T, 1, a->alpha, a->eps_host, N, d);
+    if ((rc = net_fwd(0, 2 * it + 1, it, x_update(L, YS(it), d, abx0, abv1, L, nullptr, 1)))) return rc;       // x'
     if ((rc = energy_eval(abv1, it + 1, last ? U1d : nullptr))) return rc;
-    if (!net_fwd(1, 2 * it + 1, it, v_upd(abx0, L, abv1 + d, VS(it + 1), d, nullptr, nullptr)))
-      hipLaunchKernelGGL(k_v_half, dim3(nw4), dim3(256), 0, s, O3(1, 2 * it + 1), vn, abx0, L, abv1 + d, L, VS(it + 1), d, ld, dir,
-                         dall, a->alpha, a->eps_host, N, d);
+    if ((rc = net_fwd(1, 2 * it + 1, it, v_update(L, abx0, L, abv1 + d, VS(it + 1), d, nullptr, nullptr)))) return rc;   // v'
     if (!last) (void)hipMemcpyAsync(AB(1, 2 * it + 2), abv1, sizeof(float) * NL, hipMemcpyDeviceToDevice, s);
   }
 
-  if (cb_rc) return fail(L2HMC_ERR_ARG, "the net callback failed (returned %s%lld)", "", (long long)cb_rc);
   // ---- accept probability, loss argument, adjoint seeds -----------------------------------------------------------
   float *lx = w + p.lx, *lv = w + p.lv, *dvh = w + p.dvh, *dz = w + p.dz, *dg = w + p.dg, *uu = w + p.u, *hv = w + p.hv;
   float *lam = w + p.lam, *lamU = w + p.lamU, *dv1p = w + p.dv1p, *deps = w + p.deps, *dAB = w + p.dAB;

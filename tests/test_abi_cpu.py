@@ -142,3 +142,148 @@ def test_hot_kernels_keep_their_register_budgets():
             assert vg <= 256, (k, vg)
         if f in ("train.s", "split.s", "l2hmc_abi.s"):
             assert sc == 0, (f, k, sc)
+
+
+# ---- the GEMM engine's host path (csrc/split.hip, csrc/train_split.hpp): its plan and its refusals, pinned --------------------
+_HOST = (ctypes.c_float * 16)()                      # stands in for every device pointer: nothing below reaches a launch
+_PTR = ctypes.addressof(_HOST)
+_ENERGY_CB = _ffi.ENERGY_CALLBACK(lambda *a: 1)
+_NET_CB = _ffi.NET_CALLBACK(lambda *a: 1)
+_NET_VJP_CB = _ffi.NET_VJP_CALLBACK(lambda *a: 1)
+
+
+def _fn(cb):
+    return ctypes.cast(cb, ctypes.c_void_p).value
+
+
+def _mlp3(n_in, n_h1, n_h2, n_out):
+    m = _ffi.L2hmcMlp3()
+    for k in ("W1", "b1", "W2", "b2", "W3", "b3"):
+        setattr(m, k, _PTR)
+    m.n_in, m.n_h1, m.n_h2, m.n_out = n_in, n_h1, n_h2, n_out
+    return m
+
+
+def _engine_floats(query, N, d, H, T, enc, dec):
+    enc, dec = (_mlp3(*enc) if enc else None), (_mlp3(*dec) if dec else None)
+    return query(N, d, H, T, ctypes.byref(enc) if enc else None, ctypes.byref(dec) if dec else None)
+
+
+IMAGE16 = (32, 4, 8, 5, (16, 8, 8, 8), (4, 8, 8, 16))          # image branch + decoder: 16 pixels, latent 4, H = 8
+ENGINE_SHAPES = (
+    ("no decoder: d = 10, H = 32, T = 5", (64, 10, 32, 5, None, None)),
+    ("image branch + decoder: 16 pixels", IMAGE16),
+    ("config-5 widths, 3071 chains: no planes", (3071, 50, 200, 2, (784, 512, 512, 200), (50, 1024, 1024, 784))),
+    ("config-5 widths, 3072 chains: planes", (3072, 50, 200, 2, (784, 512, 512, 200), (50, 1024, 1024, 784))),
+    ("caller-supplied nets: H = 4", (64, 4, 4, 5, None, None)),
+)
+# (l2hmc_split_workspace_floats, l2hmc_train_split_workspace_floats) of the library before the two entry points shared one
+# host path: SplitPlan / TrainSplitPlan offsets and totals are part of what that refactor had to leave alone
+ENGINE_PLAN = {
+    "no decoder: d = 10, H = 32, T = 5": (18112, 1343808),
+    "image branch + decoder: 16 pixels": (6352, 1110160),
+    "config-5 widths, 3071 chains: no planes": (47913268, 174088528),
+    "config-5 widths, 3072 chains: planes": (47926048, 174138816),
+    "caller-supplied nets: H = 4": (5416, 1117896),
+}
+
+
+def test_gemm_engine_workspace_plan_is_pinned():
+    """The two workspace queries make no HIP call: one row per family of slices the plan takes or leaves out (no decoder;
+    image branch + decoder; config 5's widths on either side of the planes threshold; the H = 4 plan of caller-supplied nets)."""
+    L = _ffi.lib()
+    for name, shape in ENGINE_SHAPES:
+        got = (_engine_floats(L.l2hmc_split_workspace_floats, *shape), _engine_floats(L.l2hmc_train_split_workspace_floats, *shape))
+        assert got == ENGINE_PLAN[name], (name, got)
+
+
+def _engine_block(which):
+    """An argument block of the 16-pixel image sampler that passes every check of its entry point (the first HIP call would
+    follow); returns it with the host objects it points to."""
+    N, d, H, T, enc, dec = IMAGE16
+    a = _ffi.L2hmcSplitArgs() if which == "sampler" else _ffi.L2hmcTrainSplitArgs()
+    keep = dict(enc=_mlp3(*enc), dec=_mlp3(*dec), xnet=_ffi.L2hmcNet(), vnet=_ffi.L2hmcNet())
+    a.xnet, a.vnet, a.H = ctypes.pointer(keep["xnet"]), ctypes.pointer(keep["vnet"]), H
+    a.aux_encoder, a.decoder = ctypes.pointer(keep["enc"]), ctypes.pointer(keep["dec"])
+    a.aux = a.masks = a.trig = a.x = a.v = a.workspace = _PTR
+    a.eps_host, a.n_chains, a.d, a.T, a.workspace_floats = 0.1, N, d, T, 1 << 40
+    if which == "sampler":
+        a.n_steps = T
+    else:
+        a.Lx = a.p = a.v1 = a.grad = _PTR
+        a.scale, a.inv_n = 1.0, 1.0 / N
+    return a, keep
+
+
+def _builtin(a, k, kind, **fields):
+    """the block's target becomes a built-in energy (no decoder, no image branch, no images)"""
+    e = k["energy"] = _ffi.L2hmcEnergy(kind=kind, mu=_PTR, prec=_PTR, temperature=1.0, **fields)
+    a.energy, a.decoder, a.aux_encoder, a.aux = ctypes.pointer(e), None, None, None
+
+
+def _set(**fields):
+    def edit(a, k):
+        for name, value in fields.items():
+            setattr(a, name, value)
+    return edit
+
+
+def _enc_out_9(a, k):
+    k["enc"].n_out = 9
+
+
+def _net_cbs(a, k):
+    a.net_cb = _fn(_NET_CB)
+    if hasattr(a, "net_vjp_cb"):
+        a.net_vjp_cb = _fn(_NET_VJP_CB)
+
+
+# (case, edit of the passing block, return code, l2hmc_last_error) -- the texts as the library gave them before the refactor
+_SHARED_WORDING = (
+    ("aux_encoder output width != H", _enc_out_9, -1, "aux_encoder must map (N, n_pix) -> (N, H)"),
+    ("decoder input width != d", _set(d=5), -1, "decoder input width != d"),
+    ("eps_host = 0 without alpha", _set(eps_host=0.0), -1, "eps must be > 0"),
+)
+ENGINE_REFUSALS = {
+    "sampler": _SHARED_WORDING + (
+        ("gemm_mode 4", _set(gemm_mode=4), -1,
+         "gemm_mode must be 0 (f32 MFMA), 1 (bf16x3), 2 (bf16x3, split in the loop) or 3 (f16x2 planes)"),
+        ("energy_cb with a decoder", _set(energy_cb=_fn(_ENERGY_CB)), -1, "energy_cb excludes decoder and energy"),
+        ("net_cb with xnet", _net_cbs, -1, "net_cb excludes xnet / vnet / aux_encoder / hmc"),
+        ("workspace one float short", _set(workspace_floats=6352 - 1), -1, "workspace too small: need 6352 floats"),
+    ),
+    "trainer": _SHARED_WORDING + (
+        ("gemm_mode 4", _set(gemm_mode=4), -1,
+         "gemm_mode must be 0 (f32 MFMA), 1 (bf16x3), 2 (bf16x3, split in the loop) or 3 (f16x2 planes for the forward "
+         "evaluations, bf16x3 for the reverse sweep)"),
+        ("energy_cb with a decoder", _set(energy_cb=_fn(_ENERGY_CB)), -1, "energy_cb excludes a built-in energy and decoder"),
+        ("net_cb with xnet", _net_cbs, -1,
+         "net_cb excludes xnet / vnet / aux_encoder (an image branch is the caller's net's own business)"),
+        ("workspace one float short", _set(workspace_floats=1110160 - 1), -1, "workspace too small: need 1110160 floats"),
+        ("net_cb without net_vjp_cb", _set(net_cb=_fn(_NET_CB)), -1,
+         "training caller-supplied nets needs BOTH net_cb and net_vjp_cb"),
+        ("energy_cb without hvp_cb", _set(energy_cb=_fn(_ENERGY_CB), decoder=None), -1,
+         "training on a caller-supplied energy needs hvp_cb (the loss differentiates through grad U)"),
+        ("dense Gaussian without hess", lambda a, k: _builtin(a, k, _ffi.ENERGY_GAUSS_DENSE), -1,
+         "dense Gaussian / mixture: hess = the RAW (n_comp, d, d) precisions"),
+        ("logistic regression", lambda a, k: _builtin(a, k, _ffi.ENERGY_LOGISTIC, n_comp=8, eta=4.0), -2,
+         "the GEMM engine does not train on the logistic-regression target (its Hessian-vector product lives in "
+         "l2hmc_train_propose_grad's tile kernel): train there, or on the same likelihood as a caller-supplied energy"),
+    ),
+}
+
+
+def _refusal(L, which, edit):
+    a, keep = _engine_block(which)
+    edit(a, keep)
+    rc = (L.l2hmc_trajectory_split if which == "sampler" else L.l2hmc_train_split_grad)(ctypes.byref(a), None)
+    return rc, L.l2hmc_last_error().decode()
+
+
+@pytest.mark.parametrize("which", ("sampler", "trainer"))
+def test_gemm_engine_refusals_are_pinned(which):
+    """Argument blocks both entry points of the GEMM engine refuse before any HIP call: return code and message, word for word.
+    Where the two word the same refusal differently, each keeps its own text."""
+    L = _ffi.lib()
+    for name, edit, rc, msg in ENGINE_REFUSALS[which]:
+        assert _refusal(L, which, edit) == (rc, msg), (which, name)

@@ -358,7 +358,7 @@ def test_a_net_outside_the_notebook_architecture_matches_the_oracle():
 def test_training_on_presplit_planes_agrees_with_the_split_in_the_loop():
     """The GEMM-engine trainer at config 5's widths and 3072 chains (the chain count from which the decoder-sized products take the
     pre-split form, csrc/gemm_xl.hpp): round 5 puts the forward pass's and the Hessian-vector products' 1024-wide products on bf16
-    planes (`vae_energy_keep`, `vae_hvp` of csrc/train_split.hpp; activations split by the producing epilogue, weights once per
+    planes (`vae_energy` with a DecPoint, `vae_hvp` of csrc/split.hip, train_split.hpp; activations split by the producing epilogue, weights once per
     call).  gemm_mode 2 keeps the split inside the k loop of every product: the same six bf16 products per block in the same order
     -- every product is bit-identical (tools/ubench_gemm_bf3.hip) -- but the BCE row sums of the energy are formed per 128-wide
     column tile instead of per 64-wide one: float32 partial sums of ~45 each (ulp 4e-6), 13 or 7 of them per chain, so U ~ 540
