@@ -8,7 +8,9 @@ out) and two Bayesian logistic regressions: every feature, and the informative l
   * `model.waic(history)`: the expected log pointwise predictive density of the rows the model was fitted to, by WAIC, its
     effective number of parameters and standard error;
   * `model.loo(history)`: the same quantity by Pareto-smoothed importance-sampling leave-one-out, with the number of rows whose
-    Pareto k-hat says the estimate cannot be trusted (`n_bad`);
+    Pareto k-hat says the estimate cannot be trusted (`n_bad`); `r_eff="auto"` accounts for the chains' autocorrelation
+    (r_eff_i = ESS / S of every row's likelihood) and adds the Monte Carlo standard error of elpd_loo and the smallest
+    importance-sampling effective sample size;
   * `log_predictive_density(history, X_test, y_test)`: the same question answered with the 200 rows neither model has seen.
 
 All three should prefer the full model, by a margin of several standard errors of the difference.
@@ -60,9 +62,12 @@ def main(chains=1024, updates=60, proposals=200, n_train=1000, seed=1):
         h = log_predictive_density(kept, X_test[:, cols], y_test)
         print("  WAIC %.1f: elpd_waic %.1f (se %.1f), p_waic %.2f, lppd %.1f; %d rows with p_waic_i > 0.4, %d underflowed" % (
             w.waic, w.elpd_waic, w.se, w.p_waic, w.lppd, w.n_high_variance, w.n_underflow))
-        o = model.loo(kept)
-        print("  LOO: elpd_loo %.1f (se %.1f), p_loo %.2f; %d rows with khat > 0.7 (n_bad), %d above the threshold %.2f, max khat %.2f" % (
-            o.elpd_loo, o.se, o.p_loo, o.n_bad, o.n_above_threshold, o.khat_threshold, float(np.max(o.khat))))
+        o = model.loo(kept, r_eff="auto")
+        print("  LOO: elpd_loo %.1f (se %.1f, Monte Carlo se %.3f, min n_eff %.0f), p_loo %.2f; %d rows with khat > 0.7 (n_bad), "
+              "%d above the threshold %.2f, max khat %.2f" % (o.elpd_loo, o.se, o.mcse_elpd_loo, o.min_n_eff, o.p_loo, o.n_bad,
+                                                               o.n_above_threshold, o.khat_threshold, float(np.max(o.khat))))
+        print("  relative efficiency of the rows' likelihoods: r_eff %.3f .. %.3f (%d degenerate), tail lengths %d .. %d" % (
+            float(np.nanmin(o.r_eff)), float(np.nanmax(o.r_eff)), o.n_reff_nan, o.tail_len_row.min(), o.tail_len_row.max()))
         print("  held-out lppd of %d rows: %.1f (se %.1f)" % (h.n_rows, h.lppd, h.se))
         results[name] = (w, h)
     (wa, ha), (wb, hb) = results["all features"], results["last feature dropped"]

@@ -761,6 +761,47 @@ int l2hmc_logistic_loo_tails(const float* draws, int64_t n_draws, int32_t d, con
                              float* cutoff /* (n_data) */, int64_t* n_tail /* (n_data) */, float* tail /* (n_data, M) */,
                              double* sums /* (2, n_data): body, sum_lik */, void* workspace, void* stream);
 
+/* l2hmc_logistic_loo_tails for a run of autocorrelated draws (`predictive.loo(r_eff=...)`): every row has its own tail length
+ * M_i = tail_len_row[i], 0 <= M_i <= tail_stride < n_draws (int64 on the device; an entry outside is clamped), chosen by the
+ * caller from the row's relative efficiency.  cutoff[i] is the element of rank M_i, n_tail[i] = L_i <= M_i, `tail` is
+ * (n_data, tail_stride) with +inf in the slots at or past L_i, and `sums` is (3, n_data): [0] body and [1] sum_lik as above,
+ * [2] body_sq = the sum over the draws NOT in the tail of (e^m + e^(m - t))^2, every float32 term squared exactly in float64
+ * (in (0, 4]): the sum of the squared importance ratios of the body is e^(-2 m) body_sq.  With every M_i =
+ * l2hmc_logistic_loo_tail_len(n_draws) = tail_stride, then cutoff, n_tail, the tail as a set, body and sum_lik are those of
+ * l2hmc_logistic_loo_tails bit for bit.  `workspace`: l2hmc_logistic_loo_mc_workspace_bytes(...) bytes (a third partial sum);
+ * its first int64 is non-zero after the call if a tail slot at or past M_i was asked for.  Reproducibility and the other
+ * argument errors are those of l2hmc_logistic_loo_tails; also L2HMC_ERR_ARG: tail_stride outside 0 .. n_draws - 1,
+ * tail_stride n_data > 2^31, tail_len_row NULL or not 8-byte aligned. */
+int64_t l2hmc_logistic_loo_mc_workspace_bytes(int64_t n_draws, int32_t n_data, int32_t d);
+int l2hmc_logistic_loo_tails_mc(const float* draws, int64_t n_draws, int32_t d, const float* packed, int32_t n_data,
+                                const int64_t* tail_len_row /* (n_data) */, int64_t tail_stride, float* cutoff /* (n_data) */,
+                                int64_t* n_tail /* (n_data) */, float* tail /* (n_data, tail_stride) */,
+                                double* sums /* (3, n_data): body, sum_lik, body_sq */, void* workspace, void* stream);
+
+/* Bayesian logistic regression: the raw sums behind the per-row relative efficiency of PSIS-LOO, r_eff_i = ESS(p(y_i | theta)) / S
+ * (Vehtari, Gelman, Gabry 2017; csrc/lik_stats.hip; l2hmc_amd/predictive.py `relative_eff`).  `draws` is a recorded history
+ * (steps, n_chains, d) float32 on the device, read in place (a first-axis slice is fine: 4-byte alignment); `packed` is that of
+ * l2hmc_logistic_predict.  The series are the likelihoods lik[t, c, i] = sigmoid((2 y_i - 1) x_i . w[t, c]) -- the float32 logits
+ * and likelihoods of l2hmc_logistic_loo_tails, bit for bit -- and the outputs are those of l2hmc_chain_stats for that derived
+ * history, which is never written, with the data row in the place of the coordinate.  `split`, Mh and C mean what they mean there:
+ *   mean  (C, n_data)            m[c, i]  = mean_t lik                                  (float64 accumulation)
+ *   m2    (C, n_data)            M2[c, i] = sum_t (lik_t - m)^2                         (float64 accumulation)
+ *   G     (n_data, max_lag + 1)  G[i, t]  = sum_c sum_{s < Mh - t} (lik_s - m[c, i]) (lik_{s+t} - m[c, i])
+ *                                (values centred in float64 and rounded to float32 once; products in float32 chunks of 8 steps
+ *                                folded into float64)
+ * l2hmc_amd/diagnostics.py `reduce_sums` and `finish` take them as they take l2hmc_chain_stats' outputs.
+ * `workspace`: l2hmc_logistic_lik_stats_workspace_bytes(...) bytes, 8-byte aligned, required -- the waves' partial lag sums, which
+ * a last kernel adds in a fixed order: at most 2 x 16 x n_data x (max_lag + 1) doubles.  No floating-point atomics: two calls
+ * give identical bits, and a row's numbers do not depend on which other rows share the call.  A non-finite draw makes the sums of
+ * its own chain (mean, m2) and of the rows it meets (G) non-finite, nothing else.
+ * L2HMC_ERR_ARG (before any launch): steps / n_chains < 1, split not 0 / 1, Mh < 4, C < 2, max_lag outside 0 .. Mh - 1, steps
+ * n_chains < 2 or > 2^40 / d, n_data outside 1 .. 1048576, d outside 1 .. 128, a NULL or misaligned pointer. */
+int64_t l2hmc_logistic_lik_stats_workspace_bytes(int64_t steps, int64_t n_chains, int32_t d, int32_t n_data, int32_t max_lag,
+                                                 int32_t split);
+int l2hmc_logistic_lik_stats(const float* draws, int64_t steps, int64_t n_chains, int32_t d, const float* packed, int32_t n_data,
+                             int32_t max_lag, int32_t split, double* mean /* (C, n_data) */, double* m2 /* (C, n_data) */,
+                             double* G /* (n_data, max_lag + 1) */, void* workspace, void* stream);
+
 /* Pareto-smoothed importance sampling of the tails of ANY log importance ratios, float64 throughout (csrc/psis.hip;
  * l2hmc_amd/psis.py `smooth_tails`, `psis`, `loo_from_log_lik`; `predictive.loo(finish="kernel")`).  Per row i:
  *   lam         (n_rows, tail_len) the L_i = n_tail[i] <= tail_len largest log ratios, descending, in slots 0 .. L_i - 1; a slot

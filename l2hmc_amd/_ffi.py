@@ -187,6 +187,12 @@ SYMBOLS = {
     "l2hmc_logistic_loo_tail_len": (C.c_int64, [C.c_int64]),
     "l2hmc_logistic_loo_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
     "l2hmc_logistic_loo_tails": (C.c_int, [_fp, C.c_int64, C.c_int32, _fp, C.c_int32, _fp, _fp, _fp, _fp, _fp, _fp]),
+    "l2hmc_logistic_loo_mc_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
+    "l2hmc_logistic_loo_tails_mc": (C.c_int, [_fp, C.c_int64, C.c_int32, _fp, C.c_int32, _fp, C.c_int64, _fp, _fp, _fp, _fp, _fp,
+                                              _fp]),
+    "l2hmc_logistic_lik_stats_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "l2hmc_logistic_lik_stats": (C.c_int, [_fp, C.c_int64, C.c_int64, C.c_int32, _fp, C.c_int32, C.c_int32, C.c_int32, _fp, _fp,
+                                           _fp, _fp, _fp]),
     "l2hmc_psis_plan": (C.c_int64, [C.c_int64, C.c_int64, C.c_int32]),
     "l2hmc_psis_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
     "l2hmc_psis_smooth": (C.c_int, [_fp, _fp, _fp, C.c_int64, C.c_int64, _fp, _fp, _fp, _fp]),

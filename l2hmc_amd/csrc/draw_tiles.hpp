@@ -67,6 +67,24 @@ __device__ __forceinline__ void tile_load(const float* __restrict__ W, long long
   }
 }
 
+// the same tile cut out of ONE step of a history (steps, N, d): the 1 <= `live` <= 16 chains from draw `draw0` on
+// (lik_stats.hip walks the steps of 16 chains); a chain at or past `live` enters as 0, like a draw past the end above.  Every
+// lane loads -- an element past the live ones reads the last live one and drops it -- so the loads need no branch.
+template <int NTM>
+__device__ __forceinline__ void tile_load_at(const float* __restrict__ W, long long draw0, int live, const TileWalk& k, int lane,
+                                             float (&pre)[4 * NTM]) {
+  const float* base = W + draw0 * k.d;
+  const int lim = live * k.d;
+#pragma unroll
+  for (int i = 0; i < 4 * NTM; ++i) {
+    const int e = lane + 64 * i;
+    // (a 32-bit byte offset from the wave-uniform base: one address register per load, not two; lim <= 16 x 128)
+    const unsigned off = 4u * (unsigned)(e < lim ? e : lim - 1);
+    const float v = *reinterpret_cast<const float*>(reinterpret_cast<const char*>(base) + off);
+    pre[i] = e < lim ? v : 0.f;
+  }
+}
+
 template <int NTM>
 __device__ __forceinline__ void tile_stage(float* lds, const float (&pre)[4 * NTM], const TileWalk& k, int lane) {
   // the walk's LDS addresses depend on the lane alone; seen as loop invariants they are hoisted out of the tile loop and

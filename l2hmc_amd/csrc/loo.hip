@@ -38,6 +38,11 @@
 //            BEFORE the addition, to the lane's own sums; once per wave the 16 draw lanes are added in the order c = 0 .. 15 and
 //            the wave's partials go to workspace[chunk][2][n].
 //   reduce   chunk_reduce_kernel: sums[k][i] = the chunks' partials added in chunk order.
+//   mc       l2hmc_logistic_loo_tails_mc (a run of autocorrelated draws: `predictive.loo(r_eff=...)`): every row has its OWN tail
+//            length tail_len_row[i] <= tail_stride -- `remaining` starts there, the tail's row stride is tail_stride -- and the
+//            gather is loo_kernel<NTM, 2>: MODE 1 with a third sum, body_sq = the sum over the draws not in the tail of
+//            (e^m + e^(m - t))^2, each float32 term squared exactly in float64 (in (0, 4]).  The first two sums are MODE 1's
+//            operations in MODE 1's order: with every length equal to M the old entry's bits come back.
 // No floating-point atomics anywhere: integer counts do not depend on arrival order, the tail is a set, the sums have a fixed
 // tree.  Every outward write is an ordinary vector store or atomic from plain C++.
 //
@@ -48,6 +53,8 @@
 // Occupancy by design: 2 workgroups per CU (2 waves per SIMD) -- every geometry must stay within 256 registers (held by
 // tests/test_loo_cpu.py from the compiler's listing) and its LDS, 32 KiB of histogram plus at most 33 KiB of staging, within
 // 80 KiB: two resident workgroups use at most 130 KiB of the 160 KiB of a CU.  Geometries <NTM feature tiles compiled>: 1, 2, 4, 8.
+// MODE 2 states the two waves per SIMD in its launch bounds (its third sum needs it at NTM = 8); MODE 0 and 1 compile as before.
+// Both entries share loo_run, and the kernels of the old entry take a NULL len_row: its outputs are bit for bit what they were.
 #include <math.h>
 
 #include "draw_tiles.hpp"
@@ -102,7 +109,7 @@ struct LooWorkspace {
   int64_t bytes;
 };
 
-static LooWorkspace loo_workspace(void* base, const LooPlan& p, int32_t n) {
+static LooWorkspace loo_workspace(void* base, const LooPlan& p, int32_t n, int nsums = 2) {
   LooWorkspace w;
   char* b = (char*)base;
   int64_t o = 0;
@@ -110,20 +117,25 @@ static LooWorkspace loo_workspace(void* base, const LooPlan& p, int32_t n) {
   w.hist = (unsigned long long*)(b + o); o += (int64_t)n * kRadixBins * 8;
   w.remaining = (long long*)(b + o); o += (int64_t)n * 8;
   w.prefix = (uint32_t*)(b + o); o += ((int64_t)n * 4 + 7) / 8 * 8;
-  w.part = (double*)(b + o); o += p.nchunks * 2 * (int64_t)n * 8;
+  w.part = (double*)(b + o); o += p.nchunks * nsums * (int64_t)n * 8;
   w.bytes = o;
   return w;
 }
 
 // MODE 0: count the digit at `shift` of the keys on their row's prefix (first: no prefix, every key).  MODE 1: gather.
+// MODE 2: gather with a tail length per row (len_row; M is the tail's row stride) and the third sum body_sq.
 template <int NTM, int MODE>
-__global__ __launch_bounds__(kLooThreads) void loo_kernel(const float* __restrict__ W, long long S, int d,
+// (MODE 2 alone asks for the two waves per SIMD of the header explicitly: its third sum took <8, 2> to 268 registers without;
+// MODE 0 and 1 keep the bounds, and with them the register allocation, they had before MODE 2 existed)
+__global__ __launch_bounds__(kLooThreads, MODE == 2 ? 2 : 1) void loo_kernel(const float* __restrict__ W, long long S, int d,
                                                           const float* __restrict__ P, int n, int NT, int ngroups,
                                                           long long nchunks, long long tpc, const uint32_t* __restrict__ prefix,
                                                           int shift, int first, unsigned long long* __restrict__ hist,
                                                           unsigned long long* __restrict__ n_tail, float* __restrict__ tail,
                                                           long long M, unsigned long long* __restrict__ err,
-                                                          double* __restrict__ part) {
+                                                          double* __restrict__ part,
+                                                          const long long* __restrict__ len_row) {
+  constexpr int K = MODE == 2 ? 3 : 2;
   constexpr int NB = kLooNB;
   constexpr int REGION = tile_region(NTM);
   __shared__ __attribute__((aligned(16))) float lds_all[4 * REGION];
@@ -163,11 +175,11 @@ __global__ __launch_bounds__(kLooThreads) void loo_kernel(const float* __restric
         }
       }
     }
-    double acc[NB][2][4];
+    double acc[NB][K][4];
 #pragma unroll
     for (int j = 0; j < NB; ++j)
 #pragma unroll
-      for (int k = 0; k < 2; ++k)
+      for (int k = 0; k < K; ++k)
 #pragma unroll
         for (int r = 0; r < 4; ++r) acc[j][k][r] = 0.0;
 
@@ -212,7 +224,9 @@ __global__ __launch_bounds__(kLooThreads) void loo_kernel(const float* __restric
               if (in_tail) {
                 const int row = 16 * (b0 + j) + 4 * q + r;
                 const unsigned long long slot = atomicAdd(&n_tail[row], 1ull);
-                if (slot < (unsigned long long)M) tail[(long long)row * M + (long long)slot] = tv;
+                const long long room_ = MODE == 2 ? (len_row[row] < M ? len_row[row] : M) : M;       // (never past the row's stride)
+                const unsigned long long room = (unsigned long long)(room_ < 0 ? 0 : room_);
+                if (slot < room) tail[(long long)row * M + (long long)slot] = tv;
                 else atomicOr(err, 1ull);
               }
               const float e = fexp(-fabsf(tv));
@@ -221,13 +235,14 @@ __global__ __launch_bounds__(kLooThreads) void loo_kernel(const float* __restric
               const float body = em[j][r] + fexp(mm[j][r] - tv);
               acc[j][0][r] += (double)((ok && !in_tail) ? body : 0.f);
               acc[j][1][r] += (double)(ok ? lik : 0.f);
+              if (MODE == 2) { const double b = (double)((ok && !in_tail) ? body : 0.f); acc[j][2][r] += b * b; }
             }
           }
         }
       }
     }
 
-    if (MODE == 1) tile_sums_out<NB, 2>(lds, acc, lane, b0, nblk, n, chunk, part);
+    if (MODE != 0) tile_sums_out<NB, K>(lds, acc, lane, b0, nblk, n, chunk, part);
   }
 
   if (MODE == 0) {
@@ -242,10 +257,14 @@ __global__ __launch_bounds__(kLooThreads) void loo_kernel(const float* __restric
 
 __global__ void loo_init_kernel(long long* __restrict__ remaining, uint32_t* __restrict__ prefix,
                                 unsigned long long* __restrict__ n_tail, float* __restrict__ tail, int n, long long M,
-                                unsigned long long* __restrict__ err) {
+                                unsigned long long* __restrict__ err, const long long* __restrict__ len_row) {
   const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i == 0) *err = 0ull;
-  if (i < n) { remaining[i] = M; prefix[i] = 0u; n_tail[i] = 0ull; }
+  if (i < n) {
+    long long rank = len_row ? len_row[i] : M;               // (a length outside 0 .. M is clamped: the tail has M slots)
+    rank = rank < 0 ? 0 : rank > M ? M : rank;
+    remaining[i] = rank; prefix[i] = 0u; n_tail[i] = 0ull;
+  }
   if (i < (long long)n * M) tail[i] = __builtin_inff();
 }
 
@@ -263,26 +282,28 @@ int64_t l2hmc_logistic_loo_workspace_bytes(int64_t n_draws, int32_t n_data, int3
   return loo_workspace(nullptr, p, n_data).bytes;
 }
 
-int l2hmc_logistic_loo_tails(const float* draws, int64_t n_draws, int32_t d, const float* packed, int32_t n_data, float* cutoff,
-                             int64_t* n_tail, float* tail, double* sums, void* workspace, void* stream) {
-  LooPlan p;
-  if (!loo_plan("l2hmc_logistic_loo_tails", n_draws, n_data, d, p)) return L2HMC_ERR_ARG;
+// the passes of both entries: len_row = nullptr is l2hmc_logistic_loo_tails (one length p.M, two sums)
+static int loo_run(const char* who, const LooPlan& p, const float* draws, int64_t n_draws, int32_t d, const float* packed,
+                   int32_t n_data, const int64_t* len_row, float* cutoff, int64_t* n_tail, float* tail, double* sums,
+                   void* workspace, void* stream) {
   if (!draws || !packed || !cutoff || !n_tail || (!tail && p.M > 0) || !sums || !workspace)
-    return fail(L2HMC_ERR_ARG, "l2hmc_logistic_loo_tails: draws, packed, cutoff, n_tail, tail, sums and workspace are required%s");
+    return fail(L2HMC_ERR_ARG, "%s: draws, packed, cutoff, n_tail, tail, sums and workspace are required", who);
   if (((uintptr_t)draws & 3) || ((uintptr_t)packed & 15) || ((uintptr_t)cutoff & 3) || ((uintptr_t)n_tail & 7) ||
-      ((uintptr_t)tail & 3) || ((uintptr_t)sums & 7) || ((uintptr_t)workspace & 7))
-    return fail(L2HMC_ERR_ARG, "l2hmc_logistic_loo_tails: draws, cutoff and tail must be 4-byte, packed 16-byte, n_tail, sums and "
-                               "workspace 8-byte aligned%s");
+      ((uintptr_t)tail & 3) || ((uintptr_t)sums & 7) || ((uintptr_t)workspace & 7) || ((uintptr_t)len_row & 7))
+    return fail(L2HMC_ERR_ARG, "%s: draws, cutoff and tail must be 4-byte, packed 16-byte, n_tail, tail_len_row, sums and "
+                               "workspace 8-byte aligned", who);
   hipStream_t s = (hipStream_t)stream;
-  const LooWorkspace ws = loo_workspace(workspace, p, n_data);
+  const int nsums = len_row ? 3 : 2;
+  const LooWorkspace ws = loo_workspace(workspace, p, n_data, nsums);
+  const long long* lens = (const long long*)len_row;
   const long long n = n_data, cells = n * p.M > n ? n * p.M : n;
   hipLaunchKernelGGL(loo_init_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s, ws.remaining, ws.prefix,
-                     (unsigned long long*)n_tail, tail, (int)n_data, p.M, ws.err);
+                     (unsigned long long*)n_tail, tail, (int)n_data, p.M, ws.err, lens);
   const dim3 grid((unsigned)(p.quads * p.ngroups)), block(kLooThreads);
 #define L2HMC_LOO_LAUNCH(NTM, MODE, shift, first)                                                                          \
   hipLaunchKernelGGL((loo_kernel<NTM, MODE>), grid, block, 0, s, draws, (long long)n_draws, (int)d, packed, (int)n_data, p.NT, \
                      p.ngroups, p.nchunks, p.tpc, (const uint32_t*)ws.prefix, (int)(shift), (int)(first), ws.hist,             \
-                     (unsigned long long*)n_tail, tail, p.M, ws.err, ws.part)
+                     (unsigned long long*)n_tail, tail, p.M, ws.err, ws.part, lens)
 #define L2HMC_LOO_PASS(MODE, shift, first)                 \
   switch (p.NTM) {                                         \
     case 1: L2HMC_LOO_LAUNCH(1, MODE, shift, first); break; \
@@ -298,13 +319,49 @@ int l2hmc_logistic_loo_tails(const float* draws, int64_t n_draws, int32_t d, con
     hipLaunchKernelGGL(radix_advance_kernel, dim3((unsigned)n_data), dim3(64), 0, s, (const long long*)ws.hist, ws.remaining,
                        ws.prefix, (int)n_data, shift, pass == kRadixPasses - 1 ? cutoff : (float*)nullptr);
   }
-  L2HMC_LOO_PASS(1, 0, 0)
+  if (len_row) { L2HMC_LOO_PASS(2, 0, 0) } else { L2HMC_LOO_PASS(1, 0, 0) }
 #undef L2HMC_LOO_PASS
 #undef L2HMC_LOO_LAUNCH
-  chunk_reduce_launch(ws.part, p.nchunks, 2LL * n_data, sums, s);
+  chunk_reduce_launch(ws.part, p.nchunks, (long long)nsums * n_data, sums, s);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(L2HMC_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
   return L2HMC_OK;
+}
+
+// the plan of the mc entry: loo_plan with the caller's tail stride in the place of M
+static bool loo_plan_mc(const char* who, int64_t n_draws, int32_t n_data, int32_t d, int64_t tail_stride, LooPlan& p) {
+  if (!loo_plan(who, n_draws, n_data, d, p)) return false;
+  if (tail_stride < 0 || tail_stride >= n_draws) {
+    fail(L2HMC_ERR_ARG, "%s: 0 <= tail_stride < n_draws (got %lld)", who, tail_stride);
+    return false;
+  }
+  p.M = tail_stride;
+  if (p.M * n_data > (1LL << 31)) { fail(L2HMC_ERR_ARG, "%s: tail too large (tail_stride n_data > 2^31): fewer rows per call", who); return false; }
+  return true;
+}
+
+int l2hmc_logistic_loo_tails(const float* draws, int64_t n_draws, int32_t d, const float* packed, int32_t n_data, float* cutoff,
+                             int64_t* n_tail, float* tail, double* sums, void* workspace, void* stream) {
+  LooPlan p;
+  if (!loo_plan("l2hmc_logistic_loo_tails", n_draws, n_data, d, p)) return L2HMC_ERR_ARG;
+  return loo_run("l2hmc_logistic_loo_tails", p, draws, n_draws, d, packed, n_data, nullptr, cutoff, n_tail, tail, sums, workspace,
+                 stream);
+}
+
+int64_t l2hmc_logistic_loo_mc_workspace_bytes(int64_t n_draws, int32_t n_data, int32_t d) {
+  LooPlan p;
+  if (!loo_plan("l2hmc_logistic_loo_mc_workspace_bytes", n_draws, n_data, d, p)) return L2HMC_ERR_ARG;
+  return loo_workspace(nullptr, p, n_data, 3).bytes;
+}
+
+int l2hmc_logistic_loo_tails_mc(const float* draws, int64_t n_draws, int32_t d, const float* packed, int32_t n_data,
+                                const int64_t* tail_len_row, int64_t tail_stride, float* cutoff, int64_t* n_tail, float* tail,
+                                double* sums, void* workspace, void* stream) {
+  LooPlan p;
+  if (!loo_plan_mc("l2hmc_logistic_loo_tails_mc", n_draws, n_data, d, tail_stride, p)) return L2HMC_ERR_ARG;
+  if (!tail_len_row) return fail(L2HMC_ERR_ARG, "l2hmc_logistic_loo_tails_mc: tail_len_row is required%s");
+  return loo_run("l2hmc_logistic_loo_tails_mc", p, draws, n_draws, d, packed, n_data, tail_len_row, cutoff, n_tail, tail, sums,
+                 workspace, stream);
 }
 
 }  // extern "C"

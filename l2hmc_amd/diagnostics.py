@@ -164,5 +164,7 @@ def finish(sums):
 
 def summarize(X, max_lag=None, split=True):
     """Per-coordinate `mean`, `sd`, `rhat`, `ess`, `truncated` of a (steps, chains, dim) history, with `n_steps`, `n_chains`,
-    `max_lag`, `min_ess` and `max_rhat` (NaN when any coordinate is degenerate: a constant or non-finite series)."""
+    `max_lag`, `min_ess` and `max_rhat` (NaN when any coordinate is degenerate: a constant or non-finite series).  On the
+    host a constant series whose value is not exactly representable may keep a tiny M2 from the rounding of its mean and then
+    is not reported as degenerate; `predictive.relative_eff` sets M2 = 0 for such a series itself, as the device does."""
     return finish(chain_sums(X, max_lag=max_lag, split=split))

@@ -244,12 +244,19 @@ class LogisticRegression(object):
         from . import predictive
         return predictive.waic(draws, self.X, self.y)
 
-    def loo(self, draws, finish="torch"):
+    def loo(self, draws, finish="torch", r_eff=None):
         """PSIS-LOO of this model's own data under the draws (`predictive.loo`): a `Summary` with elpd_loo, p_loo, looic, se,
         the per-row Pareto `khat` and `n_bad`, the number of rows where it exceeds 0.7.  `finish="kernel"`: the Pareto fit on
-        the fused kernels of csrc/psis.hip (device draws only)."""
+        the fused kernels of csrc/psis.hip (device draws only).  `r_eff="auto"` (or an array): tail lengths, `n_eff` and
+        `mcse_elpd_loo` for autocorrelated draws (`predictive.loo`)."""
         from . import predictive
-        return predictive.loo(draws, self.X, self.y, finish=finish)
+        return predictive.loo(draws, self.X, self.y, finish=finish, r_eff=r_eff)
+
+    def relative_eff(self, draws, max_lag=None, split=False):
+        """The per-row relative efficiency r_eff_i = ESS(P(y_i | x_i, w)) / S of this model's own data under a recorded history
+        (steps, chains, dim) (`predictive.relative_eff`): a `Summary` with r_eff, ess, truncated, n_nan."""
+        from . import predictive
+        return predictive.relative_eff(draws, self.X, self.y, max_lag=max_lag, split=split)
 
 
 def as_device_f32(x, device=None):

@@ -40,10 +40,15 @@ reproducible) and the dict holds device tensors; numpy or a CPU tensor is float6
 Pareto distribution to every tail (Zhang & Stephens 2009 with the prior of `loo`), smooths the tail weights and forms elpd_loo_i
 in float64 where the tails lie: torch on the device in row chunks of bounded memory, numpy on the host.
 `finish="kernel"` (opt-in, device tails only) fits and smooths on the fused float64 kernels of csrc/psis.hip instead (`psis.py`).
+
+The recorded draws are Markov chains, not independent: `relative_eff(x_hist, X, y)` gives per row r_eff_i = ESS(lik_i) / S, the
+relative efficiency of `loo::relative_eff`, with the effective sample size of `diagnostics` on the series of likelihoods
+lik[t, c, i] = sigmoid(t) of every chain.  On the device the (steps, chains, rows) array is never formed: csrc/lik_stats.hip
+fuses the logit contraction with the moment and lag sums of csrc/chain_stats.hip.
 """
 import numpy as np
 
-from . import _ffi
+from . import _ffi, diagnostics
 from ._history import as_numpy, history_shape, in_place, is_device_tensor, launch, workspace
 from .diagnostics import Summary
 
@@ -54,6 +59,7 @@ _HOST_CHUNK_ELEMS = 1 << 22   # (draws x rows) logits formed at a time on the ho
 KHAT_BAD = 0.7                # PSIS is unreliable above it whatever S is
 MIN_TAIL_FIT = 5              # a shorter tail is not fitted: khat = +inf
 _FINISH_CHUNK_BYTES = 1 << 26  # the (rows, theta grid, tail) block of the Pareto profile formed at a time by `loo_finish`
+_REFF_BYTES = 256 << 20       # the (chains, rows) moments and the lag-sum workspace of one `relative_eff` launch
 _NEG_ZERO_KEY = -5e-324       # stands for -0.0 on the host so that a float64 sort puts it before +0.0, as the device order does
 
 
@@ -211,13 +217,34 @@ def loo_tail_len(S):
     return min(S // 5, math.isqrt(9 * S - 1) + 1) if S >= 1 else 0
 
 
-def _device_tail_groups(draws, X, y, S, d, n, max_tail_bytes):
-    """The raw dict of one group of consecutive rows at a time, on the device; a group's tail stays under `max_tail_bytes`."""
+def tail_len_rows(r_eff, S):
+    """M_i = min(S // 5, ceil(3 sqrt(S / r_eff_i))) (n,) int64, in float64 on the host: the tail length `loo` prescribes for a
+    row whose draws have relative efficiency r_eff_i; a NaN or non-positive r_eff_i counts as 1."""
+    r = np.asarray(r_eff, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        r = np.where(np.isfinite(r) & (r > 0), r, 1.0)
+        return np.minimum(float(int(S) // 5), np.ceil(3.0 * np.sqrt(int(S) / r))).astype(np.int64)
+
+
+def _check_lengths(tail_len_row, n, S):
+    lens = np.ascontiguousarray(as_numpy(tail_len_row), dtype=np.int64)
+    if lens.shape != (n,) or np.any(lens < 0) or np.any(lens >= S):
+        raise ValueError("tail_len_row must be (n_rows,) = (%d,) integers in 0 .. n_draws - 1" % n)
+    return lens
+
+
+def _device_tail_groups(draws, X, y, S, d, n, max_tail_bytes, tail_len_row=None):
+    """The raw dict of one group of consecutive rows at a time, on the device; a group's tail stays under `max_tail_bytes`.
+    `tail_len_row` (n,) int64: a tail length per row (`l2hmc_logistic_loo_tails_mc`); the dict gains 'body_sq' and
+    'tail_len_row', and 'tail_len' is the largest length."""
     import torch
     dev = draws.device
     pack = _device_packer(dev, X, y, n, d, "the LOO kernels hold")
     W = in_place(draws)
     L = _ffi.lib()
+    if tail_len_row is not None:
+        yield from _device_tail_groups_mc(dev, pack, W, L, S, d, n, max_tail_bytes, tail_len_row)
+        return
     M = _ffi.check(L.l2hmc_logistic_loo_tail_len(S))
     rows = max(1, min(n, int(max_tail_bytes) // max(1, 4 * M), (1 << 31) // max(1, M)))
     flags = []                                               # every group's error word, read once after the last group
@@ -237,16 +264,42 @@ def _device_tail_groups(draws, X, y, S, d, n, max_tail_bytes):
         raise RuntimeError("l2hmc_logistic_loo_tails: a tail outgrew its %d slots: the passes disagree" % M)
 
 
-def _host_tails(draws, X, y, S, d, n):
+def _device_tail_groups_mc(dev, pack, W, L, S, d, n, max_tail_bytes, lens):
+    import torch
+    M = int(lens.max()) if n else 0
+    lens_d = torch.as_tensor(lens).to(dev)
+    rows = max(1, min(n, int(max_tail_bytes) // max(1, 4 * M), (1 << 31) // max(1, M)))
+    flags = []
+    for a in range(0, n, rows):
+        m = min(rows, n - a)
+        packed = pack(a, m)
+        ws = workspace(dev, torch.uint8, L.l2hmc_logistic_loo_mc_workspace_bytes, S, m, d)
+        cutoff = torch.empty(m, dtype=torch.float32, device=dev)
+        n_tail = torch.empty(m, dtype=torch.int64, device=dev)
+        tail = torch.empty((m, M), dtype=torch.float32, device=dev)
+        sums = torch.empty((3, m), dtype=torch.float64, device=dev)
+        group = lens_d[a:a + m].contiguous()
+        launch(dev, L.l2hmc_logistic_loo_tails_mc, W.data_ptr(), S, d, packed.data_ptr(), m, group.data_ptr(), M, cutoff.data_ptr(),
+               n_tail.data_ptr(), tail.data_ptr() if M else None, sums.data_ptr(), ws.data_ptr())
+        flags.append(ws[:8].view(torch.int64).clone())
+        yield {"cutoff": cutoff, "n_tail": n_tail, "tail": tail, "body": sums[0], "sum_lik": sums[1], "body_sq": sums[2],
+               "tail_len_row": group, "tail_len": M, "n_draws": S}
+    if bool(torch.cat(flags).any()):
+        raise RuntimeError("l2hmc_logistic_loo_tails_mc: a tail outgrew its slots: the passes disagree")
+
+
+def _host_tails(draws, X, y, S, d, n, tail_len_row=None):
     """The same raw dict in float64 numpy: per row the M + 1 smallest signed logits are kept while the draws pass in chunks
-    (a partition, not a sort), then one more pass over the draws adds the body and the likelihoods."""
+    (a partition, not a sort), then one more pass over the draws adds the body and the likelihoods.  `tail_len_row` (n,): row i
+    is cut at its own rank M_i (M is then the largest), and the dict gains 'body_sq' and 'tail_len_row'."""
     W = as_numpy(draws, np.float64).reshape(S, d)
     X = as_numpy(X, np.float64)
     y = as_numpy(y, np.float64)
     if not np.all((y == 0.0) | (y == 1.0)):
         raise ValueError("labels y must be 0 or 1")
     sign = 2.0 * y - 1.0
-    M = loo_tail_len(S)
+    M = loo_tail_len(S) if tail_len_row is None else (int(tail_len_row.max()) if n else 0)
+    Mi = np.full(n, M, dtype=np.int64) if tail_len_row is None else tail_len_row
     step = max(1, _HOST_CHUNK_ELEMS // n)
 
     def logits(a):
@@ -260,18 +313,24 @@ def _host_tails(draws, X, y, S, d, n):
             if low.shape[0] > M + 1:
                 low = np.partition(low, M, axis=0)[:M + 1]                         # NaN sorts last, as on the device
         low = np.sort(low, axis=0)
-        c = low[M]
-        keep = low[:M] < c                                                         # strictly before the cutoff
+        c = low[Mi, np.arange(n)]                                                  # the element of rank M_i of row i
+        keep = (low[:M] < c) & (np.arange(M)[:, None] < Mi)                        # strictly before the cutoff
         n_tail = keep.sum(axis=0).astype(np.int64)
         tail = np.where(keep, low[:M], np.inf).T.copy()                            # (n, M): sorted, +inf past n_tail
         m = np.minimum(np.where(c != c, 0.0, c), 0.0)
-        body, sum_lik = np.zeros(n), np.zeros(n)
+        body, sum_lik, body_sq = np.zeros(n), np.zeros(n), np.zeros(n)
         for a in range(0, S, step):
             t = logits(a)
-            body += np.where(t < c, 0.0, np.exp(m) + np.exp(m - t)).sum(axis=0)
+            rho = np.where(t < c, 0.0, np.exp(m) + np.exp(m - t))
+            body += rho.sum(axis=0)
+            if tail_len_row is not None:
+                body_sq += (rho * rho).sum(axis=0)
             sum_lik += np.exp(-np.logaddexp(0.0, -t)).sum(axis=0)
     unkey = lambda v: np.where(v == _NEG_ZERO_KEY, -0.0, v)  # noqa: E731
-    return {"cutoff": unkey(c), "n_tail": n_tail, "tail": unkey(tail), "body": body, "sum_lik": sum_lik, "tail_len": M, "n_draws": S}
+    out = {"cutoff": unkey(c), "n_tail": n_tail, "tail": unkey(tail), "body": body, "sum_lik": sum_lik, "tail_len": M, "n_draws": S}
+    if tail_len_row is not None:
+        out.update(body_sq=body_sq, tail_len_row=tail_len_row)
+    return out
 
 
 def _check_loo(draws, X, y):
@@ -280,18 +339,23 @@ def _check_loo(draws, X, y):
     return _check(draws, X, y)
 
 
-def loo_tails(draws, X, y, max_tail_bytes=256 << 20):
+def loo_tails(draws, X, y, max_tail_bytes=256 << 20, tail_len_row=None):
     """The raw material of PSIS-LOO per row of X (module docstring): {'cutoff' (n,), 'n_tail' (n,) int64, 'tail' (n, M) with
     +inf past n_tail, 'body' (n,), 'sum_lik' (n,), 'tail_len': M, 'n_draws': S}.  A ROCm tensor of draws -> the HIP kernels,
     read in place, device tensors back (float32 cutoff and tail in any order, float64 sums; bitwise reproducible); the rows go
     in groups whose tail buffer stays under `max_tail_bytes`, and the bits do not depend on the grouping.  numpy or a CPU
-    tensor -> float64 numpy arrays, the tail sorted."""
+    tensor -> float64 numpy arrays, the tail sorted.  `tail_len_row` (n,) integers (`tail_len_rows(r_eff, S)`): row i is cut at
+    its own rank M_i instead of the single M; 'tail' is (n, max M_i), 'tail_len' that maximum, and the dict gains 'tail_len_row'
+    and 'body_sq', the sum over the body of (e^m + e^(m - t))^2 (`l2hmc_logistic_loo_tails_mc` on the device)."""
     S, d, n = _check_loo(draws, X, y)
+    if tail_len_row is not None:
+        tail_len_row = _check_lengths(tail_len_row, n, S)
     if not is_device_tensor(draws):
-        return _host_tails(draws, X, y, S, d, n)
+        return _host_tails(draws, X, y, S, d, n, tail_len_row)
     import torch
-    groups = list(_device_tail_groups(draws, X, y, S, d, n, max_tail_bytes))
-    out = {k: torch.cat([g[k] for g in groups]) for k in ("cutoff", "n_tail", "tail", "body", "sum_lik")}
+    groups = list(_device_tail_groups(draws, X, y, S, d, n, max_tail_bytes, tail_len_row))
+    keys = ("cutoff", "n_tail", "tail", "body", "sum_lik") + (("body_sq", "tail_len_row") if tail_len_row is not None else ())
+    out = {k: torch.cat([g[k] for g in groups]) for k in keys}
     out["tail_len"], out["n_draws"] = groups[0]["tail_len"], S
     return out
 
@@ -458,17 +522,19 @@ def _loo_summary(khat, elpd_i, lppd_i, n_tail, S, M):
                    n_underflow=int(np.sum(np.isneginf(lppd_i))))
 
 
-def _row_chunks(tails, rows_for, middle):
+def _row_chunks(tails, rows_for, middle, extra=()):
     """(khat, elpd_loo_i, lppd_i, n_tail) as float64 / int64 numpy of one raw dict: `middle(xp, cutoff, n_tail, tail, body,
-    sum_lik, S, M)` on chunks of `rows_for(M)` rows, computed where the tails lie; only these O(n) numbers come to the host."""
+    sum_lik, S, M)` on chunks of `rows_for(M)` rows, computed where the tails lie; only these O(n) numbers come to the host.
+    `extra`: further per-row entries of the dict handed to `middle` after sum_lik; every array `middle` returns comes back,
+    n_tail last."""
     S, M = int(tails["n_draws"]), int(tails["tail_len"])
     if S < 2:
         raise ValueError("PSIS-LOO needs >= 2 draws (got %d)" % S)
     xp = _Torch() if is_device_tensor(tails["tail"]) else _Numpy()
-    keys = ("cutoff", "n_tail", "tail", "body", "sum_lik")
+    keys = ("cutoff", "n_tail", "tail", "body", "sum_lik") + tuple(extra)
     arrays = [tails[k] if isinstance(xp, _Torch) else np.asarray(tails[k]) for k in keys]
     n, rows = int(arrays[0].shape[0]), max(1, rows_for(M))
-    out = [[], [], []]
+    out = [[] for _ in range(3 + len(extra))]
     with np.errstate(all="ignore"):
         for a in range(0, n, rows):
             for o, r in zip(out, middle(xp, *(v[a:a + rows] for v in arrays), S, M)):
@@ -509,28 +575,204 @@ def _finish_rows_kernel(tails):
     return _row_chunks(tails, lambda M: _KERNEL_FINISH_BYTES // (8 * max(M, 1)), _loo_rows_kernel)
 
 
-def loo_finish(tails, finish="torch"):
+def _mc_extras(xp, elpd, lam_max, lse_w, omega, live, lam, c, Lf, body, body_sq, r_eff, S):
+    """(n_eff_i, mcse_elpd_loo_i) of a chunk of rows (module docstring, "Monte Carlo error"), relative to the row's largest
+    ratio e^lam_max as `_loo_combine` works: every weight is then <= 1 and their sum Z lies in [1, S]."""
+    zero = Lf * 0.0
+    m = xp.minimum(xp.where(xp.isnan(c), zero, c), zero)
+    body, body_sq, r_eff = xp.f64(body), xp.f64(body_sq), xp.f64(r_eff)
+    Z2 = xp.exp(2.0 * _logaddexp(xp, xp.log(body) - m - lam_max, lse_w, zero))
+    E = xp.exp(elpd)
+    zeros = zero[:, None] + xp.arange(lam.shape[-1], Lf)[None, :] * 0.0       # (omega and lam are not finite in the dead slots)
+    w2 = xp.where(live, xp.exp(2.0 * omega), zeros)
+    n_eff = r_eff * Z2 / (xp.exp(-2.0 * (m + lam_max)) * body_sq + xp.sum(w2))
+    v_body = xp.exp(-2.0 * lam_max) * ((S - Lf) - 2.0 * E * xp.exp(-m) * body + E * E * xp.exp(-2.0 * m) * body_sq)
+    v_tail = xp.sum(xp.where(live, w2 * (xp.exp(-lam) - E[:, None]) ** 2, zeros))
+    mcse = xp.sqrt((xp.maximum(v_body, zero) + v_tail) / Z2 / r_eff) / E
+    return n_eff, mcse
+
+
+def _loo_rows_mc(xp, cutoff, n_tail, tail, body, sum_lik, body_sq, r_eff, S, M):
+    """`_loo_rows` plus (n_eff_i, mcse_elpd_loo_i): the rows' tails have their own lengths, which `_psis_rows` takes per row."""
+    c, Lf, lam_c, lam = _loo_prepare(xp, cutoff, n_tail, tail)
+    khat, lam_max, lse_w, lse_wl, omega, live = _psis_rows(xp, lam, Lf, lam_c, M)
+    khat, elpd, lppd = _loo_combine(xp, khat, lam_max, lse_w, lse_wl, c, Lf, body, sum_lik, S)
+    return (khat, elpd, lppd) + _mc_extras(xp, elpd, lam_max, lse_w, omega, live, lam, c, Lf, body, body_sq, r_eff, S)
+
+
+def _loo_rows_mc_kernel(xp, cutoff, n_tail, tail, body, sum_lik, body_sq, r_eff, S, M):
+    """`_loo_rows_mc` with the middle on csrc/psis.hip (`psis.smooth_tails(weights=True)` returns omega from the kernel)."""
+    from .psis import smooth_tails
+    c, Lf, lam_c, lam = _loo_prepare(xp, cutoff, n_tail, tail)
+    khat, lse_w, lse_wl, omega = smooth_tails(lam, n_tail, lam_c, weights=True)
+    lam_max = xp.where(Lf > 0, lam[:, 0], lam_c) if M else lam_c
+    live = xp.arange(M, Lf)[None, :] < Lf[:, None]
+    khat, elpd, lppd = _loo_combine(xp, khat, lam_max, lse_w, lse_wl, c, Lf, body, sum_lik, S)
+    return (khat, elpd, lppd) + _mc_extras(xp, elpd, lam_max, lse_w, omega, live, lam, c, Lf, body, body_sq, r_eff, S)
+
+
+def _finish_rows_mc(tails, r_eff, finish):
+    """(khat, elpd_loo_i, lppd_i, n_eff_i, mcse_i, n_tail) of a raw dict with per-row tails and 'body_sq'."""
+    if "body_sq" not in tails:
+        raise ValueError("r_eff needs tails with per-row lengths: loo_tails(..., tail_len_row=tail_len_rows(r_eff, S))")
+    r = np.asarray(r_eff, dtype=np.float64)
+    if is_device_tensor(tails["tail"]):
+        import torch
+        r = torch.as_tensor(r).to(tails["tail"].device)
+    n_theta = lambda M: 30 + int(np.floor(np.sqrt(max(M, 1))))  # noqa: E731
+    if finish == "kernel":
+        return _row_chunks(dict(tails, r_eff=r), lambda M: _KERNEL_FINISH_BYTES // (8 * max(M, 1)), _loo_rows_mc_kernel,
+                           extra=("body_sq", "r_eff"))
+    return _row_chunks(dict(tails, r_eff=r), lambda M: _FINISH_CHUNK_BYTES // (8 * n_theta(M) * max(M, 1)), _loo_rows_mc,
+                       extra=("body_sq", "r_eff"))
+
+
+def _mc_fields(s, r_eff, n_eff, mcse, lens):
+    """The fields `r_eff` adds to the Summary of `_loo_summary`."""
+    r = np.asarray(r_eff, dtype=np.float64)
+    with np.errstate(all="ignore"):
+        total = float(np.sqrt(np.sum(mcse * mcse))) if not np.any(s.khat > KHAT_BAD) else float("nan")
+        low = float(np.nanmin(n_eff)) if np.any(~np.isnan(n_eff)) else float("nan")
+    s.update(r_eff=r, n_eff=n_eff, min_n_eff=low, mcse_elpd_loo_i=mcse, mcse_elpd_loo=total, n_reff_nan=int(np.isnan(r).sum()),
+             tail_len_row=np.asarray(lens, dtype=np.int64))
+    return s
+
+
+def _check_r_eff(r_eff, n):
+    r = as_numpy(r_eff, np.float64)
+    if r.shape != (n,):
+        raise ValueError("r_eff is None, \"auto\" or an array (n_rows,) = (%d,); got shape %s" % (n, r.shape))
+    with np.errstate(invalid="ignore"):
+        return np.where(r > 0, r, np.nan)                    # an entry that is not a positive number is no efficiency: NaN
+
+
+def loo_finish(tails, finish="torch", r_eff=None):
     """The `Summary` of `loo_tails`' result: per row `elpd_loo_i`, `p_loo_i`, `lppd_i`, `khat`, `n_tail`; the totals `elpd_loo`,
     `p_loo`, `lppd`, `looic` = -2 elpd_loo, `se` = sqrt(n var_i elpd_loo_i) (NaN for one row); `khat_threshold` =
     min(1 - 1 / log10 S, 0.7), `n_bad` = #{khat > 0.7}, `n_above_threshold`; `tail_len`, `n_draws`, `n_rows`, `n_underflow`.
     A tail shorter than 5 (or a fit that is not finite) is not smoothed and has khat = +inf.  `finish="kernel"` (device tails
     only; opt-in) fits and smooths on the fused float64 kernels of csrc/psis.hip instead of chunked torch: the same formulas,
-    another summation order."""
+    another summation order.  `r_eff` (n,): the tails were cut at `tail_len_rows(r_eff, S)` (`loo_tails(tail_len_row=)`), and the
+    Summary gains the Monte Carlo fields of `loo`."""
     _check_finish(finish, is_device_tensor(tails["tail"]))
+    if r_eff is not None:
+        r = _check_r_eff(r_eff, int(tails["cutoff"].shape[0]))
+        khat, elpd_i, lppd_i, n_eff, mcse, n_tail = _finish_rows_mc(tails, r, finish)
+        s = _loo_summary(khat, elpd_i, lppd_i, n_tail, int(tails["n_draws"]), int(tails["tail_len"]))
+        return _mc_fields(s, r, n_eff, mcse, as_numpy(tails["tail_len_row"]))
     khat, elpd_i, lppd_i, n_tail = (_finish_rows_kernel if finish == "kernel" else _finish_rows)(tails)
     return _loo_summary(khat, elpd_i, lppd_i, n_tail, int(tails["n_draws"]), int(tails["tail_len"]))
 
 
-def loo(draws, X, y, max_tail_bytes=256 << 20, finish="torch"):
+def loo(draws, X, y, max_tail_bytes=256 << 20, finish="torch", r_eff=None):
     """PSIS-LOO of the logistic regression (X, y) under the posterior draws: `loo_finish(loo_tails(draws, X, y))`, except that
     on the device every group of rows is finished before the next one's tails are formed, so that no more than
     `max_tail_bytes` of tails exist at a time.  Compare two models on the same rows by `elpd_loo` (higher is better) against
-    `se`; rows with khat > 0.7 (`n_bad`) are where the estimate cannot be trusted.  `finish`: see `loo_finish`."""
+    `se`; rows with khat > 0.7 (`n_bad`) are where the estimate cannot be trusted.  `finish`: see `loo_finish`.
+
+    `r_eff`: None treats the draws as independent (one tail length M, the fields above).  "auto" (a history (steps, chains,
+    dim) only) takes `relative_eff(draws, X, y).r_eff`; an array (n,) is used as given.  Row i's tail is then M_i =
+    min(S // 5, ceil(3 sqrt(S / r_eff_i))) long (`tail_len_row`; `tail_len` is the largest; a NaN or non-positive r_eff_i
+    counts as 1 there, is reported as NaN in `r_eff` and counted in `n_reff_nan`) and the Summary gains, with w the normalised smoothed weights and E_i = sum_s w_s lik_s:
+    `n_eff` = r_eff_i / sum_s w_s^2, `min_n_eff`, `mcse_elpd_loo_i` = sqrt(sum_s w_s^2 (lik_s - E_i)^2 / r_eff_i) / E_i -- the
+    first-order (delta-method) Monte Carlo standard error of elpd_loo_i; `loo` pushes a normal approximation through the log
+    instead, which agrees to first order and is not built -- `mcse_elpd_loo` = sqrt(sum_i mcse_i^2), NaN when any khat > 0.7 as
+    `loo` reports NA there, `r_eff` and `n_reff_nan`; rows with NaN r_eff have NaN in both per-row fields.  The body's part of
+    both sums comes from `body` and `body_sq` in the three-term form N_b - 2 E e^-m body + E^2 e^-2m body_sq (N_b draws
+    outside the tail), the tail's from the smoothed weights the finish holds."""
     S, d, n = _check_loo(draws, X, y)
     _check_finish(finish, is_device_tensor(draws))
+    if r_eff is not None:
+        if isinstance(r_eff, str):
+            if r_eff != "auto":
+                raise ValueError('r_eff is None, "auto" or an array (n_rows,) (got %r)' % (r_eff,))
+            r = _check_r_eff(relative_eff(draws, X, y).r_eff, n)
+        else:
+            r = _check_r_eff(r_eff, n)
+        lens = tail_len_rows(r, S)
+        if not is_device_tensor(draws):
+            return loo_finish(_host_tails(draws, X, y, S, d, n, lens), r_eff=r)
+        parts, a = [], 0
+        for g in _device_tail_groups(draws, X, y, S, d, n, max_tail_bytes, lens):
+            m = int(g["cutoff"].shape[0])
+            parts.append(_finish_rows_mc(g, r[a:a + m], finish))
+            a += m
+        khat, elpd_i, lppd_i, n_eff, mcse, n_tail = (np.concatenate([p[k] for p in parts]) for k in range(6))
+        return _mc_fields(_loo_summary(khat, elpd_i, lppd_i, n_tail, S, int(lens.max())), r, n_eff, mcse, lens)
     if not is_device_tensor(draws):
         return loo_finish(_host_tails(draws, X, y, S, d, n))
     rows_of = _finish_rows_kernel if finish == "kernel" else _finish_rows
     parts = [rows_of(g) for g in _device_tail_groups(draws, X, y, S, d, n, max_tail_bytes)]
     khat, elpd_i, lppd_i, n_tail = (np.concatenate([p[k] for p in parts]) for k in range(4))
     return _loo_summary(khat, elpd_i, lppd_i, n_tail, S, loo_tail_len(S))
+
+
+def _reff_device(draws, X, y, M, N, d, n, Mh, C, max_lag, split, max_bytes):
+    """`diagnostics.finish` of every group of consecutive rows, on the sums of `l2hmc_logistic_lik_stats`; a group's moments
+    and workspace stay under `max_bytes`."""
+    import torch
+    dev = draws.device
+    pack = _device_packer(dev, X, y, n, d, "the likelihood-statistics kernels hold")
+    W = in_place(draws)
+    L = _ffi.lib()
+    shape = (M, N, d)
+    per_row = 16 * C + _ffi.check(L.l2hmc_logistic_lik_stats_workspace_bytes(*shape, 1, max_lag, int(split)))
+    rows = max(1, min(n, int(max_bytes) // per_row))
+    for a in range(0, n, rows):
+        m = min(rows, n - a)
+        packed = pack(a, m)
+        ws = workspace(dev, torch.uint8, L.l2hmc_logistic_lik_stats_workspace_bytes, *shape, m, max_lag, int(split))
+        mean = torch.empty((C, m), dtype=torch.float64, device=dev)
+        m2 = torch.empty((C, m), dtype=torch.float64, device=dev)
+        G = torch.empty((m, max_lag + 1), dtype=torch.float64, device=dev)
+        launch(dev, L.l2hmc_logistic_lik_stats, W.data_ptr(), *shape, packed.data_ptr(), m, max_lag, int(split), mean.data_ptr(),
+               m2.data_ptr(), G.data_ptr(), ws.data_ptr())
+        yield diagnostics.finish({"mean": mean, "m2": m2, "G": G, "n_steps": Mh, "n_chains": C})
+
+
+def _reff_host(draws, X, y, M, N, d, n, Mh, C, max_lag, split):
+    """The same in float64 numpy, a chunk of rows at a time: the likelihoods of the chunk as a history (steps, chains, rows)
+    through `diagnostics`' host sums."""
+    W = as_numpy(draws, np.float64).reshape(M * N, d)
+    X = as_numpy(X, np.float64)
+    y = as_numpy(y, np.float64)
+    if not np.all((y == 0.0) | (y == 1.0)):
+        raise ValueError("labels y must be 0 or 1")
+    sign = 2.0 * y - 1.0
+    rows = max(1, _HOST_CHUNK_ELEMS // (M * N))
+    for a in range(0, n, rows):
+        with np.errstate(all="ignore"):
+            lik = np.exp(-np.logaddexp(0.0, -(W @ X[a:a + rows].T) * sign[a:a + rows])).reshape(M, N, -1)
+        mean, m2, G = diagnostics._host_sums(lik, Mh, max_lag, split)
+        series = np.concatenate([lik[:Mh], lik[M - Mh:]], axis=1) if split else lik
+        with np.errstate(invalid="ignore"):                  # a constant series has M2 = 0 exactly, whatever its mean rounds to
+            m2 = np.where(series.max(axis=0) == series.min(axis=0), 0.0, m2)
+        yield diagnostics.finish({"mean": mean, "m2": m2, "G": G, "n_steps": Mh, "n_chains": C})
+
+
+def relative_eff(draws, X, y, max_lag=None, split=False, max_bytes=_REFF_BYTES):
+    """The per-row relative efficiency of the likelihoods under a recorded history `draws` (steps, chains, dim):
+    r_eff_i = ess_i / S with S = steps x chains and ess_i the effective sample size of `diagnostics` (its `finish`, on the chain
+    sums of the series lik[t, c, i] = P(y_i | x_i, w[t, c])) -- what `loo::relative_eff` computes from whole chains, hence
+    `split=False` by default; `max_lag=None` is min(steps per chain - 1, `diagnostics.DEFAULT_MAX_LAG`).  A `Summary` of
+    `r_eff`, `ess` (n,), `truncated` (n,) bool -- no non-positive pair of autocorrelations within `max_lag`: ask for more lags
+    -- `n_truncated`, `n_nan` (rows whose series is constant or not finite: r_eff = NaN), `n_draws`, `n_steps`, `n_chains`,
+    `max_lag`.  A ROCm history goes to the kernels behind `l2hmc_logistic_lik_stats` (csrc/lik_stats.hip), read in place, the
+    rows in groups whose moments and workspace stay under `max_bytes` (the bits do not depend on the grouping); numpy or a CPU
+    tensor is float64 numpy, a chunk of rows at a time.  A matrix (draws, dim) is refused: its chains are not known.
+    A series whose values are all equal has M2 = 0 exactly on both routes, so a row whose every series is constant is NaN;
+    `diagnostics.summarize` of the same likelihoods on the host keeps whatever its rounded mean leaves (see its docstring)."""
+    if y is None:
+        raise ValueError("relative_eff needs the labels y")
+    M, N, _ = history_shape(draws, says="relative_eff needs a history (steps, chains, dim): the chains of a matrix of draws are "
+                                        "not known")
+    S, d, n = _check(draws, X, y)
+    Mh, C, max_lag = diagnostics._shape(M, N, split, max_lag)
+    if is_device_tensor(draws):
+        parts = list(_reff_device(draws, X, y, M, N, d, n, Mh, C, max_lag, split, max_bytes))
+    else:
+        parts = list(_reff_host(draws, X, y, M, N, d, n, Mh, C, max_lag, split))
+    ess = np.concatenate([p.ess for p in parts])
+    truncated = np.concatenate([p.truncated for p in parts])
+    return Summary(r_eff=ess / S, ess=ess, truncated=truncated, n_truncated=int(truncated.sum()), n_nan=int(np.isnan(ess).sum()),
+                   n_draws=S, n_steps=Mh, n_chains=C, max_lag=max_lag)
