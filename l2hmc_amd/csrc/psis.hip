@@ -1,7 +1,7 @@
 // l2hmc_psis_smooth -- Pareto-smoothed importance sampling (PSIS; Vehtari, Simpson, Gelman, Yao, Gabry 2024) of the tails of
 // any log importance ratios, float64 throughout: the generalised-Pareto fit of Zhang & Stephens (2009) with the prior of the
 // `loo` package, the smoothed tail weights and the two logsumexps a caller needs to finish an importance-weighted mean.  It is
-// the arithmetic of l2hmc_amd/predictive.py `_psis_rows`, formula for formula (nothing is folded into an equivalent form: the
+// the arithmetic of l2hmc_amd/_pareto.py `_psis_rows`, formula for formula (nothing is folded into an equivalent form: the
 // host references compute these expressions, and the tests hold the kernel to them).  Per row i, with L = n_tail[i] <= M live
 // slots of lam (descending), lam_c = lam_cutoff[i]:
 //     lam_max = lam[0] (lam_c when L = 0),  floor_c = e^(lam_c - lam_max),  x_s = e^(lam_s - lam_max) - floor_c

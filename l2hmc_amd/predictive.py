@@ -48,17 +48,18 @@ fuses the logit contraction with the moment and lag sums of csrc/chain_stats.hip
 """
 import numpy as np
 
-from . import _ffi, diagnostics
+from . import _ffi, diagnostics, psis
 from ._history import as_numpy, history_shape, in_place, is_device_tensor, launch, workspace
+from ._pareto import (KHAT_BAD, MIN_TAIL_FIT, _Numpy, _Torch, _logaddexp, _loo_summary, _psis_rows, _se_rows,  # noqa: F401
+                      _softplus_neg, lam_max, loo_tail_len, theta_grid_len)
 from .diagnostics import Summary
 
 MAX_DEVICE_ROWS = 1 << 20     # l2hmc_pack_logistic
 MAX_DEVICE_DIM = 128
 HIGH_VARIANCE = 0.4
 _HOST_CHUNK_ELEMS = 1 << 22   # (draws x rows) logits formed at a time on the host
-KHAT_BAD = 0.7                # PSIS is unreliable above it whatever S is
-MIN_TAIL_FIT = 5              # a shorter tail is not fitted: khat = +inf
 _FINISH_CHUNK_BYTES = 1 << 26  # the (rows, theta grid, tail) block of the Pareto profile formed at a time by `loo_finish`
+_KERNEL_FINISH_BYTES = 1 << 28  # the float64 (rows, M) log ratios formed at a time by the kernel finish
 _REFF_BYTES = 256 << 20       # the (chains, rows) moments and the lag-sum workspace of one `relative_eff` launch
 _NEG_ZERO_KEY = -5e-324       # stands for -0.0 on the host so that a float64 sort puts it before +0.0, as the device order does
 
@@ -104,10 +105,17 @@ def _device_packer(dev, X, y, n, d, who):
     return pack
 
 
+def _row_groups(pack, n, rows):
+    """(a, m, packed) of every group of at most `rows` consecutive rows [a, a + m), packed by `_device_packer`'s `pack`."""
+    for a in range(0, n, rows):
+        m = min(rows, n - a)
+        yield a, m, pack(a, m)
+
+
 def _device_sums(draws, X, y, S, d, n):
     import torch
     dev = draws.device
-    packed = _device_packer(dev, X, y, n, d, "the predictive kernel holds")(0, n)
+    (_, _, packed), = _row_groups(_device_packer(dev, X, y, n, d, "the predictive kernel holds"), n, n)
     W = in_place(draws)
     L = _ffi.lib()
     ws = workspace(dev, torch.float64, L.l2hmc_logistic_predict_workspace_doubles, S, n, d)
@@ -116,16 +124,18 @@ def _device_sums(draws, X, y, S, d, n):
     return sums.cpu().numpy()
 
 
-def _host_sums(draws, X, y, S, d, n):
+def _host_inputs(draws, X, y, S, d, n):
+    """(W (S, d), X (n, d), sign (n,) = 2 y - 1) in float64 numpy of host data; the labels are checked here (y=None: zeros)."""
     W = as_numpy(draws, np.float64).reshape(S, d)
     X = as_numpy(X, np.float64)
-    if y is None:
-        y = np.zeros(n)
-    else:
-        y = as_numpy(y, np.float64)
-        if not np.all((y == 0.0) | (y == 1.0)):
-            raise ValueError("labels y must be 0 or 1")
-    sign = 2.0 * y - 1.0
+    y = np.zeros(n) if y is None else as_numpy(y, np.float64)
+    if not np.all((y == 0.0) | (y == 1.0)):
+        raise ValueError("labels y must be 0 or 1")
+    return W, X, 2.0 * y - 1.0
+
+
+def _host_sums(draws, X, y, S, d, n):
+    W, X, sign = _host_inputs(draws, X, y, S, d, n)
     step = max(1, _HOST_CHUNK_ELEMS // n)
     out = {k: np.zeros(n) for k in ("sum_p", "sum_lik", "sum_ll", "sum_ll2", "m2_ll")}
     log_sum = np.full(n, -np.inf)
@@ -178,7 +188,7 @@ def finish(sums):
         p_waic_i = m2 / (S - 1)
         elpd_i = lppd_i - p_waic_i
         lppd, p_waic, elpd = float(lppd_i.sum()), float(p_waic_i.sum()), float(elpd_i.sum())
-        se = float(np.sqrt(n * elpd_i.var(ddof=1))) if n > 1 else float("nan")
+        se = _se_rows(elpd_i)
     return Summary(p_mean=p_mean, lppd_i=lppd_i, p_waic_i=p_waic_i, elpd_i=elpd_i, lppd=lppd, p_waic=p_waic, elpd_waic=elpd,
                    waic=-2.0 * elpd, se=se, n_draws=S, n_rows=n, n_high_variance=int(np.sum(p_waic_i > HIGH_VARIANCE)),
                    n_underflow=int(np.sum(np.isneginf(lppd_i))))
@@ -206,15 +216,8 @@ def log_predictive_density(draws, X_new, y_new):
     f = finish(pointwise_sums(draws, X_new, y_new))
     n = f.n_rows
     with np.errstate(all="ignore"):
-        se = float(np.sqrt(n * f.lppd_i.var(ddof=1))) if n > 1 else float("nan")
+        se = _se_rows(f.lppd_i)
     return Summary(lppd=f.lppd, lppd_i=f.lppd_i, se=se, n_draws=f.n_draws, n_rows=n, n_underflow=f.n_underflow)
-
-
-def loo_tail_len(S):
-    """M = min(S // 5, ceil(3 sqrt S)): how many of the largest importance ratios PSIS may fit and smooth."""
-    import math
-    S = int(S)
-    return min(S // 5, math.isqrt(9 * S - 1) + 1) if S >= 1 else 0
 
 
 def tail_len_rows(r_eff, S):
@@ -233,71 +236,50 @@ def _check_lengths(tail_len_row, n, S):
     return lens
 
 
-def _device_tail_groups(draws, X, y, S, d, n, max_tail_bytes, tail_len_row=None):
+def _device_tail_groups(draws, X, y, S, d, n, max_tail_bytes, lens=None):
     """The raw dict of one group of consecutive rows at a time, on the device; a group's tail stays under `max_tail_bytes`.
-    `tail_len_row` (n,) int64: a tail length per row (`l2hmc_logistic_loo_tails_mc`); the dict gains 'body_sq' and
-    'tail_len_row', and 'tail_len' is the largest length."""
+    `lens` (n,) int64: a tail length per row (`l2hmc_logistic_loo_tails_mc`, which has one more sum row); the dict gains
+    'body_sq' and 'tail_len_row', and 'tail_len' is the largest length."""
     import torch
     dev = draws.device
     pack = _device_packer(dev, X, y, n, d, "the LOO kernels hold")
     W = in_place(draws)
     L = _ffi.lib()
-    if tail_len_row is not None:
-        yield from _device_tail_groups_mc(dev, pack, W, L, S, d, n, max_tail_bytes, tail_len_row)
-        return
-    M = _ffi.check(L.l2hmc_logistic_loo_tail_len(S))
+    mc = lens is not None
+    if mc:
+        M = int(lens.max()) if n else 0
+        lens_d = torch.as_tensor(lens).to(dev)
+        entry, query = L.l2hmc_logistic_loo_tails_mc, L.l2hmc_logistic_loo_mc_workspace_bytes
+        outgrew = "l2hmc_logistic_loo_tails_mc: a tail outgrew its slots: the passes disagree"
+    else:
+        M = _ffi.check(L.l2hmc_logistic_loo_tail_len(S))
+        entry, query = L.l2hmc_logistic_loo_tails, L.l2hmc_logistic_loo_workspace_bytes
+        outgrew = "l2hmc_logistic_loo_tails: a tail outgrew its %d slots: the passes disagree" % M
     rows = max(1, min(n, int(max_tail_bytes) // max(1, 4 * M), (1 << 31) // max(1, M)))
     flags = []                                               # every group's error word, read once after the last group
-    for a in range(0, n, rows):
-        m = min(rows, n - a)
-        packed = pack(a, m)
-        ws = workspace(dev, torch.uint8, L.l2hmc_logistic_loo_workspace_bytes, S, m, d)
+    for a, m, packed in _row_groups(pack, n, rows):
+        ws = workspace(dev, torch.uint8, query, S, m, d)
         cutoff = torch.empty(m, dtype=torch.float32, device=dev)
         n_tail = torch.empty(m, dtype=torch.int64, device=dev)
         tail = torch.empty((m, M), dtype=torch.float32, device=dev)
-        sums = torch.empty((2, m), dtype=torch.float64, device=dev)
-        launch(dev, L.l2hmc_logistic_loo_tails, W.data_ptr(), S, d, packed.data_ptr(), m, cutoff.data_ptr(), n_tail.data_ptr(),
-               tail.data_ptr() if M else None, sums.data_ptr(), ws.data_ptr())
-        flags.append(ws[:8].view(torch.int64).clone())
-        yield {"cutoff": cutoff, "n_tail": n_tail, "tail": tail, "body": sums[0], "sum_lik": sums[1], "tail_len": M, "n_draws": S}
-    if bool(torch.cat(flags).any()):
-        raise RuntimeError("l2hmc_logistic_loo_tails: a tail outgrew its %d slots: the passes disagree" % M)
-
-
-def _device_tail_groups_mc(dev, pack, W, L, S, d, n, max_tail_bytes, lens):
-    import torch
-    M = int(lens.max()) if n else 0
-    lens_d = torch.as_tensor(lens).to(dev)
-    rows = max(1, min(n, int(max_tail_bytes) // max(1, 4 * M), (1 << 31) // max(1, M)))
-    flags = []
-    for a in range(0, n, rows):
-        m = min(rows, n - a)
-        packed = pack(a, m)
-        ws = workspace(dev, torch.uint8, L.l2hmc_logistic_loo_mc_workspace_bytes, S, m, d)
-        cutoff = torch.empty(m, dtype=torch.float32, device=dev)
-        n_tail = torch.empty(m, dtype=torch.int64, device=dev)
-        tail = torch.empty((m, M), dtype=torch.float32, device=dev)
-        sums = torch.empty((3, m), dtype=torch.float64, device=dev)
-        group = lens_d[a:a + m].contiguous()
-        launch(dev, L.l2hmc_logistic_loo_tails_mc, W.data_ptr(), S, d, packed.data_ptr(), m, group.data_ptr(), M, cutoff.data_ptr(),
+        sums = torch.empty((3 if mc else 2, m), dtype=torch.float64, device=dev)
+        group = lens_d[a:a + m].contiguous() if mc else None
+        launch(dev, entry, W.data_ptr(), S, d, packed.data_ptr(), m, *((group.data_ptr(), M) if mc else ()), cutoff.data_ptr(),
                n_tail.data_ptr(), tail.data_ptr() if M else None, sums.data_ptr(), ws.data_ptr())
         flags.append(ws[:8].view(torch.int64).clone())
-        yield {"cutoff": cutoff, "n_tail": n_tail, "tail": tail, "body": sums[0], "sum_lik": sums[1], "body_sq": sums[2],
-               "tail_len_row": group, "tail_len": M, "n_draws": S}
+        out = {"cutoff": cutoff, "n_tail": n_tail, "tail": tail, "body": sums[0], "sum_lik": sums[1], "tail_len": M, "n_draws": S}
+        if mc:
+            out.update(body_sq=sums[2], tail_len_row=group)
+        yield out
     if bool(torch.cat(flags).any()):
-        raise RuntimeError("l2hmc_logistic_loo_tails_mc: a tail outgrew its slots: the passes disagree")
+        raise RuntimeError(outgrew)
 
 
 def _host_tails(draws, X, y, S, d, n, tail_len_row=None):
     """The same raw dict in float64 numpy: per row the M + 1 smallest signed logits are kept while the draws pass in chunks
     (a partition, not a sort), then one more pass over the draws adds the body and the likelihoods.  `tail_len_row` (n,): row i
     is cut at its own rank M_i (M is then the largest), and the dict gains 'body_sq' and 'tail_len_row'."""
-    W = as_numpy(draws, np.float64).reshape(S, d)
-    X = as_numpy(X, np.float64)
-    y = as_numpy(y, np.float64)
-    if not np.all((y == 0.0) | (y == 1.0)):
-        raise ValueError("labels y must be 0 or 1")
-    sign = 2.0 * y - 1.0
+    W, X, sign = _host_inputs(draws, X, y, S, d, n)
     M = loo_tail_len(S) if tail_len_row is None else (int(tail_len_row.max()) if n else 0)
     Mi = np.full(n, M, dtype=np.int64) if tail_len_row is None else tail_len_row
     step = max(1, _HOST_CHUNK_ELEMS // n)
@@ -360,133 +342,12 @@ def loo_tails(draws, X, y, max_tail_bytes=256 << 20, tail_len_row=None):
     return out
 
 
-class _Numpy:
-    """The few array operations `_loo_rows` needs, over numpy ..."""
-    def __init__(self):
-        for k in ("exp", "log", "log1p", "expm1", "sqrt", "floor", "where", "isfinite", "minimum", "maximum", "isnan"):
-            setattr(self, k, getattr(np, k))
-
-    def f64(self, a):
-        return np.asarray(a, dtype=np.float64)
-
-    def arange(self, n, like):
-        return np.arange(n, dtype=np.float64)
-
-    def sort(self, a):
-        return np.sort(a, axis=-1)
-
-    def sum(self, a):
-        return a.sum(axis=-1)
-
-    def max(self, a):
-        return a.max(axis=-1) if a.shape[-1] else np.full(a.shape[:-1], -np.inf)
-
-    def take(self, a, idx):
-        return np.take_along_axis(a, idx.astype(np.int64)[..., None], axis=-1)[..., 0]
-
-    def host(self, a):
-        return np.asarray(a)
-
-
-class _Torch:
-    """... and over torch, on the device of the tails."""
-    def __init__(self):
-        import torch
-        self.t = torch
-        for k in ("exp", "log", "log1p", "expm1", "sqrt", "floor", "where", "isfinite", "minimum", "maximum", "isnan"):
-            setattr(self, k, getattr(torch, k))
-
-    def f64(self, a):
-        return a.to(self.t.float64)
-
-    def arange(self, n, like):
-        return self.t.arange(n, dtype=self.t.float64, device=like.device)
-
-    def sort(self, a):
-        return self.t.sort(a, dim=-1).values
-
-    def sum(self, a):
-        return a.sum(dim=-1)
-
-    def max(self, a):
-        return a.amax(dim=-1) if a.shape[-1] else self.t.full(a.shape[:-1], -float("inf"), dtype=a.dtype, device=a.device)
-
-    def take(self, a, idx):
-        return self.t.gather(a, -1, idx.to(self.t.int64).unsqueeze(-1)).squeeze(-1)
-
-    def host(self, a):
-        return a.cpu().numpy()
-
-
-def _softplus_neg(xp, v):
-    """softplus(-v) = log(1 + e^-v)"""
-    return xp.maximum(-v, v * 0.0) + xp.log1p(xp.exp(-xp.maximum(v, -v)))
-
-
-def _lse(xp, a, zero):
-    """logsumexp over the last axis; -inf when empty"""
-    mx = xp.max(a)
-    mx = xp.where(xp.isfinite(mx), mx, xp.where(xp.isnan(mx), mx, zero))              # centre: 0 for an empty (-inf) row
-    return mx + xp.log(xp.sum(xp.exp(a - mx[..., None])))
-
-
-def _logaddexp(xp, a, b, zero):
-    """logaddexp of two (rows,) arrays"""
-    mx = xp.maximum(a, b)
-    mx = xp.where(xp.isfinite(mx), mx, xp.where(xp.isnan(mx), mx, zero))
-    return mx + xp.log(xp.exp(a - mx) + xp.exp(b - mx))
-
-
 def _loo_prepare(xp, cutoff, n_tail, tail):
     """The first seam of `_loo_rows`: (c, L, lam_c, lam) float64 of a chunk of rows -- the tail sorted so that t ascends (the
     +inf pads last), lam = softplus(-t) descending with 0 in the pads."""
     c, Lf = xp.f64(cutoff), xp.f64(n_tail)
     t = xp.sort(xp.f64(tail))                                                      # the +inf pads last
     return c, Lf, _softplus_neg(xp, c), _softplus_neg(xp, t)
-
-
-def _psis_rows(xp, lam, Lf, lam_c, M):
-    """The middle of `_loo_rows`, and the host form of `psis.smooth_tails` (csrc/psis.hip restates it formula for formula):
-    (khat, lam_max, lse_w, lse_wl, omega, live) of a chunk of rows whose (rows, M) log ratios `lam` descend over the L live
-    slots; slot s < L holds the ratio of ascending rank j = L - s.  khat is the fitted shape or +inf where nothing was
-    smoothed; omega (rows, M) is meaningful in the live slots only."""
-    zero = Lf * 0.0
-    slot = xp.arange(M, Lf)
-    zeros = zero[:, None] + slot[None, :] * 0.0                                    # (rows, M)
-    minus_inf = zeros - float("inf")
-    live = slot[None, :] < Lf[:, None]
-    j = Lf[:, None] - slot[None, :]                                                # ascending rank of the ratio, 1 .. L
-    lam_max = xp.where(Lf > 0, lam[:, 0], lam_c) if M else lam_c
-    floor_c = xp.exp(lam_c - lam_max)                                              # the cutoff's ratio over the largest one
-    x = xp.where(live, xp.exp(lam - lam_max[:, None]) - floor_c[:, None], zeros)
-    fit = Lf >= MIN_TAIL_FIT
-    Ls = xp.where(fit, Lf, zero + MIN_TAIL_FIT)                                    # (a placeholder length where nothing is fitted)
-    # Zhang & Stephens (2009) with the prior of `loo`: the profile likelihood on a grid of theta, theta's posterior mean
-    jt = xp.arange(30 + int(np.floor(np.sqrt(max(M, 1)))), Lf) + 1.0
-    m_theta = 30.0 + xp.floor(xp.sqrt(Ls))
-    on_grid = jt[None, :] <= m_theta[:, None]
-    if M:
-        x_star = xp.take(x, xp.minimum(xp.maximum(Ls - xp.floor(Ls / 4.0 + 0.5), zero), zero + (M - 1)))   # rank floor(L/4 + 0.5)
-        x_top = x[:, 0]
-    else:
-        x_star = x_top = zero
-    theta = 1.0 / x_top[:, None] + (1.0 - xp.sqrt(m_theta[:, None] / (jt[None, :] - 0.5))) / (3.0 * x_star[:, None])
-    kj = xp.sum(xp.where(live[:, None, :], xp.log1p(-theta[:, :, None] * x[:, None, :]), zeros[:, None, :])) / Ls[:, None]
-    ell = xp.where(on_grid, Ls[:, None] * (xp.log(-theta / kj) - kj - 1.0), theta * 0.0 - float("inf"))
-    wj = xp.exp(ell - _lse(xp, ell, zero)[:, None])                                # = 1 / sum_j' exp(ell_j' - ell_j)
-    theta_hat = xp.sum(xp.where(on_grid, theta * wj, theta * 0.0))
-    k = xp.sum(xp.where(live, xp.log1p(-theta_hat[:, None] * x), zeros)) / Ls
-    sigma = -k / theta_hat
-    k = (k * Ls + 5.0) / (Ls + 10.0)
-    smooth = fit & xp.isfinite(k) & xp.isfinite(sigma)
-    lp = xp.log1p(-xp.where(live, (j - 0.5) / Ls[:, None], zeros))                 # log(1 - p_j)
-    ks = xp.where(smooth & (k != 0.0), k, zero + 1.0)[:, None]
-    qj = xp.where((k == 0.0)[:, None], -sigma[:, None] * lp, sigma[:, None] * xp.expm1(-ks * lp) / ks)
-    omega = xp.where(smooth[:, None], xp.minimum(xp.log(qj + floor_c[:, None]), zeros), lam - lam_max[:, None])
-    lse_wl = _lse(xp, xp.where(live, omega - lam, minus_inf), zero)
-    lse_w = _lse(xp, xp.where(live, omega, minus_inf), zero)
-    khat = xp.where(smooth, k, zero + float("inf"))
-    return khat, lam_max, lse_w, lse_wl, omega, live
 
 
 def _loo_combine(xp, khat, lam_max, lse_w, lse_wl, c, Lf, body, sum_lik, S):
@@ -500,83 +361,8 @@ def _loo_combine(xp, khat, lam_max, lse_w, lse_wl, c, Lf, body, sum_lik, S):
     return khat, elpd, xp.log(xp.f64(sum_lik) / S)
 
 
-def _loo_rows(xp, cutoff, n_tail, tail, body, sum_lik, S, M):
-    """(khat, elpd_loo_i, lppd_i) of a chunk of rows, float64, over the operations of `xp` alone: prepare lam / fit and smooth
-    / combine.  The tail is sorted so that t ascends: slot s < L holds the ratio of ascending rank j = L - s, and slot 0 the
-    largest."""
-    c, Lf, lam_c, lam = _loo_prepare(xp, cutoff, n_tail, tail)
-    khat, lam_max, lse_w, lse_wl, _, _ = _psis_rows(xp, lam, Lf, lam_c, M)
-    return _loo_combine(xp, khat, lam_max, lse_w, lse_wl, c, Lf, body, sum_lik, S)
-
-
-def _loo_summary(khat, elpd_i, lppd_i, n_tail, S, M):
-    n = elpd_i.shape[0]
-    with np.errstate(all="ignore"):
-        p_loo_i = lppd_i - elpd_i
-        elpd, p_loo, lppd = float(elpd_i.sum()), float(p_loo_i.sum()), float(lppd_i.sum())
-        se = float(np.sqrt(n * elpd_i.var(ddof=1))) if n > 1 else float("nan")
-        threshold = min(1.0 - 1.0 / np.log10(S), KHAT_BAD)
-    return Summary(elpd_loo_i=elpd_i, p_loo_i=p_loo_i, lppd_i=lppd_i, khat=khat, n_tail=n_tail, elpd_loo=elpd, p_loo=p_loo,
-                   lppd=lppd, looic=-2.0 * elpd, se=se, khat_threshold=threshold, n_bad=int(np.sum(khat > KHAT_BAD)),
-                   n_above_threshold=int(np.sum(khat > threshold)), tail_len=M, n_draws=S, n_rows=n,
-                   n_underflow=int(np.sum(np.isneginf(lppd_i))))
-
-
-def _row_chunks(tails, rows_for, middle, extra=()):
-    """(khat, elpd_loo_i, lppd_i, n_tail) as float64 / int64 numpy of one raw dict: `middle(xp, cutoff, n_tail, tail, body,
-    sum_lik, S, M)` on chunks of `rows_for(M)` rows, computed where the tails lie; only these O(n) numbers come to the host.
-    `extra`: further per-row entries of the dict handed to `middle` after sum_lik; every array `middle` returns comes back,
-    n_tail last."""
-    S, M = int(tails["n_draws"]), int(tails["tail_len"])
-    if S < 2:
-        raise ValueError("PSIS-LOO needs >= 2 draws (got %d)" % S)
-    xp = _Torch() if is_device_tensor(tails["tail"]) else _Numpy()
-    keys = ("cutoff", "n_tail", "tail", "body", "sum_lik") + tuple(extra)
-    arrays = [tails[k] if isinstance(xp, _Torch) else np.asarray(tails[k]) for k in keys]
-    n, rows = int(arrays[0].shape[0]), max(1, rows_for(M))
-    out = [[] for _ in range(3 + len(extra))]
-    with np.errstate(all="ignore"):
-        for a in range(0, n, rows):
-            for o, r in zip(out, middle(xp, *(v[a:a + rows] for v in arrays), S, M)):
-                o.append(xp.host(r))
-    return tuple(np.concatenate(o) for o in out) + (np.asarray(xp.host(arrays[1]), dtype=np.int64),)
-
-
-def _finish_rows(tails):
-    """`_loo_rows` in row chunks of bounded memory: the (rows, theta grid, tail) block of the Pareto profile."""
-    n_theta = lambda M: 30 + int(np.floor(np.sqrt(max(M, 1))))  # noqa: E731
-    return _row_chunks(tails, lambda M: _FINISH_CHUNK_BYTES // (8 * n_theta(M) * max(M, 1)), _loo_rows)
-
-
-def _check_finish(finish, on_device):
-    if finish not in ("torch", "kernel"):
-        raise ValueError('finish is "torch" or "kernel" (got %r)' % (finish,))
-    if finish == "kernel" and not on_device:
-        raise ValueError('finish="kernel" runs the Pareto fit of csrc/psis.hip where the tails lie, on a ROCm device; these are '
-                         'host data (numpy or a CPU tensor), which float64 numpy finishes: leave finish="torch"')
-
-
-_KERNEL_FINISH_BYTES = 1 << 28  # the float64 (rows, M) log ratios formed at a time by the kernel finish
-
-
-def _loo_rows_kernel(xp, cutoff, n_tail, tail, body, sum_lik, S, M):
-    """`_loo_rows` with the middle on csrc/psis.hip: `torch.sort` of the float32 tail, lam = softplus(-t) in float64 torch,
-    `psis.smooth_tails`, and the O(n) combine."""
-    from .psis import smooth_tails
-    c, Lf, lam_c, lam = _loo_prepare(xp, cutoff, n_tail, tail)
-    khat, lse_w, lse_wl = smooth_tails(lam, n_tail, lam_c)
-    lam_max = xp.where(Lf > 0, lam[:, 0], lam_c) if M else lam_c
-    return _loo_combine(xp, khat, lam_max, lse_w, lse_wl, c, Lf, body, sum_lik, S)
-
-
-def _finish_rows_kernel(tails):
-    """`_finish_rows` of device tails by `_loo_rows_kernel`, in row chunks of bounded memory (the float64 (rows, M) log ratios),
-    whose bits do not depend on the chunking."""
-    return _row_chunks(tails, lambda M: _KERNEL_FINISH_BYTES // (8 * max(M, 1)), _loo_rows_kernel)
-
-
 def _mc_extras(xp, elpd, lam_max, lse_w, omega, live, lam, c, Lf, body, body_sq, r_eff, S):
-    """(n_eff_i, mcse_elpd_loo_i) of a chunk of rows (module docstring, "Monte Carlo error"), relative to the row's largest
+    """(n_eff_i, mcse_elpd_loo_i) of a chunk of rows (`loo`'s docstring has the formulas), relative to the row's largest
     ratio e^lam_max as `_loo_combine` works: every weight is then <= 1 and their sum Z lies in [1, S]."""
     zero = Lf * 0.0
     m = xp.minimum(xp.where(xp.isnan(c), zero, c), zero)
@@ -592,39 +378,83 @@ def _mc_extras(xp, elpd, lam_max, lse_w, omega, live, lam, c, Lf, body, body_sq,
     return n_eff, mcse
 
 
-def _loo_rows_mc(xp, cutoff, n_tail, tail, body, sum_lik, body_sq, r_eff, S, M):
-    """`_loo_rows` plus (n_eff_i, mcse_elpd_loo_i): the rows' tails have their own lengths, which `_psis_rows` takes per row."""
+def _middle_torch(xp, lam, n_tail, Lf, lam_c, M, mc):
+    return _psis_rows(xp, lam, Lf, lam_c, M)
+
+
+def _middle_kernel(xp, lam, n_tail, Lf, lam_c, M, mc):
+    """The fit on csrc/psis.hip (`psis.smooth_tails`, which returns omega from the kernel only when the extras need it)."""
+    res = psis.smooth_tails(lam, n_tail, lam_c, weights=mc)
+    top = lam_max(xp, lam, Lf, lam_c, M)
+    live = xp.arange(M, Lf)[None, :] < Lf[:, None] if mc else None
+    return res[0], top, res[1], res[2], res[3] if mc else None, live
+
+
+_MIDDLES = {"torch": _middle_torch, "kernel": _middle_kernel}
+
+
+def _loo_rows(xp, middle, S, M, cutoff, n_tail, tail, body, sum_lik, body_sq=None, r_eff=None):
+    """(khat, elpd_loo_i, lppd_i) of a chunk of rows, float64, over the operations of `xp` alone: prepare lam / fit and smooth
+    (`middle`: a `_MIDDLES` entry, which returns (khat, lam_max, lse_w, lse_wl, omega, live)) / combine.  The tail is sorted so
+    that t ascends: slot s < L holds the ratio of ascending rank j = L - s, and slot 0 the largest; the rows' tails may have
+    their own lengths, which the fit takes per row.  With `body_sq` and `r_eff`: plus (n_eff_i, mcse_elpd_loo_i)."""
+    mc = r_eff is not None
     c, Lf, lam_c, lam = _loo_prepare(xp, cutoff, n_tail, tail)
-    khat, lam_max, lse_w, lse_wl, omega, live = _psis_rows(xp, lam, Lf, lam_c, M)
-    khat, elpd, lppd = _loo_combine(xp, khat, lam_max, lse_w, lse_wl, c, Lf, body, sum_lik, S)
-    return (khat, elpd, lppd) + _mc_extras(xp, elpd, lam_max, lse_w, omega, live, lam, c, Lf, body, body_sq, r_eff, S)
+    khat, top, lse_w, lse_wl, omega, live = middle(xp, lam, n_tail, Lf, lam_c, M, mc)
+    out = _loo_combine(xp, khat, top, lse_w, lse_wl, c, Lf, body, sum_lik, S)
+    if mc:
+        out += _mc_extras(xp, out[1], top, lse_w, omega, live, lam, c, Lf, body, body_sq, r_eff, S)
+    return out
 
 
-def _loo_rows_mc_kernel(xp, cutoff, n_tail, tail, body, sum_lik, body_sq, r_eff, S, M):
-    """`_loo_rows_mc` with the middle on csrc/psis.hip (`psis.smooth_tails(weights=True)` returns omega from the kernel)."""
-    from .psis import smooth_tails
-    c, Lf, lam_c, lam = _loo_prepare(xp, cutoff, n_tail, tail)
-    khat, lse_w, lse_wl, omega = smooth_tails(lam, n_tail, lam_c, weights=True)
-    lam_max = xp.where(Lf > 0, lam[:, 0], lam_c) if M else lam_c
-    live = xp.arange(M, Lf)[None, :] < Lf[:, None]
-    khat, elpd, lppd = _loo_combine(xp, khat, lam_max, lse_w, lse_wl, c, Lf, body, sum_lik, S)
-    return (khat, elpd, lppd) + _mc_extras(xp, elpd, lam_max, lse_w, omega, live, lam, c, Lf, body, body_sq, r_eff, S)
+def _row_chunks(tails, rows_for, middle, extra=()):
+    """(khat, elpd_loo_i, lppd_i, n_tail) as float64 / int64 numpy of one raw dict: `_loo_rows` with `middle` on chunks of
+    `rows_for(M)` rows, computed where the tails lie; only these O(n) numbers come to the host.  `extra`: further per-row
+    entries of the dict handed to `_loo_rows` after sum_lik; every array it returns comes back, n_tail last."""
+    S, M = int(tails["n_draws"]), int(tails["tail_len"])
+    if S < 2:
+        raise ValueError("PSIS-LOO needs >= 2 draws (got %d)" % S)
+    xp = _Torch() if is_device_tensor(tails["tail"]) else _Numpy()
+    keys = ("cutoff", "n_tail", "tail", "body", "sum_lik") + tuple(extra)
+    arrays = [tails[k] if isinstance(xp, _Torch) else np.asarray(tails[k]) for k in keys]
+    n, rows = int(arrays[0].shape[0]), max(1, rows_for(M))
+    out = [[] for _ in range(3 + len(extra))]
+    with np.errstate(all="ignore"):
+        for a in range(0, n, rows):
+            for o, r in zip(out, _loo_rows(xp, middle, S, M, *(v[a:a + rows] for v in arrays))):
+                o.append(xp.host(r))
+    return tuple(np.concatenate(o) for o in out) + (np.asarray(xp.host(arrays[1]), dtype=np.int64),)
 
 
-def _finish_rows_mc(tails, r_eff, finish):
-    """(khat, elpd_loo_i, lppd_i, n_eff_i, mcse_i, n_tail) of a raw dict with per-row tails and 'body_sq'."""
-    if "body_sq" not in tails:
-        raise ValueError("r_eff needs tails with per-row lengths: loo_tails(..., tail_len_row=tail_len_rows(r_eff, S))")
-    r = np.asarray(r_eff, dtype=np.float64)
-    if is_device_tensor(tails["tail"]):
-        import torch
-        r = torch.as_tensor(r).to(tails["tail"].device)
-    n_theta = lambda M: 30 + int(np.floor(np.sqrt(max(M, 1))))  # noqa: E731
+def _finish_chunk_rows(finish, M):
+    """The rows of one chunk, of bounded memory: the float64 (rows, M) log ratios of the kernel finish (whose bits do not depend
+    on the chunking), the (rows, theta grid, tail) block of the Pareto profile of the torch and numpy one."""
     if finish == "kernel":
-        return _row_chunks(dict(tails, r_eff=r), lambda M: _KERNEL_FINISH_BYTES // (8 * max(M, 1)), _loo_rows_mc_kernel,
-                           extra=("body_sq", "r_eff"))
-    return _row_chunks(dict(tails, r_eff=r), lambda M: _FINISH_CHUNK_BYTES // (8 * n_theta(M) * max(M, 1)), _loo_rows_mc,
-                       extra=("body_sq", "r_eff"))
+        return _KERNEL_FINISH_BYTES // (8 * max(M, 1))
+    return _FINISH_CHUNK_BYTES // (8 * theta_grid_len(M) * max(M, 1))
+
+
+def _finish_rows(tails, finish, r_eff=None):
+    """(khat, elpd_loo_i, lppd_i, n_tail) of a raw dict by `finish`; with `r_eff` (per-row tails and 'body_sq' in the dict)
+    (khat, elpd_loo_i, lppd_i, n_eff_i, mcse_i, n_tail)."""
+    extra = ()
+    if r_eff is not None:
+        if "body_sq" not in tails:
+            raise ValueError("r_eff needs tails with per-row lengths: loo_tails(..., tail_len_row=tail_len_rows(r_eff, S))")
+        r = np.asarray(r_eff, dtype=np.float64)
+        if is_device_tensor(tails["tail"]):
+            import torch
+            r = torch.as_tensor(r).to(tails["tail"].device)
+        tails, extra = dict(tails, r_eff=r), ("body_sq", "r_eff")
+    return _row_chunks(tails, lambda M: _finish_chunk_rows(finish, M), _MIDDLES[finish], extra)
+
+
+def _check_finish(finish, on_device):
+    if finish not in ("torch", "kernel"):
+        raise ValueError('finish is "torch" or "kernel" (got %r)' % (finish,))
+    if finish == "kernel" and not on_device:
+        raise ValueError('finish="kernel" runs the Pareto fit of csrc/psis.hip where the tails lie, on a ROCm device; these are '
+                         'host data (numpy or a CPU tensor), which float64 numpy finishes: leave finish="torch"')
 
 
 def _mc_fields(s, r_eff, n_eff, mcse, lens):
@@ -646,6 +476,18 @@ def _check_r_eff(r_eff, n):
         return np.where(r > 0, r, np.nan)                    # an entry that is not a positive number is no efficiency: NaN
 
 
+def _loo_of(raws, finish, r, lens=None):
+    """The `Summary` of the raw dicts `raws` of consecutive rows, each finished before the next is taken; `r` (n,) or None."""
+    parts, a = [], 0
+    for g in raws:
+        m = int(g["cutoff"].shape[0])
+        parts.append(_finish_rows(g, finish, None if r is None else r[a:a + m]))
+        a += m
+    cols = [np.concatenate([p[k] for p in parts]) for k in range(len(parts[0]))]
+    s = _loo_summary(cols[0], cols[1], cols[2], cols[-1], int(g["n_draws"]), int(g["tail_len"]))
+    return s if r is None else _mc_fields(s, r, cols[3], cols[4], as_numpy(g["tail_len_row"]) if lens is None else lens)
+
+
 def loo_finish(tails, finish="torch", r_eff=None):
     """The `Summary` of `loo_tails`' result: per row `elpd_loo_i`, `p_loo_i`, `lppd_i`, `khat`, `n_tail`; the totals `elpd_loo`,
     `p_loo`, `lppd`, `looic` = -2 elpd_loo, `se` = sqrt(n var_i elpd_loo_i) (NaN for one row); `khat_threshold` =
@@ -655,13 +497,8 @@ def loo_finish(tails, finish="torch", r_eff=None):
     another summation order.  `r_eff` (n,): the tails were cut at `tail_len_rows(r_eff, S)` (`loo_tails(tail_len_row=)`), and the
     Summary gains the Monte Carlo fields of `loo`."""
     _check_finish(finish, is_device_tensor(tails["tail"]))
-    if r_eff is not None:
-        r = _check_r_eff(r_eff, int(tails["cutoff"].shape[0]))
-        khat, elpd_i, lppd_i, n_eff, mcse, n_tail = _finish_rows_mc(tails, r, finish)
-        s = _loo_summary(khat, elpd_i, lppd_i, n_tail, int(tails["n_draws"]), int(tails["tail_len"]))
-        return _mc_fields(s, r, n_eff, mcse, as_numpy(tails["tail_len_row"]))
-    khat, elpd_i, lppd_i, n_tail = (_finish_rows_kernel if finish == "kernel" else _finish_rows)(tails)
-    return _loo_summary(khat, elpd_i, lppd_i, n_tail, int(tails["n_draws"]), int(tails["tail_len"]))
+    r = None if r_eff is None else _check_r_eff(r_eff, int(tails["cutoff"].shape[0]))
+    return _loo_of([tails], finish, r)
 
 
 def loo(draws, X, y, max_tail_bytes=256 << 20, finish="torch", r_eff=None):
@@ -682,29 +519,17 @@ def loo(draws, X, y, max_tail_bytes=256 << 20, finish="torch", r_eff=None):
     outside the tail), the tail's from the smoothed weights the finish holds."""
     S, d, n = _check_loo(draws, X, y)
     _check_finish(finish, is_device_tensor(draws))
+    r = lens = None
     if r_eff is not None:
         if isinstance(r_eff, str):
             if r_eff != "auto":
                 raise ValueError('r_eff is None, "auto" or an array (n_rows,) (got %r)' % (r_eff,))
-            r = _check_r_eff(relative_eff(draws, X, y).r_eff, n)
-        else:
-            r = _check_r_eff(r_eff, n)
+            r_eff = relative_eff(draws, X, y).r_eff
+        r = _check_r_eff(r_eff, n)
         lens = tail_len_rows(r, S)
-        if not is_device_tensor(draws):
-            return loo_finish(_host_tails(draws, X, y, S, d, n, lens), r_eff=r)
-        parts, a = [], 0
-        for g in _device_tail_groups(draws, X, y, S, d, n, max_tail_bytes, lens):
-            m = int(g["cutoff"].shape[0])
-            parts.append(_finish_rows_mc(g, r[a:a + m], finish))
-            a += m
-        khat, elpd_i, lppd_i, n_eff, mcse, n_tail = (np.concatenate([p[k] for p in parts]) for k in range(6))
-        return _mc_fields(_loo_summary(khat, elpd_i, lppd_i, n_tail, S, int(lens.max())), r, n_eff, mcse, lens)
-    if not is_device_tensor(draws):
-        return loo_finish(_host_tails(draws, X, y, S, d, n))
-    rows_of = _finish_rows_kernel if finish == "kernel" else _finish_rows
-    parts = [rows_of(g) for g in _device_tail_groups(draws, X, y, S, d, n, max_tail_bytes)]
-    khat, elpd_i, lppd_i, n_tail = (np.concatenate([p[k] for p in parts]) for k in range(4))
-    return _loo_summary(khat, elpd_i, lppd_i, n_tail, S, loo_tail_len(S))
+    if is_device_tensor(draws):
+        return _loo_of(_device_tail_groups(draws, X, y, S, d, n, max_tail_bytes, lens), finish, r, lens)
+    return _loo_of([_host_tails(draws, X, y, S, d, n, lens)], finish, r, lens)
 
 
 def _reff_device(draws, X, y, M, N, d, n, Mh, C, max_lag, split, max_bytes):
@@ -718,9 +543,7 @@ def _reff_device(draws, X, y, M, N, d, n, Mh, C, max_lag, split, max_bytes):
     shape = (M, N, d)
     per_row = 16 * C + _ffi.check(L.l2hmc_logistic_lik_stats_workspace_bytes(*shape, 1, max_lag, int(split)))
     rows = max(1, min(n, int(max_bytes) // per_row))
-    for a in range(0, n, rows):
-        m = min(rows, n - a)
-        packed = pack(a, m)
+    for a, m, packed in _row_groups(pack, n, rows):
         ws = workspace(dev, torch.uint8, L.l2hmc_logistic_lik_stats_workspace_bytes, *shape, m, max_lag, int(split))
         mean = torch.empty((C, m), dtype=torch.float64, device=dev)
         m2 = torch.empty((C, m), dtype=torch.float64, device=dev)
@@ -733,12 +556,7 @@ def _reff_device(draws, X, y, M, N, d, n, Mh, C, max_lag, split, max_bytes):
 def _reff_host(draws, X, y, M, N, d, n, Mh, C, max_lag, split):
     """The same in float64 numpy, a chunk of rows at a time: the likelihoods of the chunk as a history (steps, chains, rows)
     through `diagnostics`' host sums."""
-    W = as_numpy(draws, np.float64).reshape(M * N, d)
-    X = as_numpy(X, np.float64)
-    y = as_numpy(y, np.float64)
-    if not np.all((y == 0.0) | (y == 1.0)):
-        raise ValueError("labels y must be 0 or 1")
-    sign = 2.0 * y - 1.0
+    W, X, sign = _host_inputs(draws, X, y, M * N, d, n)
     rows = max(1, _HOST_CHUNK_ELEMS // (M * N))
     for a in range(0, n, rows):
         with np.errstate(all="ignore"):

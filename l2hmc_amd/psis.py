@@ -16,7 +16,7 @@ that is not finite, keeps its raw weights and has khat = +inf.
 A ROCm tensor goes to the float64 HIP kernels behind `l2hmc_psis_smooth` (csrc/psis.hip): `torch.topk` finds the M + 1 largest
 ratios of every column in order with their positions, the kernels fit and smooth, and every smoothed weight goes back to the
 draw it belongs to; all else is torch on the same device.  numpy or a CPU tensor is float64 numpy, whose fit is
-`predictive._psis_rows` -- the very operations `predictive.loo` finishes with; the kernel restates them formula for formula.
+`_pareto._psis_rows` -- the very operations `predictive.loo` finishes with; the kernel restates them formula for formula.
 
 Sums over the draws (`log_sum`, `n_eff`, elpd and lppd of `loo_from_log_lik`) are added by a fixed pairwise tree of elementwise
 additions, which depends on S alone: a column gives the same bits whichever other columns share the call, so the results of
@@ -27,23 +27,22 @@ Not here: r_eff and the Monte-Carlo standard error of elpd_loo, moment matching,
 that hold different draws (`sharding`)."""
 import numpy as np
 
-from . import _ffi, predictive
+from . import _ffi
 from ._history import as_numpy, is_device_tensor, launch, workspace
+from ._pareto import _Numpy, _centre, _khat_fields, _loo_summary, _psis_rows, lam_max, loo_tail_len, ops_of, theta_grid_len
 from .diagnostics import Summary
 
 _HOST_CHUNK_BYTES = 1 << 26  # the (rows, theta grid, tail) block of the Pareto profile formed at a time on the host
 
 
 def _host_smooth(lam, n_tail, lam_c, want_weights):
-    xp = predictive._Numpy()
+    xp = _Numpy()
     n, M = lam.shape
-    n_theta = 30 + int(np.floor(np.sqrt(max(M, 1))))
-    rows = max(1, _HOST_CHUNK_BYTES // (8 * n_theta * max(M, 1)))
+    rows = max(1, _HOST_CHUNK_BYTES // (8 * theta_grid_len(M) * max(M, 1)))
     out = [[], [], [], []]
     with np.errstate(all="ignore"):
         for a in range(0, n, rows):
-            khat, _, lse_w, lse_wl, omega, live = predictive._psis_rows(xp, lam[a:a + rows], xp.f64(n_tail[a:a + rows]),
-                                                                        lam_c[a:a + rows], M)
+            khat, _, lse_w, lse_wl, omega, live = _psis_rows(xp, lam[a:a + rows], xp.f64(n_tail[a:a + rows]), lam_c[a:a + rows], M)
             bad = np.isnan(lse_w) | np.isnan(lse_wl)
             res = (np.where(bad, np.nan, khat), lse_w, lse_wl, np.where(live, omega, -np.inf) if want_weights else omega[:, :0])
             for o, r in zip(out, res):
@@ -58,7 +57,7 @@ def smooth_tails(lam, n_tail, lam_cutoff, weights=False):
     weight of slot s relative to the row's largest ratio (-inf in the dead slots), lse_w = logsumexp_s omega_s and
     lse_wl = logsumexp_s (omega_s - lam_s); both are -inf when L_i = 0.  A NaN among a row's live slots makes that row's
     outputs NaN.  ROCm tensors -> `l2hmc_psis_smooth` (bitwise reproducible; device tensors back); anything else -> float64
-    numpy (`predictive._psis_rows`)."""
+    numpy (`_pareto._psis_rows`)."""
     shape = tuple(int(v) for v in lam.shape)
     if len(shape) != 2 or shape[0] < 1:
         raise ValueError("lam must be (n_rows, tail_len) with n_rows >= 1; got shape %s" % (shape,))
@@ -102,22 +101,17 @@ def _tree_sum(a):
 
 
 def _lse0(a):
-    """logsumexp over axis 0 (the draws) of float64 (S, n): `predictive._lse`'s centring, `_tree_sum`'s order."""
-    if hasattr(a, "amax"):
-        import torch
-        mx = a.amax(0)
-        mx = torch.where(torch.isfinite(mx), mx, torch.where(torch.isnan(mx), mx, torch.zeros_like(mx)))
-        return mx + torch.log(_tree_sum(torch.exp(a - mx[None, :])))
+    """logsumexp over axis 0 (the draws) of float64 (S, n): `_pareto._lse`'s centring, `_tree_sum`'s order."""
+    xp = ops_of(a)
     with np.errstate(all="ignore"):
-        mx = a.max(axis=0)
-        mx = np.where(np.isfinite(mx), mx, np.where(np.isnan(mx), mx, 0.0))
-        return mx + np.log(_tree_sum(np.exp(a - mx[None, :])))
+        mx = _centre(xp, xp.max(a.T), 0.0)
+        return mx + xp.log(_tree_sum(xp.exp(a - mx[None, :])))
 
 
 def _select(r):
     """(lam (n, M) descending, n_tail (n,) int64, cutoff (n,), idx (M, n) positions of the M largest, M) of float (S, n) ratios."""
     S = int(r.shape[0])
-    M = predictive.loo_tail_len(S)
+    M = loo_tail_len(S)
     if hasattr(r, "topk"):
         import torch
         vals, idx = torch.topk(r, M + 1, dim=0, largest=True, sorted=True)
@@ -155,38 +149,25 @@ def _psis(r, want_weights):
     lam, n_tail, cutoff, idx, M = _select(r)
     res = smooth_tails(lam, n_tail, cutoff, weights=want_weights)
     khat = res[0]
-    dev = hasattr(r, "topk")
-    if dev:
-        import torch
-        lam_max = torch.where(n_tail > 0, lam[:, 0], cutoff) if M else cutoff
-    else:
-        lam_max = np.where(n_tail > 0, lam[:, 0], cutoff) if M else cutoff
+    xp = ops_of(r)
+    top = lam_max(xp, lam, n_tail, cutoff, M)
     if not want_weights:
-        return khat, n_tail, lam_max, None, M
+        return khat, n_tail, top, None, M
     omega = res[3]                                           # (n, M), slot s = the draw idx[s]
-    if dev:
-        lw = r.to(torch.float64) - lam_max[None, :]
-        if M:
-            live = torch.arange(M, device=r.device)[:, None] < n_tail[None, :]
-            lw.scatter_(0, idx, torch.where(live, omega.t(), lw.gather(0, idx)))
-    else:
-        with np.errstate(all="ignore"):
-            lw = r.astype(np.float64) - lam_max[None, :]
-        if M:
-            live = np.arange(M)[:, None] < n_tail[None, :]
-            np.put_along_axis(lw, idx, np.where(live, omega.T, np.take_along_axis(lw, idx, axis=0)), axis=0)
-    return khat, n_tail, lam_max, lw, M
+    with np.errstate(all="ignore"):
+        lw = xp.f64(r) - top[None, :]
+    if M and hasattr(r, "topk"):
+        import torch
+        live = torch.arange(M, device=r.device)[:, None] < n_tail[None, :]
+        lw.scatter_(0, idx, torch.where(live, omega.t(), lw.gather(0, idx)))
+    elif M:
+        live = np.arange(M)[:, None] < n_tail[None, :]
+        np.put_along_axis(lw, idx, np.where(live, omega.T, np.take_along_axis(lw, idx, axis=0)), axis=0)
+    return khat, n_tail, top, lw, M
 
 
 def _host(a):
     return a.cpu().numpy() if hasattr(a, "cpu") else np.asarray(a)
-
-
-def _khat_fields(khat, S):
-    with np.errstate(all="ignore"):
-        threshold = min(1.0 - 1.0 / np.log10(S), predictive.KHAT_BAD) if S > 1 else predictive.KHAT_BAD
-        return dict(khat_threshold=threshold, n_bad=int(np.sum(khat > predictive.KHAT_BAD)),
-                    n_above_threshold=int(np.sum(khat > threshold)))
 
 
 def psis(log_ratios, weights=True):
@@ -226,20 +207,11 @@ def loo_from_log_lik(log_lik):
     if S < 2:
         raise ValueError("PSIS-LOO needs >= 2 draws (got %d)" % S)
     khat, n_tail, _, lw, M = _psis(-ll, True)
-    dev = hasattr(ll, "topk")
+    xp = ops_of(ll)
     import math
-    if dev:
-        import torch
-        l64 = ll.to(torch.float64)
-        lse_w = _lse0(lw)
-        elpd = _lse0(lw + l64) - lse_w
+    with np.errstate(all="ignore"):
+        l64 = xp.f64(ll)
+        elpd = _lse0(lw + l64) - _lse0(lw)
         lppd = _lse0(l64) - math.log(S)
-        khat = torch.where(torch.isnan(elpd), elpd, khat)
-    else:
-        with np.errstate(all="ignore"):
-            l64 = ll.astype(np.float64)
-            lse_w = _lse0(lw)
-            elpd = _lse0(lw + l64) - lse_w
-            lppd = _lse0(l64) - math.log(S)
-            khat = np.where(np.isnan(elpd), elpd, khat)
-    return predictive._loo_summary(_host(khat), _host(elpd), _host(lppd), _host(n_tail).astype(np.int64), S, M)
+        khat = xp.where(xp.isnan(elpd), elpd, khat)
+    return _loo_summary(_host(khat), _host(elpd), _host(lppd), _host(n_tail).astype(np.int64), S, M)

@@ -1,6 +1,6 @@
 """Shared by tests/test_psis_cpu.py, tests/test_gpu_psis.py and tools/psis_accuracy.py: tails built directly in numpy (no draws,
 no sampler), a row-at-a-time float64 restatement of PSIS on `loo_case._gpdfit` and in the manner of `loo_case.restate_row`
-(independent of l2hmc_amd/psis.py and of `predictive._psis_rows`: another summation order -- `np.mean`, `np.logaddexp.reduce`
+(independent of l2hmc_amd/psis.py and of `_pareto._psis_rows`: another summation order -- `np.mean`, `np.logaddexp.reduce`
 -- and another formation of x and of the ratios), and the gates of the kernel.
 
 A tail.  `tail(M, L, k_true, seed)` draws L importance ratios cutoff_ratio + GPD(k_true, sigma = 1) quantiles at sorted

@@ -282,3 +282,42 @@ def test_exact_inputs_with_per_row_lengths():
         assert np.array_equal(got["cutoff"].astype(np.float64), ref["cutoff"]) and np.array_equal(got["n_tail"], ref["n_tail"])
         assert np.array_equal(np.sort(got["tail"].astype(np.float64), axis=1), ref["tail"])
         assert np.any(ref["n_tail"] < lens)                  # ties at the cutoff shorten some tails
+
+
+def _bits_equal(a, b):
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    return a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a.view(np.uint8), b.view(np.uint8))
+
+
+def test_loo_with_r_eff_in_row_groups_gives_the_one_group_result():
+    """`loo(r_eff=array)` whose 50 rows go to the kernels in four groups of 13 against the one-group call, both finishes, per-row
+    tail lengths 49 .. 104 and one NaN efficiency.  The tails' bits do not depend on the grouping, nor do the kernel finish's
+    khat and elpd_loo_i.  n_eff, mcse_elpd_loo_i and the torch finish's numbers pass through torch reductions whose order could
+    depend on the chunk's shape (13 rows against 50); their gates would be the finish-against-finish ones of tests/loo_case.py
+    and tests/lik_stats_case.py, but on the MI355X every field is bit-equal under both finishes, so that is what is asserted
+    (the gates are stated after it: they say how far a field may move before the test's premise is gone)."""
+    from l2hmc_amd import predictive
+    W, X, y = lc.case(520, 50, 17, seed=77)
+    r = 0.2 + 1.8 * np.random.RandomState(77).rand(50)
+    r[11] = np.nan
+    lens = predictive.tail_len_rows(r, 520)
+    Mmax = int(lens.max())
+    assert lens.min() < Mmax and -(-50 // 13) == 4
+    Wd = _dev(W)
+    live = ~np.isnan(r)
+    for finish in ("torch", "kernel"):
+        one = predictive.loo(Wd, X, y, finish=finish, r_eff=r)
+        four = predictive.loo(Wd, X, y, finish=finish, r_eff=r, max_tail_bytes=4 * Mmax * 13)
+        assert np.array_equal(one.tail_len_row, lens) and one.tail_len == four.tail_len == Mmax and four.n_reff_nan == 1
+        fin = np.isfinite(one.khat)
+        assert np.all(np.isnan(four.n_eff[~live])) and np.all(np.isnan(four.mcse_elpd_loo_i[~live]))
+        assert np.all(np.isfinite(four.n_eff[live])) and np.all(np.isfinite(four.mcse_elpd_loo_i[live]))
+        dk = float(np.max(np.abs(one.khat - four.khat)[fin]))
+        de = float(np.max(np.abs(one.elpd_loo_i - four.elpd_loo_i)))
+        dn = float(np.max(np.abs(four.n_eff / one.n_eff - 1.0)[live]))
+        dm = float(np.max(np.abs(four.mcse_elpd_loo_i / one.mcse_elpd_loo_i - 1.0)[live]))
+        print("%-6s four groups - one group: khat %.3g elpd_loo_i %.3g n_eff %.3g mcse %.3g (the last two relative)"
+              % (finish, dk, de, dn, dm))
+        for k in ("n_tail", "tail_len_row", "khat", "elpd_loo_i", "n_eff", "mcse_elpd_loo_i"):
+            assert _bits_equal(one[k], four[k]), (finish, k)
+        assert dk <= lc.FINISH_KHAT and de <= lc.FINISH_ELPD and dn <= ls.FINISH_NEFF and dm <= ls.FINISH_MCSE

@@ -203,8 +203,9 @@ def test_loo_with_r_eff_matches_the_direct_restatement(fixture):
 
 
 def test_the_torch_finish_agrees_with_the_numpy_finish_on_host_tensors():
-    """`_loo_rows_mc` over torch's operations (CPU tensors here; the device route runs the same lines) against numpy's on the
-    same tails with per-row lengths: rows whose tail is shorter than the stride have dead slots, which must add nothing."""
+    """`_loo_rows` with the Monte Carlo extras over torch's operations (CPU tensors here; the device route runs the same lines)
+    against numpy's on the same tails with per-row lengths: rows whose tail is shorter than the stride have dead slots, which
+    must add nothing."""
     import torch
     from l2hmc_amd import predictive
     fixture = ls.FIXTURES[3]
@@ -214,9 +215,10 @@ def test_the_torch_finish_agrees_with_the_numpy_finish_on_host_tensors():
     assert lens.min() < lens.max()
     t = predictive.loo_tails(W, X, y, tail_len_row=lens)
     keys = ("cutoff", "n_tail", "tail", "body", "sum_lik", "body_sq")
-    a = predictive._loo_rows_mc(predictive._Numpy(), *(t[k] for k in keys), ref["r_eff"], M * N, int(lens.max()))
-    b = predictive._loo_rows_mc(predictive._Torch(), *(torch.as_tensor(t[k]) for k in keys), torch.as_tensor(ref["r_eff"]), M * N,
-                                int(lens.max()))
+    middle, S, Mmax = predictive._MIDDLES["torch"], M * N, int(lens.max())
+    a = predictive._loo_rows(predictive._Numpy(), middle, S, Mmax, *(t[k] for k in keys), ref["r_eff"])
+    b = predictive._loo_rows(predictive._Torch(), middle, S, Mmax, *(torch.as_tensor(t[k]) for k in keys), torch.as_tensor(ref["r_eff"]))
+    assert len(a) == len(b) == 5
     for u, v in zip(a, b):
         v = v.numpy()
         assert np.all(np.isfinite(v)) and np.max(np.abs(v / u - 1.0)) <= 1e-10
@@ -338,3 +340,41 @@ def test_new_kernels_use_no_scratch_and_keep_their_occupancy():
     asm = open(os.path.join(kr.ASM, "lik_stats.s")).read()
     lds = [int(v) for v in re.findall(r"\.amdhsa_group_segment_fixed_size (\d+)", asm)]
     assert len(lds) >= 9 and max(lds) <= 4 * 8448, lds
+
+
+@pytest.mark.parametrize("tensors", (False, True))
+def test_loo_finish_of_loo_tails_is_loo_field_for_field(tensors):
+    """`loo_finish(loo_tails(...))` and `loo(...)` give the same Summary, every field bit for bit, without `r_eff` and with one
+    (per-row lengths that differ, one NaN efficiency), on numpy and on CPU tensors."""
+    import torch
+    from l2hmc_amd import predictive
+    W, X, y = ls.ar1_case(40, 5, 3, 0.5)
+    S, n = 200, X.shape[0]
+    r = 0.2 + 1.8 * np.random.RandomState(5).rand(n)
+    r[4] = np.nan
+    lens = predictive.tail_len_rows(r, S)
+    assert lens.min() < lens.max()
+    if tensors:
+        W, X, y = (torch.as_tensor(a) for a in (W, X, y))
+    for kw, tail_kw in (({}, {}), ({"r_eff": r}, {"tail_len_row": lens})):
+        one = predictive.loo(W, X, y, **kw)
+        two = predictive.loo_finish(predictive.loo_tails(W, X, y, **tail_kw), **kw)
+        assert set(one) == set(two) and ("n_eff" in one) == bool(kw)
+        for k in one:
+            a, b = np.asarray(one[k]), np.asarray(two[k])
+            assert a.dtype == b.dtype and np.array_equal(a, b, equal_nan=True), k
+        assert one.n_rows == n and one.n_draws == S and np.all(np.isfinite(one.elpd_loo_i))
+    assert one.n_reff_nan == 1 and np.array_equal(one.tail_len_row, lens) and np.isnan(one.n_eff[4])
+
+
+def test_labels_outside_0_and_1_are_refused_on_host_input():
+    """One refusal, one text, from every host route that reads the labels."""
+    import torch
+    from l2hmc_amd import predictive
+    W, X, y = ls.ar1_case(40, 5, 2, 0.5)
+    bad = y.copy()
+    bad[2] = 0.5
+    for conv in (np.asarray, torch.as_tensor):
+        for call in (predictive.pointwise_sums, predictive.loo_tails, predictive.relative_eff):
+            with pytest.raises(ValueError, match=r"^labels y must be 0 or 1$"):
+                call(conv(W), conv(X), conv(bad))

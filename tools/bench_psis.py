@@ -24,7 +24,7 @@ import numpy as np
 import torch
 
 from bench_loo import fmt, make_case, measure
-from l2hmc_amd import _ffi, predictive
+from l2hmc_amd import _ffi, _pareto, predictive
 
 
 def main():
@@ -41,7 +41,7 @@ def main():
         M = predictive.loo_tail_len(S)
         print("draws (%d, %d) = %.0f MB, n = %d rows, tail_len M = %d" % (S, d, W.numel() * 4 / 1e6, n, M))
         tails = predictive.loo_tails(W, X, y)
-        xp = predictive._Torch()
+        xp = _pareto._Torch()
         _, _, lam_c, lam = predictive._loo_prepare(xp, tails["cutoff"], tails["n_tail"], tails["tail"])
         lam, lam_c, n_tail = lam.contiguous(), lam_c.contiguous(), tails["n_tail"].contiguous()
         ws = torch.empty(_ffi.check(L.l2hmc_psis_workspace_bytes(n, M)), dtype=torch.uint8, device="cuda")

@@ -4,7 +4,7 @@
     python tools/psis_accuracy.py [--no-gpu]
 
 CPU part (always): two float64 host references against each other -- the module's numpy path (`predictive.loo_finish`,
-`psis.loo_from_log_lik`: `predictive._psis_rows`) and the row-at-a-time restatement of tests/psis_case.py; they differ in
+`psis.loo_from_log_lik`: `_pareto._psis_rows`) and the row-at-a-time restatement of tests/psis_case.py; they differ in
 summation order and in how x is formed.  Per tested tail length M, over the five k_true x three seeds and tails shorter than
 M, the worst disagreement of khat and of elpd_loo_i; the matrices and histories the GPU tests use are measured the same way and
 count towards their M.  `MEASURED` in tests/psis_case.py holds these figures; the gate at M is 100 x the worst at any length up to M, capped at 1e-9.

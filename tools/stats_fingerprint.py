@@ -8,7 +8,7 @@ versions of `l2hmc_amd/*.py` on ONE build of the library (`L2HMC_LIB=`): a host-
     python tools/stats_fingerprint.py --cpu                 # the host inputs only
     python tools/stats_fingerprint.py --kernels             # the device kernels that share csrc/draw_tiles.hpp and radix_select.hpp
     python tools/stats_fingerprint.py --ranks 2 --backend gloo|nccl --input numpy|device      # chains sharded 2 | 4
-    python tools/stats_fingerprint.py --time                # median host time of `describe` on the tiny device history
+    python tools/stats_fingerprint.py --time                # median host time of `describe` and `loo(r_eff=)` on the tiny device history
 
 The history is a seeded AR(1) of 40 steps, 6 chains and 3 coordinates whose means and scales differ per coordinate.  `--kernels`
 runs ONE version of the Python against two builds of the library instead: `pointwise_sums`, `loo_tails` and `order_statistics`
@@ -25,12 +25,13 @@ sys.path.insert(0, ROOT)
 import numpy as np
 import torch
 
-from l2hmc_amd import diagnostics, func_utils, multivariate, predictive, quantiles, sharding
+from l2hmc_amd import diagnostics, func_utils, multivariate, predictive, psis, quantiles, sharding
 
 STEPS, CHAINS, DIM, ROWS, SCALE = 40, 6, 3, 5, 1.7
 SPLIT = 2                                 # --ranks 2: rank 0 holds chains [0, 2), rank 1 chains [2, 6)
 RANKS33 = np.arange(33) * 7               # 33 ranks: two chunks of at most 32
 PROBS = (0.1, 0.5, 0.9)
+R_EFF = np.array([0.3, 0.5, 1.0, np.nan, 2.0])   # per-row tail lengths 48, 48, 47, 47, 33 of the 240 draws; one NaN
 # (S, n, d) of tests/loo_case.case, the smallest shapes that reach every branch of the shared tile loop: 1, 2, 4, 8 compiled
 # feature tiles; two row groups of the predict plan at four blocks per wave; five tiles per chunk with a last tile of 9 draws, a
 # last chunk of one tile and dead waves; no tail at all (M = 0)
@@ -86,6 +87,55 @@ def cases(X):
     yield "log_predictive_density", lambda: predictive.log_predictive_density(X, rx, ry)
     yield "loo", lambda: predictive.loo(X, rx, ry)
     yield "acl_spectrum", lambda: func_utils.acl_spectrum(X, SCALE)
+    yield from loo_cases(X, rx, ry)
+
+
+def loo_cases(X, rx, ry):
+    """Every host route of `relative_eff`, `loo(r_eff=)`, `loo_tails`, `loo_finish` and the `psis` module on the same history;
+    the kernel finish and the row groups only where the history lies on a device."""
+    on_device = torch.is_tensor(X) and X.is_cuda
+    like = (lambda a: torch.as_tensor(a).to(X.device)) if torch.is_tensor(X) else (lambda a: a)
+    for split in (False, True):
+        for lag in (5, None):
+            yield ("relative_eff split=%d max_lag=%s" % (split, lag),
+                   lambda s=split, g=lag: predictive.relative_eff(X, rx, ry, max_lag=g, split=s))
+    lens = predictive.tail_len_rows(R_EFF, STEPS * CHAINS)
+    assert lens.tolist() == [48, 48, 47, 47, 33]
+
+    def tails(per_row):
+        t = predictive.loo_tails(X, rx, ry, tail_len_row=lens if per_row else None)
+        if torch.is_tensor(t["tail"]):
+            t["tail"] = torch.sort(t["tail"], dim=-1).values                        # its slot order is arrival order
+        return t
+
+    finishes = ("torch", "kernel") if on_device else ("torch",)
+    yield "loo r_eff=auto", lambda: predictive.loo(X, rx, ry, r_eff="auto")
+    yield "loo_tails", lambda: tails(False)
+    yield "loo_tails tail_len_row", lambda: tails(True)
+    for f in finishes:
+        yield "loo r_eff=array finish=%s" % f, lambda f=f: predictive.loo(X, rx, ry, r_eff=R_EFF, finish=f)
+        yield "loo_finish finish=%s" % f, lambda f=f: predictive.loo_finish(tails(False), finish=f)
+        yield "loo_finish r_eff finish=%s" % f, lambda f=f: predictive.loo_finish(tails(True), finish=f, r_eff=R_EFF)
+    if on_device:
+        small = 4 * 48 * 2                                    # two rows per group: three groups
+        yield "loo finish=kernel", lambda: predictive.loo(X, rx, ry, finish="kernel")
+        for f in finishes:
+            yield "loo 3 groups finish=%s" % f, lambda f=f: predictive.loo(X, rx, ry, max_tail_bytes=small, finish=f)
+            yield ("loo r_eff=array 3 groups finish=%s" % f,
+                   lambda f=f: predictive.loo(X, rx, ry, max_tail_bytes=small, finish=f, r_eff=R_EFF))
+    W = (X.detach().cpu().numpy() if torch.is_tensor(X) else X).astype(np.float64).reshape(STEPS * CHAINS, DIM)
+    ll = -np.logaddexp(0.0, -(W @ rx.T) * (2.0 * ry - 1.0))   # the (240, 5) pointwise log-likelihood matrix
+    M = predictive.loo_tail_len(STEPS * CHAINS)
+    top = -np.sort(ll, axis=0)[:M + 1]                        # the M + 1 largest ratios -ll of every column, descending
+    lam, cutoff = np.ascontiguousarray(top[:M].T), top[M].copy()
+    n_tail = (top[:M] > cutoff[None, :]).sum(axis=0).astype(np.int64)
+    yield "psis.psis", lambda: psis.psis(like(-ll))
+    yield "psis.psis 1-d", lambda: psis.psis(like(-ll[:, 0].copy()))
+    yield "psis.psis weights=False", lambda: psis.psis(like(-ll), weights=False)
+    yield "psis.loo_from_log_lik float32", lambda: psis.loo_from_log_lik(like(ll.astype(np.float32)))
+    yield "psis.loo_from_log_lik float64", lambda: psis.loo_from_log_lik(like(ll))
+    for w in (False, True):
+        yield "psis.smooth_tails weights=%d" % w, lambda w=w: psis.smooth_tails(like(lam), like(n_tail), like(cutoff), weights=w)
 
 
 def kernels():
@@ -183,16 +233,19 @@ def sharded(world, backend, on_device):
 
 
 def timed():
-    """The host side of a call is all there is to time on a history this small: median of 200 synchronised `describe`."""
+    """The host side of a call is all there is to time on a history this small: median of 200 synchronised `describe`, then of
+    200 synchronised `loo(r_eff=array)`."""
     torch.cuda.set_device(0)
     X = torch.as_tensor(history().astype(np.float32)).cuda()
-    t = []
-    for i in range(220):
-        t0 = time.perf_counter()
-        quantiles.describe(X)
-        torch.cuda.synchronize()
-        t.append(time.perf_counter() - t0)
-    print("describe (40, 6, 3) on the device: median %.1f us over 200 calls after 20" % (1e6 * float(np.median(t[20:]))), flush=True)
+    rx, ry = rows()
+    for name, call in (("describe", lambda: quantiles.describe(X)), ("loo r_eff=array", lambda: predictive.loo(X, rx, ry, r_eff=R_EFF))):
+        t = []
+        for i in range(220):
+            t0 = time.perf_counter()
+            call()
+            torch.cuda.synchronize()
+            t.append(time.perf_counter() - t0)
+        print("%s (40, 6, 3) on the device: median %.1f us over 200 calls after 20" % (name, 1e6 * float(np.median(t[20:]))), flush=True)
 
 
 def main():
