@@ -6,6 +6,11 @@ through `l2hmc_amd.loo_from_log_lik`: `torch.topk` finds every row's largest imp
 csrc/psis.hip fit the generalised Pareto tails and smooth the weights, and the Pareto k-hat says per row whether the estimate
 can be trusted.  A second feature set is compared by elpd_loo.
 
+The draws are Markov chains: the same matrix in its history form (steps, chains, rows) goes through
+`loo_from_log_lik(..., r_eff="auto", select="fused")` as well -- `relative_eff_from_log_lik` gives every row's relative
+efficiency, the fused selection of csrc/loglik_tails.hip cuts every row's tail at its own length, and the result also says how
+many effective draws stand behind each elpd_loo_i and how uncertain elpd_loo is by Monte Carlo (`mcse_elpd_loo`).
+
 The same kernels give any importance weights their diagnostic: the log weights of `ais_estimate` (the `'w'` of its returned
 state) go through `l2hmc_amd.psis.psis`, which returns their khat and effective sample size.
 
@@ -62,7 +67,8 @@ def main():
         x0 = torch.as_tensor((0.1 * rng.randn(args.chains, k)).astype(np.float32), device=dev)
         _, p, hist = sample_chain(x0, dyn, args.steps, seed=args.seed + 1, record=True)
         W = hist[args.steps // 2:].reshape(-1, k)                        # the first half is burn-in
-        s = loo_from_log_lik(poisson_log_lik(W, feats, y))
+        ll = poisson_log_lik(W, feats, y)
+        s = loo_from_log_lik(ll)
         results[name] = s
         print("%-26s accept %.2f  draws %d  elpd_loo %9.3f (se %.3f)  p_loo %6.3f  lppd %9.3f" % (
             name, float(p.mean()), s.n_draws, s.elpd_loo, s.se, s.p_loo, s.lppd))
@@ -70,6 +76,11 @@ def main():
         print("%-26s khat: max %.3f, rows above 0.7: %d, above %.3f: %d;  the three largest: %s" % (
             "", float(s.khat.max()), s.n_bad, s.khat_threshold, s.n_above_threshold,
             ", ".join("row %d khat %.3f (y = %d, elpd_loo_i %.3f)" % (i, s.khat[i], int(y[i]), s.elpd_loo_i[i]) for i in worst)))
+        m = loo_from_log_lik(ll.reshape(-1, args.chains, n), r_eff="auto", select="fused")     # the chains, not independent draws
+        print("%-26s r_eff=\"auto\": r_eff %.3f .. %.3f, tail lengths %d .. %d (independent draws: %d), elpd_loo %9.3f, "
+              "min n_eff %.0f, mcse_elpd_loo %.4f, khat max %.3f" % (
+                  "", float(np.nanmin(m.r_eff)), float(np.nanmax(m.r_eff)), int(m.tail_len_row.min()), int(m.tail_len_row.max()),
+                  s.tail_len, m.elpd_loo, m.min_n_eff, m.mcse_elpd_loo, float(m.khat.max())))
     a, b = results.values()
     diff = a.elpd_loo_i - b.elpd_loo_i
     print("elpd_loo difference (all - two): %.3f, se of the difference %.3f" % (diff.sum(), np.sqrt(n * diff.var(ddof=1))))

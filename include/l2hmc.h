@@ -681,6 +681,16 @@ int l2hmc_chain_stats_below(const float* X, int64_t steps, int64_t n_chains, int
                             const double* thresholds /* (d), device */, double* mean_out, double* m2_out, double* G_out,
                             double* workspace, void* stream);
 
+/* The same sums for the series y = (float) exp((double) x - shift[k]) of every coordinate k, formed as the value is loaded (no
+ * second history is written): the likelihoods of a log-likelihood history, whose effective sample size over the number of draws
+ * is the relative efficiency of PSIS-LOO (l2hmc_amd/psis.py `relative_eff_from_log_lik`).  `shift`: d float64 on the device,
+ * usually the coordinate's maximum -- the effective sample size does not move with it, it only keeps e^x inside float32.  The
+ * exponential is the double-precision one, rounded to float32 once.  The contract, the argument checks and the workspace size
+ * are those of l2hmc_chain_stats; a NaN value or shift makes the sums of its own coordinate NaN. */
+int l2hmc_chain_stats_exp(const float* X, int64_t steps, int64_t n_chains, int32_t d, int32_t max_lag, int32_t split,
+                          const double* shift /* (d), device */, double* mean_out, double* m2_out, double* G_out,
+                          double* workspace, void* stream);
+
 /* Exact order statistics of every coordinate of a history kept on the device (csrc/order_stats.hip; l2hmc_amd/quantiles.py
  * builds quantiles, tail-ESS and the quantile MCSE on them).
  *   X       (n_draws, d) float32, contiguous, read in place: element (i, k) at X[i d + k] -- a recorded history (M, N, d) with
@@ -777,6 +787,44 @@ int l2hmc_logistic_loo_tails_mc(const float* draws, int64_t n_draws, int32_t d, 
                                 const int64_t* tail_len_row /* (n_data) */, int64_t tail_stride, float* cutoff /* (n_data) */,
                                 int64_t* n_tail /* (n_data) */, float* tail /* (n_data, tail_stride) */,
                                 double* sums /* (3, n_data): body, sum_lik, body_sq */, void* workspace, void* stream);
+
+/* PSIS of ANY likelihood: the per-column raw material of Pareto-smoothed importance sampling of a pointwise log-likelihood
+ * matrix (csrc/loglik_tails.hip; l2hmc_amd/psis.py `loo_from_log_lik(select="fused")` and `psis(select="fused")` finish it on
+ * l2hmc_psis_smooth).  The log importance ratio of column i under draw s is -ll[s, i]: the largest ratios are the smallest ll.
+ *   ll            (n_draws, n_cols) float32, row-major and contiguous on the device, read in place; n_cols in 1 .. 512.
+ *   tail_len_col  (n_cols) int64 on the device: the tail length M_i of every column, 0 <= M_i <= tail_stride (an entry outside
+ *                 is clamped); NULL = l2hmc_logistic_loo_tail_len(n_draws) for all (clamped to tail_stride as well).
+ *   cutoff  (n_cols) float32: the element of ascending rank M_i of column i, in the total order of the monotone key of
+ *           l2hmc_order_stats (-0 before +0, every NaN after +inf).
+ *   top     (n_cols) float32: the element of rank n_draws - 1, the column's maximum; NaN when the column holds a NaN.
+ *   n_tail  (n_cols) int64: L_i = the number of ll strictly before the cutoff in that order, L_i <= M_i (ties shorten it).
+ *   tail    (n_cols, tail_stride) float32: those L_i values in ANY order in slots 0 .. L_i - 1, +inf in the other slots (may be
+ *           NULL when tail_stride = 0).
+ *   tail_pos  the same shape, int64, or NULL: the draw s every tail value came from, -1 in the other slots.
+ *   sums    (3, n_cols) float64, with c = cutoff and every term formed in float64 from the exact float32 values (the difference,
+ *           then the double-precision exp, one call per term):
+ *             [0] body = the sum over the draws NOT in the tail of e^(c - ll)   (every term in (0, 1])
+ *             [1] body_sq = the same sum of e^(2 (c - ll))      [2] lik = the sum over all draws of e^(ll - top)
+ *           so that the summed ratios of the body are e^(-c) body, their squares e^(-2 c) body_sq, and lppd = log lik + top - log S.
+ * Both ranks of every column are found by l2hmc_order_stats (one call, two ranks) and one more pass over the matrix gathers.
+ * `workspace`: l2hmc_loglik_tails_workspace_bytes(...) bytes, 16-byte aligned, required: error word | ranks | values | the
+ * select's workspace | one partial per (segment of draws, sum, column), which a last kernel adds in segment order.  The draws are
+ * cut into segments by n_draws alone and there are no floating-point atomics: every output (the tail as a set of (value, draw)
+ * pairs) is bitwise reproducible, and a column gives the same bits whichever other columns share the call.  The first int64 of the
+ * workspace is non-zero after the call if a tail slot at or past M_i was asked for (never while the select and the gather agree;
+ * the value is then not written and n_tail counts it).
+ * A column whose cutoff is not finite: c = -inf (more than M_i draws at -inf) has an empty tail and body = body_sq = NaN;
+ * c = +inf has NaN there as well; c = NaN (fewer than M_i + 1 numbers in the column) gathers every number and has three NaN
+ * sums.  The finished numbers are then NaN or infinite exactly where those of the `torch.topk` route of psis.py are.
+ * L2HMC_ERR_ARG (before any launch): n_draws < 2, n_cols outside 1 .. 512, n_draws > 2^40 / n_cols, tail_stride outside
+ * 0 .. n_draws - 1, tail_stride n_cols > 2^31, a NULL required pointer, ll / cutoff / top / tail not 4-byte, n_tail / tail_pos /
+ * tail_len_col / sums not 8-byte, workspace not 16-byte aligned. */
+int64_t l2hmc_loglik_tails_workspace_bytes(int64_t n_draws, int32_t n_cols);
+int l2hmc_loglik_tails(const float* ll, int64_t n_draws, int32_t n_cols,
+                       const int64_t* tail_len_col /* (n_cols) device, or NULL = loo_tail_len(n_draws) for all */,
+                       int64_t tail_stride, float* cutoff, float* top, int64_t* n_tail,
+                       float* tail /* (n_cols, tail_stride) */, int64_t* tail_pos /* same shape, or NULL */,
+                       double* sums /* (3, n_cols) */, void* workspace, void* stream);
 
 /* Bayesian logistic regression: the raw sums behind the per-row relative efficiency of PSIS-LOO, r_eff_i = ESS(p(y_i | theta)) / S
  * (Vehtari, Gelman, Gabry 2017; csrc/lik_stats.hip; l2hmc_amd/predictive.py `relative_eff`).  `draws` is a recorded history

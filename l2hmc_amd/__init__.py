@@ -15,12 +15,12 @@ from .training import LogisticTrainer  # noqa: F401
 from .diagnostics import summarize  # noqa: F401
 from .predictive import loo, relative_eff, waic  # noqa: F401
 from . import psis  # noqa: F401
-from .psis import loo_from_log_lik  # noqa: F401
+from .psis import loo_from_log_lik, relative_eff_from_log_lik  # noqa: F401
 from .quantiles import describe  # noqa: F401
 from .multivariate import covariance, multi_ess  # noqa: F401
 from .warmup import warmup  # noqa: F401  (the function; its module stays importable as `from l2hmc_amd.warmup import ...`)
 
 __all__ = ["Dynamics", "propose", "tf_accept", "chain_operator", "sample_chain", "ParallelTempering", "geometric_ladder",
-           "LogisticRegression", "LogisticTrainer", "summarize", "diagnostics", "warmup", "predictive", "waic", "loo", "relative_eff", "psis", "loo_from_log_lik", "quantiles", "describe",
+           "LogisticRegression", "LogisticTrainer", "summarize", "diagnostics", "warmup", "predictive", "waic", "loo", "relative_eff", "psis", "loo_from_log_lik", "relative_eff_from_log_lik", "quantiles", "describe",
            "multivariate", "covariance", "multi_ess",
            "layers", "distributions", "func_utils", "losses", "tempering"]

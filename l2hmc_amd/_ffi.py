@@ -174,6 +174,8 @@ SYMBOLS = {
     "l2hmc_chain_stats": (C.c_int, [_fp, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _fp, _fp, _fp, _fp, _fp]),
     "l2hmc_chain_stats_below": (C.c_int, [_fp, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _fp, _fp, _fp, _fp, _fp,
                                           _fp]),
+    "l2hmc_chain_stats_exp": (C.c_int, [_fp, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _fp, _fp, _fp, _fp, _fp,
+                                        _fp]),
     "l2hmc_order_stats_passes": (C.c_int32, []),
     "l2hmc_order_stats_bins": (C.c_int32, []),
     "l2hmc_order_stats_workspace_bytes": (C.c_int64, [C.c_int32, C.c_int32]),
@@ -190,6 +192,8 @@ SYMBOLS = {
     "l2hmc_logistic_loo_mc_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
     "l2hmc_logistic_loo_tails_mc": (C.c_int, [_fp, C.c_int64, C.c_int32, _fp, C.c_int32, _fp, C.c_int64, _fp, _fp, _fp, _fp, _fp,
                                               _fp]),
+    "l2hmc_loglik_tails_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int32]),
+    "l2hmc_loglik_tails": (C.c_int, [_fp, C.c_int64, C.c_int32, _fp, C.c_int64, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
     "l2hmc_logistic_lik_stats_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "l2hmc_logistic_lik_stats": (C.c_int, [_fp, C.c_int64, C.c_int64, C.c_int32, _fp, C.c_int32, C.c_int32, C.c_int32, _fp, _fp,
                                            _fp, _fp, _fp]),

@@ -26,6 +26,12 @@
 // l2hmc_chain_stats_below: the same three passes on the indicator series y = [x <= thresholds[coordinate]] (the effective sample
 // size of a quantile estimate, l2hmc_amd/quantiles.py).  The device functions take the transform as a functor (CsValue, CsBelow);
 // chain_moments_below_kernel and chain_lagsum_below_kernel are kernels of their own, pass 3 is shared as it is.
+//
+// l2hmc_chain_stats_exp: a third functor, CsExp -- the series y = (float) exp((double) x - shift[coordinate]), the likelihoods
+// of a log-likelihood history (l2hmc_amd/psis.py `relative_eff_from_log_lik`; the shift, the column's maximum, only keeps e^x
+// inside float32: the effective sample size does not move with it).  The double `exp` is evaluated as the value is loaded,
+// once per pass and lag tile: chain_moments_exp_kernel and chain_lagsum_exp_kernel, pass 3 shared again.
+#include <math.h>
 #include "l2hmc_kernels.hpp"
 
 namespace l2hmc {
@@ -87,6 +93,10 @@ struct CsBelow {
   double thr;
   __device__ __forceinline__ float operator()(float v) const { return (double)v <= thr ? 1.f : 0.f; }
 };
+struct CsExp {
+  double shift;
+  __device__ __forceinline__ float operator()(float v) const { return (float)exp((double)v - shift); }
+};
 
 // ---- pass 1 ---------------------------------------------------------------------------------------------------------------
 template <class F>
@@ -134,6 +144,15 @@ __global__ __launch_bounds__(kCsThreads) void chain_moments_below_kernel(const f
   const long long j = (long long)blockIdx.x * kCsThreads + threadIdx.x;
   if (j >= J) return;
   cs_moments(X, J, Mh, row1, j, mean_out, m2_out, CsBelow{thresholds[j % d]});
+}
+
+__global__ __launch_bounds__(kCsThreads) void chain_moments_exp_kernel(const float* __restrict__ X, long long J, long long Mh,
+                                                                       long long row1, int d, const double* __restrict__ shift,
+                                                                       double* __restrict__ mean_out,
+                                                                       double* __restrict__ m2_out) {
+  const long long j = (long long)blockIdx.x * kCsThreads + threadIdx.x;
+  if (j >= J) return;
+  cs_moments(X, J, Mh, row1, j, mean_out, m2_out, CsExp{shift[j % d]});
 }
 
 // ---- pass 2 ---------------------------------------------------------------------------------------------------------------
@@ -184,8 +203,9 @@ __device__ __forceinline__ void cs_series(const float* __restrict__ X, long long
   }
 }
 
-// kBelow: the series are indicators of "at or below thresholds[coordinate]" (a thread's coordinate never changes across chunks)
-template <bool kBelow>
+// kSeries 1: the series are indicators of "at or below thresholds[coordinate]" (a thread's coordinate never changes across
+// chunks); 2: they are exp(x - thresholds[coordinate]), the argument then being the shift; 0: the values themselves
+template <int kSeries>
 __device__ __forceinline__ void cs_lagsum(const float* __restrict__ X, long long J, long long Mh, long long row1, int d, int nslot,
                                           long long nchunks, int max_lag, const double* __restrict__ mean,
                                           const double* __restrict__ thresholds, double* __restrict__ part) {
@@ -206,8 +226,12 @@ __device__ __forceinline__ void cs_lagsum(const float* __restrict__ X, long long
     // out of this loop and held in ~100 vector registers across it.  They cost a scalar compare each: recompute them per chunk.
     long long mh = Mh;
     asm volatile("" : "+s"(mh));
-    if constexpr (kBelow) {
+    if constexpr (kSeries == 1) {
       const CsBelow f{thresholds[j % d]};
+      if (tau0 == 0) cs_series<true>(base, j, J, tau0, mh, m, dacc, f);
+      else cs_series<false>(base, j, J, tau0, mh, m, dacc, f);
+    } else if constexpr (kSeries == 2) {
+      const CsExp f{thresholds[j % d]};
       if (tau0 == 0) cs_series<true>(base, j, J, tau0, mh, m, dacc, f);
       else cs_series<false>(base, j, J, tau0, mh, m, dacc, f);
     } else {
@@ -239,7 +263,7 @@ __global__ __launch_bounds__(kCsThreads) void chain_lagsum_kernel(const float* _
                                                                   long long row1, int d, int nslot, long long nchunks,
                                                                   int max_lag, const double* __restrict__ mean,
                                                                   double* __restrict__ part) {
-  cs_lagsum<false>(X, J, Mh, row1, d, nslot, nchunks, max_lag, mean, nullptr, part);
+  cs_lagsum<0>(X, J, Mh, row1, d, nslot, nchunks, max_lag, mean, nullptr, part);
 }
 
 __global__ __launch_bounds__(kCsThreads) void chain_lagsum_below_kernel(const float* __restrict__ X, long long J, long long Mh,
@@ -247,7 +271,15 @@ __global__ __launch_bounds__(kCsThreads) void chain_lagsum_below_kernel(const fl
                                                                         int max_lag, const double* __restrict__ mean,
                                                                         const double* __restrict__ thresholds,
                                                                         double* __restrict__ part) {
-  cs_lagsum<true>(X, J, Mh, row1, d, nslot, nchunks, max_lag, mean, thresholds, part);
+  cs_lagsum<1>(X, J, Mh, row1, d, nslot, nchunks, max_lag, mean, thresholds, part);
+}
+
+__global__ __launch_bounds__(kCsThreads) void chain_lagsum_exp_kernel(const float* __restrict__ X, long long J, long long Mh,
+                                                                      long long row1, int d, int nslot, long long nchunks,
+                                                                      int max_lag, const double* __restrict__ mean,
+                                                                      const double* __restrict__ shift,
+                                                                      double* __restrict__ part) {
+  cs_lagsum<2>(X, J, Mh, row1, d, nslot, nchunks, max_lag, mean, shift, part);
 }
 
 // ---- pass 3 ---------------------------------------------------------------------------------------------------------------
@@ -313,6 +345,27 @@ int l2hmc_chain_stats_below(const float* X, int64_t steps, int64_t n_chains, int
                      p.Mh, p.row0[1], (int)d, thresholds, mean_out, m2_out);
   hipLaunchKernelGGL(chain_lagsum_below_kernel, dim3((unsigned)p.nb, (unsigned)p.ntile, (unsigned)p.halves), dim3(kCsThreads), 0,
                      s, X, p.J, p.Mh, p.row0[1], (int)d, p.nslot, p.nchunks, (int)max_lag, (const double*)mean_out, thresholds,
+                     workspace);
+  hipLaunchKernelGGL(chain_lagsum_reduce_kernel, dim3((unsigned)((d * nlag + 255) / 256)), dim3(256), 0, s,
+                     (const double*)workspace, p.nb * p.halves, p.nb, (int)d, p.nslot, nlag, G_out);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(L2HMC_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
+  return L2HMC_OK;
+}
+
+int l2hmc_chain_stats_exp(const float* X, int64_t steps, int64_t n_chains, int32_t d, int32_t max_lag, int32_t split,
+                          const double* shift, double* mean_out, double* m2_out, double* G_out, double* workspace,
+                          void* stream) {
+  ChainStatsPlan p;
+  if (!chain_stats_plan("l2hmc_chain_stats_exp", steps, n_chains, d, max_lag, split, p)) return L2HMC_ERR_ARG;
+  if (!X || !shift || !mean_out || !m2_out || !G_out || !workspace)
+    return fail(L2HMC_ERR_ARG, "l2hmc_chain_stats_exp: X, shift, mean_out, m2_out, G_out and workspace are required%s");
+  hipStream_t s = (hipStream_t)stream;
+  const long long nlag = (long long)max_lag + 1;
+  hipLaunchKernelGGL(chain_moments_exp_kernel, dim3((unsigned)p.nchunks, (unsigned)p.halves), dim3(kCsThreads), 0, s, X, p.J,
+                     p.Mh, p.row0[1], (int)d, shift, mean_out, m2_out);
+  hipLaunchKernelGGL(chain_lagsum_exp_kernel, dim3((unsigned)p.nb, (unsigned)p.ntile, (unsigned)p.halves), dim3(kCsThreads), 0,
+                     s, X, p.J, p.Mh, p.row0[1], (int)d, p.nslot, p.nchunks, (int)max_lag, (const double*)mean_out, shift,
                      workspace);
   hipLaunchKernelGGL(chain_lagsum_reduce_kernel, dim3((unsigned)((d * nlag + 255) / 256)), dim3(256), 0, s,
                      (const double*)workspace, p.nb * p.halves, p.nb, (int)d, p.nslot, nlag, G_out);

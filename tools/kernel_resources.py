@@ -6,7 +6,9 @@
 
 Round 6's rule: after every change of arithmetic look at `.amdhsa_private_segment_fixed_size` -- the f16x2
 commit doubled the fragment registers and the two-tiles-per-wave kernels spilled 220-630 bytes per lane inside their step loops for
-half a round.  `resources()` is also what tests/test_abi_cpu.py::test_hot_kernels_do_not_spill reads."""
+half a round.  `resources()` is also what tests/test_abi_cpu.py::test_hot_kernels_do_not_spill reads, and the per-unit tests
+of the statistics kernels (tests/test_loo_cpu.py, tests/test_loglik_cpu.py: `loglik_init_kernel` and `loglik_gather_kernel` of
+loglik_tails.s, `chain_moments_exp_kernel` and `chain_lagsum_exp_kernel` of chain_stats.s)."""
 import glob
 import os
 import re
