@@ -850,6 +850,58 @@ int l2hmc_logistic_lik_stats(const float* draws, int64_t steps, int64_t n_chains
                              int32_t max_lag, int32_t split, double* mean /* (C, n_data) */, double* m2 /* (C, n_data) */,
                              double* G /* (n_data, max_lag + 1) */, void* workspace, void* stream);
 
+/* Generalised linear models: the pointwise log-likelihood matrix, the raw material of PSIS-LOO and the sums behind the posterior
+ * predictive mean and WAIC over every recorded draw (csrc/glm.hip, the family in csrc/glm_family.hpp; l2hmc_amd/glm.py and
+ * `PoissonRegression` turn them into numbers).  Additive to ABI 6.  Common arguments:
+ *   draws       (n_draws, d) float32 row-major on the device, read in place (a first-axis slice of a history: 4-byte alignment).
+ *   packed      the buffer l2hmc_pack_logistic wrote for (X, y) with the same d, the responses y in the label slot (counts up
+ *               to 2^24 are exact in float32), 16-byte aligned.
+ *   row_consts  (3, n_data) float32 on the device, contiguous: [0] the offset o_i (log exposure), [1] g_i = lgamma(y_i + 1)
+ *               formed in float64 and rounded once, [2] the saturated log-likelihood sat_i = y log y - y - lgamma(y + 1) (0 at
+ *               y = 0), the supremum of ll over eta.
+ *   family      L2HMC_GLM_POISSON: with eta = x_i . w_s (float32, f32-input MFMA), h = eta + o_i and mu = exp(h) (hardware
+ *               exp2), ll = fma(y_i, h, -mu) - g_i, four float32 roundings.  Any other value is L2HMC_ERR_ARG.
+ * Every kernel forms ll by the one device function of the family: the bits of ll[s, i] depend on (draws, X, y, row_consts)
+ * alone -- not on the entry, the pass, the chunk or the rows that share a call.
+ *
+ * l2hmc_glm_log_lik writes out (n_draws, n_data) float32 row-major, out[s n_data + i] = ll[s, i]: the very values the two
+ * fused entries work on.  The slow route (the caller forms it in row groups), and the feed of l2hmc_loglik_tails and
+ * l2hmc_chain_stats_exp.  Also L2HMC_ERR_ARG: n_draws n_data > 2^40.
+ *
+ * l2hmc_glm_predict: sums (4, n_data) float64 over the draws: [0] sum mu   [1] sum exp((double) ll - sat_i), one double-precision
+ * exp per term, every term in (0, 1] up to the rounding of sat_i, so that lppd_i = log(sums[1] / n_draws) + sat_i and no pass
+ * looks for a shift   [2] sum ll   [3] sum ll^2 (formed and added in float64).  `workspace`:
+ * l2hmc_glm_predict_workspace_doubles(...) doubles, required; the waves' partials are added in chunk order: no floating-point
+ * atomics, two calls give identical bits.
+ *
+ * l2hmc_glm_loo_tails: the outputs of l2hmc_loglik_tails (cutoff, top, n_tail, tail with +inf pads, sums (3, n_data) = body,
+ * body_sq, lik; no tail_pos) of the matrix l2hmc_glm_log_lik would write, which is never formed: four fused count passes of a
+ * radix select on the keys of ll (pass 0 also takes the row's largest key with an integer atomic maximum), then one gather.
+ * tail_len_row (n_data) int64 on the device or NULL (= l2hmc_logistic_loo_tail_len(n_draws) for all), clamped to
+ * 0 .. tail_stride; `tail` is (n_data, tail_stride).  Every term of the sums is the double-precision exp of the exact difference
+ * of two float32 values, one call per term: the per-term bound and the table of non-finite cutoffs of l2hmc_loglik_tails hold.
+ * cutoff, top, n_tail, the tail as a set AND the three sums equal those of l2hmc_loglik_tails on the written matrix bit for
+ * bit: the terms are added in that entry's order (segments of max(64, ceil(n_draws / 2048)) consecutive draws, each in draw
+ * order, then the segments in order -- cut by n_draws alone, so a row's bits do not depend on the other rows of the call).
+ * `workspace`: l2hmc_glm_loo_workspace_bytes(...) bytes, 8-byte aligned, required: error word | histograms | ranks | prefixes |
+ * largest keys | partial sums; its first int64 is non-zero after the call if a tail slot at or past a row's length
+ * was asked for (never while the passes agree).
+ * L2HMC_ERR_ARG (before any launch): an unknown family, n_draws < 2, n_data outside 1 .. 1048576, d outside 1 .. 128,
+ * n_draws > 2^40 / d, tail_stride outside 0 .. n_draws - 1, tail_stride n_data > 2^31, a NULL required pointer (tail may be
+ * NULL when tail_stride = 0), draws / row_consts / cutoff / top / tail / out not 4-byte, packed not 16-byte, n_tail /
+ * tail_len_row / sums / workspace not 8-byte aligned. */
+enum { L2HMC_GLM_POISSON = 1 };
+int l2hmc_glm_log_lik(const float* draws, int64_t n_draws, int32_t d, const float* packed, const float* row_consts /* (3, n_data) */,
+                      int32_t n_data, int32_t family, float* out /* (n_draws, n_data) */, void* stream);
+int64_t l2hmc_glm_predict_workspace_doubles(int64_t n_draws, int32_t n_data, int32_t d);
+int l2hmc_glm_predict(const float* draws, int64_t n_draws, int32_t d, const float* packed, const float* row_consts, int32_t n_data,
+                      int32_t family, double* sums /* (4, n_data) */, double* workspace, void* stream);
+int64_t l2hmc_glm_loo_workspace_bytes(int64_t n_draws, int32_t n_data, int32_t d);
+int l2hmc_glm_loo_tails(const float* draws, int64_t n_draws, int32_t d, const float* packed, const float* row_consts,
+                        int32_t n_data, int32_t family, const int64_t* tail_len_row /* (n_data) device, or NULL */,
+                        int64_t tail_stride, float* cutoff, float* top, int64_t* n_tail, float* tail /* (n_data, tail_stride) */,
+                        double* sums /* (3, n_data): body, body_sq, lik */, void* workspace, void* stream);
+
 /* Pareto-smoothed importance sampling of the tails of ANY log importance ratios, float64 throughout (csrc/psis.hip;
  * l2hmc_amd/psis.py `smooth_tails`, `psis`, `loo_from_log_lik`; `predictive.loo(finish="kernel")`).  Per row i:
  *   lam         (n_rows, tail_len) the L_i = n_tail[i] <= tail_len largest log ratios, descending, in slots 0 .. L_i - 1; a slot

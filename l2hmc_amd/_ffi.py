@@ -13,6 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.abspath(os.environ["L2HMC_LIB"]) if os.environ.get("L2HMC_LIB") else os.path.join(_HERE, "csrc", "libl2hmc_hip.so")
 
 ENERGY_GAUSS_DIAG, ENERGY_GAUSS_DENSE, ENERGY_GMM, ENERGY_ROUGHWELL, ENERGY_FUNNEL = 1, 2, 3, 4, 5
+GLM_POISSON = 1           # include/l2hmc.h L2HMC_GLM_POISSON: the family of the l2hmc_glm_* entries
 ENERGY_LOGISTIC = 7       # Bayesian logistic regression (6 is vae.ENERGY_VAE, the Python-side tag of the decoder posterior)
 
 _fp = C.c_void_p  # device pointers travel as integers
@@ -197,6 +198,12 @@ SYMBOLS = {
     "l2hmc_logistic_lik_stats_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "l2hmc_logistic_lik_stats": (C.c_int, [_fp, C.c_int64, C.c_int64, C.c_int32, _fp, C.c_int32, C.c_int32, C.c_int32, _fp, _fp,
                                            _fp, _fp, _fp]),
+    "l2hmc_glm_log_lik": (C.c_int, [_fp, C.c_int64, C.c_int32, _fp, _fp, C.c_int32, C.c_int32, _fp, _fp]),
+    "l2hmc_glm_predict_workspace_doubles": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
+    "l2hmc_glm_predict": (C.c_int, [_fp, C.c_int64, C.c_int32, _fp, _fp, C.c_int32, C.c_int32, _fp, _fp, _fp]),
+    "l2hmc_glm_loo_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int32, C.c_int32]),
+    "l2hmc_glm_loo_tails": (C.c_int, [_fp, C.c_int64, C.c_int32, _fp, _fp, C.c_int32, C.c_int32, _fp, C.c_int64, _fp, _fp, _fp, _fp,
+                                      _fp, _fp, _fp]),
     "l2hmc_psis_plan": (C.c_int64, [C.c_int64, C.c_int64, C.c_int32]),
     "l2hmc_psis_workspace_bytes": (C.c_int64, [C.c_int64, C.c_int64]),
     "l2hmc_psis_smooth": (C.c_int, [_fp, _fp, _fp, C.c_int64, C.c_int64, _fp, _fp, _fp, _fp]),

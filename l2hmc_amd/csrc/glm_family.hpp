@@ -1,0 +1,38 @@
+// The likelihood of a generalised linear model, stated once for every kernel of glm.hip: a family is a struct with
+//     ll(eta, y, a, b)   the pointwise log-likelihood of a row with response y under the linear predictor eta = x_i . w_s,
+//                        a and b the row's first two constants (row_consts[0], row_consts[1])
+//     mean(eta, a)       the predictive mean
+// and an ABI number (include/l2hmc.h L2HMC_GLM_*).  The next family (binomial with trials, probit) is one more struct here and
+// one more case in glm.hip's dispatch, not another copy of three kernels.
+//
+// THE INVARIANT THE SELECT AND THE GATHER OF glm.hip RELY ON: every kernel -- the matrix writer, the four count passes, the
+// gather, the predictive sums -- computes ll by ONE device function, Family::ll, from the eta that tile_logits of draw_tiles.hpp
+// returns and from nothing else.  The function is a fixed sequence of correctly rounded float32 operations spelled out one by
+// one (__fadd_rn, fmaf, __fsub_rn and the hardware exp2 of fexp) under `fp contract(off)`: there is no bare `y * h - mu` that
+// the compiler could contract into a fused multiply-add in one instantiation and not in another.  The bits of ll_si therefore
+// depend on (W, X, y, row constants) alone -- not on the pass, the chunk, the kernel or the row grouping of the caller.  A key
+// counted in one launch is the key compared in the next, and l2hmc_glm_log_lik writes the very float32 values the fused
+// kernels select among (tests/test_gpu_glm.py holds the fused tails against the written matrix bit for bit).
+#pragma once
+#include "l2hmc_kernels.hpp"
+
+namespace l2hmc {
+
+// Poisson regression with the log link and an offset (log exposure) o_i:
+//     h = eta + o_i    mu = exp(h)    ll = y_i h - mu - g_i,   g_i = lgamma(y_i + 1) (float64 on the host, rounded once)
+// Four roundings: the sum h, the product h log2(e) inside fexp (then the hardware exp2), the fused y h - mu, the difference.
+struct PoissonLog {
+  static constexpr int kAbi = 1;          // L2HMC_GLM_POISSON
+  static __device__ __forceinline__ float ll(float eta, float y, float o, float g) {
+#pragma clang fp contract(off)
+    const float h = __fadd_rn(eta, o);
+    const float mu = fexp(h);
+    return __fsub_rn(fmaf(y, h, -mu), g);
+  }
+  static __device__ __forceinline__ float mean(float eta, float o) {
+#pragma clang fp contract(off)
+    return fexp(__fadd_rn(eta, o));
+  }
+};
+
+}  // namespace l2hmc

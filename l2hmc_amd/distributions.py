@@ -259,6 +259,96 @@ class LogisticRegression(object):
         return predictive.relative_eff(draws, self.X, self.y, max_lag=max_lag, split=split)
 
 
+class PoissonRegression(object):
+    """Bayesian Poisson regression with the log link: counts y_i ~ Poisson(exp(x_i . w + offset_i)) (offset = log exposure,
+    default 0) and a N(0, prior_var I) prior on the weights w (d <= 128 features).  The posterior's energy
+
+        U(w) = sum_i [exp(x_i . w + o_i) - y_i (x_i . w + o_i)] + |w|^2 / (2 prior_var)
+
+    is NOT fused into the trajectory kernels: `get_energy_function()` is a `UserEnergy` with the analytic gradient
+    X^T (mu - y) + w / prior_var as differentiable torch code, so sampling, `warmup` and the GEMM-engine `Trainer` run on the
+    slow path.  Everything computed FROM the recorded history is fused HIP (csrc/glm.hip; `l2hmc_amd.glm`): the predictive
+    mean, WAIC and PSIS-LOO never form the (draws, rows) log-likelihood matrix."""
+
+    def __init__(self, X, y, offset=None, prior_var=1.0):
+        from . import glm
+        X = np.asarray(X, dtype=np.float64)
+        y = np.asarray(y, dtype=np.float64)
+        if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1:
+            raise ValueError("X must be (n_data, d) with n_data, d >= 1, got shape %s" % (X.shape,))
+        n, d = X.shape
+        if d > 128:
+            raise ValueError("PoissonRegression supports d <= 128 features (got %d)" % d)
+        if n > 1 << 20:
+            raise ValueError("PoissonRegression supports at most 1048576 data rows (got %d)" % n)
+        if y.shape != (n,):
+            raise ValueError("y must be (n_data,) = (%d,), got shape %s" % (n, y.shape))
+        if not np.all(np.isfinite(X)):
+            raise ValueError("X must be finite")
+        if not np.all(np.isfinite(y)) or not np.all((y >= 0.0) & (y == np.floor(y)) & (y <= glm.MAX_COUNT)):
+            raise ValueError("counts y must be non-negative integers <= 2^24")
+        offset = np.zeros(n) if offset is None else np.asarray(offset, dtype=np.float64)
+        if offset.shape != (n,) or not np.all(np.isfinite(offset)):
+            raise ValueError("offset must be finite (n_data,) = (%d,), got shape %s" % (n, offset.shape))
+        prior_var = float(prior_var)
+        if not (np.isfinite(prior_var) and prior_var > 0.0):
+            raise ValueError("prior_var must be finite and > 0, got %r" % (prior_var,))
+        self.X = np.ascontiguousarray(X, dtype=np.float32)
+        self.y = np.ascontiguousarray(y, dtype=np.float32)
+        self.offset = np.ascontiguousarray(offset, dtype=np.float32)
+        self.prior_var = prior_var
+        self.dim = d
+        self._glm = glm.Glm(self.X, self.y, self.offset)
+        self._torch = {}
+
+    def _data(self, x):
+        key = (str(x.device), x.dtype)
+        if key not in self._torch:
+            self._torch[key] = tuple(torch.as_tensor(a).to(device=x.device, dtype=x.dtype) for a in (self.X, self.y, self.offset))
+        return self._torch[key]
+
+    def energy(self, x):
+        """U(w) of each row of the torch tensor x (N, d), in x's own device and dtype; differentiable."""
+        X, y, o = self._data(x)
+        h = x @ X.t() + o
+        return (torch.exp(h) - y * h).sum(dim=1) + 0.5 * x.square().sum(dim=1) / self.prior_var
+
+    def grad_energy(self, x):
+        """grad U = X^T (mu - y) + w / prior_var, (N, d); differentiable (the trainer's Hessian-vector products)."""
+        X, y, o = self._data(x)
+        return (torch.exp(x @ X.t() + o) - y) @ X + x / self.prior_var
+
+    def get_energy_function(self):
+        return UserEnergy(self.energy, self.grad_energy, x_dim=self.dim)
+
+    def log_density(self, W):
+        """Unnormalised log posterior -U(w) of each row of W (n_w, d), in float64."""
+        W = np.asarray(W, dtype=np.float64)
+        h = W @ self.X.astype(np.float64).T + self.offset.astype(np.float64)
+        return -((np.exp(h) - self.y.astype(np.float64) * h).sum(axis=1) + 0.5 * np.square(W).sum(axis=1) / self.prior_var)
+
+    def log_lik(self, draws, rows=None):
+        """The pointwise log-likelihood matrix (S, m) of a range of rows (`glm.Glm.log_lik`): the slow route."""
+        return self._glm.log_lik(draws, rows=rows)
+
+    def predict_mean(self, draws, X=None, offset=None):
+        """The posterior predictive mean of every row of X (default: the model's own rows) under the draws."""
+        return self._glm.predict_mean(draws, X=X, offset=offset)
+
+    def waic(self, draws):
+        """WAIC of this model's own data under the draws: a `Summary` with elpd_waic, p_waic, lppd, se, elpd_i,
+        n_high_variance, n_underflow."""
+        return self._glm.waic(draws)
+
+    def loo(self, draws, r_eff=None, max_lag=None, split=False, max_tail_bytes=256 << 20):
+        """PSIS-LOO of this model's own data under the draws (`glm.Glm.loo`): the fields of `loo_from_log_lik`."""
+        return self._glm.loo(draws, r_eff=r_eff, max_lag=max_lag, split=split, max_tail_bytes=max_tail_bytes)
+
+    def relative_eff(self, draws, max_lag=None, split=False, max_bytes=256 << 20):
+        """The per-row relative efficiency of this model's own data under a recorded history (`glm.Glm.relative_eff`)."""
+        return self._glm.relative_eff(draws, max_lag=max_lag, split=split, max_bytes=max_bytes)
+
+
 def as_device_f32(x, device=None):
     """numpy / torch input -> contiguous float32 tensor on the GPU."""
     if not isinstance(x, torch.Tensor):

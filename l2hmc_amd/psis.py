@@ -517,6 +517,17 @@ def relative_eff_from_log_lik(log_lik, max_lag=None, split=False):
                    n_draws=S, n_steps=Mh, n_chains=C, max_lag=max_lag)
 
 
+def _loo_of_parts(parts, S, r, lens):
+    """The `Summary` of the `_finish_raw` results `parts` of consecutive column groups (`loo_from_log_lik`, `glm.Glm.loo`);
+    `r` (n,) and `lens` (n,), or None for independent draws."""
+    cols = [np.concatenate([p[j] for p in parts]) for j in range(len(parts[0]))]
+    s = _loo_summary(cols[0], cols[1], cols[2], cols[-1], S, loo_tail_len(S) if lens is None else int(lens.max()))
+    if r is None:
+        return s
+    from .predictive import _mc_fields
+    return _mc_fields(s, r, cols[3], cols[4], lens)
+
+
 def loo_from_log_lik(log_lik, r_eff=None, select="topk", max_lag=None, split=False):
     """PSIS-LOO of any model from its pointwise log-likelihood matrix (S, n), log p(y_i | theta_s), draws first -- or the history
     form (steps, chains, n), which is read as (steps x chains, n); float32 or float64, numpy or a ROCm tensor.  The ratios are
@@ -581,9 +592,4 @@ def loo_from_log_lik(log_lik, r_eff=None, select="topk", max_lag=None, split=Fal
         _check_flags(flags)
     else:
         parts.append(_finish_raw(_host_raw(ll, lens), S, r))
-    cols = [np.concatenate([p[j] for p in parts]) for j in range(len(parts[0]))]
-    s = _loo_summary(cols[0], cols[1], cols[2], cols[-1], S, loo_tail_len(S) if lens is None else int(lens.max()))
-    if r is None:
-        return s
-    from .predictive import _mc_fields
-    return _mc_fields(s, r, cols[3], cols[4], lens)
+    return _loo_of_parts(parts, S, r, lens)
