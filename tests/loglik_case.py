@@ -194,10 +194,30 @@ def sum_bounds(ll32, exact):
                               (ll - top[None, :], ll - top[None, :], np.ones_like(out_of_tail))):
             t = np.where(mask, np.exp(a), ld(0))
             total = t.sum(axis=0)
-            per_term = (t * (np.abs(dist) + 2) * (ld(2.0) ** -52 + eps_ld)).sum(axis=0)
+            # a term that is zero (a draw at -inf under a finite cutoff or maximum: e^-inf; a tail member) is exact and adds a
+            # zero bound -- not 0 x its infinite distance, a NaN
+            per_term = np.where(t == 0, ld(0), t * (np.abs(dist) + 2) * (ld(2.0) ** -52 + eps_ld)).sum(axis=0)
             ref.append(total.astype(np.float64))
             bound.append((per_term + S * ld(2.0) ** -53 * total).astype(np.float64))
     return np.stack(ref), np.stack(bound)
+
+
+def sums_within(got, ref, bound):
+    """The sums of a matrix that holds -inf: NaN exactly where the reference is NaN (a draw at -inf outside the tail of a column
+    whose cutoff is -inf: e^(-inf + inf)), and within the bound everywhere else."""
+    got, nan = np.asarray(got), np.isnan(ref)
+    with np.errstate(all="ignore"):
+        return bool(np.array_equal(np.isnan(got), nan) and np.all((np.abs(got - ref) <= bound)[~nan]))
+
+
+def minus_inf_matrix():
+    """(ll (70, 3) float32, lens): `matrix(70, 3)` with two -inf in column 1 (fewer than the tail length 14: they are tail
+    members under a finite cutoff) and twenty in column 2 (more: the cutoff is -inf, the tail is empty, body is NaN)."""
+    ll = matrix(70, 3)
+    ll[[3, 41], 1] = -np.inf
+    ll[5:65:3, 2] = -np.inf
+    assert np.isneginf(ll).sum(axis=0).tolist() == [0, 2, 20]
+    return ll
 
 
 # ---- the device entries, straight (need a GPU) -------------------------------------------------------------------------------

@@ -86,6 +86,58 @@ def test_fixtures_have_full_tails_and_surprising_rows():
     assert len(np.unique(ll[:, 0])) < 35
 
 
+@pytest.mark.parametrize("S", gc.EDGE_S)
+def test_edge_case_sits_on_the_edges_it_names(S):
+    """`glm_case.edge_case`, on the float64 h of its float32 inputs: no draw within 0.05 of the float32 overflow of mu; the
+    overflow rows have between 1 and M - 1, and more than M, draws above 88.8 (ll64 below -FLT_MAX exactly there); the zero row
+    has mu below the smallest float32 subnormal in every draw; the underflow row has ll - sat < -745 in every draw and is the
+    ONE row the host route counts in `n_underflow`; the large count cancels eleven digits; the edge rows stand at index 0 and
+    past 32, the last row of the ragged data block is ordinary, and the ordinary rows are those of `case(S, 32, 3)`."""
+    import l2hmc_amd
+    from l2hmc_amd import glm
+    from l2hmc_amd._pareto import loo_tail_len
+    W, X, y, o, ordinary = gc.edge_case(S)
+    M = gc.tail_len(S)
+    assert M == loo_tail_len(S) and X.shape == (gc.EDGE_N, 3) and X.dtype == y.dtype == o.dtype == W.dtype == np.float32
+    W0, X0, y0, o0 = gc.case(S, 32, 3)
+    assert np.array_equal(W, W0) and np.array_equal(X[ordinary], X0) and np.array_equal(y[ordinary], y0) and np.array_equal(o[ordinary], o0)
+    at = gc.EDGE_ROWS
+    assert min(at.values()) == 0 and max(at.values()) > 32 and ordinary[-1] and gc.EDGE_N % 16 != 0 and ordinary.sum() == 32
+    ll, h = gc.log_lik(W, X, y, o)
+    assert np.abs(h - gc.MU_OVERFLOW_H).min() >= 0.05
+    flt_max = float(np.finfo(np.float32).max)
+    over = h > 88.8
+    assert np.array_equal(over, h > gc.MU_OVERFLOW_H) and np.array_equal(over, ll < -flt_max) and np.all(np.abs(ll[~over]) < flt_max)
+    count = over.sum(axis=0)
+    assert 1 <= count[at["overflow_few"]] <= M - 1 and M < count[at["overflow_many"]] < S
+    assert count.sum() == count[at["overflow_few"]] + count[at["overflow_many"]]
+    assert y[at["zero"]] == 0 and np.all(np.exp(h[:, at["zero"]]) < 2.0 ** -150)
+    sat = glm.row_constants(y, o)[2].astype(np.float64)
+    dead = np.all(ll - sat < -745.0, axis=0)
+    assert dead.tolist() == [i == at["underflow"] for i in range(gc.EDGE_N)]
+    big = at["large"]
+    assert y[big] == 100000 and np.all(np.abs(ll[:, big]) < 1e-5 * y[big] * h[:, big])       # y h ~ 1.15e6 against |ll| < 11.5
+    f = l2hmc_amd.PoissonRegression(X, y, offset=o).waic(W)
+    assert f.n_underflow == 1 and np.isneginf(f.lppd_i[at["underflow"]])
+
+
+def test_long_history_shapes_sit_in_their_segment_and_chunk_branches():
+    """The long histories of tests/test_gpu_glm_geometries.py, through the workspace-size entries: the gather's segments are
+    max(64, ceil(S / 2048)) draws -- 65 at S = 131073 (2017 segments, the last of 33 draws: two tiles and one draw), 69 at
+    140001 (2029, the last a full one: four tiles and 5 draws) and at 140003 (2030, the last of 2 draws) -- and the predictive
+    sums' chunks are 4 tiles (three rows are one row group: 4096 chunks are aimed for, the floor holds)."""
+    from l2hmc_amd import _ffi
+    L = _ffi.lib()
+    ws, wp = L.l2hmc_glm_loo_workspace_bytes, L.l2hmc_glm_predict_workspace_doubles
+    n = 3
+    for (S, d), (seg, nseg, last, chunks) in (((131073, 40), (65, 2017, 33, 2049)), ((140001, 40), (69, 2029, 69, 2188)),
+                                              ((140001, 100), (69, 2029, 69, 2188)), ((140003, 100), (69, 2030, 2, 2188))):
+        assert seg == max(64, -(-S // 2048)) and nseg == -(-S // seg) and last == S - (nseg - 1) * seg
+        assert ws(S, n, d) == 8 + n * (256 * 8 + 8 + 8 + 4 + 4) + nseg * 3 * n * 8, (S, d)
+        assert wp(S, n, d) == chunks * 4 * n and chunks == -(-(-(-S // 16)) // 4), (S, d)
+    assert max(64, -(-131072 // 2048)) == 64                 # 131073 is the first S with segments that are no multiple of 16
+
+
 def test_row_constants_and_saturation():
     """g = lgamma(y + 1), sat = y log y - y - g (0 at y = 0) is the supremum of ll over eta: exp(ll - sat) <= 1."""
     from scipy.special import gammaln

@@ -11,9 +11,7 @@ pytestmark = pytest.mark.gpu
 _CACHE = {}
 
 
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view({4: np.uint32, 8: np.uint64}[a.dtype.itemsize])
+_bits = gc.bits
 
 
 def _setup(S, n, d, exact=False):
@@ -38,29 +36,7 @@ def _raw(m, Wd, lens=None):
     return out
 
 
-def _check_raw(ll32, lens, got):
-    """`got` against `lk.select_exact` and `lk.sum_bounds` of the written matrix; the worst sum error over its bound."""
-    from l2hmc_amd._pareto import loo_tail_len
-    S, n = ll32.shape
-    eff = np.full(n, loo_tail_len(S), dtype=np.int64) if lens is None else lens
-    ex = lk.select_exact(ll32, eff)
-    assert int(got["flag"][0]) == 0
-    assert np.array_equal(_bits(got["cutoff"]), _bits(ex["cutoff"])) and np.array_equal(_bits(got["top"]), _bits(ex["top"]))
-    assert np.array_equal(got["n_tail"], ex["n_tail"]) and np.all(got["n_tail"] <= eff)
-    assert got["tail"].shape == (n, int(eff.max()))
-    for i in range(n):
-        L = int(ex["n_tail"][i])
-        assert np.all(np.isposinf(got["tail"][i, L:])), i
-        assert sorted(lk.keys(got["tail"][i, :L]).tolist()) == [p[0] for p in ex["pairs"][i]], i
-    ref, bound = lk.sum_bounds(ll32, ex)
-    err = np.abs(got["sums"] - ref)
-    worst = float(np.max(err / bound))
-    print("worst sum error / bound %.3g" % worst)
-    assert np.all(err <= bound), worst
-    if n <= 512:                                             # ... and they are the matrix gather's own sums: the same terms, the same order
-        mat = lk.device_raw(ll32, lens, want_pos=False)
-        assert np.array_equal(_bits(got["sums"]), _bits(mat["sums"]))
-    return worst
+_check_raw = gc.check_raw                                   # (shared with tests/test_gpu_glm_geometries.py)
 
 
 @pytest.mark.parametrize("S,n,d", gc.SHAPES)
@@ -99,8 +75,9 @@ def test_fused_tails_with_ties(S, n, d):
 
 
 def test_segments_that_are_no_multiple_of_a_tile():
-    """S = 140001 > 131072: the gather's segments are ceil(S / 2048) = 69 draws, cut out of the history at any draw, the last
-    one ragged; the count passes run beyond their floor of 4 tiles per chunk (9)."""
+    """S = 140001 > 131072: the gather's segments are ceil(S / 2048) = 69 draws, cut out of the history at any draw, each four
+    full tiles and one of 5 draws (140001 = 2029 x 69: the last segment is a full one; tests/test_gpu_glm_geometries.py has
+    the short last segments); the count passes run beyond their floor of 4 tiles per chunk (9)."""
     S, n, d = 140001, 3, 2
     m, _, _, _, _, Wd, ll32 = _setup(S, n, d)
     _check_raw(ll32, None, _raw(m, Wd))

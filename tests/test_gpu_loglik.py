@@ -123,6 +123,48 @@ def test_a_nan_stays_in_its_column():
     assert np.isnan(p.khat[1]) and np.isnan(p.n_eff[1]) and np.all(np.isfinite(p.khat[[0, 2]]))
 
 
+def test_minus_inf_draws_follow_the_table_of_non_finite_cutoffs():
+    """`minus_inf_matrix` (70, 3): two -inf in column 1 are tail members under a finite cutoff, twenty in column 2 make the
+    cutoff -inf, the tail empty and body and body_sq NaN (csrc/loglik_tails.hip, the table of its header).  The raw outputs are
+    the exact selection, with the draws, and the sums lie inside the repaired `sum_bounds` (NaN exactly where the reference
+    is); the finished numbers share the NaN pattern of the numpy route (khat and elpd_loo_i NaN in both columns) and column 0
+    stays within the gates."""
+    import torch
+    from l2hmc_amd import psis
+    from l2hmc_amd._pareto import loo_tail_len
+    ll = lk.minus_inf_matrix()
+    S, n = ll.shape
+    M = loo_tail_len(S)
+    for lens in (None, lk.lengths_for(S, n), np.array([M, 1, M - 1], dtype=np.int64)):
+        got = lk.device_raw(ll, lens)
+        eff = np.full(n, M, dtype=np.int64) if lens is None else lens
+        ex = lk.select_exact(ll, eff)
+        assert got["flag"] == 0
+        assert np.array_equal(_bits(got["cutoff"]), _bits(ex["cutoff"])) and np.array_equal(_bits(got["top"]), _bits(ex["top"]))
+        assert np.array_equal(got["n_tail"], ex["n_tail"])
+        for i in range(n):
+            L = int(ex["n_tail"][i])
+            assert np.all(np.isposinf(got["tail"][i, L:])) and np.all(got["tail_pos"][i, L:] == -1), i
+            assert sorted(zip(lk.keys(got["tail"][i, :L]).tolist(), got["tail_pos"][i, :L].tolist())) == ex["pairs"][i], i
+        ref, bound = lk.sum_bounds(ll, ex)
+        assert lk.sums_within(got["sums"], ref, bound), (got["sums"], ref, bound)
+        if lens is None:
+            assert np.isfinite(got["cutoff"][1]) and got["n_tail"][1] == M and np.isneginf(got["tail"][1]).sum() == 2
+            assert np.isneginf(got["cutoff"][2]) and got["n_tail"][2] == 0 and np.isfinite(got["top"][2])
+            assert np.isnan(got["sums"][:2, 2]).all() and np.isfinite(got["sums"][2, 2]) and np.all(np.isfinite(got["sums"][:, :2]))
+    gk, ge, gn, gm = lk.gate(S)
+    for r in (None, np.ones(n)):
+        a, b = psis.loo_from_log_lik(torch.as_tensor(ll).cuda(), r_eff=r, select="fused"), psis.loo_from_log_lik(ll, r_eff=r)
+        keys = ("khat", "elpd_loo_i", "lppd_i") + (("n_eff", "mcse_elpd_loo_i") if r is not None else ())
+        for k in keys:
+            assert np.array_equal(np.isnan(a[k]), np.isnan(b[k])), (k, a[k], b[k])
+        assert np.isnan(b.khat[1:]).all() and np.isnan(b.elpd_loo_i[1:]).all() and np.array_equal(a.n_tail, b.n_tail)
+        assert abs(a.khat[0] - b.khat[0]) <= gk and abs(a.elpd_loo_i[0] - b.elpd_loo_i[0]) <= ge
+        assert np.all(np.abs(a.lppd_i - b.lppd_i) <= ge)
+        if r is not None:
+            assert _rel(a.n_eff, b.n_eff)[0] <= gn and _rel(a.mcse_elpd_loo_i, b.mcse_elpd_loo_i)[0] <= gm
+
+
 @pytest.mark.parametrize("fixture", [ls.FIXTURES[0], ls.FIXTURES[2], ls.FIXTURES[8]])
 def test_chain_stats_exp_against_the_exponentiated_history(fixture):
     """`l2hmc_chain_stats_exp(X, shift)` against `l2hmc_chain_stats` of Y = exp(X - shift) formed in float64 torch and rounded to

@@ -13,6 +13,10 @@ chunks AND two row groups (n > 32) in every branch: NTM = 1 (70, 35, 5); NTM = 2
 (70, 35, 40); NTM = 8 (300, 50, 128) -- all on the floor tpc = 4 -- and tpc = 5: (65609, 33, 1) [NTM = 1; 4101 tiles, 821
 chunks, a last tile of 9 draws, a last chunk of one tile, three dead waves in the last workgroup of a row group] and
 (70000, 35, 17) [NTM = 2; 875 chunks]; the exact-input and the row-group checks run at S = 65609 and 70000 too.
+(c) Fewer live feature tiles than the compiled geometry holds (the masks `tg < NT` of block_fragments and tile_logits, the
+label offset 512 NT, the zeroed LDS columns, tile_load's `e < tile_elems`; csrc/draw_tiles.hpp): NT 3 / NTM 4 is (70, 35, 40),
+NT 5 / NTM 8 is (70, 35, 72) (d = 100 and 112 are not used: their reference khat lies within one gate-width of a threshold);
+and both beyond the floor, tpc = 5: (65609, 33, 40) [NT 3 / NTM 4] and (65609, 33, 72) [NT 5 / NTM 8], 821 chunks each.
 tests/test_loo_cpu.py pins these shapes to their chunk counts.  (4, 3, 2) has M = 0: no tail at all."""
 import numpy as np
 import pytest
@@ -22,8 +26,9 @@ from tests import loo_case as lc
 from tests import predictive_case as pc
 
 pytestmark = pytest.mark.gpu
-SHAPES = lc.FIXTURES + [(70, 35, 5), (70, 35, 40), (4, 3, 2)]
-BIG = [(65609, 33, 1), (70000, 35, 17)]                        # tpc = 5: more than the floor of 4 tiles per chunk
+SHAPES = lc.FIXTURES + [(70, 35, 5), (70, 35, 40), (70, 35, 72), (4, 3, 2)]
+# tpc = 5: more than the floor of 4 tiles per chunk; d = 40 and 72 run it with NT 3 / NTM 4 and NT 5 / NTM 8
+BIG = [(65609, 33, 1), (70000, 35, 17), (65609, 33, 40), (65609, 33, 72)]
 RAW = ("cutoff", "n_tail", "tail", "body", "sum_lik")
 _CASES = {}
 

@@ -13,7 +13,11 @@ import torch
 from tests import predictive_case as pc
 
 pytestmark = pytest.mark.gpu
-SHAPES = [(21, 1, 1), (37, 17, 3), (16, 16, 16), (523, 33, 17), (300, 50, 128), (4099, 100, 25)]
+SHAPES = [(21, 1, 1), (37, 17, 3), (16, 16, 16), (523, 33, 17), (300, 50, 128), (4099, 100, 25),
+          # live feature tiles NT = ceil(d / 16) under the compiled NTM: 3 / 4 (the first launch of predict_kernel<4, 2>) and
+          # 4 / 4, 5 / 8, 7 / 8 with a full last tile -- the masks `tg < NT` of block_fragments and tile_logits, the label offset
+          # 512 NT, the zeroed LDS columns and tile_load's `e < tile_elems` (csrc/draw_tiles.hpp); two row groups each
+          (70, 35, 40), (70, 35, 50), (70, 35, 72), (70, 35, 112)]
 SUMS = ("sum_p", "sum_lik", "sum_ll", "sum_ll2")
 _CASES = {}
 
@@ -51,7 +55,8 @@ def _gate(got, ref, bounds, what):
 @pytest.mark.parametrize("S,n,d", SHAPES)
 def test_sums_and_finished_numbers_match_the_host_path(S, n, d):
     """The smallest shapes that exercise every mask: a last draw tile with 5, 5, 16, 11, 12 and 3 live draws, a last data block
-    with 1, 1, 16, 1, 2 and 4 live rows, d below, at and across the 16-feature tiles; logits reach +-10."""
+    with 1, 1, 16, 1, 2 and 4 live rows, d below, at and across the 16-feature tiles; logits reach +-10.  The (70, 35, d) shapes
+    run fewer live feature tiles than the compiled geometry holds (d = 40, 72, 112) and the full NTM = 4 (d = 50)."""
     from l2hmc_amd import predictive
     W, X, y, ref, bounds = _case(S, n, d)
     sums = predictive.pointwise_sums(_dev(W), _dev(X), _dev(y))

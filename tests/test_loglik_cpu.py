@@ -154,6 +154,36 @@ def test_one_order_for_signed_zeros_and_nan_cutoffs():
     assert s.n_tail[1] == 5 and np.isnan(s.khat[1]) and np.isnan(s.elpd_loo_i[1]) and np.all(np.isfinite(s.elpd_loo_i[[0, 2]]))
 
 
+def test_sum_bounds_of_columns_that_hold_minus_inf():
+    """`loglik_case.sum_bounds`: a zero term adds a zero bound.  A 5 x 3 matrix with tail length 2: column 0 finite, column 1
+    with one -inf (a tail member under a finite cutoff: its body terms are masked, its lik term is e^-inf = 0), column 2 with
+    three -inf (the cutoff is -inf: the -inf draws outside the empty tail give e^(-inf + inf) = NaN in body and body_sq, and lik
+    stays finite).  The finite column's bound is what the unrepaired expression gives, bit for bit.  The numpy route of
+    `minus_inf_matrix` gives NaN khat and elpd_loo_i in both columns that hold a -inf, and serves the third."""
+    from l2hmc_amd import psis
+    ll = np.array([[-1.0, -2.0, -np.inf], [-3.0, -np.inf, -1.0], [-0.5, -0.25, -np.inf], [-2.0, -4.0, -np.inf], [-1.5, -1.0, -2.0]],
+                  dtype=np.float32)
+    lens = np.full(3, 2, dtype=np.int64)
+    ex = lk.select_exact(ll, lens)
+    assert ex["n_tail"].tolist() == [2, 2, 0] and np.isneginf(ex["cutoff"]).tolist() == [False, False, True]
+    ref, bound = lk.sum_bounds(ll, ex)
+    assert np.all(np.isfinite(ref[:, :2])) and np.all(np.isfinite(bound[:, :2])) and np.all(bound[:, :2] > 0)
+    assert np.isnan(ref[:2, 2]).all() and np.isfinite(ref[2, 2]) and np.isfinite(bound[2, 2])
+    ld = np.longdouble
+    c, top, x = ld(ex["cutoff"][0]), ld(ex["top"][0]), ll[:, 0].astype(ld)
+    out = ~ex["in_tail"][:, 0]
+    u = ld(2.0) ** -52 + ld(np.finfo(ld).eps)
+    want = [((np.exp(m * (c - x)) * (np.abs(c - x) + 2) * u)[out]).sum() + 5 * ld(2.0) ** -53 * np.exp(m * (c - x))[out].sum() for m in (1, 2)]
+    want.append((np.exp(x - top) * (np.abs(x - top) + 2) * u).sum() + 5 * ld(2.0) ** -53 * np.exp(x - top).sum())
+    assert np.array_equal(bound[:, 0], np.array(want).astype(np.float64))
+    assert abs(ref[2, 1] - (1.0 + np.exp(-0.75) + np.exp(-1.75) + np.exp(-3.75))) <= bound[2, 1]
+    assert lk.sums_within(ref, ref, bound) and not lk.sums_within(np.where(np.isnan(ref), 0.0, ref), ref, bound)
+    big = lk.minus_inf_matrix()
+    s = psis.loo_from_log_lik(big, r_eff=np.ones(3))
+    for k in ("khat", "elpd_loo_i"):
+        assert np.isnan(s[k][1:]).all() and np.isfinite(s[k][0]), k
+
+
 def test_refusals():
     """A matrix with "auto", an unknown select or r_eff word, a wrong r_eff shape, the fused route on host data, and -- on a
     device-like input, refused before anything is touched -- `topk` with r_eff (names select="fused") and a float64 matrix with

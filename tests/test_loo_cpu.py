@@ -194,13 +194,14 @@ def test_gpu_shapes_sit_in_their_chunk_branch():
         rest = ws(S, n, d) - 8 - n * (256 * 8 + 8) - (n * 4 + 7) // 8 * 8
         assert rest > 0 and rest % (16 * n) == 0
         return rest // (16 * n)
-    for (S, n, d), tpc in (((70, 35, 5), 4), ((523, 33, 17), 4), ((300, 50, 128), 4), ((4099, 100, 25), 4), ((65536, 33, 1), 4),
-                           ((65537, 33, 1), 5), ((65609, 33, 1), 5), ((65609, 37, 19), 5), ((70000, 35, 17), 5),
-                           ((4096000, 1000, 25), 250)):
+    for (S, n, d), tpc in (((70, 35, 5), 4), ((70, 35, 72), 4), ((523, 33, 17), 4), ((300, 50, 128), 4), ((4099, 100, 25), 4),
+                           ((65536, 33, 1), 4), ((65537, 33, 1), 5), ((65609, 33, 1), 5), ((65609, 37, 19), 5), ((70000, 35, 17), 5),
+                           ((65609, 33, 40), 5), ((65609, 33, 72), 5), ((4096000, 1000, 25), 250)):
         tiles = (S + 15) // 16
         assert chunks(S, n, d) == -(-tiles // tpc), (S, n, d)
         assert tpc == max(4, -(-tiles // 1024))
     assert chunks(65609, 33, 1) == 821 and chunks(65609, 33, 1) % 4 == 1 and chunks(70000, 35, 17) == 875
+    assert chunks(65609, 33, 40) == 821 and chunks(65609, 33, 72) == 821     # NT 3 / NTM 4 and NT 5 / NTM 8 beyond the floor
     assert chunks(70000, 12, 17) == chunks(70000, 35, 17)            # the chunks do not depend on the rows of a call
 
 
