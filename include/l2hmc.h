@@ -214,6 +214,11 @@ const char* l2hmc_last_error(void);
  * without arguments: "gemm_xlp_kernel" (decoder products on pre-split bf16 planes, from 3072 chains at config 5's widths
  * in gemm_mode 1), "gemm_nt_kernel", or "net_eval_kernel" for a built-in / caller-supplied energy.  Copies at most n - 1 characters, returns the full length. */
 int32_t l2hmc_last_kernel(char* buf, int32_t n);
+/* The same call's __global__ function.  It differs from l2hmc_last_kernel where a kernel has a second body that computes the same
+ * bits: "traj_fast_cc_kernel<1, 1, 4, 3, 1, 1>" (one workgroup per CU; PK last, the bound in front of it) for a common sampler
+ * launch of "traj_fast_kernel<1, 1, 4, 3, 1>" whose grid has at most one workgroup per CU (L2HMC_FAST_ONE_WAVE=0 / 1 in the
+ * environment forces the choice for such a launch). */
+int32_t l2hmc_last_kernel_body(char* buf, int32_t n);
 
 /* Number of floats of the fragment-ordered weight buffer for both nets, or a negative
  * L2HMC_ERR_* if (d, H) is outside the fused kernels' range. */

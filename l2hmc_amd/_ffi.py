@@ -130,6 +130,7 @@ SYMBOLS = {
     "l2hmc_abi_version": (C.c_int, []),
     "l2hmc_last_error": (C.c_char_p, []),
     "l2hmc_last_kernel": (C.c_int32, [C.c_char_p, C.c_int32]),
+    "l2hmc_last_kernel_body": (C.c_int32, [C.c_char_p, C.c_int32]),
     "l2hmc_bf16_planes": (C.c_int, [_fp, C.c_int32, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]),
     "l2hmc_struct_bytes": (C.c_int64, [C.c_int32]),
     "l2hmc_packed_nets_floats": (C.c_int64, [C.c_int32, C.c_int32]),
@@ -255,10 +256,12 @@ def lib():
     return _lib
 
 
-def last_kernel():
-    """Name of the kernel the last trajectory / training call of this thread launched (as rocprofv3 spells it)."""
+def last_kernel(body=False):
+    """Name of the kernel the last trajectory / training call of this thread launched (as rocprofv3 spells it).
+    body=True: the __global__ function that ran it -- the sampler kernel has a second body for grids of at most one workgroup
+    per CU, traj_fast_cc_kernel<..., 1, 1>, which computes the same bits under the same kernel name."""
     buf = C.create_string_buffer(96)
-    lib().l2hmc_last_kernel(buf, 96)
+    (lib().l2hmc_last_kernel_body if body else lib().l2hmc_last_kernel)(buf, 96)
     return buf.value.decode()
 
 

@@ -9,7 +9,12 @@ namespace l2hmc {
 
 thread_local char g_err[512] = "";
 thread_local char g_kernel[96] = "";      // the kernel the last trajectory / training call of this thread launched
-void note_kernel(const char* fmt, long long a, long long b, long long c, long long d) { snprintf(g_kernel, sizeof(g_kernel), fmt, a, b, c, d); }
+// ... and the __global__ function that ran it, where one kernel of that name has more than one (traj_fast_cc_kernel, traj_fast.hpp)
+thread_local char g_kernel_body[96] = "";
+void note_kernel(const char* fmt, long long a, long long b, long long c, long long d) {
+  snprintf(g_kernel, sizeof(g_kernel), fmt, a, b, c, d);
+  snprintf(g_kernel_body, sizeof(g_kernel_body), "%s", g_kernel);
+}
 
 int fail(int code, const char* fmt, const char* a, long long b, long long c) {
   snprintf(g_err, sizeof(g_err), fmt, a, b, c);
@@ -518,12 +523,14 @@ bool pick_geometry_of(int ekind, int d, long long N, int v, int& DT, int& NW, in
 struct EnvOverrides {
   bool f32_mfma;   // L2HMC_F32_MFMA=1: every trajectory on the f32-input MFMA, as variant 200 + v does per call (read once per process)
   int lane_res;    // L2HMC_LANE_RES=0/1/2: where the lane kernel keeps its weights, -1 = by the measured rule (read per call: tests switch it)
+  int one_wave;    // L2HMC_FAST_ONE_WAVE=0/1: the sampler's one-workgroup-per-CU body never / at every grid, -1 = by the grid (read per call: tests switch it)
 };
 
 static EnvOverrides read_env() {
   static const bool f32 = [] { const char* e = getenv("L2HMC_F32_MFMA"); return e && e[0] && e[0] != '0'; }();
   const char* e = getenv("L2HMC_LANE_RES");
-  return {f32, (e != nullptr && e[0] >= '0' && e[0] <= '2') ? e[0] - '0' : -1};
+  const char* o = getenv("L2HMC_FAST_ONE_WAVE");
+  return {f32, (e != nullptr && e[0] >= '0' && e[0] <= '2') ? e[0] - '0' : -1, (o != nullptr && (o[0] == '0' || o[0] == '1')) ? o[0] - '0' : -1};
 }
 
 // `variant` (include/l2hmc.h), decoded once: every selection rule reads these fields.
@@ -689,6 +696,15 @@ static int plan_trajectory(const L2hmcTrajectoryArgs& a, KArgs& k, int KH, int c
       p.lds = plan_lds_fast(k, p.NW, p.DT, true);
       if (p.lds <= kMaxLdsBytes) {
         p.f16 = 1;
+        // The sampler's common launch (all three draws in-kernel, p_out + x_next and no other output: the test traj_fast_kernel makes
+        // at entry) of the diagonal Gaussian's one-tile four-wave kernel, on a grid of at most one workgroup per CU: the body
+        // compiled for one workgroup per CU, which may use the registers the two-wave bound keeps for a second workgroup that never
+        // arrives at such a grid (traj_fast.hpp).  L2HMC_FAST_ONE_WAVE=0 / 1 in the environment forces the choice for such a launch.
+        const int all3 = L2HMC_RNG_V | L2HMC_RNG_DIR | L2HMC_RNG_U;
+        const bool common = (k.rng_flags & all3) == all3 && k.p_out != nullptr && k.x_next != nullptr && k.x_hist == nullptr &&
+                            k.logjac_out == nullptr && k.x_out == nullptr && k.v_out == nullptr;
+        if (k.ekind == L2HMC_ENERGY_GAUSS_DIAG && p.DT == 1 && p.NW == 4 && common)
+          p.one_wave = env.one_wave >= 0 ? env.one_wave != 0 : (a.n_chains + 15) / 16 <= cus;
         return L2HMC_OK;
       }
     }
@@ -711,8 +727,12 @@ static void note_plan(const TrajPlan& p) {
       return note_kernel(p.half ? "traj_tile_kernel<%lld, %lld, %lld, %lld, true>" : "traj_tile_kernel<%lld, %lld, %lld, %lld, false>",
                          p.ek, p.DT, p.KH, p.tpw);
     case FAM_FAST:
-      return note_kernel(p.f16 ? "traj_fast_kernel<%lld, %lld, %lld, %lld, 1>" : "traj_fast_kernel<%lld, %lld, %lld, %lld>", p.ek, p.DT,
-                         p.NW, p.KH);
+      note_kernel(p.f16 ? "traj_fast_kernel<%lld, %lld, %lld, %lld, 1>" : "traj_fast_kernel<%lld, %lld, %lld, %lld>", p.ek, p.DT, p.NW,
+                  p.KH);
+      // (the same kernel to its callers -- same statements, same bits -- so l2hmc_last_kernel keeps the name; l2hmc_last_kernel_body
+      //  tells the two apart: WB = 1 in front of PK)
+      if (p.one_wave) snprintf(g_kernel_body, sizeof(g_kernel_body), "traj_fast_cc_kernel<%d, %d, %d, %d, 1, 1>", p.ek, p.DT, p.NW, p.KH);
+      return;
     case FAM_LADDER: return note_kernel("traj_ladder_kernel<%lld, %lld, %lld, %lld>", p.ek, p.DT, p.NW, p.KH);
     default: return note_kernel("traj_kernel<%lld, %lld, %lld, %lld>", p.ek, p.DT, p.NW, p.KH);
   }
@@ -729,7 +749,7 @@ static int launch_plan(const TrajPlan& p, const KArgs& k, hipStream_t s, const L
     }
     if constexpr (EK == L2HMC_ENERGY_GAUSS_DIAG || EK == L2HMC_ENERGY_ROUGHWELL) {
       if (p.family == FAM_TILE) return launch_tile_ek<EK>(p, k, s);
-      if (p.family == FAM_FAST && p.f16) return launch_fast16_ek<EK>(p, k, s);
+      if (p.family == FAM_FAST && p.f16) return p.one_wave ? launch_fast16_one_wave(p, k, s) : launch_fast16_ek<EK>(p, k, s);
     }
     return launch_ek<EK>(p, k, s);           // general, fast, small, energy, p_accept
   });
@@ -758,6 +778,12 @@ int32_t l2hmc_last_kernel(char* buf, int32_t n) {
   if (!buf || n < 1) return fail(L2HMC_ERR_ARG, "l2hmc_last_kernel: bad argument%s");
   snprintf(buf, (size_t)n, "%s", g_kernel);
   return (int32_t)strlen(g_kernel);
+}
+
+int32_t l2hmc_last_kernel_body(char* buf, int32_t n) {
+  if (!buf || n < 1) return fail(L2HMC_ERR_ARG, "l2hmc_last_kernel_body: bad argument%s");
+  snprintf(buf, (size_t)n, "%s", g_kernel_body);
+  return (int32_t)strlen(g_kernel_body);
 }
 
 const char* l2hmc_last_error(void) { return g_err; }

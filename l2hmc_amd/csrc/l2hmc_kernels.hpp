@@ -1135,6 +1135,7 @@ struct TrajPlan {
   bool half = false;        // tile: the last dimension slice holds <= 2 dimensions
   int DP = 0, HPR = 0, RES = 0;   // lane: compiled dimensions, hidden units per register pair, weight residency
   int f16 = 0;              // f16x2 contractions (PK / F16 of the fast, small and wide kernels)
+  bool one_wave = false;    // fast: the common-launch body under the one-workgroup-per-CU bound (traj_fast_cc_kernel)
   long long lds = 0;        // dynamic LDS bytes
 };
 
@@ -1198,6 +1199,8 @@ template <int EK>   // traj_kernel, traj_fast_kernel (f32-input MFMA), traj_smal
 int launch_ek(const TrajPlan& p, const KArgs& k, hipStream_t s);
 template <int EK>   // traj_fast_kernel<EK, ., ., ., 1>: traj_f16_ek<EK>.hip (diagonal Gaussian, Rough Well)
 int launch_fast16_ek(const TrajPlan& p, const KArgs& k, hipStream_t s);
+// traj_fast_cc_kernel<1, 1, 4, ., 1, 1>: traj_f16_one_wave.hip (diagonal Gaussian, one tile per wave, common launches)
+int launch_fast16_one_wave(const TrajPlan& p, const KArgs& k, hipStream_t s);
 template <int EK>   // traj_tile_kernel: traj_tile_inst.hip (diagonal Gaussian, Rough Well)
 int launch_tile_ek(const TrajPlan& p, const KArgs& k, hipStream_t s);
 template <int EK>   // traj_ladder_kernel: traj_ladder_ek<EK>.hip, apart from the plain kernels' units so that their code objects stay as they were

@@ -344,7 +344,9 @@ __device__ __forceinline__ f4 l1_part16(const f4 (&z)[DT], f4 acc, const WF16* W
 // a launch draws and writes is launch-uniform, but the general body tests it lane by lane at every proposal boundary; with CC
 // those tests are constants (traj_fast_kernel below picks the body by one uniform branch at entry).  The same statements either
 // way: the same bits.
-template <int EK, int DT, int NW, int KH, int PK, bool CC>
+// OW: what the one-workgroup-per-CU kernel (traj_fast_cc_kernel below) spends its register headroom on, a bit per item; 0 in every
+// other kernel.  Bit 0: both nets' tail fragments and constant rows are loaded once per launch, in front of the proposal loop.
+template <int EK, int DT, int NW, int KH, int PK, bool CC, int OW = 0>
 __device__ __forceinline__ void traj_fast_body(const KArgs& A);
 
 template <int EK, int DT, int NW, int KH, int PK = 0>
@@ -356,8 +358,11 @@ template <int EK, int DT, int NW, int KH, int PK = 0>
 // 450-630 bytes per lane to SCRATCH inside the step loop (`.amdhsa_private_segment_fixed_size`).  One wave per SIMD for DT = 2: the
 // overflow goes to AGPRs (v_accvgpr_*), no scratch -- Rough Well d = 32 / 16 384 chains 62.1 -> 39.4 us per proposal, d = 96 ... 128
 // 207 -> 160 (it had been SLOWER than the f32-input form it replaced: 44.9 / 181).  DT = 1 keeps the two-wave bound (8192 chains =
-// two workgroups per CU; and with 512 registers the scheduler's choices cost 5-7 % there), and so does the f32-input form of
-// DT = 2 (44-184 bytes of scratch; one wave per SIMD measured 5-9 % slower: dense Gaussian d = 32 41.9 -> 45.6 us).
+// two workgroups per CU), and so does the f32-input form of DT = 2 (44-184 bytes of scratch; one wave per SIMD measured 5-9 % slower:
+// dense Gaussian d = 32 41.9 -> 45.6 us).  The 5-7 % that 512 registers cost DT = 1 in round 6 were not the scheduler's choices: with
+// AGPRs in the budget the compiler takes the AGPR form of every MFMA result and copies each out with four v_accvgpr_read_b32 --
+// 60 VALU instructions more per step (524 against 464).  -mllvm -amdgpu-mfma-vgpr-form keeps the results in VGPRs; the launches
+// whose grid leaves one workgroup per CU take traj_fast_cc_kernel (below), compiled with it (profiles/sampler_one_wave.txt).
 #ifndef L2HMC_FAST_WAVES_DT2
 #define L2HMC_FAST_WAVES_DT2 1
 #endif
@@ -375,7 +380,20 @@ __global__ __launch_bounds__(64 * NW, (DT >= 2 && PK == 1) ? L2HMC_FAST_WAVES_DT
   }
 }
 
-template <int EK, int DT, int NW, int KH, int PK, bool CC>
+// The common-launch body under a bound of its own (WB workgroups per CU; PK stays the last argument: l2hmc_last_kernel's readers tell
+// the arithmetic by it).  WB = 1 for the launches whose grid has no more workgroups than the device has CUs -- the second workgroup the
+// two-wave bound of traj_fast_kernel keeps half of every SIMD's register file for never arrives there.  Its translation unit
+// (traj_f16_one_wave.hip) is compiled with -mllvm -amdgpu-mfma-vgpr-form: see the note at L2HMC_FAST_WAVES above.  The planner
+// (plan_trajectory) sends it common launches only, so the body is picked without the entry test.
+#ifndef L2HMC_ONE_WAVE_ITEMS
+#define L2HMC_ONE_WAVE_ITEMS 1
+#endif
+template <int EK, int DT, int NW, int KH, int WB, int PK>
+__global__ __launch_bounds__(64 * NW, WB) void traj_fast_cc_kernel(const KArgs A) {
+  traj_fast_body<EK, DT, NW, KH, PK, true, L2HMC_ONE_WAVE_ITEMS>(A);
+}
+
+template <int EK, int DT, int NW, int KH, int PK, bool CC, int OW>
 __device__ __forceinline__ void traj_fast_body(const KArgs& A) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   lds_poison(smem);
@@ -588,6 +606,18 @@ __device__ __forceinline__ void traj_fast_body(const KArgs& A) {
   bool fwd_n = (A.dir != nullptr && !rng_d) ? (live ? A.dir[chain] != 0 : true) : (A.dir_all != 0);
   float u_n = (A.u != nullptr && !rng_u && live) ? A.u[chain] : 0.f;
   const bool have_u = CC || A.u != nullptr || rng_u;
+  // OW bit 0: both nets' tails once per launch.  The backward direction's cS row is the forward one negated (fc[DPp + dim] = -cs
+  // above), so the forward row is held and every proposal flips its sign bit for the lanes that run backward: the same bits.
+  constexpr bool ONCE = (OW & 1) != 0;
+  static_assert(!ONCE || (DT == 1 && PK == 1), "tails once per launch: the one-tile f16x2 body only");
+  TailK<DT, F16> tkx1;
+  f4 cSx1[ONCE ? DT : 1], cSv1[ONCE ? DT : 1];
+  if constexpr (ONCE) {
+    load_tailk<DT>(tkx1, fwx, fcx, 0, NTp, w, lane);
+    load_tailk<DT>(tk, fwv, fcv, 0, NTp, w, lane);
+#pragma unroll
+    for (int t = 0; t < DT; ++t) { cSx1[t] = tkx1.cS[t]; cSv1[t] = tk.cS[t]; }
+  }
   for (int m = 0; m < A.M; ++m) {
     const long long moff = (long long)m * A.N;
     const unsigned long long prop = A.rng_prop0 + (unsigned long long)m;
@@ -649,12 +679,25 @@ __device__ __forceinline__ void traj_fast_body(const KArgs& A) {
     // the f32-input form of DT = 2, which spills under the two-wave bound already.  Same values, same arithmetic: same bits.
     // (Measured and not kept, profiles/sampler_invariant_work.txt: loading everything but the direction's cS row once per launch, in
     //  front of the proposal loop -- 20 ds_read_b128 fewer per proposal, and 0.7 % SLOWER at 4096 chains: the registers stay live
-    //  through the epilogue and the allocator's choices in the step loop change.)
+    //  through the epilogue and the allocator's choices in the step loop change.  The one-workgroup-per-CU body, whose step loop
+    //  it leaves alone, does it: ONCE above, 1.2 % faster there, profiles/sampler_one_wave.txt.)
     constexpr bool RT = DT == 1 || PK == 1;
     TailK<DT, F16> tkx;
-    if constexpr (RT) load_tailk<DT>(tkx, fwx, fcx, dofs, NTp, w, lane);
-    const TailK<DT, F16>& TKX = *(RT ? &tkx : &tk);
-    load_tailk<DT>(tk, fwv, fcv, dofs, NTp, w, lane);
+    if constexpr (RT && !ONCE) load_tailk<DT>(tkx, fwx, fcx, dofs, NTp, w, lane);
+    const TailK<DT, F16>& TKX = *(ONCE ? &tkx1 : RT ? &tkx : &tk);
+    if constexpr (ONCE) {
+      const int sb = fwd ? 0 : (int)0x80000000u;
+#pragma unroll
+      for (int t = 0; t < DT; ++t) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          tkx1.cS[t][r] = __int_as_float(__float_as_int(cSx1[t][r]) ^ sb);
+          tk.cS[t][r] = __int_as_float(__float_as_int(cSv1[t][r]) ^ sb);
+        }
+      }
+    } else {
+      load_tailk<DT>(tk, fwv, fcv, dofs, NTp, w, lane);
+    }
     // VNet's evaluation for the next step's first half-update rides beside this step's second one (tail_fast2 above; f16x2 with
     // resident tails; -DL2HMC_FAST_SERIAL_TAILS: four tails per step, one after the other)
 #ifndef L2HMC_FAST_SERIAL_TAILS
