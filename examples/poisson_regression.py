@@ -1,8 +1,9 @@
 """Poisson regression with the fused model criticism: the model of examples/loo_any_likelihood.py, sampled on the same slow
 path (a torch-callable energy with an analytic gradient), with `PoissonRegression`'s fused calls in the place of the torch
-log-likelihood matrix -- the (draws, rows) matrix is never formed.
+log-likelihood matrix -- the (draws, rows) matrix is never formed.  `--fused` samples on the fused target instead
+(`get_energy_function(fused=True)`: U and grad U inside the trajectory kernel, no torch callback per leapfrog step).
 
-    python examples/poisson_regression.py [--rows 200] [--chains 256] [--steps 200]
+    python examples/poisson_regression.py [--rows 200] [--chains 256] [--steps 200] [--fused]
 """
 import argparse
 import os
@@ -24,6 +25,7 @@ def main():
     ap.add_argument("--chains", type=int, default=256)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--burn-in", type=int, default=100)
+    ap.add_argument("--fused", action="store_true", help="sample on the fused Poisson target (default: the torch-callable slow path)")
     a = ap.parse_args()
     rng = np.random.RandomState(0)
     X = rng.randn(a.rows, a.dim) * 0.5
@@ -34,7 +36,7 @@ def main():
     model = PoissonRegression(X, y, offset=np.log(exposure), prior_var=4.0)
 
     dev = torch.device("cuda")
-    dyn = Dynamics(a.dim, model.get_energy_function(), T=10, eps=0.02, hmc=True, device=dev)
+    dyn = Dynamics(a.dim, model.get_energy_function(fused=a.fused), T=10, eps=0.02, hmc=True, device=dev)
     x0 = torch.zeros(a.chains, a.dim, device=dev)
     _, _, hist = sample_chain(x0, dyn, a.steps, seed=1, record=True)
     draws = hist[a.burn_in:]                                 # (steps, chains, dim): read where it lies

@@ -43,7 +43,8 @@ enum {
   L2HMC_ENERGY_ROUGHWELL = 4,   /* rough well                     distributions.py:84-97       */
   L2HMC_ENERGY_FUNNEL = 5,      /* Gaussian funnel                distributions.py:155-180     */
   /* (6 is the Python binding's tag of the VAE decoder posterior, which runs on the GEMM engine) */
-  L2HMC_ENERGY_LOGISTIC = 7     /* Bayesian logistic regression   (l2hmc_pack_logistic)        */
+  L2HMC_ENERGY_LOGISTIC = 7,    /* Bayesian logistic regression   (l2hmc_pack_logistic)        */
+  L2HMC_ENERGY_POISSON = 8      /* Bayesian Poisson regression, log link and offsets (l2hmc_pack_logistic) */
 };
 
 /* One S/T/Q network in the reference's own parameter layout: `Linear` keeps W as
@@ -77,6 +78,16 @@ typedef struct L2hmcNet {
  *                p_accept forms) only -- `variant` 8, 16, 32 return L2HMC_ERR_UNSUPPORTED; the training entry points return
  *                L2HMC_ERR_UNSUPPORTED for it.  The packed data is staged in LDS when it fits, else streamed from L2
  *                (L2HMC_LOGISTIC_LDS=0 in the environment: always streamed)
+ *   POISSON    : Bayesian Poisson regression with the log link on n data rows x_i (d features), counts y_i, per-row offsets o_i
+ *                (log exposure) and a N(0, sigma^2 I) prior:  with h_i = x_i . w + o_i and mu_i = exp(h_i),
+ *                        U(w) = sum_i [mu_i - y_i h_i] + |w|^2 / (2 sigma^2),   grad U = X^T (mu - y) + w / sigma^2;
+ *                n_comp = n (>= 1), mu = the buffer written by l2hmc_pack_logistic with the counts in the label slot (the buffer the
+ *                l2hmc_glm_* entries read), prec = the offsets: l2hmc_poisson_offset_floats(n) = 16 ceil(n / 16) floats, o_i then
+ *                zeros (required: pass zeros for a model without offsets), eta = sigma^2 (> 0), logc = NULL (ignored), easy = 0
+ *                (ignored).  d <= 128.  Runs where LOGISTIC runs, with the data and the offsets staged in LDS or streamed by the
+ *                same rule; exp overflows as IEEE float32 does (mu = inf: U and grad U are non-finite, the accept rule rejects).
+ *                Every training entry point returns L2HMC_ERR_UNSUPPORTED for it: train on the same likelihood as a
+ *                caller-supplied energy (energy_cb), then sample with the trained nets on this kind
  * temperature divides U and grad U (dynamics.py:204-212); 1.0 when unused.
  * anneal_beta in (0, 1): the AIS bridge of utils/ais.py:46-47 with the standard-normal initial
  * energy its caller uses (eval_vae.py:55-56):  U := (1 - beta) |x|^2 / 2 + beta U(x);  0 (or 1) = off. */
@@ -242,6 +253,8 @@ int l2hmc_pack_gaussian(const float* i_sigma, int32_t d, float* packed, void* st
  * 1 ... 128, a NULL buffer. */
 int64_t l2hmc_packed_logistic_floats(int32_t n_data, int32_t d);
 int l2hmc_pack_logistic(const float* X, const float* y, int32_t n_data, int32_t d, float* packed, void* stream);
+/* Floats of the offset buffer of L2HMC_ENERGY_POISSON (L2hmcEnergy.prec): 16 ceil(n_data / 16), the tail zero-padded. */
+int64_t l2hmc_poisson_offset_floats(int32_t n_data);
 
 /* The fused generalised-leapfrog trajectory:
  *   Dynamics.forward / .backward           dynamics.py:246-300  (n_steps = T)

@@ -5,7 +5,7 @@
 //   stage    element e is (draw e / d, feature e % d), walked without a division, written to the wave's own LDS region as
 //            [16 draws][16 NTM + 4]; feature columns d .. 16 NTM - 1 are zeroed once and never written: they add nothing;
 //   logits   lane (c, q) reads the B operand {w[16 t + c][16 tg + 4 q + r]} with one 16-byte LDS read per feature tile and gets
-//            L^T[i, c] in C/D layout (f32-input MFMA, the operand layouts of logistic_grad in l2hmc_kernels.hpp): the logits of
+//            L^T[i, c] in C/D layout (f32-input MFMA, the operand layouts of regression_grad in l2hmc_kernels.hpp): the logits of
 //            draw c, rows 4 q + r of each data block, feature tiles added in the order tg = 0 .. NT - 1 onto zero;
 //   end      once per wave the 16 draw lanes of every float64 sum are added through LDS in the order c = 0 .. 15 and go to
 //            part[chunk][K][n]; chunk_reduce_kernel then adds the chunks' partials in chunk order.  No floating-point atomics.

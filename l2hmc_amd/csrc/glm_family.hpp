@@ -21,6 +21,8 @@ namespace l2hmc {
 // Poisson regression with the log link and an offset (log exposure) o_i:
 //     h = eta + o_i    mu = exp(h)    ll = y_i h - mu - g_i,   g_i = lgamma(y_i + 1) (float64 on the host, rounded once)
 // Four roundings: the sum h, the product h log2(e) inside fexp (then the hardware exp2), the fused y h - mu, the difference.
+// The family's second statement is PoissonLink in l2hmc_kernels.hpp (the ENERGY of the fused sampling target, L2HMC_ENERGY_POISSON):
+// it forms h and mu by these same two operations, so a trajectory moves on the mu these statistics evaluate.  Change both or neither.
 struct PoissonLog {
   static constexpr int kAbi = 1;          // L2HMC_GLM_POISSON
   static __device__ __forceinline__ float ll(float eta, float y, float o, float g) {

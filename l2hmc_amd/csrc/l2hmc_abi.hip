@@ -344,7 +344,7 @@ long long plan_lds(KArgs& k, bool with_nets, bool with_schedule, int NW, int DT)
   if (NW > 1) o += 2LL * NW * 256;       // 2 buffers x NW waves x 1 partial vector
   k.xb_stride = DP + 4;
   k.o_XB = (int)o;
-  const bool lr = k.ekind == L2HMC_ENERGY_LOGISTIC;
+  const bool lr = is_data_regression(k.ekind);
   if (NW > 1 && (k.ekind == L2HMC_ENERGY_GAUSS_DENSE || k.ekind == L2HMC_ENERGY_GMM || lr))
     o += 16LL * k.xb_stride;
   k.o_red = (int)o;
@@ -356,13 +356,14 @@ long long plan_lds(KArgs& k, bool with_nets, bool with_schedule, int NW, int DT)
   if (k.ekind == L2HMC_ENERGY_GAUSS_DIAG) o += DP;
   if ((k.ekind == L2HMC_ENERGY_GAUSS_DENSE || k.ekind == L2HMC_ENERGY_GMM) && !wg)
     o += (long long)nc * gauss_floats(NT);
-  if (lr && NW > 1) o += (long long)NW * NT * 256;      // logistic regression: every wave's partial gradient of all tiles
+  if (lr && NW > 1) o += (long long)NW * NT * 256;      // data regression: every wave's partial gradient of all tiles
   k.o_logc = (int)o;
   o += round4(nc);
   if (lr) {
     // the data fragments staged in LDS when they fit beside everything else (the ladder's tables included), else streamed
     // from L2 by every gradient; L2HMC_LOGISTIC_LDS=0 in the environment always streams (read per call: tests run both paths)
-    const long long need = logistic_floats(k.ncomp, k.d);
+    // (Poisson regression: the offsets go with the data, 16 floats per block behind the last one)
+    const long long need = logistic_floats(k.ncomp, k.d) + (k.ekind == L2HMC_ENERGY_POISSON ? poisson_offset_floats(k.ncomp) : 0);
     const char* env = getenv("L2HMC_LOGISTIC_LDS");
     k.easy = !(env != nullptr && env[0] == '0') && (o + need + kLadLds) * 4 <= kMaxLdsBytes;
     if (k.easy) {
@@ -446,6 +447,16 @@ int check_energy(const L2hmcEnergy* e, int d) {
       if (!(e->eta > 0.f) || !(e->eta <= 3.402823466e38f))
         return fail(L2HMC_ERR_ARG, "logistic regression needs eta = prior variance sigma^2 > 0 and finite%s");
       break;
+    case L2HMC_ENERGY_POISSON:
+      if (!e->mu) return fail(L2HMC_ERR_ARG, "Poisson regression needs the packed data (mu, l2hmc_pack_logistic with the counts as labels)%s");
+      if (!e->prec)
+        return fail(L2HMC_ERR_ARG, "Poisson regression needs the offsets (prec: l2hmc_poisson_offset_floats(n_data) floats, zeros for none)%s");
+      if (e->n_comp < 1 || e->n_comp > kLogisticMaxRows)
+        return fail(L2HMC_ERR_ARG, "Poisson regression needs 1 <= n_comp = n_data <= 1048576 (got %s%lld)", "", e->n_comp);
+      if (d > kLogisticMaxDim) return fail(L2HMC_ERR_ARG, "Poisson regression supports d <= 128 (got %s%lld)", "", d);
+      if (!(e->eta > 0.f) || !(e->eta <= 3.402823466e38f))
+        return fail(L2HMC_ERR_ARG, "Poisson regression needs eta = prior variance sigma^2 > 0 and finite%s");
+      break;
     default:
       return fail(L2HMC_ERR_ARG, "unknown energy kind %s%lld", "", e->kind);
   }
@@ -456,8 +467,8 @@ int check_energy(const L2hmcEnergy* e, int d) {
 
 void fill_energy(KArgs& k, const L2hmcEnergy* e) {
   k.ekind = e->kind;
-  k.ncomp = (e->kind == L2HMC_ENERGY_GMM || e->kind == L2HMC_ENERGY_LOGISTIC) ? e->n_comp : 1;
-  k.easy = e->kind == L2HMC_ENERGY_LOGISTIC ? 0 : e->easy;     // (logistic regression: "staged in LDS", set by plan_lds)
+  k.ncomp = (e->kind == L2HMC_ENERGY_GMM || is_data_regression(e->kind)) ? e->n_comp : 1;
+  k.easy = is_data_regression(e->kind) ? 0 : e->easy;     // (data regression: "staged in LDS", set by plan_lds)
   k.mu = e->mu;
   k.prec = e->prec;
   k.logc = e->logc;
@@ -502,7 +513,7 @@ bool pick_geometry(int d, long long N, int v, int& DT, int& NW, int cus = 0) {
   return NT <= 32;
 }
 
-// Logistic regression: four waves per 16-chain tile, 1 or 2 state tiles each -- the data contractions dominate the kernel and its
+// Logistic and Poisson regression: four waves per 16-chain tile, 1 or 2 state tiles each -- the data contractions dominate the kernel and its
 // waves split the data blocks among themselves (one wave per tile would stream all of X alone).  Geometry v = 1 (variant 101):
 // one wave, d <= 16 only (wider one-wave forms carry 2-4 tiles of state next to the contraction's fragments and spill).
 bool pick_geometry_logistic(int d, int v, int& DT, int& NW) {
@@ -516,7 +527,7 @@ bool pick_geometry_logistic(int d, int v, int& DT, int& NW) {
   return v == 0 || DT == 1;
 }
 bool pick_geometry_of(int ekind, int d, long long N, int v, int& DT, int& NW, int cus = 0) {
-  return ekind == L2HMC_ENERGY_LOGISTIC ? pick_geometry_logistic(d, v, DT, NW) : pick_geometry(d, N, v, DT, NW, cus);
+  return is_data_regression(ekind) ? pick_geometry_logistic(d, v, DT, NW) : pick_geometry(d, N, v, DT, NW, cus);
 }
 
 // The environment's overrides of the selection rules, read at the top of every l2hmc_trajectory call (and nowhere else).
@@ -580,10 +591,12 @@ static int plan_trajectory(const L2hmcTrajectoryArgs& a, KArgs& k, int KH, int c
   p.KH = KH <= 3 ? 3 : 4;
   const bool nets = a.packed_nets != nullptr, has_u = a.u != nullptr || (a.rng_flags & L2HMC_RNG_U);
   const bool plain = k.beta == 1.f && k.temperature == 1.f;     // neither tempered nor annealed
-  // logistic regression: the general kernel only (the data contractions live in its grad U)
-  const bool lr = k.ekind == L2HMC_ENERGY_LOGISTIC;
+  // logistic / Poisson regression: the general kernel only (the data contractions live in its grad U)
+  const bool lr = is_data_regression(k.ekind);
   if (lr && (v.forced == FAM_LANE || v.forced == FAM_WIDE || v.forced == FAM_TILE))
-    return fail(L2HMC_ERR_UNSUPPORTED, "variant %s%lld: the logistic-regression target runs on the general kernel only (variant 0 or 100 + v)",
+    return fail(L2HMC_ERR_UNSUPPORTED, k.ekind == L2HMC_ENERGY_POISSON
+                    ? "variant %s%lld: the Poisson-regression target runs on the general kernel only (variant 0 or 100 + v)"
+                    : "variant %s%lld: the logistic-regression target runs on the general kernel only (variant 0 or 100 + v)",
                 "", v.value);
   if (lr) {
     int rc = plan_geometry(a, v, cus, p);
@@ -743,7 +756,7 @@ static int launch_plan(const TrajPlan& p, const KArgs& k, hipStream_t s, const L
   return on_energy_kind(p.ek, [&](auto ek) {
     constexpr int EK = decltype(ek)::value;
     if (p.family == FAM_LADDER) return launch_ladder_ek<EK>(p, k, *lg, s);
-    if constexpr (EK != L2HMC_ENERGY_FUNNEL && EK != L2HMC_ENERGY_LOGISTIC) {
+    if constexpr (EK != L2HMC_ENERGY_FUNNEL && !is_data_regression(EK)) {
       if (p.family == FAM_LANE) return launch_lane_ek<EK>(p, k, s);
       if (p.family == FAM_WIDE) return launch_wide_ek<EK>(p, k, s);
     }
@@ -855,6 +868,11 @@ int64_t l2hmc_packed_logistic_floats(int32_t n_data, int32_t d) {
   if (n_data < 1 || n_data > kLogisticMaxRows) return fail(L2HMC_ERR_ARG, "logistic regression: 1 <= n_data <= 1048576 (got %s%lld)", "", n_data);
   if (d < 1 || d > kLogisticMaxDim) return fail(L2HMC_ERR_ARG, "logistic regression: 1 <= d <= 128 (got %s%lld)", "", d);
   return logistic_floats(n_data, d);
+}
+
+int64_t l2hmc_poisson_offset_floats(int32_t n_data) {
+  if (n_data < 1 || n_data > kLogisticMaxRows) return fail(L2HMC_ERR_ARG, "Poisson regression: 1 <= n_data <= 1048576 (got %s%lld)", "", n_data);
+  return poisson_offset_floats(n_data);
 }
 
 int l2hmc_pack_logistic(const float* X, const float* y, int32_t n_data, int32_t d, float* packed, void* stream) {

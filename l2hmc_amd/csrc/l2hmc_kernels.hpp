@@ -79,6 +79,10 @@ __device__ __forceinline__ void lds_poison(float* smem) {
 #endif
 }
 int check_energy(const L2hmcEnergy* e, int d);
+// what every training entry point answers for L2HMC_ENERGY_POISSON (no kernel holds its Hessian-vector product X^T [mu (X u)])
+constexpr const char* kPoissonTrainRefusal =
+    "no training kernel for the Poisson-regression target: train on the same likelihood as a caller-supplied energy "
+    "(energy_cb / hvp_cb of l2hmc_train_split_grad), then sample with the trained nets on the fused kind%s";
 int device_cus();      // l2hmc_abi.hip: compute units of the current device (256 when the query fails)
 struct KArgs;
 // traj_wide.hip: the LDS plan of the LDS-resident-state kernel for d > 256 (elementwise energies) and its waves per workgroup
@@ -112,6 +116,12 @@ constexpr int kLogisticMaxRows = 1 << 20;
 constexpr int kLogisticMaxDim = 128;      // the general kernel's register-resident geometries (NW * DT <= 8 tiles)
 __host__ __device__ inline int logistic_block_floats(int NT) { return 512 * NT + 16; }
 inline long long logistic_floats(int n, int d) { return (long long)((n + 15) / 16) * logistic_block_floats(tiles_of(d)); }
+// Bayesian Poisson regression (L2HMC_ENERGY_POISSON): the same packed buffer with the counts in the label slot, and the per-row
+// offsets beside it (L2hmcEnergy.prec): poisson_offset_floats(n) floats, 16 per data block, zero beyond n_data.
+__host__ __device__ inline int poisson_offset_floats(int n) { return 16 * ((n + 15) >> 4); }
+// The data-regression kinds: grad U is two contractions over the packed data (regression_grad) -- the general kernel only, four
+// waves splitting the data blocks, the data staged in LDS or streamed.  Every host rule and kernel branch for them asks this.
+__host__ __device__ constexpr bool is_data_regression(int ek) { return ek == L2HMC_ENERGY_LOGISTIC || ek == L2HMC_ENERGY_POISSON; }
 inline int khid_of(int H) { return (H + 1 + 3) / 4; }
 
 // ------------------------------------------------------------------------------------------
@@ -493,15 +503,53 @@ __device__ __forceinline__ void load_energy_regs(EnergyRegs<EK, DT>& er, const K
 // Wave w takes the data blocks w, w + NW, ... over ALL NT state tiles: with NW > 1 the state goes to LDS first (the exchange of
 // dense_matvec), and every wave's partial gradient of all tiles comes back through LDS, summed over the waves in wave order.
 // STAGED: the fragments are read from LDS (staged by stage_energy), else streamed from global memory / L2.
-template <int DT, int NW, bool STAGED>
-__device__ __forceinline__ float logistic_grad(const KArgs& A, float* smem, int w, int lane, const f4 (&x)[DT], f4 (&g)[DT],
-                                               bool wantU) {
+//
+// The body is regression_grad<Link, ...>: one body for every data-regression kind, the link between the two contractions a
+// small struct built from a row's linear predictor L, response y and offset o -- residual() is the row's entry of the
+// gradient contraction's B operand, u_term() its term of U (evaluated only when U is wanted).  kOffset: the kind has per-row
+// offsets (A.prec, 16 per data block).
+struct LogitLink {          // L2HMC_ENERGY_LOGISTIC
+  static constexpr bool kOffset = false;
+  float l, y, e, inv;
+  // r = sigmoid(L) - y with e = exp(-|L|): sigmoid = 1 / (1 + e) (L >= 0) or e / (1 + e); softplus(L) = max(L, 0) + log(1 + e)
+  __device__ __forceinline__ LogitLink(float L, float y_, float) : l(L), y(y_) {
+    e = fexp(-fabsf(l));
+    inv = __builtin_amdgcn_rcpf(1.f + e);
+  }
+  __device__ __forceinline__ float residual() const { return (l >= 0.f ? inv : e * inv) - y; }
+  __device__ __forceinline__ float u_term() const { return fmaf(-y, l, fmaxf(l, 0.f) + 0.6931471805599453f * __builtin_amdgcn_logf(1.f + e)); }
+};
+// L2HMC_ENERGY_POISSON, the log link with an offset: h = L + o, mu = exp(h), r = mu - y, U term mu - y h.  The family is stated
+// twice in this library: PoissonLog in glm_family.hpp (the log-likelihood and mean of the history statistics, glm.hip) and here
+// (the energy that is sampled).  h and mu are formed by PoissonLog's own operations -- __fadd_rn, then the hardware exp2 of fexp,
+// under `fp contract(off)` -- so the mu a trajectory moves on is the mu the statistics of its history evaluate; a change to one
+// statement is a change to the other.  Overflow is IEEE's: mu = inf gives a non-finite U and gradient, which the accept rule rejects.
+struct PoissonLink {
+  static constexpr bool kOffset = true;
+  float h, y, mu;
+  __device__ __forceinline__ PoissonLink(float L, float y_, float o) : y(y_) {
+#pragma clang fp contract(off)
+    h = __fadd_rn(L, o);
+    mu = fexp(h);
+  }
+  __device__ __forceinline__ float residual() const { return __fsub_rn(mu, y); }
+  __device__ __forceinline__ float u_term() const { return fmaf(-y, h, mu); }      // mu - y h, one rounding
+};
+template <class Link, int DT, int NW, bool STAGED>
+__device__ __forceinline__ float regression_grad(const KArgs& A, float* smem, int w, int lane, const f4 (&x)[DT], f4 (&g)[DT],
+                                                 bool wantU) {
   constexpr int NTM = NW * DT;              // compiled tiles (>= A.NT)
   const int NT = A.NT, n = A.ncomp, nblk = (n + 15) >> 4, BS = logistic_block_floats(NT);
   const int c = lane & 15, q = lane >> 4;
   const float* P;
   if constexpr (STAGED) P = smem + A.o_mu;
   else P = A.mu;
+  // the offsets: staged behind the data blocks (stage_energy), or the caller's buffer
+  [[maybe_unused]] const float* O = nullptr;
+  if constexpr (Link::kOffset) {
+    if constexpr (STAGED) O = P + (size_t)nblk * BS;
+    else O = A.prec;
+  }
   const float* XB = smem + A.o_XB;
   if constexpr (NW > 1) {
 #pragma unroll
@@ -524,6 +572,8 @@ __device__ __forceinline__ float logistic_grad(const KArgs& A, float* smem, int 
       xt[tg] = tg < NT ? lds4(blk + ((NT + tg) * 64 + lane) * 4) : splat(0.f);
     }
     const f4 y = lds4(blk + 512 * NT + 4 * q);
+    [[maybe_unused]] f4 off = splat(0.f);
+    if constexpr (Link::kOffset) off = lds4(O + 16 * ib + 4 * q);
     f4 L = splat(0.f);
 #pragma unroll
     for (int tg = 0; tg < NTM; ++tg) {
@@ -536,18 +586,16 @@ __device__ __forceinline__ float logistic_grad(const KArgs& A, float* smem, int 
         for (int r = 0; r < 4; ++r) L = MFMA16(xa[tg][r], B[r], L);
       }
     }
-    // r = sigmoid(L) - y with e = exp(-|L|): sigmoid = 1 / (1 + e) (L >= 0) or e / (1 + e); softplus(L) = max(L, 0) + log(1 + e)
+    // the residuals and U terms of this lane's four rows; rows beyond n_data are masked (a padded row would add softplus(0) or
+    // exp(0) to U)
     const int row0 = 16 * ib + 4 * q;
     f4 res;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const float l = L[r];
-      const float e = fexp(-fabsf(l));
-      const float inv = __builtin_amdgcn_rcpf(1.f + e);
-      const float sg = l >= 0.f ? inv : e * inv;
+      const Link row(L[r], y[r], off[r]);
       const bool live = row0 + r < n;
-      res[r] = live ? sg - y[r] : 0.f;
-      if (wantU) Ud += live ? fmaf(-y[r], l, fmaxf(l, 0.f) + 0.6931471805599453f * __builtin_amdgcn_logf(1.f + e)) : 0.f;
+      res[r] = live ? row.residual() : 0.f;
+      if (wantU) Ud += live ? row.u_term() : 0.f;
     }
 #pragma unroll
     for (int tg = 0; tg < NTM; ++tg) {
@@ -704,10 +752,12 @@ __device__ __forceinline__ void grad_energy(const KArgs& A, float* smem, int w, 
         U = 0.5f * (lp + sum_sq / s_eff + n * logf(6.283185307179586f * s_eff));
       }
     }
-  } else if constexpr (EK == L2HMC_ENERGY_LOGISTIC) {
+  } else if constexpr (is_data_regression(EK)) {
     {
-      // data term (the NLL of the labels), then the N(0, sigma^2 I) prior; padded dimensions hold x = 0 and add nothing
-      U = A.easy ? logistic_grad<DT, NW, true>(A, smem, w, lane, x, g, wantU) : logistic_grad<DT, NW, false>(A, smem, w, lane, x, g, wantU);
+      // data term (the NLL of the labels / counts), then the N(0, sigma^2 I) prior; padded dimensions hold x = 0 and add nothing
+      using Link = std::conditional_t<EK == L2HMC_ENERGY_POISSON, PoissonLink, LogitLink>;
+      U = A.easy ? regression_grad<Link, DT, NW, true>(A, smem, w, lane, x, g, wantU)
+                 : regression_grad<Link, DT, NW, false>(A, smem, w, lane, x, g, wantU);
       const float iv = 1.f / A.eta;
 #pragma unroll
       for (int t = 0; t < DT; ++t) {
@@ -1011,12 +1061,16 @@ __device__ __forceinline__ void stage_energy(const KArgs& A, float* smem, int ti
     }
     if (EK == L2HMC_ENERGY_GMM)
       for (int i = tid; i < nc; i += nthr) smem[A.o_logc + i] = A.logc[i];
-  } else if (EK == L2HMC_ENERGY_LOGISTIC) {
+  } else if (is_data_regression(EK)) {
     if (A.easy) {
       const int n4 = ((A.ncomp + 15) >> 4) * logistic_block_floats(A.NT) / 4;
       const f4* src = reinterpret_cast<const f4*>(A.mu);
       f4* dst = reinterpret_cast<f4*>(smem + A.o_mu);
       for (int i = tid; i < n4; i += nthr) dst[i] = src[i];
+      if (EK == L2HMC_ENERGY_POISSON) {      // the offsets behind the data blocks (regression_grad reads them there)
+        const f4* so = reinterpret_cast<const f4*>(A.prec);
+        for (int i = tid; i < poisson_offset_floats(A.ncomp) / 4; i += nthr) dst[n4 + i] = so[i];
+      }
     }
   }
 }
@@ -1038,7 +1092,7 @@ enum { LAD_TEMP = 0, LAD_U = 16, LAD_LAB = 32, LAD_INV = 48, LAD_TRIP = 64, LAD_
 // (logistic regression keeps all 512 at every DT: its data contractions hold the state of every tile of the workgroup, the
 //  prefetched fragments and the partial gradients on top of the trajectory's registers -- under the 256 cap they spilled)
 template <int EK, int DT>
-constexpr int traj_waves_per_simd() { return (DT <= 2 && EK != L2HMC_ENERGY_LOGISTIC) ? L2HMC_WAVES_PER_SIMD : 1; }
+constexpr int traj_waves_per_simd() { return (DT <= 2 && !is_data_regression(EK)) ? L2HMC_WAVES_PER_SIMD : 1; }
 template <int EK, int DT, int NW, int KH>
 __global__ __launch_bounds__(64 * NW, (traj_waves_per_simd<EK, DT>())) void traj_kernel(const KArgs A) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -1164,7 +1218,8 @@ template <auto V> using ic = std::integral_constant<decltype(V), V>;
 template <auto A, auto B, class F>
 int on_either(bool first, F&& f) { return first ? f(ic<A>{}) : f(ic<B>{}); }
 
-// f(ic<EK>) for a built-in energy kind (L2HMC_ENERGY_GAUSS_DIAG = 1 ... L2HMC_ENERGY_FUNNEL = 5, L2HMC_ENERGY_LOGISTIC = 7)
+// f(ic<EK>) for a built-in energy kind (L2HMC_ENERGY_GAUSS_DIAG = 1 ... L2HMC_ENERGY_FUNNEL = 5, L2HMC_ENERGY_LOGISTIC = 7,
+// L2HMC_ENERGY_POISSON = 8)
 template <class F>
 int on_energy_kind(int ek, F&& f) {
   switch (ek) {
@@ -1174,6 +1229,7 @@ int on_energy_kind(int ek, F&& f) {
     case 4: return f(ic<4>{});
     case 5: return f(ic<5>{});
     case 7: return f(ic<7>{});
+    case 8: return f(ic<8>{});
   }
   return fail(L2HMC_ERR_ARG, "unknown energy kind%s");
 }
@@ -1182,7 +1238,7 @@ int on_energy_kind(int ek, F&& f) {
 template <int DT_, int NW_> struct Geom { static constexpr int DT = DT_, NW = NW_; };
 template <class... G> struct Geoms {};
 using GeneralGeoms = Geoms<Geom<1, 1>, Geom<2, 1>, Geom<4, 1>, Geom<1, 4>, Geom<2, 4>, Geom<4, 4>, Geom<8, 4>>;
-// logistic regression (d <= 128): four waves with one or two state tiles each, and one wave for d <= 16 (variant 101)
+// the data-regression kinds (d <= 128): four waves with one or two state tiles each, and one wave for d <= 16 (variant 101)
 using LogisticGeoms = Geoms<Geom<1, 1>, Geom<1, 4>, Geom<2, 4>>;
 using FastGeoms = Geoms<Geom<1, 1>, Geom<2, 1>, Geom<1, 4>, Geom<2, 4>, Geom<2, 2>>;
 

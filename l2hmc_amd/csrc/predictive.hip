@@ -4,7 +4,7 @@
 //     p1 = sigmoid(l)    lik = sigmoid(z)    ll = log lik = min(z, 0) - log(1 + exp(-|l|))
 //     sums (4, n) float64 = sum_s p1, sum_s lik, sum_s ll, sum_s ll^2
 // l2hmc_amd/predictive.py turns the sums into numbers; include/l2hmc.h states the contract.  The (S, n) matrix of log-likelihoods
-// is never written: the logit contraction (f32-input MFMA, the operand layouts of logistic_grad in l2hmc_kernels.hpp) is fused
+// is never written: the logit contraction (f32-input MFMA, the operand layouts of regression_grad in l2hmc_kernels.hpp) is fused
 // with the reduction over draws.
 //
 // Work unit = one WAVE: a group of NB consecutive 16-row data blocks x a chunk of consecutive 16-draw tiles.  The wave keeps the

@@ -421,7 +421,7 @@ __device__ __forceinline__ void t_net_bwd(const TCtx& X, const float* W, float* 
 // One wave's share of  X^T f(X z)  for the 16 chains: it takes the 16-row data blocks wave, wave + 4, ... of the packed data P
 // (l2hmc_pack_logistic, layout at logistic_block_floats; streamed from global memory / L2) over all tD state tiles and leaves
 // its partial (16, ldd) result in `part`; the caller sums the four partials in wave order.  Per block two f32 MFMA contractions
-// with no LDS trip between them, exactly as logistic_grad (l2hmc_kernels.hpp) runs them in the trajectory kernel:
+// with no LDS trip between them, exactly as regression_grad (l2hmc_kernels.hpp) runs them in the trajectory kernel:
 //   logits  L^T[i, c] = sum_k XA[i, k] z[c, k]   -- B operand: lane (c, q) reads z[c][16 tg + 4 q + r] from the LDS matrix; the
 //           result is in C/D layout, lane (c, q) holding data rows 4 q + r of the block,
 //   result  o^T[k, c] += sum_i XT[k, i] f[i, c]  -- that C/D layout is the B operand (k-step r = row 4 q + r) of this one, so
@@ -429,7 +429,7 @@ __device__ __forceinline__ void t_net_bwd(const TCtx& X, const float* W, float* 
 //           HV: f = s (1 - s) (X u), a third contraction M^T = XA u^T sharing the A operand (the data term of Hessian(z) u).
 // A padded data row is a zero row of XA and a zero column of XT: it adds nothing to either result and is masked only in U
 // (softplus(0) = log 2 per row).  wantU (!HV, wave-uniform): this lane's share of the data term of U goes to Upart[wave * 64 + lane].
-// sigmoid / softplus are logistic_grad's forms (one v_exp_f32, one v_rcp_f32, log1p as v_log_f32(1 + e)).
+// sigmoid / softplus are regression_grad's forms (one v_exp_f32, one v_rcp_f32, log1p as v_log_f32(1 + e)).
 constexpr int TLNT = kLogisticMaxDim / 16;      // compiled state tiles (>= tD)
 template <bool HV>
 __device__ __forceinline__ void t_logistic(const TCtx& X, const float* P, int n, const float* z, const float* u, float* part,
@@ -1179,7 +1179,7 @@ static int launch_train(const TrainPlan& p, const TArgs& k, long long blocks, hi
       return on_either<1, 4>(p.NW == 1, [&](auto NW) {
         return on_energy_kind(p.ek, [&](auto ek) {
           constexpr int EK = decltype(ek)::value;
-          if constexpr (NW == 1 && EK != L2HMC_ENERGY_FUNNEL && EK != L2HMC_ENERGY_LOGISTIC) {
+          if constexpr (NW == 1 && EK != L2HMC_ENERGY_FUNNEL && !is_data_regression(EK)) {
             if (p.family == FAM_SMALL) return launch_kernel(train_small_kernel<EK, KH, TEMP>, blocks, 128, p.lds, s, k);
           }
           if constexpr (EK == L2HMC_ENERGY_GAUSS_DIAG || EK == L2HMC_ENERGY_ROUGHWELL ||
@@ -1256,6 +1256,7 @@ int64_t l2hmc_train_grad_floats(int32_t d, int32_t H) {
 
 int64_t l2hmc_train_fused_lds_bytes(int32_t ek, int32_t n_comp, int32_t d, int32_t H, int32_t T) {
   if (d < 1 || H < 1 || T < 1) return fail(L2HMC_ERR_ARG, "l2hmc_train_fused_lds_bytes: bad argument%s");
+  if (ek == L2HMC_ENERGY_POISSON) return fail(L2HMC_ERR_UNSUPPORTED, kPoissonTrainRefusal);
   if (ek != L2HMC_ENERGY_GAUSS_DIAG && ek != L2HMC_ENERGY_GAUSS_DENSE && ek != L2HMC_ENERGY_GMM &&
       ek != L2HMC_ENERGY_ROUGHWELL && ek != L2HMC_ENERGY_FUNNEL)
     return fail(L2HMC_ERR_UNSUPPORTED, "no fused training kernel for this energy kind%s");
@@ -1307,6 +1308,7 @@ static int train_launch(const L2hmcTrainArgs* a, const L2hmcTrainStep* st, void*
       !a->grad || !a->workspace)
     return fail(L2HMC_ERR_ARG, "l2hmc_train_propose_grad: NULL pointer%s");
   const int ek = a->energy.kind;
+  if (ek == L2HMC_ENERGY_POISSON) return fail(L2HMC_ERR_UNSUPPORTED, kPoissonTrainRefusal);
   if (ek != L2HMC_ENERGY_GAUSS_DIAG && ek != L2HMC_ENERGY_GAUSS_DENSE && ek != L2HMC_ENERGY_GMM &&
       ek != L2HMC_ENERGY_ROUGHWELL && ek != L2HMC_ENERGY_FUNNEL && ek != L2HMC_ENERGY_LOGISTIC)
     return fail(L2HMC_ERR_UNSUPPORTED, "training supports the Gaussian, GMM, Rough-Well, funnel and logistic-regression targets (analytic Hessian-vector products)%s");

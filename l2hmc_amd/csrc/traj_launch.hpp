@@ -13,16 +13,17 @@ int launch_tiles(K kern, int NW, const TrajPlan& p, const KArgs& k, hipStream_t 
   return launch_kernel(kern, (k.N + 15) / 16, 64 * NW, p.lds, s, k, extra...);
 }
 
-// the general kernel's geometries for energy kind EK (logistic regression: d <= 128, at most 8 tiles per workgroup)
+// the general kernel's geometries for energy kind EK (data regression: d <= 128, at most 8 tiles per workgroup)
 template <int EK>
-using GeneralGeomsOf = std::conditional_t<EK == L2HMC_ENERGY_LOGISTIC, LogisticGeoms, GeneralGeoms>;
+using GeneralGeomsOf = std::conditional_t<is_data_regression(EK), LogisticGeoms, GeneralGeoms>;
 
 template <int EK>
 int launch_ek(const TrajPlan& p, const KArgs& k, hipStream_t s) {
-  // (logistic regression: the general, energy and p_accept kernels only -- no instruction-lean or small-d form)
-  if constexpr (EK == L2HMC_ENERGY_LOGISTIC) {
+  // (logistic / Poisson regression: the general, energy and p_accept kernels only -- no instruction-lean or small-d form)
+  if constexpr (is_data_regression(EK)) {
     if (p.family != FAM_GENERAL && p.family != FAM_ENERGY && p.family != FAM_PACCEPT)
-      return fail(L2HMC_ERR_UNSUPPORTED, "the logistic-regression target runs on the general kernel only%s");
+      return fail(L2HMC_ERR_UNSUPPORTED, EK == L2HMC_ENERGY_POISSON ? "the Poisson-regression target runs on the general kernel only%s"
+                                                                     : "the logistic-regression target runs on the general kernel only%s");
   }
   switch (p.family) {
     case FAM_GENERAL:
@@ -30,14 +31,14 @@ int launch_ek(const TrajPlan& p, const KArgs& k, hipStream_t s) {
         return on_either<3, 4>(p.KH == 3, [&](auto KH) { return launch_tiles(traj_kernel<EK, DT, NW, KH>, NW, p, k, s); });
       });
     case FAM_FAST:
-      if constexpr (EK != L2HMC_ENERGY_LOGISTIC) {     // (refused above: not instantiated)
+      if constexpr (!is_data_regression(EK)) {     // (refused above: not instantiated)
         return on_geometry(FastGeoms{}, p.DT, p.NW, "fast ", [&](auto DT, auto NW) {
           return on_either<3, 4>(p.KH == 3, [&](auto KH) { return launch_tiles(traj_fast_kernel<EK, DT, NW, KH>, NW, p, k, s); });
         });
       }
       break;
     case FAM_SMALL:
-      if constexpr (EK == L2HMC_ENERGY_FUNNEL || EK == L2HMC_ENERGY_LOGISTIC) {
+      if constexpr (EK == L2HMC_ENERGY_FUNNEL || is_data_regression(EK)) {
         return fail(L2HMC_ERR_UNSUPPORTED, "no small-d kernel for the funnel%s");
       } else {
         return on_either<3, 4>(p.KH == 3, [&](auto KH) {

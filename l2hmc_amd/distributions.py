@@ -187,6 +187,32 @@ class LogisticEnergy(EnergyFunction):
         return self._dev[key]
 
 
+class PoissonEnergy(EnergyFunction):
+    """U(w) = sum_i [exp(h_i) - y_i h_i] + |w|^2 / (2 prior_var), h_i = x_i . w + offset_i, on the fused kernels
+    (L2HMC_ENERGY_POISSON): the data set is packed once per device into the buffer `LogisticEnergy` uses, the counts in its
+    label slot (`l2hmc_pack_logistic`: what `glm.Glm` packs for the history statistics), and the offsets go beside it, zero-padded
+    to whole 16-row blocks (`l2hmc_poisson_offset_floats`; L2hmcEnergy.prec)."""
+
+    def __init__(self, X, y, offset, prior_var):
+        n, d = X.shape
+        EnergyFunction.__init__(self, _ffi.ENERGY_POISSON, d, n_comp=n, eta=prior_var)
+        self._host = {'X': X, 'y': y, 'offset': np.zeros(n, dtype=np.float32) if offset is None else offset}
+
+    def _buffers(self, device):
+        key = str(device)
+        if key not in self._dev:
+            L = _ffi.lib()
+            X = torch.as_tensor(np.ascontiguousarray(self._host['X'], dtype=np.float32), device=device)
+            y = torch.as_tensor(np.ascontiguousarray(self._host['y'], dtype=np.float32), device=device)
+            n, d = X.shape
+            packed = torch.empty(_ffi.check(L.l2hmc_packed_logistic_floats(n, d)), dtype=torch.float32, device=device)
+            _ffi.check(L.l2hmc_pack_logistic(X.data_ptr(), y.data_ptr(), n, d, packed.data_ptr(), _ffi.current_stream(device)))
+            off = torch.zeros(_ffi.check(L.l2hmc_poisson_offset_floats(n)), dtype=torch.float32, device=device)
+            off[:n] = torch.as_tensor(np.ascontiguousarray(self._host['offset'], dtype=np.float32), device=device)
+            self._dev[key] = {'mu': packed, 'prec': off, 'logc': None, '_X': X, '_y': y}
+        return self._dev[key]
+
+
 class LogisticRegression(object):
     """Bayesian logistic regression: labels y_i in {0, 1} with P(y_i = 1 | w) = sigmoid(x_i . w) and a N(0, prior_var I) prior
     on the weights w (d = X.shape[1] <= 128 features; add a column of ones for an intercept).  The posterior's energy
@@ -265,10 +291,16 @@ class PoissonRegression(object):
 
         U(w) = sum_i [exp(x_i . w + o_i) - y_i (x_i . w + o_i)] + |w|^2 / (2 prior_var)
 
-    is NOT fused into the trajectory kernels: `get_energy_function()` is a `UserEnergy` with the analytic gradient
-    X^T (mu - y) + w / prior_var as differentiable torch code, so sampling, `warmup` and the GEMM-engine `Trainer` run on the
-    slow path.  Everything computed FROM the recorded history is fused HIP (csrc/glm.hip; `l2hmc_amd.glm`): the predictive
-    mean, WAIC and PSIS-LOO never form the (draws, rows) log-likelihood matrix."""
+    and its gradient X^T (mu - y) + w / prior_var exist in two forms.  `get_energy_function(fused=True)` is a `PoissonEnergy`:
+    U and grad U fused into the general trajectory kernel (L2HMC_ENERGY_POISSON: the two f32 MFMA contractions over the packed
+    data of the logistic-regression target with the log link between them), so HMC and L2HMC sampling, `warmup`, parallel
+    tempering and AIS run on it like on any built-in target; exp overflows as float32 does, and a proposal whose energy is
+    not finite is rejected.  `get_energy_function()` -- the default -- is a `UserEnergy` with the same gradient as
+    differentiable torch code: the slow path (one host round trip per leapfrog step), and the one a sampler TRAINS on, since
+    no training kernel holds the Hessian-vector product X^T [mu (X u)]: `Trainer(dynamics)` on the slow-path energy, then
+    `load_state_dict` into a `Dynamics` on the fused one.  Everything computed FROM the recorded history is fused HIP
+    (csrc/glm.hip; `l2hmc_amd.glm`): the predictive mean, WAIC and PSIS-LOO never form the (draws, rows) log-likelihood matrix,
+    and they evaluate mu by the very float32 operations the fused energy uses."""
 
     def __init__(self, X, y, offset=None, prior_var=1.0):
         from . import glm
@@ -318,7 +350,11 @@ class PoissonRegression(object):
         X, y, o = self._data(x)
         return (torch.exp(x @ X.t() + o) - y) @ X + x / self.prior_var
 
-    def get_energy_function(self):
+    def get_energy_function(self, fused=False):
+        """The posterior's energy: a `UserEnergy` (torch code, the slow path; what `Trainer` takes), or with `fused=True` a
+        `PoissonEnergy` on the fused trajectory kernels (sampling, warm-up, tempering, AIS)."""
+        if fused:
+            return PoissonEnergy(self.X, self.y, self.offset, self.prior_var)
         return UserEnergy(self.energy, self.grad_energy, x_dim=self.dim)
 
     def log_density(self, W):
