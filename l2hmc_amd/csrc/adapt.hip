@@ -168,12 +168,6 @@ __global__ void adapt_finish_kernel(double* st, float* alpha) {
   *alpha = (float)st[kSLogEps];
 }
 
-static int adapt_launched() {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(L2HMC_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
-  return L2HMC_OK;
-}
-
 }  // namespace l2hmc
 
 using namespace l2hmc;
@@ -198,7 +192,7 @@ int l2hmc_adapt_init(double* state, const float* alpha, int32_t search, double t
   if (!(log_eps_min < log_eps_max)) return fail(L2HMC_ERR_ARG, "l2hmc_adapt_init: log_eps_min must be below log_eps_max%s");
   hipLaunchKernelGGL(adapt_init_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, state, alpha, (int)search, target_accept,
                      gamma, t0, kappa, log_eps_min, log_eps_max);
-  return adapt_launched();
+  return launched();
 }
 
 int l2hmc_adapt_update(const float* p, int64_t n, int32_t mode, double* sums2, double* state, float* alpha, double* trace_row4,
@@ -221,13 +215,13 @@ int l2hmc_adapt_update(const float* p, int64_t n, int32_t mode, double* sums2, d
     hipLaunchKernelGGL(adapt_update_kernel<float>, dim3(1), dim3(reduce ? kAdThreads : 64), 0, s, p, (long long)n, (long long)n,
                        (int)mode, sums2, state, alpha, trace_row4);
   }
-  return adapt_launched();
+  return launched();
 }
 
 int l2hmc_adapt_finish(double* state, float* alpha, void* stream) {
   if (!state || !alpha) return fail(L2HMC_ERR_ARG, "l2hmc_adapt_finish: state and alpha are required%s");
   hipLaunchKernelGGL(adapt_finish_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, state, alpha);
-  return adapt_launched();
+  return launched();
 }
 
 }  // extern "C"

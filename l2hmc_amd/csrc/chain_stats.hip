@@ -327,9 +327,7 @@ int l2hmc_chain_stats(const float* X, int64_t steps, int64_t n_chains, int32_t d
                      p.J, p.Mh, p.row0[1], (int)d, p.nslot, p.nchunks, (int)max_lag, (const double*)mean_out, workspace);
   hipLaunchKernelGGL(chain_lagsum_reduce_kernel, dim3((unsigned)((d * nlag + 255) / 256)), dim3(256), 0, s,
                      (const double*)workspace, p.nb * p.halves, p.nb, (int)d, p.nslot, nlag, G_out);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(L2HMC_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
-  return L2HMC_OK;
+  return launched();
 }
 
 int l2hmc_chain_stats_below(const float* X, int64_t steps, int64_t n_chains, int32_t d, int32_t max_lag, int32_t split,
@@ -348,9 +346,7 @@ int l2hmc_chain_stats_below(const float* X, int64_t steps, int64_t n_chains, int
                      workspace);
   hipLaunchKernelGGL(chain_lagsum_reduce_kernel, dim3((unsigned)((d * nlag + 255) / 256)), dim3(256), 0, s,
                      (const double*)workspace, p.nb * p.halves, p.nb, (int)d, p.nslot, nlag, G_out);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(L2HMC_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
-  return L2HMC_OK;
+  return launched();
 }
 
 int l2hmc_chain_stats_exp(const float* X, int64_t steps, int64_t n_chains, int32_t d, int32_t max_lag, int32_t split,
@@ -369,9 +365,7 @@ int l2hmc_chain_stats_exp(const float* X, int64_t steps, int64_t n_chains, int32
                      workspace);
   hipLaunchKernelGGL(chain_lagsum_reduce_kernel, dim3((unsigned)((d * nlag + 255) / 256)), dim3(256), 0, s,
                      (const double*)workspace, p.nb * p.halves, p.nb, (int)d, p.nslot, nlag, G_out);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(L2HMC_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
-  return L2HMC_OK;
+  return launched();
 }
 
 }  // extern "C"

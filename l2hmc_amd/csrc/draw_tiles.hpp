@@ -1,5 +1,6 @@
-// The draw-tile contraction of the logistic-regression history statistics, stated once: predict_kernel (predictive.hip) and
-// loo_kernel (loo.hip) stream 16-draw tiles of a history W (S, d) past the data blocks a wave keeps in registers.
+// The draw-tile statistics kernels' common ground, stated once.  predict_kernel (predictive.hip), loo_kernel (loo.hip), the
+// lik_*_kernels (lik_stats.hip) and the three kernels of glm.hip stream 16-draw tiles of a history W (S, d) past the data blocks
+// a wave keeps in registers; this file holds what they share, on the device and on the host.
 //   load     a tile is 16 d contiguous floats of W whatever d is.  The lanes load it with coalesced SCALAR loads (the base of a
 //            history slice is only 4-byte aligned), element e = lane + 64 i, one tile ahead of its use; 0 past the end of W;
 //   stage    element e is (draw e / d, feature e % d), walked without a division, written to the wave's own LDS region as
@@ -11,12 +12,16 @@
 //            part[chunk][K][n]; chunk_reduce_kernel then adds the chunks' partials in chunk order.  No floating-point atomics.
 // The LDS region is private to the wave (LDS operations of a wave execute in order; wave_lds_fence keeps the compiler from moving
 // them), so the tile loop has no workgroup barrier.
+//   plan     draw_plan: the argument checks, the compiled feature-tile count (draw_ntm) and the split of the draws into chunks
+//            of tpc tiles -- from n_draws ALONE for the tails (the order in which float64 terms are added must not depend on how
+//            many rows a call holds), or filling kDrawUnits waves for the sums and the matrix; on_feature_tiles names the
+//            kernel of a plan.  Every unit's plan is a DrawPlan and nothing else decides these numbers.
 #pragma once
 #include "l2hmc_kernels.hpp"
 
 namespace l2hmc {
 
-// the argument checks both entries share; false with the message set
+// the argument checks every entry on a history shares; false with the message set
 static bool logistic_history_args_ok(const char* who, int64_t n_draws, int32_t n_data, int32_t d) {
   if (n_draws < 2) { fail(L2HMC_ERR_ARG, "%s: n_draws >= 2 (got %lld)", who, n_draws); return false; }
   if (n_data < 1 || n_data > kLogisticMaxRows) {
@@ -26,6 +31,57 @@ static bool logistic_history_args_ok(const char* who, int64_t n_draws, int32_t n
   if (d < 1 || d > kLogisticMaxDim) { fail(L2HMC_ERR_ARG, "%s: 1 <= d <= 128 (got %lld)", who, d); return false; }
   if (n_draws > (1LL << 40) / d) { fail(L2HMC_ERR_ARG, "%s: draws too large (n_draws d > 2^40)", who); return false; }
   return true;
+}
+
+constexpr int kDrawChunks = 1024;         // by_draws: draw chunks aimed for, whatever n is
+constexpr int kDrawUnits = 4096;          // else: waves aimed for (two resident sets of 256 CUs x 8)
+constexpr int kDrawMinTiles = 4;          // draw tiles per chunk at least: the end-of-wave reduction costs about one tile
+
+// the feature tiles a kernel is compiled for: 1, 2, 4, 8 (d <= 128)
+inline int draw_ntm(int NT) { return NT <= 2 ? NT : NT <= 4 ? 4 : 8; }
+
+// f(ic<NTM>) for the compiled feature-tile count of a plan
+template <class F>
+void on_feature_tiles(int NTM, F&& f) {
+  switch (NTM) {
+    case 1: f(ic<1>{}); break;
+    case 2: f(ic<2>{}); break;
+    case 4: f(ic<4>{}); break;
+    default: f(ic<8>{}); break;
+  }
+}
+
+// NB 16-row data blocks per wave make a row group; a chunk is tpc consecutive 16-draw tiles; a quad is four chunks
+struct DrawPlan {
+  int NT, NTM, nblk, ngroups;
+  long long ntiles, tpc, nchunks, quads;
+};
+
+// by_draws: tpc from n_draws alone, aiming for kDrawChunks chunks; else the chunks fill kDrawUnits waves with the row groups
+static bool draw_plan(const char* who, int64_t n_draws, int32_t n_data, int32_t d, int NB, bool by_draws, DrawPlan& p) {
+  if (!logistic_history_args_ok(who, n_draws, n_data, d)) return false;
+  p.NT = tiles_of(d);
+  p.NTM = draw_ntm(p.NT);
+  p.nblk = (n_data + 15) / 16;
+  p.ngroups = (p.nblk + NB - 1) / NB;
+  p.ntiles = (n_draws + 15) / 16;
+  long long want = by_draws ? kDrawChunks : (kDrawUnits + p.ngroups - 1) / p.ngroups;
+  if (want > p.ntiles) want = p.ntiles;
+  p.tpc = (p.ntiles + want - 1) / want;
+  if (p.tpc < kDrawMinTiles) p.tpc = kDrawMinTiles;
+  p.nchunks = (p.ntiles + p.tpc - 1) / p.tpc;                // no empty chunk
+  p.quads = (p.nchunks + 3) / 4;
+  return true;
+}
+
+// the segments of consecutive draws whose float64 terms loglik_gather_kernel (loglik_tails.hip) and glm_loo_kernel<*, *, 1>
+// (glm.hip) add in draw order: a function of n_draws ALONE, and one function, because the two routes promise the same bits
+constexpr int kDrawSegments = 2048;       // segments aimed for
+constexpr int kDrawMinSegment = 64;       // draws per segment at least
+inline void draw_segments(int64_t n_draws, long long& rows, long long& nseg) {
+  rows = (n_draws + kDrawSegments - 1) / kDrawSegments;
+  if (rows < kDrawMinSegment) rows = kDrawMinSegment;
+  nseg = (n_draws + rows - 1) / rows;                        // no empty segment
 }
 
 constexpr int tile_stride(int NTM) { return 16 * NTM + 4; }       // floats per staged draw (a multiple of 4: 16-byte reads)

@@ -14,16 +14,15 @@
 //   matrix   glm_loglik_kernel: ll of a (16 draws) x (16 NB rows) tile goes to out (S, n) float32 with ordinary vector stores;
 //            a draw at or past S and a row at or past n are never written.  The slow route, and the tests' hinge: it yields
 //            the very values the fused kernels select among.
-//   tails    the structure of loo_kernel (loo.hip) on the keys radix_key(ll): the log importance ratio is -ll, so the largest
-//            ratios are the smallest ll.  A workgroup is four waves on the SAME two data blocks and four consecutive chunks;
-//            tpc, the 16-draw tiles of a count chunk (about kGlmChunks chunks), and the draws of a gather segment are
-//            functions of n_draws ALONE.
-//     count    glm_loo_kernel<F, NTM, 0>, four passes of 8 bits: one LDS histogram [32 rows][256 bins] uint32 per workgroup,
-//              integer LDS atomics, flushed (non-zero bins) to the global int64 histogram with integer atomics.  Pass 0 counts
-//              every key (the 16 draw lanes that share the first lane's bin add through one ballot) and ALSO takes the row's
-//              largest key: a running maximum per lane, the 16 draw lanes reduced by shuffles, one integer atomicMax per row
-//              and wave -- the row's `top`, a NaN when the row holds one (its key is the last).
-//     advance  radix_advance_kernel (radix_select.hpp); after the last pass the prefix is the cutoff's key.
+//   tails    a radix select and a gather on the keys radix_key(ll): the log importance ratio is -ll, so the largest ratios are
+//            the smallest ll.  A workgroup is four waves on the SAME two data blocks and four consecutive chunks; tpc, the
+//            16-draw tiles of a count chunk, comes from draw_plan(by_draws) of draw_tiles.hpp -- the function l2hmc_logistic_loo_tails
+//            plans with -- and the draws of a gather segment from glm_plan below: both functions of n_draws ALONE.
+//     count    glm_loo_kernel<F, NTM, 0>: the count pass of radix_select.hpp over one LDS histogram [32 rows][256 bins] per
+//              workgroup.  Pass 0 ALSO takes the row's largest key: a running maximum per lane, the 16 draw lanes reduced by
+//              shuffles, one integer atomicMax per row and wave -- the row's `top`, a NaN when the row holds one (its key is
+//              the last).
+//     advance  radix_advance_kernel, driven by radix_select_passes; after the last pass the prefix is the cutoff's key.
 //     gather   glm_loo_kernel<F, NTM, 1>: a key strictly below the cutoff's takes slot atomicAdd(n_tail[row], 1) of the row's
 //              tail; a slot at or past the row's length is not written and raises the error word (it cannot happen while the
 //              invariant holds).  Every term is formed as loglik_tails.hip forms it -- in float64 from the exact float32
@@ -39,7 +38,7 @@
 //              the three-term body variance of the finish amplifies to 2e-11 of mcse_elpd_loo_i when a row's draws lie close
 //              together.)  The partials go to workspace[segment][3][n].
 //     reduce   chunk_reduce_kernel: sums[k][i] = the segments' partials added in segment order.
-//   predict  glm_predict_kernel, the structure of predict_kernel (predictive.hip): sums (4, n) float64 = sum mu,
+//   predict  glm_predict_kernel, planned like the matrix (draw_plan, filling kDrawUnits waves): sums (4, n) float64 = sum mu,
 //            sum exp((double) ll - sat_i) (one double exp per term; in (0, 1] up to the rounding of sat), sum ll, sum ll^2
 //            (formed and added in float64, one fma).  A draw at or past S and a row at or past n never count; partials are
 //            added in chunk order.
@@ -65,16 +64,9 @@ namespace l2hmc {
 constexpr int kGlmThreads = 256;          // 4 waves
 constexpr int kGlmNB = 2;                 // 16-row data blocks per wave
 constexpr int kGlmRows = 16 * kGlmNB;     // rows of a workgroup's histogram
-constexpr int kGlmChunks = 1024;          // draw chunks aimed for by the tails, whatever n is
-constexpr int kGlmUnits = 4096;           // waves the matrix and the predictive sums aim for
-constexpr int kGlmMinTiles = 4;           // draw tiles per chunk at least
 constexpr int kGlmTerms = 16 * 16 * 3;    // gather: the float64 terms of one data block of one tile
-constexpr int kGlmSegments = 2048;        // gather: segments aimed for, and
-constexpr int kGlmMinSegment = 64;        //         draws per segment at least -- the plan of loglik_tails.hip, on purpose
 
-struct GlmPlan {
-  int NT, NTM, nblk, ngroups;
-  long long ntiles, tpc, nchunks, quads;
+struct GlmPlan : DrawPlan {
   long long seg_rows, nseg, seg_quads;    // the gather's segments of consecutive draws (a function of n_draws alone)
 };
 
@@ -83,28 +75,11 @@ static bool glm_family_ok(const char* who, int32_t family) {
   return true;
 }
 
-// by_draws: tpc from n_draws alone (the tails); else the chunks fill kGlmUnits waves with the row groups (matrix, predict)
+// draw_plan (by_draws: the tails; else the matrix and the predictive sums) and the gather's segments
 static bool glm_plan(const char* who, int32_t family, int64_t n_draws, int32_t n_data, int32_t d, bool by_draws, GlmPlan& p) {
   if (!glm_family_ok(who, family)) return false;
-  if (!logistic_history_args_ok(who, n_draws, n_data, d)) return false;
-  p.NT = tiles_of(d);
-  p.NTM = p.NT <= 2 ? p.NT : p.NT <= 4 ? 4 : 8;
-  p.nblk = (n_data + 15) / 16;
-  p.ngroups = (p.nblk + kGlmNB - 1) / kGlmNB;
-  p.ntiles = (n_draws + 15) / 16;
-  if (by_draws) {
-    p.tpc = (p.ntiles + kGlmChunks - 1) / kGlmChunks;
-  } else {
-    long long want = (kGlmUnits + p.ngroups - 1) / p.ngroups;
-    if (want > p.ntiles) want = p.ntiles;
-    p.tpc = (p.ntiles + want - 1) / want;
-  }
-  if (p.tpc < kGlmMinTiles) p.tpc = kGlmMinTiles;
-  p.nchunks = (p.ntiles + p.tpc - 1) / p.tpc;                // no empty chunk
-  p.quads = (p.nchunks + 3) / 4;
-  p.seg_rows = (n_draws + kGlmSegments - 1) / kGlmSegments;
-  if (p.seg_rows < kGlmMinSegment) p.seg_rows = kGlmMinSegment;
-  p.nseg = (n_draws + p.seg_rows - 1) / p.seg_rows;          // no empty segment
+  if (!draw_plan(who, n_draws, n_data, d, kGlmNB, by_draws, p)) return false;
+  draw_segments(n_draws, p.seg_rows, p.nseg);                // (loglik_tails.hip's: the two routes add in one order)
   p.seg_quads = (p.nseg + 3) / 4;
   return true;
 }
@@ -191,16 +166,15 @@ struct GlmWorkspace {
 
 static GlmWorkspace glm_workspace(void* base, const GlmPlan& p, int32_t n) {
   GlmWorkspace w;
-  char* b = (char*)base;
-  int64_t o = 0;
-  w.err = (unsigned long long*)(b + o); o += 8;
-  w.hist = (unsigned long long*)(b + o); o += (int64_t)n * kRadixBins * 8;
-  w.remaining = (long long*)(b + o); o += (int64_t)n * 8;
-  w.ranks = (long long*)(b + o); o += (int64_t)n * 8;
-  w.prefix = (uint32_t*)(b + o); o += (int64_t)n * 4;
-  w.topkey = (uint32_t*)(b + o); o += (int64_t)n * 4;
-  w.part = (double*)(b + o); o += p.nseg * 3 * (int64_t)n * 8;
-  w.bytes = o;
+  Carve c{(char*)base};
+  w.err = c.take<unsigned long long>(1);
+  w.hist = c.take<unsigned long long>((int64_t)n * kRadixBins);
+  w.remaining = c.take<long long>(n);
+  w.ranks = c.take<long long>(n);
+  w.prefix = c.take<uint32_t>(n);
+  w.topkey = c.take<uint32_t>(n);
+  w.part = c.take<double>(p.nseg * 3 * (int64_t)n);
+  w.bytes = c.off;
   return w;
 }
 
@@ -248,7 +222,7 @@ __global__ __launch_bounds__(kGlmThreads, 2) void glm_loo_kernel(const float* __
   // gather: the terms of one data block of one tile, [16 draws][16 rows][3 sums] float64 per wave, added serially in draw order
   __shared__ double red_all[MODE == 1 ? 4 * kGlmTerms : 1];
   if (MODE == 0) {
-    for (int i = threadIdx.x; i < kGlmRows * kRadixBins; i += kGlmThreads) hl[i] = 0u;
+    radix_hist_clear<kGlmRows, kGlmThreads>(hl);
   } else if (threadIdx.x < kGlmRows) {
     const int i = threadIdx.x, row = 16 * b0 + i;
     const bool live = row < n;
@@ -345,18 +319,11 @@ __global__ __launch_bounds__(kGlmThreads, 2) void glm_loo_kernel(const float* __
             if (MODE == 0) {
               uint32_t* hrow = hl + (16 * j + 4 * q + r) * kRadixBins;
               if (first) {
-                // the 16 draw lanes of this row: those in the first lane's bin are added by it in one atomic
-                const int bin = (int)(key >> 24);
-                const int lead = __shfl(bin, lane & 48, 64);
-                const bool same = ok && bin == lead;
-                const unsigned long long bal = __ballot(same);
-                const int cnt = __popc((unsigned)((bal >> (lane & 48)) & 0xFFFFull));
-                if (c == 0) { if (cnt) atomicAdd(&hrow[lead], (uint32_t)cnt); }
-                else if (ok && !same) atomicAdd(&hrow[bin], 1u);
-                const uint32_t mine = ok ? key : 0u;
+                radix_count_first(hrow, key, ok, lane, c);
+                const uint32_t mine = ok ? key : 0u;         // ... and the running largest key of the row
                 pre_key[j][r] = mine > pre_key[j][r] ? mine : pre_key[j][r];
               } else {
-                if (ok && (key >> (shift + kRadixBits)) == pre_key[j][r]) atomicAdd(&hrow[(key >> shift) & (kRadixBins - 1)], 1u);
+                radix_count_next(hrow, key, ok, shift, pre_key[j][r]);
               }
             } else {
               const uint32_t ckey = __float_as_uint(ck4[r]);
@@ -419,14 +386,7 @@ __global__ __launch_bounds__(kGlmThreads, 2) void glm_loo_kernel(const float* __
     }
   }
 
-  if (MODE == 0) {
-    __syncthreads();
-    for (int i = threadIdx.x; i < kGlmRows * kRadixBins; i += kGlmThreads) {
-      const uint32_t cnt = hl[i];
-      const int row = 16 * b0 + (i >> kRadixBits);
-      if (cnt && row < n) atomicAdd(&hist[(long long)row * kRadixBins + (i & (kRadixBins - 1))], (unsigned long long)cnt);
-    }
-  }
+  if (MODE == 0) radix_hist_flush<kGlmRows, kGlmThreads>(hl, b0, n, hist);
 }
 
 // ---- the predictive sums ------------------------------------------------------------------------------------------------------
@@ -509,20 +469,6 @@ __global__ __launch_bounds__(kGlmThreads, 2) void glm_predict_kernel(const float
 
 using namespace l2hmc;
 
-#define L2HMC_GLM_GEOMETRIES(LAUNCH) \
-  switch (p.NTM) {                   \
-    case 1: LAUNCH(1); break;        \
-    case 2: LAUNCH(2); break;        \
-    case 4: LAUNCH(4); break;        \
-    default: LAUNCH(8); break;       \
-  }
-
-static int glm_launched() {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(L2HMC_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
-  return L2HMC_OK;
-}
-
 extern "C" {
 
 int l2hmc_glm_log_lik(const float* draws, int64_t n_draws, int32_t d, const float* packed, const float* row_consts, int32_t n_data,
@@ -537,12 +483,11 @@ int l2hmc_glm_log_lik(const float* draws, int64_t n_draws, int32_t d, const floa
   hipStream_t s = (hipStream_t)stream;
   const long long units = (long long)p.ngroups * p.nchunks;
   const dim3 grid((unsigned)((units + 3) / 4)), block(kGlmThreads);
-#define L2HMC_GLM_LAUNCH(NTM)                                                                                                 \
-  hipLaunchKernelGGL((glm_loglik_kernel<PoissonLog, NTM>), grid, block, 0, s, draws, (long long)n_draws, (int)d, packed, row_consts, \
-                     (int)n_data, p.NT, p.ngroups, p.nchunks, p.tpc, out)
-  L2HMC_GLM_GEOMETRIES(L2HMC_GLM_LAUNCH)
-#undef L2HMC_GLM_LAUNCH
-  return glm_launched();
+  on_feature_tiles(p.NTM, [&](auto ntm) {
+    hipLaunchKernelGGL((glm_loglik_kernel<PoissonLog, decltype(ntm)::value>), grid, block, 0, s, draws, (long long)n_draws, (int)d,
+                       packed, row_consts, (int)n_data, p.NT, p.ngroups, p.nchunks, p.tpc, out);
+  });
+  return launched();
 }
 
 int64_t l2hmc_glm_predict_workspace_doubles(int64_t n_draws, int32_t n_data, int32_t d) {
@@ -564,13 +509,12 @@ int l2hmc_glm_predict(const float* draws, int64_t n_draws, int32_t d, const floa
   hipStream_t s = (hipStream_t)stream;
   const long long units = (long long)p.ngroups * p.nchunks;
   const dim3 grid((unsigned)((units + 3) / 4)), block(kGlmThreads);
-#define L2HMC_GLM_LAUNCH(NTM)                                                                                                  \
-  hipLaunchKernelGGL((glm_predict_kernel<PoissonLog, NTM>), grid, block, 0, s, draws, (long long)n_draws, (int)d, packed, row_consts, \
-                     (int)n_data, p.NT, p.ngroups, p.nchunks, p.tpc, workspace)
-  L2HMC_GLM_GEOMETRIES(L2HMC_GLM_LAUNCH)
-#undef L2HMC_GLM_LAUNCH
+  on_feature_tiles(p.NTM, [&](auto ntm) {
+    hipLaunchKernelGGL((glm_predict_kernel<PoissonLog, decltype(ntm)::value>), grid, block, 0, s, draws, (long long)n_draws, (int)d,
+                       packed, row_consts, (int)n_data, p.NT, p.ngroups, p.nchunks, p.tpc, workspace);
+  });
   chunk_reduce_launch(workspace, p.nchunks, 4LL * n_data, sums, s);
-  return glm_launched();
+  return launched();
 }
 
 int64_t l2hmc_glm_loo_workspace_bytes(int64_t n_draws, int32_t n_data, int32_t d) {
@@ -603,28 +547,22 @@ int l2hmc_glm_loo_tails(const float* draws, int64_t n_draws, int32_t d, const fl
                      ws.topkey, (unsigned long long*)n_tail, tail, (int)n_data, (long long)tail_stride,
                      (long long)l2hmc_logistic_loo_tail_len(n_draws), (const long long*)tail_len_row, ws.err);
   const dim3 grid((unsigned)(p.quads * p.ngroups)), gather_grid((unsigned)(p.seg_quads * p.ngroups)), block(kGlmThreads);
-#define L2HMC_GLM_LAUNCH_MODE(NTM, MODE, shift, first)                                                                           \
-  hipLaunchKernelGGL((glm_loo_kernel<PoissonLog, NTM, MODE>), (MODE) == 1 ? gather_grid : grid, block, 0, s, draws,                \
-                     (long long)n_draws, (int)d, packed, row_consts, (int)n_data, p.NT, p.ngroups,                                \
-                     (MODE) == 1 ? p.nseg : p.nchunks, (MODE) == 1 ? p.seg_rows : p.tpc, (const uint32_t*)ws.prefix, (int)(shift), \
-                     (int)(first), ws.hist, ws.topkey, (const long long*)ws.ranks, top, (unsigned long long*)n_tail, tail,         \
-                     (long long)tail_stride, ws.err, ws.part)
-  for (int pass = 0; pass < kRadixPasses; ++pass) {
-    const int shift = 32 - kRadixBits * (pass + 1);
-    hipError_t e = hipMemsetAsync(ws.hist, 0, (size_t)n * kRadixBins * sizeof(long long), s);
-    if (e != hipSuccess) return fail(L2HMC_ERR_HIP, "hipMemsetAsync: %s", hipGetErrorString(e));
-#define L2HMC_GLM_LAUNCH(NTM) L2HMC_GLM_LAUNCH_MODE(NTM, 0, shift, pass == 0)
-    L2HMC_GLM_GEOMETRIES(L2HMC_GLM_LAUNCH)
-#undef L2HMC_GLM_LAUNCH
-    hipLaunchKernelGGL(radix_advance_kernel, dim3((unsigned)n_data), dim3(64), 0, s, (const long long*)ws.hist, ws.remaining,
-                       ws.prefix, (int)n_data, shift, pass == kRadixPasses - 1 ? cutoff : (float*)nullptr);
-  }
-#define L2HMC_GLM_LAUNCH(NTM) L2HMC_GLM_LAUNCH_MODE(NTM, 1, 0, 0)
-  L2HMC_GLM_GEOMETRIES(L2HMC_GLM_LAUNCH)
-#undef L2HMC_GLM_LAUNCH
-#undef L2HMC_GLM_LAUNCH_MODE
+  auto pass = [&](auto mode, int shift, bool first) {
+    constexpr int MODE = decltype(mode)::value;
+    on_feature_tiles(p.NTM, [&](auto ntm) {
+      hipLaunchKernelGGL((glm_loo_kernel<PoissonLog, decltype(ntm)::value, MODE>), MODE == 1 ? gather_grid : grid, block, 0, s, draws,
+                         (long long)n_draws, (int)d, packed, row_consts, (int)n_data, p.NT, p.ngroups,
+                         MODE == 1 ? p.nseg : p.nchunks, MODE == 1 ? p.seg_rows : p.tpc, (const uint32_t*)ws.prefix, shift,
+                         (int)first, ws.hist, ws.topkey, (const long long*)ws.ranks, top, (unsigned long long*)n_tail, tail,
+                         (long long)tail_stride, ws.err, ws.part);
+    });
+  };
+  const int rc = radix_select_passes(ws.hist, ws.remaining, ws.prefix, (int)n_data, cutoff, s,
+                                     [&](int shift, bool first) { pass(ic<0>{}, shift, first); });
+  if (rc) return rc;
+  pass(ic<1>{}, 0, false);
   chunk_reduce_launch(ws.part, p.nseg, 3LL * n_data, sums, s);
-  return glm_launched();
+  return launched();
 }
 
 }  // extern "C"

@@ -1,4 +1,6 @@
-// The likelihood of a generalised linear model, stated once for every kernel of glm.hip: a family is a struct with
+// The likelihoods of the draw-tile statistics kernels, each stated once: PoissonLog for every kernel of glm.hip, and
+// BernoulliLogit (at the end) for the logistic kernels of predictive.hip, loo.hip and lik_stats.hip.  For glm.hip a family is a
+// struct with
 //     ll(eta, y, a, b)   the pointwise log-likelihood of a row with response y under the linear predictor eta = x_i . w_s,
 //                        a and b the row's first two constants (row_consts[0], row_consts[1])
 //     mean(eta, a)       the predictive mean
@@ -34,6 +36,32 @@ struct PoissonLog {
   static __device__ __forceinline__ float mean(float eta, float o) {
 #pragma clang fp contract(off)
     return fexp(__fadd_rn(eta, o));
+  }
+};
+
+// Logistic regression, the link of the logistic history statistics (predictive.hip, loo.hip, lik_stats.hip -- NOT a family of
+// glm.hip: their keys are the signed logit t, not ll, and their sums are float32 terms, a different and faster contract):
+//     t = (2 y_i - 1) eta    e = exp(-|t|)    lik = sigmoid(t) = 1 / (1 + e) for t >= 0, e / (1 + e) below
+// THE SAME INVARIANT: the tail gather of loo.hip and the series of lik_stats.hip (`relative_eff` feeds `loo(r_eff="auto")`) form
+// the likelihood by ONE device function, lik, and every kernel the signed logit by signed_logit (the sign is exact); `sums`
+// forms what predict_kernel needs from one e and one reciprocal by the same operations.  Each value is one expression, as it
+// stands: the units compile with the default contraction, so splitting one changes bits.  Change all callers or none.
+struct BernoulliLogit {
+  static __device__ __forceinline__ float signed_logit(float eta, float y) { return y > 0.5f ? eta : -eta; }
+  static __device__ __forceinline__ float lik(float t) {
+    const float e = fexp(-fabsf(t));
+    const float inv = __builtin_amdgcn_rcpf(1.f + e);
+    return t >= 0.f ? inv : e * inv;
+  }
+  // p1 = sigmoid(eta), lik = sigmoid(z) and ll = log lik = min(z, 0) - log(1 + e) of z = signed_logit(eta, y): |z| = |eta|
+  static __device__ __forceinline__ void sums(float eta, float y, float& p1, float& lik, float& ll) {
+    const float e = fexp(-fabsf(eta));
+    const float inv = __builtin_amdgcn_rcpf(1.f + e);
+    const float lo = e * inv;
+    const float z = signed_logit(eta, y);
+    p1 = eta >= 0.f ? inv : lo;
+    lik = z >= 0.f ? inv : lo;
+    ll = fminf(z, 0.f) - 0.6931471805599453f * __builtin_amdgcn_logf(1.f + e);
   }
 };
 

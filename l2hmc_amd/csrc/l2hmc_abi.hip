@@ -1045,9 +1045,7 @@ int l2hmc_step(const L2hmcNet* xnet, const L2hmcNet* vnet, const L2hmcEnergy* en
   if (logjac_inout)
     hipLaunchKernelGGL(add_inplace_kernel, dim3((unsigned)((n_chains + 255) / 256)), dim3(256), 0, s, logjac_inout, lj,
                        (long long)n_chains);
-  e = hipGetLastError();
-  if (e != hipSuccess) return fail(L2HMC_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
-  return L2HMC_OK;
+  return launched();
 }
 
 int l2hmc_energy(const L2hmcEnergy* energy, const float* x, int64_t n_chains, int32_t d,
@@ -1097,17 +1095,13 @@ int l2hmc_mh_select(const float* x, const float* Lx, const float* px, const floa
   const long long n = n_chains * (long long)d;
   hipLaunchKernelGGL(mh_select_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
                      (hipStream_t)stream, x, Lx, px, u, (long long)n_chains, d, x_next);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(L2HMC_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
-  return L2HMC_OK;
+  return launched();
 }
 
 int l2hmc_loss_terms(const float* v1, int64_t n, float scale, double inv_n, double* out3, void* stream) {
   if (!v1 || !out3 || n < 0 || !(scale > 0.f)) return fail(L2HMC_ERR_ARG, "l2hmc_loss_terms: bad argument%s");
   hipLaunchKernelGGL(loss_terms_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, v1, (long long)n, scale, inv_n, out3);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(L2HMC_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
-  return L2HMC_OK;
+  return launched();
 }
 
 int l2hmc_adam_step(float* params, const float* grad, float* m, float* v, int64_t n, float lr, float beta1,
@@ -1117,9 +1111,7 @@ int l2hmc_adam_step(float* params, const float* grad, float* m, float* v, int64_
   if (n == 0) return L2HMC_OK;
   hipLaunchKernelGGL(adam_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, params, grad,
                      m, v, (long long)n, adam_lr_t(lr, beta1, beta2, step), beta1, beta2, epsilon, last_is_log_eps);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(L2HMC_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
-  return L2HMC_OK;
+  return launched();
 }
 
 int l2hmc_ais_begin_step(const float* x, const float* U_final, const float* normals, float refreshment,
@@ -1129,9 +1121,7 @@ int l2hmc_ais_begin_step(const float* x, const float* U_final, const float* norm
   if (n_chains == 0) return L2HMC_OK;
   hipLaunchKernelGGL(ais_begin_kernel, dim3((unsigned)((n_chains + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      x, U_final, normals, refreshment, dbeta, w, v, (long long)n_chains, d);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(L2HMC_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
-  return L2HMC_OK;
+  return launched();
 }
 
 int l2hmc_ais_end_step(const float* Lx, const float* Lv, const float* p, const float* u, float* x, float* v,
@@ -1141,9 +1131,7 @@ int l2hmc_ais_end_step(const float* Lx, const float* Lv, const float* p, const f
   if (n_chains == 0) return L2HMC_OK;
   hipLaunchKernelGGL(ais_end_kernel, dim3((unsigned)((n_chains + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      Lx, Lv, p, u, x, v, alpha_sum, (long long)n_chains, d);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(L2HMC_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
-  return L2HMC_OK;
+  return launched();
 }
 
 int l2hmc_rng_fill(uint64_t seed, uint64_t proposal0, int64_t chain_offset, int64_t n_chains,
@@ -1155,9 +1143,7 @@ int l2hmc_rng_fill(uint64_t seed, uint64_t proposal0, int64_t chain_offset, int6
   hipLaunchKernelGGL(rng_fill_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                      (unsigned long long)seed, (unsigned long long)proposal0, (long long)chain_offset,
                      (long long)n_chains, d, n_proposals, v_out, dir_out, u_out);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(L2HMC_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
-  return L2HMC_OK;
+  return launched();
 }
 
 int64_t l2hmc_autocov_workspace_doubles(int64_t steps, int64_t n_chains, int32_t d) {
@@ -1187,9 +1173,7 @@ int l2hmc_autocov(const float* X, int64_t steps, int64_t n_chains, int32_t d, do
     hipLaunchKernelGGL(autocov_finish_kernel, dim3((unsigned)((steps - 1 + 255) / 256)), dim3(256), 0, s,
                        sums_out, (long long)steps, inv, A_out);
   }
-  e = hipGetLastError();
-  if (e != hipSuccess) return fail(L2HMC_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
-  return L2HMC_OK;
+  return launched();
 }
 
 }  // extern "C"

@@ -1193,6 +1193,26 @@ struct TrajPlan {
   long long lds = 0;        // dynamic LDS bytes
 };
 
+// The end of every entry that launched something: the launches' error, or L2HMC_OK.
+inline int launched() {
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(L2HMC_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
+  return L2HMC_OK;
+}
+
+// A workspace handed out front to back: take<T>(count) is the next `count` elements of T, pad(a) rounds the offset up to a
+// multiple of `a` bytes.  Only the offsets count under a null base: `off` after the last take is the workspace's size.
+struct Carve {
+  char* base;
+  int64_t off = 0;
+  template <class T> T* take(int64_t count) {
+    T* p = reinterpret_cast<T*>(base + off);
+    off += count * (int64_t)sizeof(T);
+    return p;
+  }
+  void pad(int64_t a) { off = (off + a - 1) / a * a; }
+};
+
 // One kernel launch: the LDS limit, the dynamic-LDS attribute above 48 KiB, the grid size, the launch and its error.
 template <class K, class... X>
 int launch_kernel(K kern, long long blocks, int threads, long long lds_bytes, hipStream_t s, const X&... args) {
@@ -1205,9 +1225,7 @@ int launch_kernel(K kern, long long blocks, int threads, long long lds_bytes, hi
   }
   if (blocks > 0x7fffffffLL) return fail(L2HMC_ERR_UNSUPPORTED, "too many chains%s");
   hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(threads), (size_t)lds_bytes, s, args...);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(L2HMC_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
-  return L2HMC_OK;
+  return launched();
 }
 
 // Template arguments from run-time values: f is a generic lambda called with std::integral_constant arguments, so every branch

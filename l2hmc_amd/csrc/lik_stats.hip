@@ -8,8 +8,9 @@
 //
 // Work unit = one WAVE: 16 consecutive chains x ONE 16-row data block, walking the steps.  The draw tile of step t is the 16 d
 // contiguous floats at draw t N + c0 (tile_load_at: chains at or past N enter as 0 and are masked below, as a draw past S is in
-// predict_kernel).  The logits come from tile_logits ALONE -- the bits the LOO passes see -- and the likelihood is loo_kernel's
-// float32 expression.  Lane (c, q) holds the four series (chain c0 + c, rows 4 q + r).
+// predict_kernel).  The logits come from tile_logits ALONE -- the bits the LOO passes see -- and the likelihood from
+// BernoulliLogit::lik (glm_family.hpp), the function loo_kernel's gather calls.  Lane (c, q) holds the four series (chain
+// c0 + c, rows 4 q + r).
 //
 //   pass 1  lik_moments_kernel: two walks over the steps, float64 throughout: m = sum lik / Mh, then M2 = sum (lik - m)^2 (fma).
 //           Every lane writes its own four (chain, row) entries: no cross-lane sum at all.
@@ -35,6 +36,7 @@
 // 256 registers (both held by tests/test_lik_stats_cpu.py from the compiler's listing).  A 16-lag ring spilled at every geometry.
 // LDS: 4 x at most 8448 bytes.  Geometries <NTM feature tiles compiled>: 1, 2, 4, 8.
 #include "draw_tiles.hpp"
+#include "glm_family.hpp"
 
 namespace l2hmc {
 
@@ -68,7 +70,7 @@ static bool lik_stats_plan(const char* who, int64_t steps, int64_t n_chains, int
   }
   p.row1 = steps - p.Mh;
   p.NT = tiles_of(d);
-  p.NTM = p.NT <= 2 ? p.NT : p.NT <= 4 ? 4 : 8;
+  p.NTM = draw_ntm(p.NT);
   p.nblk = (n_data + 15) / 16;
   p.ncb = (n_chains + 15) / 16;
   p.nbx = p.ncb < kLsWalks ? p.ncb : kLsWalks;            // a function of n_chains alone
@@ -78,7 +80,8 @@ static bool lik_stats_plan(const char* who, int64_t steps, int64_t n_chains, int
   return true;
 }
 
-// the likelihoods of the loaded tile: lane (c, q) gets sigmoid(t) of chain c, rows 4 q + r of data block b (loo_kernel's bits)
+// the likelihoods of the loaded tile: lane (c, q) gets sigmoid(t) of chain c, rows 4 q + r of data block b -- the logits of
+// tile_logits through BernoulliLogit::lik, as loo_kernel's gather forms them
 template <int NTM>
 __device__ __forceinline__ f4 lik_of_tile(float* lds, const float (&pre)[4 * NTM], const TileWalk& walk, int lane,
                                           const f4 (&xa)[1][NTM], const f4& yv, int NT, int b, int nblk) {
@@ -89,12 +92,7 @@ __device__ __forceinline__ f4 lik_of_tile(float* lds, const float (&pre)[4 * NTM
   wave_lds_fence();
   f4 out;
 #pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const float tv = yv[r] > 0.5f ? T[0][r] : -T[0][r];      // the signed logit (the sign is exact)
-    const float e = fexp(-fabsf(tv));
-    const float inv = __builtin_amdgcn_rcpf(1.f + e);
-    out[r] = tv >= 0.f ? inv : e * inv;
-  }
+  for (int r = 0; r < 4; ++r) out[r] = BernoulliLogit::lik(BernoulliLogit::signed_logit(T[0][r], yv[r]));
   return out;
 }
 
@@ -300,22 +298,15 @@ int l2hmc_logistic_lik_stats(const float* draws, int64_t steps, int64_t n_chains
   const dim3 block(kLsThreads), grid1((unsigned)((units1 + 3) / 4)),
       grid2((unsigned)((units2 + 3) / 4), (unsigned)p.ntile, (unsigned)p.halves);
   if (units1 > 4LL * 0x7fffffffLL) return fail(L2HMC_ERR_ARG, "l2hmc_logistic_lik_stats: history too large%s");
-#define L2HMC_LIK_LAUNCH(NTM)                                                                                                   \
-  hipLaunchKernelGGL((lik_moments_kernel<NTM>), grid1, block, 0, s, draws, N, (int)d, packed, (int)n_data, p.NT, p.Mh, p.row1,   \
-                     p.ncb, p.halves, mean, m2);                                                                                 \
-  hipLaunchKernelGGL((lik_lagsum_kernel<NTM>), grid2, block, 0, s, draws, N, (int)d, packed, (int)n_data, p.NT, p.Mh, p.row1,    \
-                     p.ncb, p.nbx, p.nlag, (const double*)mean, (double*)workspace)
-  switch (p.NTM) {
-    case 1: L2HMC_LIK_LAUNCH(1); break;
-    case 2: L2HMC_LIK_LAUNCH(2); break;
-    case 4: L2HMC_LIK_LAUNCH(4); break;
-    default: L2HMC_LIK_LAUNCH(8); break;
-  }
-#undef L2HMC_LIK_LAUNCH
+  on_feature_tiles(p.NTM, [&](auto ntm) {
+    constexpr int NTM = decltype(ntm)::value;
+    hipLaunchKernelGGL((lik_moments_kernel<NTM>), grid1, block, 0, s, draws, N, (int)d, packed, (int)n_data, p.NT, p.Mh, p.row1,
+                       p.ncb, p.halves, mean, m2);
+    hipLaunchKernelGGL((lik_lagsum_kernel<NTM>), grid2, block, 0, s, draws, N, (int)d, packed, (int)n_data, p.NT, p.Mh, p.row1,
+                       p.ncb, p.nbx, p.nlag, (const double*)mean, (double*)workspace);
+  });
   chunk_reduce_launch((const double*)workspace, p.halves * p.nbx, (long long)n_data * p.nlag, G, s);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(L2HMC_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
-  return L2HMC_OK;
+  return launched();
 }
 
 }  // extern "C"

@@ -57,8 +57,6 @@
 namespace l2hmc {
 
 constexpr int kLtThreads = 256;
-constexpr int kLtSegments = 2048;          // segments aimed for
-constexpr int kLtMinRows = 64;             // draws per segment at least
 constexpr int kLtMaxCols = 512;            // l2hmc_order_stats: d <= 512
 
 struct LoglikPlan {
@@ -69,9 +67,7 @@ static bool loglik_plan(const char* who, int64_t n_draws, int32_t n_cols, Loglik
   if (n_draws < 2) { fail(L2HMC_ERR_ARG, "%s: n_draws >= 2 (got %lld)", who, (long long)n_draws); return false; }
   if (n_cols < 1 || n_cols > kLtMaxCols) { fail(L2HMC_ERR_ARG, "%s: 1 <= n_cols <= 512 (got %lld)", who, (long long)n_cols); return false; }
   if (n_draws > (1LL << 40) / n_cols) { fail(L2HMC_ERR_ARG, "%s: matrix too large (n_draws n_cols > 2^40)", who); return false; }
-  p.rows = (n_draws + kLtSegments - 1) / kLtSegments;
-  if (p.rows < kLtMinRows) p.rows = kLtMinRows;
-  p.nseg = (n_draws + p.rows - 1) / p.rows;              // no empty segment
+  draw_segments(n_draws, p.rows, p.nseg);
   return true;
 }
 
@@ -89,16 +85,15 @@ struct LoglikWorkspace {
 
 static LoglikWorkspace loglik_workspace(void* base, const LoglikPlan& p, int32_t n) {
   LoglikWorkspace w;
-  char* b = (char*)base;
-  int64_t o = 0;
-  w.err = (unsigned long long*)(b + o); o += 16;
-  w.ranks = (long long*)(b + o); o += (int64_t)n * 16;
-  w.n_nan = (long long*)(b + o); o += (int64_t)n * 8;
-  w.values = (float*)(b + o); o += ((int64_t)n * 8 + 15) / 16 * 16;
-  o = (o + 15) / 16 * 16;
-  w.select = (void*)(b + o); o += l2hmc_order_stats_workspace_bytes(n, 2);
-  w.part = (double*)(b + o); o += p.nseg * 3 * (int64_t)n * 8;
-  w.bytes = o;
+  Carve c{(char*)base};
+  w.err = c.take<unsigned long long>(2);                     // (the word and its pad)
+  w.ranks = c.take<long long>(2 * (int64_t)n);
+  w.n_nan = c.take<long long>(n);
+  w.values = c.take<float>(((int64_t)n * 2 + 3) / 4 * 4);    // (2, n), its length padded to 16 B
+  c.pad(16);
+  w.select = c.take<char>(l2hmc_order_stats_workspace_bytes(n, 2));
+  w.part = c.take<double>(p.nseg * 3 * (int64_t)n);
+  w.bytes = c.off;
   return w;
 }
 
@@ -212,9 +207,7 @@ int l2hmc_loglik_tails(const float* ll, int64_t n_draws, int32_t n_cols, const i
                      (long long)n_draws, (int)n_cols, p.rows, p.nseg, (const float*)ws.values, (const long long*)ws.ranks,
                      (long long)tail_stride, cutoff, top, (unsigned long long*)n_tail, tail, (long long*)tail_pos, ws.err, ws.part);
   chunk_reduce_launch(ws.part, p.nseg, 3 * n, sums, s);
-  e = hipGetLastError();
-  if (e != hipSuccess) return fail(L2HMC_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
-  return L2HMC_OK;
+  return launched();
 }
 
 }  // extern "C"

@@ -18,20 +18,14 @@
 // the pass, the chunk, the plan or the row grouping of the caller.  A key counted in one pass is the key compared in the next,
 // and exactly the keys below the selected one reach the tail.
 //
-// The tile loop is draw_tiles.hpp's, shared with predict_kernel (predictive.hip), with the same masks (a draw at or past S, a
-// row at or past n never counts).  Work unit = one wave: NB = 2 consecutive 16-row data blocks x a chunk of tpc 16-draw tiles.
-// tpc depends on S ALONE (about kLooChunks chunks), so the order in which float64 terms are added does not depend on how many
-// rows a call holds.  A workgroup is four waves on the SAME data blocks and four consecutive chunks; blockIdx.x = quad * ngroups
-// + group.
+// The tile loop and the plan are draw_tiles.hpp's (a draw at or past S, a row at or past n never counts), the signed logit and
+// the likelihood BernoulliLogit's (glm_family.hpp).  Work unit = one wave: NB = 2 consecutive 16-row data blocks x a chunk of
+// tpc 16-draw tiles, planned by draw_plan(by_draws): tpc depends on S ALONE, so the order in which float64 terms are added does
+// not depend on how many rows a call holds.  A workgroup is four waves on the SAME data blocks and four consecutive chunks;
+// blockIdx.x = quad * ngroups + group.
 //
-//   count    loo_kernel<NTM, 0>: the workgroup keeps one LDS histogram [32 rows][256 bins] uint32 (32 KiB) of the next digit of
-//            the keys that share their row's prefix, added to with integer LDS atomics and flushed -- non-zero bins only -- to
-//            the global int64 histogram (n, 256) with integer atomics.  In pass 0 every key counts and the top digit (sign and
-//            high exponent) concentrates in a few bins: the 16 draw lanes of a row would add to one address.  There the 16 lanes
-//            compare their bin with the first lane's; those that agree are counted by a ballot and added by that lane in ONE
-//            atomic, the others add for themselves.  Later passes count only the keys on the prefix: few, plain atomics.
-//   advance  radix_advance_kernel: one wave per row scans the 256 bins for the digit in which the remaining rank falls; after
-//            the last pass the prefix is the cutoff's key and the cutoff is written.
+//   count    loo_kernel<NTM, 0>: the count pass of radix_select.hpp over one LDS histogram [32 rows][256 bins] (32 KiB).
+//   advance  radix_advance_kernel; radix_select_passes drives the four passes, and after the last the cutoff is written.
 //   gather   loo_kernel<NTM, 1>: a key below the cutoff's key takes slot atomicAdd(n_tail[row], 1) (an integer atomic) of the
 //            row's tail; a slot at or past M is not written and raises the error word of the workspace (it cannot happen while
 //            the invariant holds).  Every other live draw adds its body term, every live draw its sigmoid, converted to float64
@@ -58,6 +52,7 @@
 #include <math.h>
 
 #include "draw_tiles.hpp"
+#include "glm_family.hpp"
 #include "radix_select.hpp"
 
 namespace l2hmc {
@@ -65,12 +60,9 @@ namespace l2hmc {
 constexpr int kLooThreads = 256;          // 4 waves on the same rows
 constexpr int kLooNB = 2;                 // 16-row data blocks per wave
 constexpr int kLooRows = 16 * kLooNB;     // rows of a workgroup's histogram
-constexpr int kLooChunks = 1024;          // draw chunks aimed for, whatever n is
-constexpr int kLooMinTiles = 4;           // draw tiles per chunk at least
 
-struct LooPlan {
-  int NT, NTM, nblk, ngroups;
-  long long ntiles, tpc, nchunks, quads, M;
+struct LooPlan : DrawPlan {
+  long long M;                            // the tail's length (its row stride in the mc entry)
 };
 
 // M = min(floor(S / 5), ceil(3 sqrt S)) in integers
@@ -84,18 +76,9 @@ static long long loo_tail_len(long long S) {
 }
 
 static bool loo_plan(const char* who, int64_t n_draws, int32_t n_data, int32_t d, LooPlan& p) {
-  if (!logistic_history_args_ok(who, n_draws, n_data, d)) return false;
+  if (!draw_plan(who, n_draws, n_data, d, kLooNB, true, p)) return false;
   p.M = loo_tail_len(n_draws);
   if (p.M * n_data > (1LL << 31)) { fail(L2HMC_ERR_ARG, "%s: tail too large (tail_len n_data > 2^31): fewer rows per call", who); return false; }
-  p.NT = tiles_of(d);
-  p.NTM = p.NT <= 2 ? p.NT : p.NT <= 4 ? 4 : 8;
-  p.nblk = (n_data + 15) / 16;
-  p.ngroups = (p.nblk + kLooNB - 1) / kLooNB;
-  p.ntiles = (n_draws + 15) / 16;
-  p.tpc = (p.ntiles + kLooChunks - 1) / kLooChunks;          // a function of n_draws alone
-  if (p.tpc < kLooMinTiles) p.tpc = kLooMinTiles;
-  p.nchunks = (p.ntiles + p.tpc - 1) / p.tpc;                // no empty chunk
-  p.quads = (p.nchunks + 3) / 4;
   return true;
 }
 
@@ -111,14 +94,14 @@ struct LooWorkspace {
 
 static LooWorkspace loo_workspace(void* base, const LooPlan& p, int32_t n, int nsums = 2) {
   LooWorkspace w;
-  char* b = (char*)base;
-  int64_t o = 0;
-  w.err = (unsigned long long*)(b + o); o += 8;
-  w.hist = (unsigned long long*)(b + o); o += (int64_t)n * kRadixBins * 8;
-  w.remaining = (long long*)(b + o); o += (int64_t)n * 8;
-  w.prefix = (uint32_t*)(b + o); o += ((int64_t)n * 4 + 7) / 8 * 8;
-  w.part = (double*)(b + o); o += p.nchunks * nsums * (int64_t)n * 8;
-  w.bytes = o;
+  Carve c{(char*)base};
+  w.err = c.take<unsigned long long>(1);
+  w.hist = c.take<unsigned long long>((int64_t)n * kRadixBins);
+  w.remaining = c.take<long long>(n);
+  w.prefix = c.take<uint32_t>(n);
+  c.pad(8);
+  w.part = c.take<double>(p.nchunks * nsums * (int64_t)n);
+  w.bytes = c.off;
   return w;
 }
 
@@ -147,7 +130,7 @@ __global__ __launch_bounds__(kLooThreads, MODE == 2 ? 2 : 1) void loo_kernel(con
   float* lds = lds_all + w * REGION;
   tile_region_clear<NTM>(lds, lane);
   if (MODE == 0) {
-    for (int i = threadIdx.x; i < kLooRows * kRadixBins; i += kLooThreads) hl[i] = 0u;
+    radix_hist_clear<kLooRows, kLooThreads>(hl);
     __syncthreads();
   }
 
@@ -202,23 +185,13 @@ __global__ __launch_bounds__(kLooThreads, MODE == 2 ? 2 : 1) void loo_kernel(con
         if (b0 + j < nblk) {                                 // wave-uniform
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            const float tv = yv[j][r] > 0.5f ? T[j][r] : -T[j][r];        // the signed logit (the sign is exact)
+            const float tv = BernoulliLogit::signed_logit(T[j][r], yv[j][r]);
             const uint32_t key = radix_key(tv);
             const bool ok = valid && row_ok[j][r];
             if (MODE == 0) {
               uint32_t* hrow = hl + (16 * j + 4 * q + r) * kRadixBins;
-              if (first) {
-                // the 16 draw lanes of this row: those in the first lane's bin are added by it in one atomic
-                const int bin = (int)(key >> 24);
-                const int lead = __shfl(bin, lane & 48, 64);
-                const bool same = ok && bin == lead;
-                const unsigned long long bal = __ballot(same);
-                const int cnt = __popc((unsigned)((bal >> (lane & 48)) & 0xFFFFull));
-                if (c == 0) { if (cnt) atomicAdd(&hrow[lead], (uint32_t)cnt); }
-                else if (ok && !same) atomicAdd(&hrow[bin], 1u);
-              } else {
-                if (ok && (key >> (shift + kRadixBits)) == pre_key[j][r]) atomicAdd(&hrow[(key >> shift) & (kRadixBins - 1)], 1u);
-              }
+              if (first) radix_count_first(hrow, key, ok, lane, c);
+              else radix_count_next(hrow, key, ok, shift, pre_key[j][r]);
             } else {
               const bool in_tail = ok && key < pre_key[j][r];
               if (in_tail) {
@@ -229,9 +202,7 @@ __global__ __launch_bounds__(kLooThreads, MODE == 2 ? 2 : 1) void loo_kernel(con
                 if (slot < room) tail[(long long)row * M + (long long)slot] = tv;
                 else atomicOr(err, 1ull);
               }
-              const float e = fexp(-fabsf(tv));
-              const float inv = __builtin_amdgcn_rcpf(1.f + e);
-              const float lik = tv >= 0.f ? inv : e * inv;
+              const float lik = BernoulliLogit::lik(tv);
               const float body = em[j][r] + fexp(mm[j][r] - tv);
               acc[j][0][r] += (double)((ok && !in_tail) ? body : 0.f);
               acc[j][1][r] += (double)(ok ? lik : 0.f);
@@ -245,14 +216,7 @@ __global__ __launch_bounds__(kLooThreads, MODE == 2 ? 2 : 1) void loo_kernel(con
     if (MODE != 0) tile_sums_out<NB, K>(lds, acc, lane, b0, nblk, n, chunk, part);
   }
 
-  if (MODE == 0) {
-    __syncthreads();
-    for (int i = threadIdx.x; i < kLooRows * kRadixBins; i += kLooThreads) {
-      const uint32_t cnt = hl[i];
-      const int row = 16 * b0 + (i >> kRadixBits);
-      if (cnt && row < n) atomicAdd(&hist[(long long)row * kRadixBins + (i & (kRadixBins - 1))], (unsigned long long)cnt);
-    }
-  }
+  if (MODE == 0) radix_hist_flush<kLooRows, kLooThreads>(hl, b0, n, hist);
 }
 
 __global__ void loo_init_kernel(long long* __restrict__ remaining, uint32_t* __restrict__ prefix,
@@ -300,32 +264,20 @@ static int loo_run(const char* who, const LooPlan& p, const float* draws, int64_
   hipLaunchKernelGGL(loo_init_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s, ws.remaining, ws.prefix,
                      (unsigned long long*)n_tail, tail, (int)n_data, p.M, ws.err, lens);
   const dim3 grid((unsigned)(p.quads * p.ngroups)), block(kLooThreads);
-#define L2HMC_LOO_LAUNCH(NTM, MODE, shift, first)                                                                          \
-  hipLaunchKernelGGL((loo_kernel<NTM, MODE>), grid, block, 0, s, draws, (long long)n_draws, (int)d, packed, (int)n_data, p.NT, \
-                     p.ngroups, p.nchunks, p.tpc, (const uint32_t*)ws.prefix, (int)(shift), (int)(first), ws.hist,             \
-                     (unsigned long long*)n_tail, tail, p.M, ws.err, ws.part, lens)
-#define L2HMC_LOO_PASS(MODE, shift, first)                 \
-  switch (p.NTM) {                                         \
-    case 1: L2HMC_LOO_LAUNCH(1, MODE, shift, first); break; \
-    case 2: L2HMC_LOO_LAUNCH(2, MODE, shift, first); break; \
-    case 4: L2HMC_LOO_LAUNCH(4, MODE, shift, first); break; \
-    default: L2HMC_LOO_LAUNCH(8, MODE, shift, first); break; \
-  }
-  for (int pass = 0; pass < kRadixPasses; ++pass) {
-    const int shift = 32 - kRadixBits * (pass + 1);
-    hipError_t e = hipMemsetAsync(ws.hist, 0, (size_t)n * kRadixBins * sizeof(long long), s);
-    if (e != hipSuccess) return fail(L2HMC_ERR_HIP, "hipMemsetAsync: %s", hipGetErrorString(e));
-    L2HMC_LOO_PASS(0, shift, pass == 0)
-    hipLaunchKernelGGL(radix_advance_kernel, dim3((unsigned)n_data), dim3(64), 0, s, (const long long*)ws.hist, ws.remaining,
-                       ws.prefix, (int)n_data, shift, pass == kRadixPasses - 1 ? cutoff : (float*)nullptr);
-  }
-  if (len_row) { L2HMC_LOO_PASS(2, 0, 0) } else { L2HMC_LOO_PASS(1, 0, 0) }
-#undef L2HMC_LOO_PASS
-#undef L2HMC_LOO_LAUNCH
+  auto pass = [&](auto mode, int shift, bool first) {
+    on_feature_tiles(p.NTM, [&](auto ntm) {
+      hipLaunchKernelGGL((loo_kernel<decltype(ntm)::value, decltype(mode)::value>), grid, block, 0, s, draws, (long long)n_draws,
+                         (int)d, packed, (int)n_data, p.NT, p.ngroups, p.nchunks, p.tpc, (const uint32_t*)ws.prefix, shift,
+                         (int)first, ws.hist, (unsigned long long*)n_tail, tail, p.M, ws.err, ws.part, lens);
+    });
+  };
+  const int rc = radix_select_passes(ws.hist, ws.remaining, ws.prefix, (int)n_data, cutoff, s,
+                                     [&](int shift, bool first) { pass(ic<0>{}, shift, first); });
+  if (rc) return rc;
+  if (len_row) pass(ic<2>{}, 0, false);
+  else pass(ic<1>{}, 0, false);
   chunk_reduce_launch(ws.part, p.nchunks, (long long)nsums * n_data, sums, s);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(L2HMC_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
-  return L2HMC_OK;
+  return launched();
 }
 
 // the plan of the mc entry: loo_plan with the caller's tail stride in the place of M

@@ -311,9 +311,7 @@ int l2hmc_moment_sums(const float* X, int64_t steps, int64_t n_chains, int32_t d
   hipLaunchKernelGGL(moment_reduce_kernel, dim3((unsigned)((d * d + d + 255) / 256), (unsigned)p.nsets), dim3(256), 0, s,
                      (const double*)workspace, p.nbx * p.nseg, p.stride, p.set_stride, p.P, p.T, (int)d, sum_out, cross_out,
                      batch_sum_out, batch_cross_out);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(L2HMC_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
-  return L2HMC_OK;
+  return launched();
 }
 
 }  // extern "C"

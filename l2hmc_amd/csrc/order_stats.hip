@@ -229,9 +229,7 @@ int l2hmc_order_stats_count(const float* X, int64_t n_draws, int32_t d, int32_t 
     case 16: order_count_launch<16>(p, runs, s, X, n_draws, d, n_ranks, pass, prefix, hist, n_nan); break;
     default: order_count_launch<32>(p, runs, s, X, n_draws, d, n_ranks, pass, prefix, hist, n_nan); break;
   }
-  e = hipGetLastError();
-  if (e != hipSuccess) return fail(L2HMC_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
-  return L2HMC_OK;
+  return launched();
 }
 
 int l2hmc_order_stats_advance(const int64_t* hist, int64_t* remaining, uint32_t* prefix, int32_t d, int32_t n_ranks,
@@ -244,9 +242,7 @@ int l2hmc_order_stats_advance(const int64_t* hist, int64_t* remaining, uint32_t*
   hipLaunchKernelGGL(radix_advance_kernel, dim3((unsigned)n), dim3(64), 0, (hipStream_t)stream,
                      (const long long*)hist, (long long*)remaining, prefix, n, 32 - kRadixBits * (pass + 1),
                      pass == kRadixPasses - 1 ? values : (float*)nullptr);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(L2HMC_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
-  return L2HMC_OK;
+  return launched();
 }
 
 int l2hmc_order_stats(const float* X, int64_t n_draws, int32_t d, const int64_t* ranks, int32_t n_ranks, float* values,

@@ -10,7 +10,7 @@
 // Work unit = one WAVE: a group of NB consecutive 16-row data blocks x a chunk of consecutive 16-draw tiles.  The wave keeps the
 // XA fragments and labels of its data blocks in registers for the whole launch and streams the draw tiles past them; the tile
 // loop -- load one tile ahead, stage into the wave's own LDS region, contract, and the end-of-wave reduction -- is the one of
-// draw_tiles.hpp, shared with loo.hip.  Here, per tile:
+// draw_tiles.hpp, and p1, lik and ll come from BernoulliLogit::sums (glm_family.hpp).  Here, per tile:
 //   sum      each of p1, lik, ll is converted to float64 and added to the lane's own sum of (draw lane c, row 4 q + r); ll^2 is
 //            formed and added in float64 (one fma).  A draw at or past S is EXCLUDED by a select on the lane (a zero draw would
 //            add p1 = 0.5 and ll = -log 2).  No float32 partial sums anywhere.
@@ -18,41 +18,23 @@
 //   end      the 16 NB rows x 4 sums go to workspace[chunk][4][n]; rows at or past n are never written.
 //   pass 2   chunk_reduce_kernel: sums[k][i] = the chunks' partials added in chunk order.  No floating-point atomics: two
 //            calls give identical bits.
-// Units are ordered (chunk, group) with the group fastest, so the waves of a workgroup read the same draws.  The planner aims
-// for kPredictUnits waves: at S large / n small the chunks supply them, at n large / S small the data-block groups do.
+// Units are ordered (chunk, group) with the group fastest, so the waves of a workgroup read the same draws.  The plan is
+// draw_plan's (draw_tiles.hpp), aiming for kDrawUnits waves: at S large / n small the chunks supply them, at n large / S small
+// the data-block groups do.
 //
 // Occupancy by design: 2 waves per SIMD (8 per CU) -- the main kernel must stay within 256 registers (held by
 // tests/test_predictive_cpu.py from the compiler's listing); its LDS (at most 4 x 8448 bytes per workgroup) never limits that.
 // Geometries <NTM feature tiles compiled, NB data blocks per wave>: <1, 4>, <2, 4>, <4, 2>, <8, 2> -- 32 NB registers of
 // float64 sums and 4 NTM NB of fragments per lane.
 #include "draw_tiles.hpp"
+#include "glm_family.hpp"
 
 namespace l2hmc {
 
 constexpr int kPredictThreads = 256;      // 4 independent waves
-constexpr int kPredictUnits = 4096;       // waves the planner aims for (two resident sets of 256 CUs x 8)
-constexpr int kPredictMinTiles = 4;       // draw tiles per chunk at least: the end-of-wave reduction costs about one tile
 
-struct PredictPlan {
-  int NT, NTM, NB, nblk, ngroups;
-  long long ntiles, tpc, nchunks;         // 16-draw tiles, tiles per chunk, chunks
-};
-
-static bool predict_plan(const char* who, int64_t n_draws, int32_t n_data, int32_t d, PredictPlan& p) {
-  if (!logistic_history_args_ok(who, n_draws, n_data, d)) return false;
-  p.NT = tiles_of(d);
-  p.NTM = p.NT <= 2 ? p.NT : p.NT <= 4 ? 4 : 8;
-  p.NB = p.NTM <= 2 ? 4 : 2;
-  p.nblk = (n_data + 15) / 16;
-  p.ngroups = (p.nblk + p.NB - 1) / p.NB;
-  p.ntiles = (n_draws + 15) / 16;
-  long long want = (kPredictUnits + p.ngroups - 1) / p.ngroups;
-  if (want > p.ntiles) want = p.ntiles;
-  p.tpc = (p.ntiles + want - 1) / want;
-  if (p.tpc < kPredictMinTiles) p.tpc = kPredictMinTiles;
-  p.nchunks = (p.ntiles + p.tpc - 1) / p.tpc;          // no empty chunk
-  return true;
-}
+// data blocks per wave: 4 at NTM <= 2 feature tiles (d <= 32), else 2
+constexpr int predict_nb(int d) { return d <= 32 ? 4 : 2; }
 
 template <int NTM, int NB>
 __global__ __launch_bounds__(kPredictThreads) void predict_kernel(const float* __restrict__ W, long long S, int d,
@@ -101,15 +83,8 @@ __global__ __launch_bounds__(kPredictThreads) void predict_kernel(const float* _
         const f4 L = Lg[j];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          // e = exp(-|l|): sigmoid(a) = 1 / (1 + e) for a >= 0, e / (1 + e) below, for a = l and a = z (|z| = |l|)
-          const float l = L[r];
-          const float e = fexp(-fabsf(l));
-          const float inv = __builtin_amdgcn_rcpf(1.f + e);
-          const float lo = e * inv;
-          const float z = yv[j][r] > 0.5f ? l : -l;
-          const float p1 = l >= 0.f ? inv : lo;
-          const float lik = z >= 0.f ? inv : lo;
-          const float ll = fminf(z, 0.f) - 0.6931471805599453f * __builtin_amdgcn_logf(1.f + e);
+          float p1, lik, ll;
+          BernoulliLogit::sums(L[r], yv[j][r], p1, lik, ll);
           const double dll = (double)(valid ? ll : 0.f);
           acc[j][0][r] += (double)(valid ? p1 : 0.f);
           acc[j][1][r] += (double)(valid ? lik : 0.f);
@@ -130,15 +105,15 @@ using namespace l2hmc;
 extern "C" {
 
 int64_t l2hmc_logistic_predict_workspace_doubles(int64_t n_draws, int32_t n_data, int32_t d) {
-  PredictPlan p;
-  if (!predict_plan("l2hmc_logistic_predict_workspace_doubles", n_draws, n_data, d, p)) return L2HMC_ERR_ARG;
+  DrawPlan p;
+  if (!draw_plan("l2hmc_logistic_predict_workspace_doubles", n_draws, n_data, d, predict_nb(d), false, p)) return L2HMC_ERR_ARG;
   return p.nchunks * 4 * (int64_t)n_data;
 }
 
 int l2hmc_logistic_predict(const float* draws, int64_t n_draws, int32_t d, const float* packed, int32_t n_data, double* sums,
                            double* workspace, void* stream) {
-  PredictPlan p;
-  if (!predict_plan("l2hmc_logistic_predict", n_draws, n_data, d, p)) return L2HMC_ERR_ARG;
+  DrawPlan p;
+  if (!draw_plan("l2hmc_logistic_predict", n_draws, n_data, d, predict_nb(d), false, p)) return L2HMC_ERR_ARG;
   if (!draws || !packed || !sums || !workspace)
     return fail(L2HMC_ERR_ARG, "l2hmc_logistic_predict: draws, packed, sums and workspace are required%s");
   if (((uintptr_t)draws & 3) || ((uintptr_t)packed & 15) || ((uintptr_t)sums & 7) || ((uintptr_t)workspace & 7))
@@ -146,20 +121,13 @@ int l2hmc_logistic_predict(const float* draws, int64_t n_draws, int32_t d, const
   hipStream_t s = (hipStream_t)stream;
   const long long units = (long long)p.ngroups * p.nchunks;
   const dim3 grid((unsigned)((units + 3) / 4)), block(kPredictThreads);
-#define L2HMC_PREDICT_LAUNCH(NTM, NB)                                                                                    \
-  hipLaunchKernelGGL((predict_kernel<NTM, NB>), grid, block, 0, s, draws, (long long)n_draws, (int)d, packed, (int)n_data, \
-                     p.NT, p.ngroups, p.nchunks, p.tpc, workspace)
-  switch (p.NTM) {
-    case 1: L2HMC_PREDICT_LAUNCH(1, 4); break;
-    case 2: L2HMC_PREDICT_LAUNCH(2, 4); break;
-    case 4: L2HMC_PREDICT_LAUNCH(4, 2); break;
-    default: L2HMC_PREDICT_LAUNCH(8, 2); break;
-  }
-#undef L2HMC_PREDICT_LAUNCH
+  on_feature_tiles(p.NTM, [&](auto ntm) {
+    constexpr int NTM = decltype(ntm)::value, NB = predict_nb(16 * NTM);
+    hipLaunchKernelGGL((predict_kernel<NTM, NB>), grid, block, 0, s, draws, (long long)n_draws, (int)d, packed, (int)n_data, p.NT,
+                       p.ngroups, p.nchunks, p.tpc, workspace);
+  });
   chunk_reduce_launch(workspace, p.nchunks, 4LL * n_data, sums, s);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(L2HMC_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
-  return L2HMC_OK;
+  return launched();
 }
 
 }  // extern "C"

@@ -83,12 +83,11 @@ struct PsisWorkspace {
 
 static PsisWorkspace psis_workspace(void* base, const PsisPlan& p, int64_t n_rows, int64_t M) {
   PsisWorkspace w;
-  char* b = (char*)base;
-  int64_t o = 0;
-  w.err = (unsigned long long*)(b + o); o += 8;
-  w.x = (double*)(b + o); o += n_rows * M * 8;
-  w.prof = (double*)(b + o); o += n_rows * p.n_theta * 8;
-  w.bytes = o;
+  Carve c{(char*)base};
+  w.err = c.take<unsigned long long>(1);
+  w.x = c.take<double>(n_rows * M);
+  w.prof = c.take<double>(n_rows * p.n_theta);
+  w.bytes = c.off;
   return w;
 }
 
@@ -360,9 +359,7 @@ int l2hmc_psis_smooth(const double* lam, const int64_t* n_tail, const double* la
   hipLaunchKernelGGL(psis_finish_kernel, dim3((unsigned)(n < kPsisMaxGridRows ? n : kPsisMaxGridRows)), dim3(kPsisThreads), 0, s,
                      lam, (const long long*)n_tail, lam_cutoff, n, M, p.n_theta, (const double*)ws.x, (const double*)ws.prof, out,
                      weights, ws.err);
-  e = hipGetLastError();
-  if (e != hipSuccess) return fail(L2HMC_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
-  return L2HMC_OK;
+  return launched();
 }
 
 }  // extern "C"

@@ -792,9 +792,7 @@ int l2hmc_vae_energy(const L2hmcMlp3* decoder, const float* aux, const float* x,
   mlp3_transposes(s, *decoder, ws);
   rc = vae_energy(s, *decoder, aux, x, d, n_chains, d, ws, w + p.lg, w + p.rowsum, U_out, nullptr, grad_out, d, beta);
   if (rc) return rc;
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(L2HMC_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
-  return L2HMC_OK;
+  return launched();
 }
 
 int l2hmc_p_accept_energies(const float* U0, const float* v0, const float* U1, const float* v1, const float* log_jac,
@@ -804,9 +802,7 @@ int l2hmc_p_accept_energies(const float* U0, const float* v0, const float* U1, c
   if (n_chains == 0) return L2HMC_OK;
   hipLaunchKernelGGL(k_accept_from_energies, dim3(nblk(n_chains)), dim3(256), 0, (hipStream_t)stream, U0, v0, U1, v1,
                      log_jac, p_out, (long long)n_chains, d);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(L2HMC_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
-  return L2HMC_OK;
+  return launched();
 }
 
 int l2hmc_trajectory_split(const L2hmcSplitArgs* a, void* stream) {
@@ -887,9 +883,7 @@ int l2hmc_trajectory_split(const L2hmcSplitArgs* a, void* stream) {
   if (a->v_out) (void)hipMemcpyAsync(a->v_out, vc, sizeof(float) * N * d, hipMemcpyDeviceToDevice, s);
   hipLaunchKernelGGL(k_finish, dim3(nblk(N * d)), dim3(256), 0, s, U0d, w + p.K0, U1d, w + p.K1, c.ld, a->u, a->x,
                      xc, L, a->p_out, a->logjac_out, a->x_next, N, d);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(L2HMC_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
-  return L2HMC_OK;
+  return launched();
 }
 
 }  // extern "C"

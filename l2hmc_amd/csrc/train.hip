@@ -1219,9 +1219,7 @@ static int reduce_slots(float* part, int slots, int n_grad, float* grad, const F
     hipLaunchKernelGGL(train_final_kernel, dim3((unsigned)((n_grad + 255) / 256 + 1 + mh_blocks)), dim3(256), 0, s, part, slots,
                        n_grad, grad, *f);
   }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(L2HMC_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
-  return L2HMC_OK;
+  return launched();
 }
 
 }  // namespace l2hmc
@@ -1408,9 +1406,7 @@ int l2hmc_adam_step_terms(float* params, const float* grad, float* m, float* v, 
     return fail(L2HMC_ERR_ARG, "l2hmc_adam_step_terms: bad argument%s");
   hipLaunchKernelGGL(adam_terms_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, params, grad, m, v,
                      (long long)n, adam_lr_t(lr, beta1, beta2, step), beta1, beta2, epsilon, last_is_log_eps, terms6, scale, loss_out);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(L2HMC_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
-  return L2HMC_OK;
+  return launched();
 }
 
 }  // extern "C"

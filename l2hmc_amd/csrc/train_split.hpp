@@ -963,9 +963,7 @@ int l2hmc_train_split_grad(const L2hmcTrainSplitArgs* a, void* stream) {
   if (cb_rc) return fail(L2HMC_ERR_ARG, "the net reverse callback failed (returned %s%lld)", "", (long long)cb_rc);
   if (unets) {         // the nets' parameter gradients were accumulated by the callbacks; what is the library's is d loss / d eps
     hipLaunchKernelGGL(k_sum_chain, dim3(1), dim3(256), 0, s, deps, N, a->grad);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(L2HMC_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
-    return L2HMC_OK;
+    return launched();
   }
   // ---- parameter gradients: one contraction over all (evaluation, chain) rows per weight matrix ---------------------
   const SNetOff o = snet_off(d, H);
@@ -1033,9 +1031,7 @@ int l2hmc_train_split_grad(const L2hmcTrainSplitArgs* a, void* stream) {
     launch_gemm_tn(s, a->aux, enc.n_in, de1, enc.n_h1, N, enc.n_in, enc.n_h1, G + oW1, enc.n_h1, 1, part, p.part_cap);
     colsum_into(s, de1, enc.n_h1, N, enc.n_h1, G + ob1, nullptr, nullptr, 0, 0, part, p.part_cap);
   }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(L2HMC_ERR_HIP, "kernel launch: %s", hipGetErrorString(e));
-  return L2HMC_OK;
+  return launched();
 }
 
 }  // extern "C"

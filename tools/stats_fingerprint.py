@@ -11,8 +11,10 @@ versions of `l2hmc_amd/*.py` on ONE build of the library (`L2HMC_LIB=`): a host-
     python tools/stats_fingerprint.py --time                # median host time of `describe` and `loo(r_eff=)` on the tiny device history
 
 The history is a seeded AR(1) of 40 steps, 6 chains and 3 coordinates whose means and scales differ per coordinate.  `--kernels`
-runs ONE version of the Python against two builds of the library instead: `pointwise_sums`, `loo_tails` and `order_statistics`
-are declared bitwise reproducible, so a refactor of their kernels must leave every line as it was too."""
+runs ONE version of the Python against two builds of the library instead: `pointwise_sums`, `loo_tails` (with and without a
+tail length per row), `order_statistics`, `relative_eff` and the statistics of a `glm.Glm` over Poisson counts (`log_lik`,
+`pointwise_sums`, `loo_tails`, `relative_eff`) are declared bitwise reproducible, so a refactor of their kernels must leave
+every line as it was too."""
 import argparse
 import hashlib
 import os
@@ -25,7 +27,7 @@ sys.path.insert(0, ROOT)
 import numpy as np
 import torch
 
-from l2hmc_amd import diagnostics, func_utils, multivariate, predictive, psis, quantiles, sharding
+from l2hmc_amd import diagnostics, func_utils, glm, multivariate, predictive, psis, quantiles, sharding
 
 STEPS, CHAINS, DIM, ROWS, SCALE = 40, 6, 3, 5, 1.7
 SPLIT = 2                                 # --ranks 2: rank 0 holds chains [0, 2), rank 1 chains [2, 6)
@@ -36,6 +38,9 @@ R_EFF = np.array([0.3, 0.5, 1.0, np.nan, 2.0])   # per-row tail lengths 48, 48, 
 # feature tiles; two row groups of the predict plan at four blocks per wave; five tiles per chunk with a last tile of 9 draws, a
 # last chunk of one tile and dead waves; no tail at all (M = 0)
 KERNEL_SHAPES = ((70, 35, 5), (523, 33, 17), (70, 35, 40), (300, 50, 128), (4099, 100, 25), (65609, 33, 1), (4, 3, 2))
+# the Poisson kernels alone: n_draws > 131072 cuts the gather's segments off a tile boundary (tests/test_gpu_glm.py: 69-draw
+# segments at d = 2; tests/test_gpu_glm_geometries.py: 65-draw segments and a short last one under the late loads of d = 40)
+GLM_LONG_SHAPES = ((140001, 3, 2), (131073, 3, 40))
 
 
 def history():
@@ -138,25 +143,52 @@ def loo_cases(X, rx, ry):
         yield "psis.smooth_tails weights=%d" % w, lambda w=w: psis.smooth_tails(like(lam), like(n_tail), like(cutoff), weights=w)
 
 
+def _sorted_tail(tails):
+    tails["tail"] = torch.sort(tails["tail"], dim=-1).values                        # its slot order is arrival order
+    return tails
+
+
 def kernels():
-    """One line per (statistic, shape) of the kernels behind `pointwise_sums`, `loo_tails` and `order_statistics`."""
-    from tests import loo_case
+    """One line per (statistic, shape) of the draw-tile and radix-select kernels: the logistic `pointwise_sums`, `loo_tails`
+    (one tail length, then one per row), `order_statistics` and `relative_eff`, and the same of a Poisson `glm.Glm`."""
+    from tests import glm_case, lik_stats_case, loglik_case, loo_case
     torch.cuda.set_device(0)
+    cuda = lambda a: torch.as_tensor(a).cuda()  # noqa: E731
+    line = lambda res, name, label: print("%s  %s %s" % (sha(res), name, label), flush=True)  # noqa: E731
     inputs = []
     for S, n, d in KERNEL_SHAPES:
-        inputs.append(("(%d, %d, %d)" % (S, n, d),) + tuple(torch.as_tensor(a).cuda() for a in loo_case.case(S, n, d)))
-    W, X, y = (torch.as_tensor(a).cuda() for a in loo_case.case(40 * 13, 33, 17))
+        inputs.append(("(%d, %d, %d)" % (S, n, d),) + tuple(cuda(a) for a in loo_case.case(S, n, d)))
+    W, X, y = (cuda(a) for a in loo_case.case(40 * 13, 33, 17))
     hist = W.reshape(40, 13, 17)[3:]                          # a base that is not 16-byte aligned
     assert hist.is_contiguous() and hist.data_ptr() % 16
     inputs.append(("(40, 13, 17)[3:], 33 rows", hist, X, y))
     for label, W, X, y in inputs:
         S = W.numel() // W.shape[-1]
         ranks = np.unique([0, 1, S // 3, S // 2, S - 2, S - 1])
-        tails = predictive.loo_tails(W, X, y)
-        tails["tail"] = torch.sort(tails["tail"], dim=-1).values                    # its slot order is arrival order
-        for name, res in (("pointwise_sums", predictive.pointwise_sums(W, X, y)), ("loo_tails", tails),
-                          ("order_statistics", quantiles.order_statistics(W, ranks))):
-            print("%s  %s %s" % (sha(res), name, label), flush=True)
+        lens = loglik_case.lengths_for(S, X.shape[0])
+        line(predictive.pointwise_sums(W, X, y), "pointwise_sums", label)
+        line(_sorted_tail(predictive.loo_tails(W, X, y)), "loo_tails", label)
+        line(_sorted_tail(predictive.loo_tails(W, X, y, tail_len_row=lens)), "loo_tails tail_len_row", label)
+        line(quantiles.order_statistics(W, ranks), "order_statistics", label)
+    for S, n, d in KERNEL_SHAPES + GLM_LONG_SHAPES:
+        W, X, y, o = glm_case.case(S, n, d)
+        label, Wd, model = "(%d, %d, %d)" % (S, n, d), cuda(W), glm.Glm(X, y, o)
+        line(model.log_lik(Wd), "glm log_lik", label)
+        line(model.pointwise_sums(Wd), "glm pointwise_sums", label)
+        line(_sorted_tail(model.loo_tails(Wd)), "glm loo_tails", label)
+        line(_sorted_tail(model.loo_tails(Wd, tail_len_row=loglik_case.lengths_for(S, n))), "glm loo_tails tail_len_row", label)
+    # the history forms: the smallest (steps, chains, d, rows) of tests/lik_stats_case.py, whole chains and split ones
+    M, N, d, rho, max_lag, _ = min(lik_stats_case.FIXTURES, key=lambda f: f[0] * f[1] * f[2])
+    W, X, y = lik_stats_case.ar1_case(M, N, d, rho)
+    rng = np.random.RandomState(19)
+    o = rng.uniform(-1.0, 2.0, size=X.shape[0]).astype(np.float32)
+    counts = rng.poisson(np.exp(X.astype(np.float64) @ W.reshape(-1, d).mean(axis=0) + o)).astype(np.float32)
+    Wd, model = cuda(W), glm.Glm(X, counts, o)
+    for split in (False, True):
+        label = "(%d, %d, %d), %d rows, split=%d" % (M, N, d, X.shape[0], split)
+        lag = min(max_lag, (M // 2 if split else M) - 1)
+        line(predictive.relative_eff(Wd, X, y, max_lag=lag, split=split), "relative_eff", label)
+        line(model.relative_eff(Wd, max_lag=lag, split=split), "glm relative_eff", label)
 
 
 def device_inputs(X, dev):
@@ -251,7 +283,7 @@ def timed():
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--cpu", action="store_true", help="numpy and CPU-tensor inputs only (no GPU needed)")
-    ap.add_argument("--kernels", action="store_true", help="the device kernels of predictive and quantiles, shape by shape")
+    ap.add_argument("--kernels", action="store_true", help="the device kernels of predictive, quantiles and glm, shape by shape")
     ap.add_argument("--ranks", type=int, default=1)
     ap.add_argument("--backend", default="gloo", choices=("gloo", "nccl"))
     ap.add_argument("--input", default="numpy", choices=("numpy", "device"))
