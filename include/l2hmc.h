@@ -44,7 +44,9 @@ enum {
   L2HMC_ENERGY_FUNNEL = 5,      /* Gaussian funnel                distributions.py:155-180     */
   /* (6 is the Python binding's tag of the VAE decoder posterior, which runs on the GEMM engine) */
   L2HMC_ENERGY_LOGISTIC = 7,    /* Bayesian logistic regression   (l2hmc_pack_logistic)        */
-  L2HMC_ENERGY_POISSON = 8      /* Bayesian Poisson regression, log link and offsets (l2hmc_pack_logistic) */
+  L2HMC_ENERGY_POISSON = 8,     /* Bayesian Poisson regression, log link and offsets (l2hmc_pack_logistic) */
+  L2HMC_ENERGY_BINOMIAL = 9     /* Bayesian binomial (trials) / negative-binomial (fixed dispersion) regression: logit link, per-row
+                                   offsets and weights (l2hmc_pack_logistic, l2hmc_binomial_aux_floats) */
 };
 
 /* One S/T/Q network in the reference's own parameter layout: `Linear` keeps W as
@@ -88,6 +90,20 @@ typedef struct L2hmcNet {
  *                same rule; exp overflows as IEEE float32 does (mu = inf: U and grad U are non-finite, the accept rule rejects).
  *                Every training entry point returns L2HMC_ERR_UNSUPPORTED for it: train on the same likelihood as a
  *                caller-supplied energy (energy_cb), then sample with the trained nets on this kind
+ *   BINOMIAL   : one energy for two regressions on n data rows x_i (d features) with a N(0, sigma^2 I) prior: with a per-row
+ *                offset o_i and weight m_i, t_i = x_i . w + o_i,
+ *                        U(w) = sum_i [m_i softplus(t_i) - y_i t_i] + |w|^2 / (2 sigma^2),   grad U = X^T (m sigmoid(t) - y) + w / sigma^2.
+ *                Binomial regression with the logit link: y_i successes out of m_i trials, o_i the offset.  Negative-binomial
+ *                regression (NB2: mean mu_i = exp(x_i . w + offset_i), variance mu + mu^2 / phi, phi fixed): m_i = y_i + phi,
+ *                o_i = offset_i - log phi, so that sigmoid(t) = mu / (mu + phi).  The log-likelihood is -[m softplus(t) - y t]
+ *                plus a constant of the row (log C(m, y); lgamma(y + phi) - lgamma(phi) - lgamma(y + 1)), which the energy drops.
+ *                n_comp = n (>= 1), mu = the buffer written by l2hmc_pack_logistic with y in the label slot, prec = the row
+ *                constants: l2hmc_binomial_aux_floats(n) = 32 ceil(n / 16) floats, per 16-row block [16 offsets | 16 weights],
+ *                zero beyond n (required), eta = sigma^2 (> 0), logc = NULL (ignored), easy = 0 (ignored).  d <= 128.  Runs where
+ *                POISSON runs, the data and the row constants staged in LDS or streamed by the same rule.  Nothing overflows:
+ *                the residual is bounded by max(m, y) and softplus(t) = max(t, 0) + log(1 + exp(-|t|)).  Every training entry
+ *                point returns L2HMC_ERR_UNSUPPORTED for it: train on the same likelihood as a caller-supplied energy
+ *                (energy_cb), then sample with the trained nets on this kind
  * temperature divides U and grad U (dynamics.py:204-212); 1.0 when unused.
  * anneal_beta in (0, 1): the AIS bridge of utils/ais.py:46-47 with the standard-normal initial
  * energy its caller uses (eval_vae.py:55-56):  U := (1 - beta) |x|^2 / 2 + beta U(x);  0 (or 1) = off. */
@@ -255,6 +271,9 @@ int64_t l2hmc_packed_logistic_floats(int32_t n_data, int32_t d);
 int l2hmc_pack_logistic(const float* X, const float* y, int32_t n_data, int32_t d, float* packed, void* stream);
 /* Floats of the offset buffer of L2HMC_ENERGY_POISSON (L2hmcEnergy.prec): 16 ceil(n_data / 16), the tail zero-padded. */
 int64_t l2hmc_poisson_offset_floats(int32_t n_data);
+/* Floats of the row-constant buffer of L2HMC_ENERGY_BINOMIAL (L2hmcEnergy.prec): 32 ceil(n_data / 16) -- per 16-row data block
+ * [16 offsets | 16 weights], rows beyond n_data zero.  L2HMC_ERR_ARG for n_data outside 1 ... 1048576. */
+int64_t l2hmc_binomial_aux_floats(int32_t n_data);
 
 /* The fused generalised-leapfrog trajectory:
  *   Dynamics.forward / .backward           dynamics.py:246-300  (n_steps = T)
@@ -878,7 +897,16 @@ int l2hmc_logistic_lik_stats(const float* draws, int64_t steps, int64_t n_chains
  *               formed in float64 and rounded once, [2] the saturated log-likelihood sat_i = y log y - y - lgamma(y + 1) (0 at
  *               y = 0), the supremum of ll over eta.
  *   family      L2HMC_GLM_POISSON: with eta = x_i . w_s (float32, f32-input MFMA), h = eta + o_i and mu = exp(h) (hardware
- *               exp2), ll = fma(y_i, h, -mu) - g_i, four float32 roundings.  Any other value is L2HMC_ERR_ARG.
+ *               exp2), ll = fma(y_i, h, -mu) - g_i, four float32 roundings.
+ *               L2HMC_GLM_BINOMIAL and L2HMC_GLM_NEGBINOMIAL: row_consts is (4, n_data): [0] the offset o_i, [1] the weight m_i,
+ *               [2] sat_i = y log(y / m) + (m - y) log(1 - y / m) + c_i (0 log 0 = 0), [3] the constant c_i, each formed in float64
+ *               and rounded once.  With t = eta + o_i, e = exp(-|t|) (hardware exp2) and softplus(t) = max(t, 0) + log(1 + e):
+ *               ll = fma(y_i, t, -(m_i softplus(t))) + c_i -- the float32 operations of L2HMC_ENERGY_BINOMIAL, whose U term is
+ *               c_i - ll bit for bit.  BINOMIAL: m_i trials, c_i = log C(m_i, y_i), predictive mean m_i sigmoid(t).
+ *               NEGBINOMIAL (NB2, dispersion phi): m_i = y_i + phi, o_i = offset_i - log phi, c_i = lgamma(y_i + phi) -
+ *               lgamma(phi) - lgamma(y_i + 1); sums[0] adds exp(t) = mu / phi (the caller multiplies by phi; +inf as IEEE
+ *               gives it).  The absolute error of a float32 ll grows with m |t| (as the Poisson family's with y |h|).
+ *               Any other value (0, 2, 5, ...) is L2HMC_ERR_ARG "unknown family".
  * Every kernel forms ll by the one device function of the family: the bits of ll[s, i] depend on (draws, X, y, row_consts)
  * alone -- not on the entry, the pass, the chunk or the rows that share a call.
  *
@@ -908,8 +936,8 @@ int l2hmc_logistic_lik_stats(const float* draws, int64_t steps, int64_t n_chains
  * n_draws > 2^40 / d, tail_stride outside 0 .. n_draws - 1, tail_stride n_data > 2^31, a NULL required pointer (tail may be
  * NULL when tail_stride = 0), draws / row_consts / cutoff / top / tail / out not 4-byte, packed not 16-byte, n_tail /
  * tail_len_row / sums / workspace not 8-byte aligned. */
-enum { L2HMC_GLM_POISSON = 1 };
-int l2hmc_glm_log_lik(const float* draws, int64_t n_draws, int32_t d, const float* packed, const float* row_consts /* (3, n_data) */,
+enum { L2HMC_GLM_POISSON = 1, L2HMC_GLM_BINOMIAL = 3, L2HMC_GLM_NEGBINOMIAL = 4 };
+int l2hmc_glm_log_lik(const float* draws, int64_t n_draws, int32_t d, const float* packed, const float* row_consts /* (3 or 4, n_data) */,
                       int32_t n_data, int32_t family, float* out /* (n_draws, n_data) */, void* stream);
 int64_t l2hmc_glm_predict_workspace_doubles(int64_t n_draws, int32_t n_data, int32_t d);
 int l2hmc_glm_predict(const float* draws, int64_t n_draws, int32_t d, const float* packed, const float* row_consts, int32_t n_data,

@@ -14,8 +14,10 @@ LIB_PATH = os.path.abspath(os.environ["L2HMC_LIB"]) if os.environ.get("L2HMC_LIB
 
 ENERGY_GAUSS_DIAG, ENERGY_GAUSS_DENSE, ENERGY_GMM, ENERGY_ROUGHWELL, ENERGY_FUNNEL = 1, 2, 3, 4, 5
 GLM_POISSON = 1           # include/l2hmc.h L2HMC_GLM_POISSON: the family of the l2hmc_glm_* entries
+GLM_BINOMIAL, GLM_NEGBINOMIAL = 3, 4      # L2HMC_GLM_BINOMIAL, L2HMC_GLM_NEGBINOMIAL (2 is not a family)
 ENERGY_LOGISTIC = 7       # Bayesian logistic regression (6 is vae.ENERGY_VAE, the Python-side tag of the decoder posterior)
 ENERGY_POISSON = 8        # Bayesian Poisson regression, log link with offsets (sampling only: no training kernel)
+ENERGY_BINOMIAL = 9       # binomial (trials) / negative-binomial (fixed dispersion) regression (sampling only)
 
 _fp = C.c_void_p  # device pointers travel as integers
 
@@ -142,6 +144,7 @@ SYMBOLS = {
     "l2hmc_packed_logistic_floats": (C.c_int64, [C.c_int32, C.c_int32]),
     "l2hmc_pack_logistic": (C.c_int, [_fp, _fp, C.c_int32, C.c_int32, _fp, _fp]),
     "l2hmc_poisson_offset_floats": (C.c_int64, [C.c_int32]),
+    "l2hmc_binomial_aux_floats": (C.c_int64, [C.c_int32]),
     "l2hmc_trajectory": (C.c_int, [C.POINTER(L2hmcTrajectoryArgs), _fp]),
     "l2hmc_trajectory_ladder": (C.c_int, [C.POINTER(L2hmcTrajectoryArgs), C.POINTER(L2hmcLadderArgs), _fp]),
     "l2hmc_energy": (C.c_int, [C.POINTER(L2hmcEnergy), _fp, C.c_int64, C.c_int32, _fp, _fp, _fp]),

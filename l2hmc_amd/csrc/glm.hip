@@ -1,5 +1,5 @@
 // l2hmc_glm_log_lik, l2hmc_glm_loo_tails, l2hmc_glm_predict -- model criticism of a generalised linear model (Poisson regression
-// with the log link; glm_family.hpp) over every recorded draw, from a history that stays where the sampler wrote it: the
+// with the log link, binomial regression with trials and NB2 negative-binomial regression; glm_family.hpp) over every recorded draw, from a history that stays where the sampler wrote it: the
 // pointwise log-likelihood matrix when it is wanted, the per-row raw material of PSIS-LOO (Vehtari, Gelman, Gabry 2017; Vehtari,
 // Simpson, Gelman, Yao, Gabry 2024) and the sums behind the posterior predictive mean and WAIC without it.  For draws W (S, d),
 // the data packed by l2hmc_pack_logistic (rows x_i, the responses y_i in the label slot) and the row constants (3, n) float32
@@ -42,6 +42,8 @@
 //            sum exp((double) ll - sat_i) (one double exp per term; in (0, 1] up to the rounding of sat), sum ll, sum ll^2
 //            (formed and added in float64, one fma).  A draw at or past S and a row at or past n never count; partials are
 //            added in chunk order.
+// The kernels and their launches are templates over the family in glm_kernels.hpp; this unit holds the entries, the plans, the
+// workspace and the Poisson instantiations, glm_binomial.hip those of the binomial and the negative-binomial family.
 // No floating-point atomics anywhere: integer counts and maxima do not depend on arrival order, the tail is a set, the sums have
 // a fixed tree.  Every outward write is an ordinary vector store or an integer atomic from plain C++.  A row's bits do not
 // depend on the other rows of the call.
@@ -53,26 +55,32 @@
 // Measured (profiles/glm_bench.txt, 1000 x 4096 draws of d = 25 against 1000 rows): a count pass 6.0 to 8.9 ms, as
 // l2hmc_logistic_loo_tails' (6.0 to 8.1); the gather 21.8 ms against 7.7 -- three double exp per element, as in
 // loglik_tails.hip -- of which the draw-order sums cost 3.9 (the lane-wise form took 17.9).
-#include <math.h>
-
-#include "draw_tiles.hpp"
-#include "glm_family.hpp"
-#include "radix_select.hpp"
+#include "glm_kernels.hpp"
 
 namespace l2hmc {
 
-constexpr int kGlmThreads = 256;          // 4 waves
-constexpr int kGlmNB = 2;                 // 16-row data blocks per wave
-constexpr int kGlmRows = 16 * kGlmNB;     // rows of a workgroup's histogram
-constexpr int kGlmTerms = 16 * 16 * 3;    // gather: the float64 terms of one data block of one tile
-
-struct GlmPlan : DrawPlan {
-  long long seg_rows, nseg, seg_quads;    // the gather's segments of consecutive draws (a function of n_draws alone)
-};
+L2HMC_GLM_LAUNCHES(extern, BinomialLogit)
+L2HMC_GLM_PREDICT(extern, BinomialLogit)
+L2HMC_GLM_PREDICT(extern, NegBinomialLog)
 
 static bool glm_family_ok(const char* who, int32_t family) {
-  if (family != PoissonLog::kAbi) { fail(L2HMC_ERR_ARG, "%s: unknown family %lld (L2HMC_GLM_POISSON = 1)", who, family); return false; }
+  if (family != PoissonLog::kAbi && family != BinomialLogit::kAbi && family != NegBinomialLog::kAbi) {
+    fail(L2HMC_ERR_ARG, "%s: unknown family %lld (L2HMC_GLM_POISSON = 1, L2HMC_GLM_BINOMIAL = 3, L2HMC_GLM_NEGBINOMIAL = 4)", who, family);
+    return false;
+  }
   return true;
+}
+
+// f(family struct tag) for a checked family.  LL_ONLY: the kernel uses ll alone, which the negative binomial shares with the
+// binomial -- one instantiation serves both.
+template <class T> struct family_tag { using type = T; };
+template <bool LL_ONLY, class Fn>
+static void on_family(int32_t family, Fn&& fn) {
+  switch (family) {
+    case PoissonLog::kAbi: fn(family_tag<PoissonLog>{}); break;
+    case BinomialLogit::kAbi: fn(family_tag<BinomialLogit>{}); break;
+    case NegBinomialLog::kAbi: fn(family_tag<std::conditional_t<LL_ONLY, BinomialLogit, NegBinomialLog>>{}); break;
+  }
 }
 
 // draw_plan (by_draws: the tails; else the matrix and the predictive sums) and the gather's segments
@@ -82,72 +90,6 @@ static bool glm_plan(const char* who, int32_t family, int64_t n_draws, int32_t n
   draw_segments(n_draws, p.seg_rows, p.nseg);                // (loglik_tails.hip's: the two routes add in one order)
   p.seg_quads = (p.nseg + 3) / 4;
   return true;
-}
-
-// the constants of the rows a lane meets: rc[k][j][r] = row_consts[k][16 (b0 + j) + 4 q + r], 0 for a dead row
-template <int NB, int KC>
-__device__ __forceinline__ void row_constants(const float* __restrict__ RC, int n, int b0, int nblk, int q, float (&rc)[KC][NB][4],
-                                              bool (&row_ok)[NB][4]) {
-#pragma unroll
-  for (int j = 0; j < NB; ++j) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int row = 16 * (b0 + j) + 4 * q + r;
-      row_ok[j][r] = b0 + j < nblk && row < n;
-#pragma unroll
-      for (int k = 0; k < KC; ++k) rc[k][j][r] = row_ok[j][r] ? RC[(long long)k * n + row] : 0.f;
-    }
-  }
-}
-
-// ---- the matrix ---------------------------------------------------------------------------------------------------------------
-template <typename F, int NTM>
-__global__ __launch_bounds__(kGlmThreads, 2) void glm_loglik_kernel(const float* __restrict__ W, long long S, int d,
-                                                                    const float* __restrict__ P, const float* __restrict__ RC,
-                                                                    int n, int NT, int ngroups, long long nchunks, long long tpc,
-                                                                    float* __restrict__ out) {
-  constexpr int NB = kGlmNB;
-  constexpr int REGION = tile_region(NTM);
-  __shared__ __attribute__((aligned(16))) float lds_all[4 * REGION];
-  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, c = lane & 15, q = lane >> 4;
-  const long long u = (long long)blockIdx.x * 4 + w;
-  if (u >= (long long)ngroups * nchunks) return;             // (no workgroup barrier anywhere: a wave may leave alone)
-  float* lds = lds_all + w * REGION;
-  tile_region_clear<NTM>(lds, lane);
-  const int group = (int)(u % ngroups);
-  const long long chunk = u / ngroups;
-  const int nblk = (n + 15) >> 4, b0 = group * NB;
-  f4 xa[NB][NTM], yv[NB];
-  block_fragments<NTM, NB>(P, NT, b0, nblk, lane, xa, yv);
-  float rc[2][NB][4];
-  bool row_ok[NB][4];
-  row_constants<NB, 2>(RC, n, b0, nblk, q, rc, row_ok);
-
-  const long long ntiles = (S + 15) >> 4;
-  const long long t0 = chunk * tpc, t1 = t0 + tpc < ntiles ? t0 + tpc : ntiles;
-  const TileWalk walk = tile_walk(lane, d, S);
-  float pre[4 * NTM];
-  tile_load<NTM>(W, t0, walk, lane, pre);
-  for (long long t = t0; t < t1; ++t) {
-    tile_stage<NTM>(lds, pre, walk, lane);
-    wave_lds_fence();
-    f4 E[NB];
-    tile_logits<NTM, NB>(lds, xa, c, q, NT, b0, nblk, E);
-    wave_lds_fence();
-    if (t + 1 < t1) tile_load<NTM>(W, t + 1, walk, lane, pre);
-    const long long draw = 16 * t + c;
-    const bool valid = draw < S;
-#pragma unroll
-    for (int j = 0; j < NB; ++j) {
-      if (b0 + j < nblk) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const float ll = F::ll(E[j][r], yv[j][r], rc[0][j][r], rc[1][j][r]);
-          if (valid && row_ok[j][r]) out[draw * n + (16 * (b0 + j) + 4 * q + r)] = ll;
-        }
-      }
-    }
-  }
 }
 
 // ---- the tails ----------------------------------------------------------------------------------------------------------------
@@ -192,279 +134,6 @@ __global__ void glm_loo_init_kernel(long long* __restrict__ remaining, long long
   if (i < (long long)n * stride) tail[i] = __builtin_inff();
 }
 
-// MODE 0: count the digit at `shift` of the keys on their row's prefix (first: no prefix, every key, and the row's largest key).
-// MODE 1: gather.
-template <typename F, int NTM, int MODE>
-__global__ __launch_bounds__(kGlmThreads, 2) void glm_loo_kernel(const float* __restrict__ W, long long S, int d,
-                                                                 const float* __restrict__ P, const float* __restrict__ RC, int n,
-                                                                 int NT, int ngroups, long long nchunks, long long tpc,
-                                                                 const uint32_t* __restrict__ prefix, int shift, int first,
-                                                                 unsigned long long* __restrict__ hist,
-                                                                 uint32_t* __restrict__ topkey, const long long* __restrict__ ranks,
-                                                                 float* __restrict__ top, unsigned long long* __restrict__ n_tail,
-                                                                 float* __restrict__ tail, long long stride,
-                                                                 unsigned long long* __restrict__ err, double* __restrict__ part) {
-  constexpr int NB = kGlmNB;
-  constexpr int REGION = tile_region(NTM);
-  __shared__ __attribute__((aligned(16))) float lds_all[4 * REGION];
-  __shared__ uint32_t hl[MODE == 0 ? kGlmRows * kRadixBins : 1];
-  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, c = lane & 15, q = lane >> 4;
-  const int group = (int)(blockIdx.x % (unsigned)ngroups);
-  const long long chunk = (long long)(blockIdx.x / (unsigned)ngroups) * 4 + w;
-  const bool live_wave = chunk < nchunks;                    // (wave-uniform; a dead wave still meets the barriers below)
-  float* lds = lds_all + w * REGION;
-  tile_region_clear<NTM>(lds, lane);
-  const int nblk = (n + 15) >> 4, b0 = group * NB;
-  // gather: the four numbers of every row of the workgroup -- offset, g, the cutoff's key, the row's maximum -- wait in LDS and
-  // are read per tile: held in registers across the float64 exponentials (whose constants the compiler keeps in registers
-  // too) they pushed the widest geometry into scratch
-  __shared__ __attribute__((aligned(16))) float rowc[MODE == 1 ? 4 * kGlmRows : 4];
-  // gather: the terms of one data block of one tile, [16 draws][16 rows][3 sums] float64 per wave, added serially in draw order
-  __shared__ double red_all[MODE == 1 ? 4 * kGlmTerms : 1];
-  if (MODE == 0) {
-    radix_hist_clear<kGlmRows, kGlmThreads>(hl);
-  } else if (threadIdx.x < kGlmRows) {
-    const int i = threadIdx.x, row = 16 * b0 + i;
-    const bool live = row < n;
-    const float tv = live ? radix_unkey(topkey[row]) : 0.f;
-    rowc[i] = live ? RC[row] : 0.f;
-    rowc[kGlmRows + i] = live ? RC[(long long)n + row] : 0.f;
-    rowc[2 * kGlmRows + i] = __uint_as_float(live ? prefix[row] : 0u);
-    rowc[3 * kGlmRows + i] = tv;
-    if (live && blockIdx.x < (unsigned)ngroups) top[row] = tv;          // (the first quad of chunks writes the row's maximum out)
-  }
-  __syncthreads();
-
-  if (live_wave) {
-    f4 xa[NB][NTM], yv[NB];
-    block_fragments<NTM, NB>(P, NT, b0, nblk, lane, xa, yv);
-    float rc[2][NB][4];               // count: the row's offset and g
-    bool row_ok[NB][4];
-    uint32_t pre_key[NB][4];          // count: the row's prefix above the digit (pass 0: the running largest key)
-    if (MODE == 0) row_constants<NB, 2>(RC, n, b0, nblk, q, rc, row_ok);
-#pragma unroll
-    for (int j = 0; j < NB; ++j) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = 16 * (b0 + j) + 4 * q + r;
-        if (MODE == 0) {
-          const uint32_t key = (row_ok[j][r] && !first) ? prefix[row] : 0u;
-          pre_key[j][r] = first ? 0u : key >> (shift + kRadixBits);
-        } else {
-          row_ok[j][r] = b0 + j < nblk && row < n;
-          rc[0][j][r] = rc[1][j][r] = 0.f;
-          pre_key[j][r] = 0u;
-        }
-      }
-    }
-    // gather: lane L < 48 owns the sum k = L / 16 of row L % 16 of either data block, added in DRAW ORDER over the segment
-    double sacc[NB];
-#pragma unroll
-    for (int j = 0; j < NB; ++j) sacc[j] = 0.0;
-    double* red = red_all + (MODE == 1 ? w * kGlmTerms : 0);
-
-    // count: the chunk is tpc 16-draw tiles.  gather: the chunk is ONE SEGMENT of `tpc` consecutive draws [r0, r1), the
-    // segments of loglik_gather_kernel (loglik_tails.hip) -- not a multiple of 16 when n_draws > 131072, so its tiles are cut
-    // out at any draw (tile_load_at; the logits of a draw do not depend on its place in a tile) and the last one is ragged
-    const long long ntiles = (S + 15) >> 4;
-    const long long r0 = chunk * tpc, r1 = r0 + tpc < S ? r0 + tpc : S;
-    const long long t0 = MODE == 1 ? 0 : chunk * tpc;
-    const long long t1 = MODE == 1 ? (r1 - r0 + 15) >> 4 : (t0 + tpc < ntiles ? t0 + tpc : ntiles);
-    const TileWalk walk = tile_walk(lane, d, S);
-    float pre[4 * NTM];
-    auto load = [&](long long t) {
-      if (MODE == 1) {
-        const long long draw0 = r0 + 16 * t;
-        tile_load_at<NTM>(W, draw0, (int)(r1 - draw0 < 16 ? r1 - draw0 : 16), walk, lane, pre);
-      } else {
-        tile_load<NTM>(W, t, walk, lane, pre);
-      }
-    };
-    load(t0);
-
-    constexpr bool kLate = MODE == 1 && NTM >= 4;
-    for (long long t = t0; t < t1; ++t) {
-      tile_stage<NTM>(lds, pre, walk, lane);
-      wave_lds_fence();
-      f4 E[NB];
-      if (kLate) {
-        // ... and the X fragments (4 NTM NB registers) are read again for every tile, L2-hot, instead of being held across
-        // the exponentials; the pointer is made opaque so that the loads are not hoisted back out of the loop
-        const float* Pt = P;
-        asm volatile("" : "+s"(Pt));
-        block_fragments<NTM, NB>(Pt, NT, b0, nblk, lane, xa, yv);
-      }
-      tile_logits<NTM, NB>(lds, xa, c, q, NT, b0, nblk, E);
-      wave_lds_fence();
-      // the next tile's loads are in flight during this tile's arithmetic -- except where their 4 NTM registers would push
-      // the gather's float64 arithmetic into scratch (kLate): there they are issued after it and only the other resident
-      // wave's arithmetic can cover their latency (not measured apart; the whole NTM = 8 gather takes 9.8 ms where the
-      // logistic one, three float32 transcendentals per element, takes 6.9: profiles/glm_bench.txt)
-      if (!kLate && t + 1 < t1) load(t + 1);
-      const bool valid = MODE == 1 ? r0 + 16 * t + c < r1 : 16 * t + c < S;
-#pragma unroll
-      for (int j = 0; j < NB; ++j) {
-        if (b0 + j < nblk) {                                 // wave-uniform
-          f4 o4 = splat(0.f), g4 = o4, ck4 = o4, tp4 = o4;
-          if (MODE == 1) {
-            const float* rp = rowc + 16 * j + 4 * q;         // (opaque: the reads stay inside the loop)
-            asm volatile("" : "+v"(rp));
-            o4 = lds4(rp); g4 = lds4(rp + kGlmRows); ck4 = lds4(rp + 2 * kGlmRows); tp4 = lds4(rp + 3 * kGlmRows);
-          }
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const float v = MODE == 1 ? F::ll(E[j][r], yv[j][r], o4[r], g4[r]) : F::ll(E[j][r], yv[j][r], rc[0][j][r], rc[1][j][r]);
-            const uint32_t key = radix_key(v);
-            const bool ok = valid && row_ok[j][r];
-            if (MODE == 0) {
-              uint32_t* hrow = hl + (16 * j + 4 * q + r) * kRadixBins;
-              if (first) {
-                radix_count_first(hrow, key, ok, lane, c);
-                const uint32_t mine = ok ? key : 0u;         // ... and the running largest key of the row
-                pre_key[j][r] = mine > pre_key[j][r] ? mine : pre_key[j][r];
-              } else {
-                radix_count_next(hrow, key, ok, shift, pre_key[j][r]);
-              }
-            } else {
-              const uint32_t ckey = __float_as_uint(ck4[r]);
-              const bool in_tail = ok && key < ckey;
-              if (in_tail) {
-                const int row = 16 * (b0 + j) + 4 * q + r;
-                const unsigned long long slot = atomicAdd(&n_tail[row], 1ull);
-                if (slot < (unsigned long long)ranks[row]) tail[(long long)row * stride + (long long)slot] = v;
-                else atomicOr(err, 1ull);
-              }
-              const double vd = (double)v, a = (double)radix_unkey(ckey) - vd;
-              const bool in_body = ok && !in_tail;
-              double* slot3 = red + (c * 16 + 4 * q + r) * 3;
-              slot3[0] = in_body ? exp(a) : 0.0;
-              slot3[1] = in_body ? exp(2.0 * a) : 0.0;
-              slot3[2] = ok ? exp(vd - (double)tp4[r]) : 0.0;
-            }
-          }
-          if (MODE == 1) {
-            // the 16 draws of the tile onto the running sum, one after the other: ((s + t_0) + t_1) + ... -- the order of a
-            // thread of loglik_gather_kernel over its segment (a draw past the segment adds 0.0, which changes nothing)
-            wave_lds_fence();
-            if (lane < 48) {
-              double a = sacc[j];
-#pragma unroll
-              for (int cc = 0; cc < 16; ++cc) a += red[(cc * 16 + (lane & 15)) * 3 + (lane >> 4)];
-              sacc[j] = a;
-            }
-            wave_lds_fence();
-          }
-        }
-      }
-      if (kLate) __builtin_amdgcn_sched_barrier(0);        // (the scheduler must not lift the loads back over the arithmetic)
-      if (kLate && t + 1 < t1) load(t + 1);
-    }
-
-    if (MODE == 0 && first) {
-#pragma unroll
-      for (int j = 0; j < NB; ++j) {
-        if (b0 + j < nblk) {
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            uint32_t m = pre_key[j][r];
-#pragma unroll
-            for (int o = 1; o < 16; o *= 2) {
-              const uint32_t other = (uint32_t)__shfl_xor((int)m, o, 64);
-              m = other > m ? other : m;
-            }
-            if (c == 0 && row_ok[j][r]) atomicMax(&topkey[16 * (b0 + j) + 4 * q + r], m);
-          }
-        }
-      }
-    }
-    if (MODE == 1 && lane < 48) {
-#pragma unroll
-      for (int j = 0; j < NB; ++j) {
-        const int row = 16 * (b0 + j) + (lane & 15);
-        if (b0 + j < nblk && row < n) part[(chunk * 3 + (lane >> 4)) * (long long)n + row] = sacc[j];
-      }
-    }
-  }
-
-  if (MODE == 0) radix_hist_flush<kGlmRows, kGlmThreads>(hl, b0, n, hist);
-}
-
-// ---- the predictive sums ------------------------------------------------------------------------------------------------------
-// (NTM = 8 sits at exactly 256 registers, by late loads and per-tile re-reads of the X fragments (kLate).  The plain form --
-// fragments held, loads ahead, one wave per SIMD, 298 registers -- was measured beside it: `waic` of 800 000 x 128 draws against
-// 1000 rows 10.17 ms against 7.93 ms, profiles/glm_bench.txt.  Should a compiler tip this form into scratch, the test of the
-// listing fails and `NTM == 8 ? 1 : 2` here with kLate = false below is the fallback.)
-template <typename F, int NTM>
-__global__ __launch_bounds__(kGlmThreads, 2) void glm_predict_kernel(const float* __restrict__ W, long long S, int d,
-                                                                     const float* __restrict__ P, const float* __restrict__ RC,
-                                                                     int n, int NT, int ngroups, long long nchunks, long long tpc,
-                                                                     double* __restrict__ part) {
-  constexpr int NB = kGlmNB;
-  constexpr int REGION = tile_region(NTM);
-  __shared__ __attribute__((aligned(16))) float lds_all[4 * REGION];
-  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, c = lane & 15, q = lane >> 4;
-  const long long u = (long long)blockIdx.x * 4 + w;
-  if (u >= (long long)ngroups * nchunks) return;             // (no workgroup barrier anywhere: a wave may leave alone)
-  float* lds = lds_all + w * REGION;
-  tile_region_clear<NTM>(lds, lane);
-  const int group = (int)(u % ngroups);
-  const long long chunk = u / ngroups;
-  const int nblk = (n + 15) >> 4, b0 = group * NB;
-  f4 xa[NB][NTM], yv[NB];
-  block_fragments<NTM, NB>(P, NT, b0, nblk, lane, xa, yv);
-  float rc[3][NB][4];
-  bool row_ok[NB][4];
-  row_constants<NB, 3>(RC, n, b0, nblk, q, rc, row_ok);
-  double acc[NB][4][4];
-#pragma unroll
-  for (int j = 0; j < NB; ++j)
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) acc[j][k][r] = 0.0;
-
-  const long long ntiles = (S + 15) >> 4;
-  const long long t0 = chunk * tpc, t1 = t0 + tpc < ntiles ? t0 + tpc : ntiles;
-  const TileWalk walk = tile_walk(lane, d, S);
-  float pre[4 * NTM];
-  tile_load<NTM>(W, t0, walk, lane, pre);
-  constexpr bool kLate = NTM >= 8;                            // (as in the gather above: late loads, streamed X fragments)
-  for (long long t = t0; t < t1; ++t) {
-    tile_stage<NTM>(lds, pre, walk, lane);
-    wave_lds_fence();
-    f4 E[NB];
-    if (kLate) {
-      const float* Pt = P;
-      asm volatile("" : "+s"(Pt));
-      block_fragments<NTM, NB>(Pt, NT, b0, nblk, lane, xa, yv);
-    }
-    tile_logits<NTM, NB>(lds, xa, c, q, NT, b0, nblk, E);
-    wave_lds_fence();
-    if (!kLate && t + 1 < t1) tile_load<NTM>(W, t + 1, walk, lane, pre);  // in flight during this tile's arithmetic
-    const bool valid = 16 * t + c < S;
-#pragma unroll
-    for (int j = 0; j < NB; ++j) {
-      if (b0 + j < nblk) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const bool ok = valid && row_ok[j][r];
-          const float mu = F::mean(E[j][r], rc[0][j][r]);
-          const float ll = F::ll(E[j][r], yv[j][r], rc[0][j][r], rc[1][j][r]);
-          const double dll = ok ? (double)ll : 0.0;
-          acc[j][0][r] += ok ? (double)mu : 0.0;
-          acc[j][1][r] += ok ? exp((double)ll - (double)rc[2][j][r]) : 0.0;
-          acc[j][2][r] += dll;
-          acc[j][3][r] = fma(dll, dll, acc[j][3][r]);
-          __builtin_amdgcn_sched_barrier(0);                // one element's exp at a time: interleaved they spill
-        }
-      }
-    }
-    if (kLate) __builtin_amdgcn_sched_barrier(0);
-    if (kLate && t + 1 < t1) tile_load<NTM>(W, t + 1, walk, lane, pre);
-  }
-  tile_sums_out<NB, 4>(lds, acc, lane, b0, nblk, n, chunk, part);
-}
-
 }  // namespace l2hmc
 
 using namespace l2hmc;
@@ -481,11 +150,8 @@ int l2hmc_glm_log_lik(const float* draws, int64_t n_draws, int32_t d, const floa
   if (((uintptr_t)draws & 3) || ((uintptr_t)packed & 15) || ((uintptr_t)row_consts & 3) || ((uintptr_t)out & 3))
     return fail(L2HMC_ERR_ARG, "%s: draws, row_consts and out must be 4-byte, packed 16-byte aligned", who);
   hipStream_t s = (hipStream_t)stream;
-  const long long units = (long long)p.ngroups * p.nchunks;
-  const dim3 grid((unsigned)((units + 3) / 4)), block(kGlmThreads);
-  on_feature_tiles(p.NTM, [&](auto ntm) {
-    hipLaunchKernelGGL((glm_loglik_kernel<PoissonLog, decltype(ntm)::value>), grid, block, 0, s, draws, (long long)n_draws, (int)d,
-                       packed, row_consts, (int)n_data, p.NT, p.ngroups, p.nchunks, p.tpc, out);
+  on_family<true>(family, [&](auto fam) {
+    glm_launch_matrix<typename decltype(fam)::type>(p, s, draws, (long long)n_draws, (int)d, packed, row_consts, (int)n_data, out);
   });
   return launched();
 }
@@ -507,11 +173,8 @@ int l2hmc_glm_predict(const float* draws, int64_t n_draws, int32_t d, const floa
       ((uintptr_t)workspace & 7))
     return fail(L2HMC_ERR_ARG, "%s: draws and row_consts must be 4-byte, packed 16-byte, sums and workspace 8-byte aligned", who);
   hipStream_t s = (hipStream_t)stream;
-  const long long units = (long long)p.ngroups * p.nchunks;
-  const dim3 grid((unsigned)((units + 3) / 4)), block(kGlmThreads);
-  on_feature_tiles(p.NTM, [&](auto ntm) {
-    hipLaunchKernelGGL((glm_predict_kernel<PoissonLog, decltype(ntm)::value>), grid, block, 0, s, draws, (long long)n_draws, (int)d,
-                       packed, row_consts, (int)n_data, p.NT, p.ngroups, p.nchunks, p.tpc, workspace);
+  on_family<false>(family, [&](auto fam) {
+    glm_launch_predict<typename decltype(fam)::type>(p, s, draws, (long long)n_draws, (int)d, packed, row_consts, (int)n_data, workspace);
   });
   chunk_reduce_launch(workspace, p.nchunks, 4LL * n_data, sums, s);
   return launched();
@@ -546,15 +209,12 @@ int l2hmc_glm_loo_tails(const float* draws, int64_t n_draws, int32_t d, const fl
   hipLaunchKernelGGL(glm_loo_init_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, s, ws.remaining, ws.ranks, ws.prefix,
                      ws.topkey, (unsigned long long*)n_tail, tail, (int)n_data, (long long)tail_stride,
                      (long long)l2hmc_logistic_loo_tail_len(n_draws), (const long long*)tail_len_row, ws.err);
-  const dim3 grid((unsigned)(p.quads * p.ngroups)), gather_grid((unsigned)(p.seg_quads * p.ngroups)), block(kGlmThreads);
+  const GlmTailArgs targs{ws.prefix, ws.hist, ws.topkey, ws.ranks, top, (unsigned long long*)n_tail, tail, (long long)tail_stride,
+                          ws.err, ws.part};
   auto pass = [&](auto mode, int shift, bool first) {
-    constexpr int MODE = decltype(mode)::value;
-    on_feature_tiles(p.NTM, [&](auto ntm) {
-      hipLaunchKernelGGL((glm_loo_kernel<PoissonLog, decltype(ntm)::value, MODE>), MODE == 1 ? gather_grid : grid, block, 0, s, draws,
-                         (long long)n_draws, (int)d, packed, row_consts, (int)n_data, p.NT, p.ngroups,
-                         MODE == 1 ? p.nseg : p.nchunks, MODE == 1 ? p.seg_rows : p.tpc, (const uint32_t*)ws.prefix, shift,
-                         (int)first, ws.hist, ws.topkey, (const long long*)ws.ranks, top, (unsigned long long*)n_tail, tail,
-                         (long long)tail_stride, ws.err, ws.part);
+    on_family<true>(family, [&](auto fam) {
+      glm_launch_tails<typename decltype(fam)::type, decltype(mode)::value>(p, s, draws, (long long)n_draws, (int)d, packed, row_consts,
+                                                                            (int)n_data, shift, first, targs);
     });
   };
   const int rc = radix_select_passes(ws.hist, ws.remaining, ws.prefix, (int)n_data, cutoff, s,

@@ -1,11 +1,12 @@
-// The likelihoods of the draw-tile statistics kernels, each stated once: PoissonLog for every kernel of glm.hip, and
-// BernoulliLogit (at the end) for the logistic kernels of predictive.hip, loo.hip and lik_stats.hip.  For glm.hip a family is a
-// struct with
-//     ll(eta, y, a, b)   the pointwise log-likelihood of a row with response y under the linear predictor eta = x_i . w_s,
-//                        a and b the row's first two constants (row_consts[0], row_consts[1])
-//     mean(eta, a)       the predictive mean
-// and an ABI number (include/l2hmc.h L2HMC_GLM_*).  The next family (binomial with trials, probit) is one more struct here and
-// one more case in glm.hip's dispatch, not another copy of three kernels.
+// The likelihoods of the draw-tile statistics kernels, each stated once: PoissonLog, BinomialLogit and NegBinomialLog for every
+// kernel of glm.hip, and BernoulliLogit (at the end) for the logistic kernels of predictive.hip, loo.hip and lik_stats.hip.  For
+// glm.hip a family is a struct with
+//     kConsts            the number of per-row constants ll takes: 2 (row_consts[0], row_consts[1]) or 3 (and row_consts[3];
+//                        row_consts[2] is sat for every family, which only the predictive sums read)
+//     ll(eta, y, a, b[, c])   the pointwise log-likelihood of a row with response y under the linear predictor eta = x_i . w_s
+//     mean(eta, a[, b])  the predictive mean
+// and an ABI number (include/l2hmc.h L2HMC_GLM_*).  The kernels call them through family_ll / family_mean below.  The next
+// family (probit) is one more struct here and one more case in glm.hip's dispatch, not another copy of three kernels.
 //
 // THE INVARIANT THE SELECT AND THE GATHER OF glm.hip RELY ON: every kernel -- the matrix writer, the four count passes, the
 // gather, the predictive sums -- computes ll by ONE device function, Family::ll, from the eta that tile_logits of draw_tiles.hpp
@@ -27,6 +28,7 @@ namespace l2hmc {
 // it forms h and mu by these same two operations, so a trajectory moves on the mu these statistics evaluate.  Change both or neither.
 struct PoissonLog {
   static constexpr int kAbi = 1;          // L2HMC_GLM_POISSON
+  static constexpr int kConsts = 2;       // ll reads the offset and g
   static __device__ __forceinline__ float ll(float eta, float y, float o, float g) {
 #pragma clang fp contract(off)
     const float h = __fadd_rn(eta, o);
@@ -38,6 +40,40 @@ struct PoissonLog {
     return fexp(__fadd_rn(eta, o));
   }
 };
+
+// Binomial regression with m_i trials and the logit link, and NB2 negative-binomial regression with fixed dispersion phi: ONE
+// log-likelihood with a per-row offset o_i, weight m_i and constant c_i (include/l2hmc.h says what each family puts there),
+//     t = eta + o_i    ll = y_i t - m_i softplus(t) + c_i
+// formed by BinomialLink of l2hmc_kernels.hpp -- the struct the fused sampling target (L2HMC_ENERGY_BINOMIAL) moves on -- so
+// there is one statement of the operations, not two to keep alike.  The families differ in the predictive mean only:
+// m sigmoid(t) for the binomial; exp(t) = mu / phi for the negative binomial (the host multiplies the sum by phi).
+struct BinomialLogit {
+  static constexpr int kAbi = 3;          // L2HMC_GLM_BINOMIAL
+  static constexpr int kConsts = 3;       // ll reads the offset, the weight and c
+  static __device__ __forceinline__ float ll(float eta, float y, float o, float m, float c) { return BinomialLink(eta, y, o, m).ll(c); }
+  static __device__ __forceinline__ float mean(float eta, float o, float m) {
+#pragma clang fp contract(off)
+    return __fmul_rn(m, BinomialLink(eta, 0.f, o, m).sigmoid());
+  }
+};
+struct NegBinomialLog {
+  static constexpr int kAbi = 4;          // L2HMC_GLM_NEGBINOMIAL
+  static constexpr int kConsts = 3;
+  static __device__ __forceinline__ float ll(float eta, float y, float o, float m, float c) { return BinomialLogit::ll(eta, y, o, m, c); }
+  static __device__ __forceinline__ float mean(float eta, float o, float m) { return fexp(BinomialLink(eta, 0.f, o, m).t); }
+};
+
+// what the kernels of glm.hip call: the family's ll and mean with as many constants as it declares (k2 is row_consts[3])
+template <typename F>
+__device__ __forceinline__ float family_ll(float eta, float y, float k0, float k1, [[maybe_unused]] float k2) {
+  if constexpr (F::kConsts == 3) return F::ll(eta, y, k0, k1, k2);
+  else return F::ll(eta, y, k0, k1);
+}
+template <typename F>
+__device__ __forceinline__ float family_mean(float eta, float k0, [[maybe_unused]] float k1) {
+  if constexpr (F::kConsts == 3) return F::mean(eta, k0, k1);
+  else return F::mean(eta, k0);
+}
 
 // Logistic regression, the link of the logistic history statistics (predictive.hip, loo.hip, lik_stats.hip -- NOT a family of
 // glm.hip: their keys are the signed logit t, not ll, and their sums are float32 terms, a different and faster contract):

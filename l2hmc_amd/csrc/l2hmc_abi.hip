@@ -362,8 +362,9 @@ long long plan_lds(KArgs& k, bool with_nets, bool with_schedule, int NW, int DT)
   if (lr) {
     // the data fragments staged in LDS when they fit beside everything else (the ladder's tables included), else streamed
     // from L2 by every gradient; L2HMC_LOGISTIC_LDS=0 in the environment always streams (read per call: tests run both paths)
-    // (Poisson regression: the offsets go with the data, 16 floats per block behind the last one)
-    const long long need = logistic_floats(k.ncomp, k.d) + (k.ekind == L2HMC_ENERGY_POISSON ? poisson_offset_floats(k.ncomp) : 0);
+    // (Poisson regression: the offsets go with the data, 16 floats per block behind the last one; binomial regression: 32,
+    //  the offsets and the weights)
+    const long long need = logistic_floats(k.ncomp, k.d) + regression_aux_floats(k.ekind, k.ncomp);
     const char* env = getenv("L2HMC_LOGISTIC_LDS");
     k.easy = !(env != nullptr && env[0] == '0') && (o + need + kLadLds) * 4 <= kMaxLdsBytes;
     if (k.easy) {
@@ -456,6 +457,18 @@ int check_energy(const L2hmcEnergy* e, int d) {
       if (d > kLogisticMaxDim) return fail(L2HMC_ERR_ARG, "Poisson regression supports d <= 128 (got %s%lld)", "", d);
       if (!(e->eta > 0.f) || !(e->eta <= 3.402823466e38f))
         return fail(L2HMC_ERR_ARG, "Poisson regression needs eta = prior variance sigma^2 > 0 and finite%s");
+      break;
+    case L2HMC_ENERGY_BINOMIAL:
+      if (!e->mu)
+        return fail(L2HMC_ERR_ARG, "binomial regression needs the packed data (mu, l2hmc_pack_logistic with the responses as labels)%s");
+      if (!e->prec)
+        return fail(L2HMC_ERR_ARG, "binomial regression needs the offsets and weights (prec: l2hmc_binomial_aux_floats(n_data) floats, "
+                                   "per 16 rows [16 offsets | 16 weights])%s");
+      if (e->n_comp < 1 || e->n_comp > kLogisticMaxRows)
+        return fail(L2HMC_ERR_ARG, "binomial regression needs 1 <= n_comp = n_data <= 1048576 (got %s%lld)", "", e->n_comp);
+      if (d > kLogisticMaxDim) return fail(L2HMC_ERR_ARG, "binomial regression supports d <= 128 (got %s%lld)", "", d);
+      if (!(e->eta > 0.f) || !(e->eta <= 3.402823466e38f))
+        return fail(L2HMC_ERR_ARG, "binomial regression needs eta = prior variance sigma^2 > 0 and finite%s");
       break;
     default:
       return fail(L2HMC_ERR_ARG, "unknown energy kind %s%lld", "", e->kind);
@@ -594,7 +607,9 @@ static int plan_trajectory(const L2hmcTrajectoryArgs& a, KArgs& k, int KH, int c
   // logistic / Poisson regression: the general kernel only (the data contractions live in its grad U)
   const bool lr = is_data_regression(k.ekind);
   if (lr && (v.forced == FAM_LANE || v.forced == FAM_WIDE || v.forced == FAM_TILE))
-    return fail(L2HMC_ERR_UNSUPPORTED, k.ekind == L2HMC_ENERGY_POISSON
+    return fail(L2HMC_ERR_UNSUPPORTED, k.ekind == L2HMC_ENERGY_BINOMIAL
+                    ? "variant %s%lld: the binomial-regression target runs on the general kernel only (variant 0 or 100 + v)"
+                    : k.ekind == L2HMC_ENERGY_POISSON
                     ? "variant %s%lld: the Poisson-regression target runs on the general kernel only (variant 0 or 100 + v)"
                     : "variant %s%lld: the logistic-regression target runs on the general kernel only (variant 0 or 100 + v)",
                 "", v.value);
@@ -873,6 +888,11 @@ int64_t l2hmc_packed_logistic_floats(int32_t n_data, int32_t d) {
 int64_t l2hmc_poisson_offset_floats(int32_t n_data) {
   if (n_data < 1 || n_data > kLogisticMaxRows) return fail(L2HMC_ERR_ARG, "Poisson regression: 1 <= n_data <= 1048576 (got %s%lld)", "", n_data);
   return poisson_offset_floats(n_data);
+}
+
+int64_t l2hmc_binomial_aux_floats(int32_t n_data) {
+  if (n_data < 1 || n_data > kLogisticMaxRows) return fail(L2HMC_ERR_ARG, "binomial regression: 1 <= n_data <= 1048576 (got %s%lld)", "", n_data);
+  return binomial_aux_floats(n_data);
 }
 
 int l2hmc_pack_logistic(const float* X, const float* y, int32_t n_data, int32_t d, float* packed, void* stream) {

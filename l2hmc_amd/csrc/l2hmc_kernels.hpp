@@ -83,6 +83,10 @@ int check_energy(const L2hmcEnergy* e, int d);
 constexpr const char* kPoissonTrainRefusal =
     "no training kernel for the Poisson-regression target: train on the same likelihood as a caller-supplied energy "
     "(energy_cb / hvp_cb of l2hmc_train_split_grad), then sample with the trained nets on the fused kind%s";
+// ... and for L2HMC_ENERGY_BINOMIAL (its Hessian-vector product is X^T [m s (1 - s) (X u)])
+constexpr const char* kBinomialTrainRefusal =
+    "no training kernel for the binomial / negative-binomial regression target: train on the same likelihood as a caller-supplied "
+    "energy (energy_cb / hvp_cb of l2hmc_train_split_grad), then sample with the trained nets on the fused kind%s";
 int device_cus();      // l2hmc_abi.hip: compute units of the current device (256 when the query fails)
 struct KArgs;
 // traj_wide.hip: the LDS plan of the LDS-resident-state kernel for d > 256 (elementwise energies) and its waves per workgroup
@@ -121,7 +125,16 @@ inline long long logistic_floats(int n, int d) { return (long long)((n + 15) / 1
 __host__ __device__ inline int poisson_offset_floats(int n) { return 16 * ((n + 15) >> 4); }
 // The data-regression kinds: grad U is two contractions over the packed data (regression_grad) -- the general kernel only, four
 // waves splitting the data blocks, the data staged in LDS or streamed.  Every host rule and kernel branch for them asks this.
-__host__ __device__ constexpr bool is_data_regression(int ek) { return ek == L2HMC_ENERGY_LOGISTIC || ek == L2HMC_ENERGY_POISSON; }
+__host__ __device__ constexpr bool is_data_regression(int ek) {
+  return ek == L2HMC_ENERGY_LOGISTIC || ek == L2HMC_ENERGY_POISSON || ek == L2HMC_ENERGY_BINOMIAL;
+}
+// Binomial / negative-binomial regression (L2HMC_ENERGY_BINOMIAL): the same packed buffer, and two per-row constants beside it
+// (L2hmcEnergy.prec): per 16-row data block 32 floats, [16 offsets | 16 weights], zero beyond n_data.
+__host__ __device__ inline int binomial_aux_floats(int n) { return 32 * ((n + 15) >> 4); }
+// the floats of L2hmcEnergy.prec that travel with the packed data of a data-regression kind (staged behind the data blocks)
+__host__ __device__ inline int regression_aux_floats(int ek, int n) {
+  return ek == L2HMC_ENERGY_POISSON ? poisson_offset_floats(n) : ek == L2HMC_ENERGY_BINOMIAL ? binomial_aux_floats(n) : 0;
+}
 inline int khid_of(int H) { return (H + 1 + 3) / 4; }
 
 // ------------------------------------------------------------------------------------------
@@ -507,9 +520,11 @@ __device__ __forceinline__ void load_energy_regs(EnergyRegs<EK, DT>& er, const K
 // The body is regression_grad<Link, ...>: one body for every data-regression kind, the link between the two contractions a
 // small struct built from a row's linear predictor L, response y and offset o -- residual() is the row's entry of the
 // gradient contraction's B operand, u_term() its term of U (evaluated only when U is wanted).  kOffset: the kind has per-row
-// offsets (A.prec, 16 per data block).
+// offsets (A.prec, 16 per data block).  kWeight: it has per-row weights too, and a link built from (L, y, o, m); A.prec then
+// holds kAux = 32 floats per data block, [16 offsets | 16 weights].
 struct LogitLink {          // L2HMC_ENERGY_LOGISTIC
-  static constexpr bool kOffset = false;
+  static constexpr bool kOffset = false, kWeight = false;
+  static constexpr int kAux = 0;
   float l, y, e, inv;
   // r = sigmoid(L) - y with e = exp(-|L|): sigmoid = 1 / (1 + e) (L >= 0) or e / (1 + e); softplus(L) = max(L, 0) + log(1 + e)
   __device__ __forceinline__ LogitLink(float L, float y_, float) : l(L), y(y_) {
@@ -525,7 +540,8 @@ struct LogitLink {          // L2HMC_ENERGY_LOGISTIC
 // under `fp contract(off)` -- so the mu a trajectory moves on is the mu the statistics of its history evaluate; a change to one
 // statement is a change to the other.  Overflow is IEEE's: mu = inf gives a non-finite U and gradient, which the accept rule rejects.
 struct PoissonLink {
-  static constexpr bool kOffset = true;
+  static constexpr bool kOffset = true, kWeight = false;
+  static constexpr int kAux = 16;
   float h, y, mu;
   __device__ __forceinline__ PoissonLink(float L, float y_, float o) : y(y_) {
 #pragma clang fp contract(off)
@@ -534,6 +550,43 @@ struct PoissonLink {
   }
   __device__ __forceinline__ float residual() const { return __fsub_rn(mu, y); }
   __device__ __forceinline__ float u_term() const { return fmaf(-y, h, mu); }      // mu - y h, one rounding
+};
+// L2HMC_ENERGY_BINOMIAL, the logit link with an offset o and a weight m per row: binomial regression with m trials, and NB2
+// negative-binomial regression with fixed dispersion phi as m = y + phi, o = offset - log phi (include/l2hmc.h):
+//     t = L + o    e = exp(-|t|)    s = sigmoid(t) = 1 / (1 + e) for t >= 0, e / (1 + e) below    sp = softplus(t) = max(t, 0) + log(1 + e)
+//     r = m s - y  (one fma)        U term = m sp - y t  (the product, then one fma)        ll = y t - m sp + c = c - U term
+// THE ONE STATEMENT of the family: BinomialLogit and NegBinomialLog of glm_family.hpp (the history statistics, glm.hip) build
+// this struct and call ll(), sigmoid() and t, so the t and the softplus a trajectory moves on are the ones the statistics of its
+// history evaluate.  A fixed sequence of individually rounded float32 operations under `fp contract(off)`: one hardware exp2
+// (fexp), one reciprocal, one hardware log2.  Nothing overflows: 0 <= s <= 1, |r| <= max(m, y), and sp <= max(t, 0) + log 2.
+struct BinomialLink {
+  static constexpr bool kOffset = true, kWeight = true;
+  static constexpr int kAux = 32;
+  float t, y, m, e, inv;
+  __device__ __forceinline__ BinomialLink(float L, float y_, float o, float m_) : y(y_), m(m_) {
+#pragma clang fp contract(off)
+    t = __fadd_rn(L, o);
+    e = fexp(-fabsf(t));
+    inv = __builtin_amdgcn_rcpf(__fadd_rn(1.f, e));
+  }
+  __device__ __forceinline__ float sigmoid() const {
+#pragma clang fp contract(off)
+    return t >= 0.f ? inv : __fmul_rn(e, inv);
+  }
+  __device__ __forceinline__ float softplus() const {
+#pragma clang fp contract(off)
+    return __fadd_rn(fmaxf(t, 0.f), __fmul_rn(0.6931471805599453f, __builtin_amdgcn_logf(__fadd_rn(1.f, e))));
+  }
+  __device__ __forceinline__ float residual() const { return fmaf(m, sigmoid(), -y); }
+  __device__ __forceinline__ float u_term() const {
+#pragma clang fp contract(off)
+    return fmaf(-y, t, __fmul_rn(m, softplus()));
+  }
+  // the log-likelihood of the row with its constant c (log C(m, y), or the NB2 one): the negation is exact, the sum one rounding
+  __device__ __forceinline__ float ll(float c) const {
+#pragma clang fp contract(off)
+    return __fadd_rn(-u_term(), c);
+  }
 };
 template <class Link, int DT, int NW, bool STAGED>
 __device__ __forceinline__ float regression_grad(const KArgs& A, float* smem, int w, int lane, const f4 (&x)[DT], f4 (&g)[DT],
@@ -573,7 +626,9 @@ __device__ __forceinline__ float regression_grad(const KArgs& A, float* smem, in
     }
     const f4 y = lds4(blk + 512 * NT + 4 * q);
     [[maybe_unused]] f4 off = splat(0.f);
-    if constexpr (Link::kOffset) off = lds4(O + 16 * ib + 4 * q);
+    if constexpr (Link::kOffset) off = lds4(O + Link::kAux * ib + 4 * q);
+    [[maybe_unused]] f4 wt = splat(0.f);
+    if constexpr (Link::kWeight) wt = lds4(O + Link::kAux * ib + 16 + 4 * q);
     f4 L = splat(0.f);
 #pragma unroll
     for (int tg = 0; tg < NTM; ++tg) {
@@ -592,10 +647,17 @@ __device__ __forceinline__ float regression_grad(const KArgs& A, float* smem, in
     f4 res;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      const Link row(L[r], y[r], off[r]);
-      const bool live = row0 + r < n;
-      res[r] = live ? row.residual() : 0.f;
-      if (wantU) Ud += live ? row.u_term() : 0.f;
+      if constexpr (Link::kWeight) {
+        const Link row(L[r], y[r], off[r], wt[r]);
+        const bool live = row0 + r < n;
+        res[r] = live ? row.residual() : 0.f;
+        if (wantU) Ud += live ? row.u_term() : 0.f;
+      } else {
+        const Link row(L[r], y[r], off[r]);
+        const bool live = row0 + r < n;
+        res[r] = live ? row.residual() : 0.f;
+        if (wantU) Ud += live ? row.u_term() : 0.f;
+      }
     }
 #pragma unroll
     for (int tg = 0; tg < NTM; ++tg) {
@@ -755,7 +817,8 @@ __device__ __forceinline__ void grad_energy(const KArgs& A, float* smem, int w, 
   } else if constexpr (is_data_regression(EK)) {
     {
       // data term (the NLL of the labels / counts), then the N(0, sigma^2 I) prior; padded dimensions hold x = 0 and add nothing
-      using Link = std::conditional_t<EK == L2HMC_ENERGY_POISSON, PoissonLink, LogitLink>;
+      using Link = std::conditional_t<EK == L2HMC_ENERGY_BINOMIAL, BinomialLink,
+                                      std::conditional_t<EK == L2HMC_ENERGY_POISSON, PoissonLink, LogitLink>>;
       U = A.easy ? regression_grad<Link, DT, NW, true>(A, smem, w, lane, x, g, wantU)
                  : regression_grad<Link, DT, NW, false>(A, smem, w, lane, x, g, wantU);
       const float iv = 1.f / A.eta;
@@ -1071,6 +1134,10 @@ __device__ __forceinline__ void stage_energy(const KArgs& A, float* smem, int ti
         const f4* so = reinterpret_cast<const f4*>(A.prec);
         for (int i = tid; i < poisson_offset_floats(A.ncomp) / 4; i += nthr) dst[n4 + i] = so[i];
       }
+      if (EK == L2HMC_ENERGY_BINOMIAL) {     // ... and the [offsets | weights] of every block
+        const f4* so = reinterpret_cast<const f4*>(A.prec);
+        for (int i = tid; i < binomial_aux_floats(A.ncomp) / 4; i += nthr) dst[n4 + i] = so[i];
+      }
     }
   }
 }
@@ -1237,7 +1304,7 @@ template <auto A, auto B, class F>
 int on_either(bool first, F&& f) { return first ? f(ic<A>{}) : f(ic<B>{}); }
 
 // f(ic<EK>) for a built-in energy kind (L2HMC_ENERGY_GAUSS_DIAG = 1 ... L2HMC_ENERGY_FUNNEL = 5, L2HMC_ENERGY_LOGISTIC = 7,
-// L2HMC_ENERGY_POISSON = 8)
+// L2HMC_ENERGY_POISSON = 8, L2HMC_ENERGY_BINOMIAL = 9)
 template <class F>
 int on_energy_kind(int ek, F&& f) {
   switch (ek) {
@@ -1248,6 +1315,7 @@ int on_energy_kind(int ek, F&& f) {
     case 5: return f(ic<5>{});
     case 7: return f(ic<7>{});
     case 8: return f(ic<8>{});
+    case 9: return f(ic<9>{});
   }
   return fail(L2HMC_ERR_ARG, "unknown energy kind%s");
 }

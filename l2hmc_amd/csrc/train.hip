@@ -1255,6 +1255,7 @@ int64_t l2hmc_train_grad_floats(int32_t d, int32_t H) {
 int64_t l2hmc_train_fused_lds_bytes(int32_t ek, int32_t n_comp, int32_t d, int32_t H, int32_t T) {
   if (d < 1 || H < 1 || T < 1) return fail(L2HMC_ERR_ARG, "l2hmc_train_fused_lds_bytes: bad argument%s");
   if (ek == L2HMC_ENERGY_POISSON) return fail(L2HMC_ERR_UNSUPPORTED, kPoissonTrainRefusal);
+  if (ek == L2HMC_ENERGY_BINOMIAL) return fail(L2HMC_ERR_UNSUPPORTED, kBinomialTrainRefusal);
   if (ek != L2HMC_ENERGY_GAUSS_DIAG && ek != L2HMC_ENERGY_GAUSS_DENSE && ek != L2HMC_ENERGY_GMM &&
       ek != L2HMC_ENERGY_ROUGHWELL && ek != L2HMC_ENERGY_FUNNEL)
     return fail(L2HMC_ERR_UNSUPPORTED, "no fused training kernel for this energy kind%s");
@@ -1307,6 +1308,7 @@ static int train_launch(const L2hmcTrainArgs* a, const L2hmcTrainStep* st, void*
     return fail(L2HMC_ERR_ARG, "l2hmc_train_propose_grad: NULL pointer%s");
   const int ek = a->energy.kind;
   if (ek == L2HMC_ENERGY_POISSON) return fail(L2HMC_ERR_UNSUPPORTED, kPoissonTrainRefusal);
+  if (ek == L2HMC_ENERGY_BINOMIAL) return fail(L2HMC_ERR_UNSUPPORTED, kBinomialTrainRefusal);
   if (ek != L2HMC_ENERGY_GAUSS_DIAG && ek != L2HMC_ENERGY_GAUSS_DENSE && ek != L2HMC_ENERGY_GMM &&
       ek != L2HMC_ENERGY_ROUGHWELL && ek != L2HMC_ENERGY_FUNNEL && ek != L2HMC_ENERGY_LOGISTIC)
     return fail(L2HMC_ERR_UNSUPPORTED, "training supports the Gaussian, GMM, Rough-Well, funnel and logistic-regression targets (analytic Hessian-vector products)%s");

@@ -213,6 +213,37 @@ class PoissonEnergy(EnergyFunction):
         return self._dev[key]
 
 
+class BinomialEnergy(EnergyFunction):
+    """U(w) = sum_i [m_i softplus(t_i) - y_i t_i] + |w|^2 / (2 prior_var), t_i = x_i . w + o_i, on the fused kernels
+    (L2HMC_ENERGY_BINOMIAL): binomial regression (m = trials, o = offset) and negative-binomial regression with fixed
+    dispersion (m = y + phi, o = offset - log phi).  The data set is packed once per device into the buffer `LogisticEnergy`
+    uses, y in its label slot, and the row constants go beside it: per 16-row block [16 offsets | 16 weights], zero-padded
+    (`l2hmc_binomial_aux_floats`; L2hmcEnergy.prec)."""
+
+    def __init__(self, X, y, offset, weight, prior_var):
+        n, d = X.shape
+        EnergyFunction.__init__(self, _ffi.ENERGY_BINOMIAL, d, n_comp=n, eta=prior_var)
+        self._host = {'X': X, 'y': y, 'offset': offset, 'weight': weight}
+
+    def _buffers(self, device):
+        key = str(device)
+        if key not in self._dev:
+            L = _ffi.lib()
+            X = torch.as_tensor(np.ascontiguousarray(self._host['X'], dtype=np.float32), device=device)
+            y = torch.as_tensor(np.ascontiguousarray(self._host['y'], dtype=np.float32), device=device)
+            n, d = X.shape
+            packed = torch.empty(_ffi.check(L.l2hmc_packed_logistic_floats(n, d)), dtype=torch.float32, device=device)
+            _ffi.check(L.l2hmc_pack_logistic(X.data_ptr(), y.data_ptr(), n, d, packed.data_ptr(), _ffi.current_stream(device)))
+            floats = _ffi.check(L.l2hmc_binomial_aux_floats(n))
+            aux = np.zeros((floats // 32, 2, 16), dtype=np.float32)
+            for k, name in enumerate(('offset', 'weight')):
+                rows = np.zeros(16 * (floats // 32), dtype=np.float32)
+                rows[:n] = self._host[name]
+                aux[:, k, :] = rows.reshape(-1, 16)
+            self._dev[key] = {'mu': packed, 'prec': torch.as_tensor(aux.reshape(-1), device=device), 'logc': None, '_X': X, '_y': y}
+        return self._dev[key]
+
+
 class LogisticRegression(object):
     """Bayesian logistic regression: labels y_i in {0, 1} with P(y_i = 1 | w) = sigmoid(x_i . w) and a N(0, prior_var I) prior
     on the weights w (d = X.shape[1] <= 128 features; add a column of ones for an intercept).  The posterior's energy
@@ -383,6 +414,161 @@ class PoissonRegression(object):
     def relative_eff(self, draws, max_lag=None, split=False, max_bytes=256 << 20):
         """The per-row relative efficiency of this model's own data under a recorded history (`glm.Glm.relative_eff`)."""
         return self._glm.relative_eff(draws, max_lag=max_lag, split=split, max_bytes=max_bytes)
+
+
+class _WeightedLogitRegression(object):
+    """What `BinomialRegression` and `NegativeBinomialRegression` share: one likelihood (include/l2hmc.h, L2HMC_ENERGY_BINOMIAL)
+
+        ll_i = y_i t_i - m_i softplus(t_i) + c_i,   t_i = x_i . w + o_i,    U(w) = sum_i [m_i softplus(t_i) - y_i t_i] + |w|^2 / (2 prior_var)
+
+    with per-row constants (o, m, c) that the subclass's family forms in float64 (`glm.Binomial`, `glm.NegBinomial`) and that
+    are rounded to float32 once.  `get_energy_function(fused=True)` is a `BinomialEnergy`: U and grad U = X^T (m sigmoid(t) - y)
+    + w / prior_var fused into the general trajectory kernel, so HMC and L2HMC sampling, `warmup`, parallel tempering and AIS
+    run on it like on any built-in target; nothing in it can overflow.  `get_energy_function()` -- the default -- is a
+    `UserEnergy` with the same gradient as differentiable torch code: the slow path, and the one a sampler TRAINS on (no
+    training kernel holds the Hessian-vector product X^T [m s (1 - s) (X u)]): `Trainer(dynamics)` on the slow-path energy,
+    then `load_state_dict` into a `Dynamics` on the fused one.  Everything computed FROM the recorded history is fused HIP
+    (csrc/glm.hip; `l2hmc_amd.glm`) and evaluates t and softplus by the very float32 operations the fused energy uses.  A
+    float32 ll loses absolute accuracy in proportion to m |t|."""
+
+    _name = None
+
+    def _init(self, X, y, offset, prior_var, family, weight, check_y):
+        from . import glm
+        X = np.asarray(X, dtype=np.float64)
+        y = np.asarray(y, dtype=np.float64)
+        if X.ndim != 2 or X.shape[0] < 1 or X.shape[1] < 1:
+            raise ValueError("X must be (n_data, d) with n_data, d >= 1, got shape %s" % (X.shape,))
+        n, d = X.shape
+        if d > 128:
+            raise ValueError("%s supports d <= 128 features (got %d)" % (self._name, d))
+        if n > 1 << 20:
+            raise ValueError("%s supports at most 1048576 data rows (got %d)" % (self._name, n))
+        if y.shape != (n,):
+            raise ValueError("y must be (n_data,) = (%d,), got shape %s" % (n, y.shape))
+        if not np.all(np.isfinite(X)):
+            raise ValueError("X must be finite")
+        weight = check_y(y, n)
+        offset = np.zeros(n) if offset is None else np.asarray(offset, dtype=np.float64)
+        if offset.shape != (n,) or not np.all(np.isfinite(offset)):
+            raise ValueError("offset must be finite (n_data,) = (%d,), got shape %s" % (n, offset.shape))
+        prior_var = float(prior_var)
+        if not (np.isfinite(prior_var) and prior_var > 0.0):
+            raise ValueError("prior_var must be finite and > 0, got %r" % (prior_var,))
+        self.X = np.ascontiguousarray(X, dtype=np.float32)
+        self.y = np.ascontiguousarray(y, dtype=np.float32)
+        self.offset = np.ascontiguousarray(offset, dtype=np.float32)
+        self.prior_var = prior_var
+        self.dim = d
+        self._glm = glm.Glm(self.X, self.y, self.offset, family, None if weight is None else np.ascontiguousarray(weight, dtype=np.float32))
+        self._o, self._m = self._glm.consts[0], self._glm.consts[1]      # the float32 (o, m) of the likelihood: the kernels' own
+        self._torch = {}
+
+    def _data(self, x):
+        key = (str(x.device), x.dtype)
+        if key not in self._torch:
+            self._torch[key] = tuple(torch.as_tensor(a).to(device=x.device, dtype=x.dtype) for a in (self.X, self.y, self._o, self._m))
+        return self._torch[key]
+
+    def energy(self, x):
+        """U(w) of each row of the torch tensor x (N, d), in x's own device and dtype; differentiable."""
+        X, y, o, m = self._data(x)
+        t = x @ X.t() + o
+        return (m * torch.nn.functional.softplus(t) - y * t).sum(dim=1) + 0.5 * x.square().sum(dim=1) / self.prior_var
+
+    def grad_energy(self, x):
+        """grad U = X^T (m sigmoid(t) - y) + w / prior_var, (N, d); differentiable (the trainer's Hessian-vector products)."""
+        X, y, o, m = self._data(x)
+        return (m * torch.sigmoid(x @ X.t() + o) - y) @ X + x / self.prior_var
+
+    def get_energy_function(self, fused=False):
+        """The posterior's energy: a `UserEnergy` (torch code, the slow path; what `Trainer` takes), or with `fused=True` a
+        `BinomialEnergy` on the fused trajectory kernels (sampling, warm-up, tempering, AIS)."""
+        if fused:
+            return BinomialEnergy(self.X, self.y, self._o, self._m, self.prior_var)
+        return UserEnergy(self.energy, self.grad_energy, x_dim=self.dim)
+
+    def log_density(self, W):
+        """Unnormalised log posterior -U(w) of each row of W (n_w, d), in float64 (the constants c_i are not part of U)."""
+        W = np.asarray(W, dtype=np.float64)
+        o, m, _ = self._glm.lik.terms(self.y, self.offset, self._glm.weight)
+        t = W @ self.X.astype(np.float64).T + o
+        return -((m * np.logaddexp(0.0, t) - self.y.astype(np.float64) * t).sum(axis=1) + 0.5 * np.square(W).sum(axis=1) / self.prior_var)
+
+    def log_lik(self, draws, rows=None):
+        """The pointwise log-likelihood matrix (S, m) of a range of rows (`glm.Glm.log_lik`): the slow route."""
+        return self._glm.log_lik(draws, rows=rows)
+
+    def waic(self, draws):
+        """WAIC of this model's own data under the draws: a `Summary` with elpd_waic, p_waic, lppd, se, elpd_i,
+        n_high_variance, n_underflow."""
+        return self._glm.waic(draws)
+
+    def loo(self, draws, r_eff=None, max_lag=None, split=False, max_tail_bytes=256 << 20):
+        """PSIS-LOO of this model's own data under the draws (`glm.Glm.loo`): the fields of `loo_from_log_lik`."""
+        return self._glm.loo(draws, r_eff=r_eff, max_lag=max_lag, split=split, max_tail_bytes=max_tail_bytes)
+
+    def relative_eff(self, draws, max_lag=None, split=False, max_bytes=256 << 20):
+        """The per-row relative efficiency of this model's own data under a recorded history (`glm.Glm.relative_eff`)."""
+        return self._glm.relative_eff(draws, max_lag=max_lag, split=split, max_bytes=max_bytes)
+
+
+class BinomialRegression(_WeightedLogitRegression):
+    """Bayesian binomial regression with the logit link: y_i successes out of trials_i ~ Binomial(trials_i, sigmoid(x_i . w +
+    offset_i)) and a N(0, prior_var I) prior on the weights w (d <= 128 features) -- aggregated binary data without one row
+    per trial.  `trials`: integers with 1 <= trials <= 2^24 and 0 <= y <= trials; a scalar broadcasts.  trials = 1 is
+    `LogisticRegression`'s posterior."""
+
+    _name = "BinomialRegression"
+
+    def __init__(self, X, y, trials, offset=None, prior_var=1.0):
+        from . import glm
+
+        def check_y(y, n):
+            m = np.asarray(trials, dtype=np.float64)
+            if m.ndim == 0:
+                m = np.full(n, float(m))
+            if m.shape != (n,):
+                raise ValueError("trials must be a scalar or (n_data,) = (%d,), got shape %s" % (n, m.shape))
+            if not np.all(np.isfinite(m)) or not np.all((m >= 1.0) & (m == np.floor(m)) & (m <= glm.MAX_COUNT)):
+                raise ValueError("trials must be integers with 1 <= trials <= 2^24")
+            if not np.all(np.isfinite(y)) or not np.all((y >= 0.0) & (y == np.floor(y)) & (y <= m)):
+                raise ValueError("successes y must be integers with 0 <= y <= trials")
+            return m
+        self._init(X, y, offset, prior_var, glm.Binomial(), None, check_y)
+        self.trials = self._glm.weight
+
+    def predict_mean(self, draws, X=None, offset=None, trials=None):
+        """The posterior predictive mean E[y | x] = trials x mean over the draws of sigmoid(x . w + offset) of every row of X
+        (default: the model's own rows, offsets and trials; new rows take `offset`, default 0, and `trials`, default 1: the
+        success probability)."""
+        return self._glm.predict_mean(draws, X=X, offset=offset, weight=trials)
+
+
+class NegativeBinomialRegression(_WeightedLogitRegression):
+    """Bayesian negative-binomial regression (NB2) with the log link: counts y_i with mean mu_i = exp(x_i . w + offset_i) and
+    variance mu_i + mu_i^2 / dispersion, the dispersion phi a fixed finite scalar > 0 (not sampled), and a N(0, prior_var I)
+    prior on the weights w (d <= 128 features; counts <= 2^24) -- the overdispersed alternative to `PoissonRegression`, which
+    it approaches as phi grows; compare the two by `loo`."""
+
+    _name = "NegativeBinomialRegression"
+
+    def __init__(self, X, y, dispersion, offset=None, prior_var=1.0):
+        from . import glm
+        phi = float(dispersion)
+        if not (np.isfinite(phi) and phi > 0.0):
+            raise ValueError("dispersion must be finite and > 0, got %r" % (dispersion,))
+
+        def check_y(y, n):
+            if not np.all(np.isfinite(y)) or not np.all((y >= 0.0) & (y == np.floor(y)) & (y <= glm.MAX_COUNT)):
+                raise ValueError("counts y must be non-negative integers <= 2^24")
+            return None
+        self._init(X, y, offset, prior_var, glm.NegBinomial(phi), None, check_y)
+        self.dispersion = phi
+
+    def predict_mean(self, draws, X=None, offset=None):
+        """The posterior predictive mean of every row of X (default: the model's own rows) under the draws."""
+        return self._glm.predict_mean(draws, X=X, offset=offset)
 
 
 def as_device_f32(x, device=None):

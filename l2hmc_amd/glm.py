@@ -1,5 +1,6 @@
 """Model criticism of a generalised linear model over every recorded draw -- the host side of csrc/glm.hip, behind
-`distributions.PoissonRegression`:
+`distributions.PoissonRegression`, `BinomialRegression` and `NegativeBinomialRegression` (the likelihood is a family object:
+`Poisson`, `Binomial`, `NegBinomial` below -- the ABI number, the row constants, the float64 host ll and the mean):
 
     m = PoissonRegression(X, y, offset=log_exposure)
     ll = m.log_lik(x_hist[burn_in:], rows=slice(0, 512))      # the (S, 512) matrix, when it is wanted (the slow route)
@@ -16,7 +17,13 @@ A ROCm tensor of draws goes to the kernels where it lies (a first-axis slice of 
 (draws, rows) matrix is formed only by `log_lik` and, a group of at most 512 rows at a time, by `relative_eff`, which hands
 each group to `l2hmc_chain_stats_exp` with shift = sat.  `loo` finishes through `psis._finish_raw` / `l2hmc_psis_smooth` where
 the tails lie, the rows in groups whose tails stay under `max_tail_bytes`, as `predictive.loo` groups them.  numpy or a CPU
-tensor is float64 numpy: the matrix in float64, then the numpy routes of `psis`."""
+tensor is float64 numpy: the matrix in float64, then the numpy routes of `psis`.
+
+The binomial and the negative binomial share one log-likelihood (csrc/glm_family.hpp; include/l2hmc.h): with a per-row offset
+o_i, weight m_i and constant c_i, t = eta + o_i and ll = y_i t - m_i softplus(t) + c_i.  Their row constants are (4, n):
+[o, m, sat, c] with sat = y log(y / m) + (m - y) log(1 - y / m) + c (0 log 0 = 0), each formed in float64 and rounded once.
+A float32 ll loses absolute accuracy in proportion to m |t| (the products y t and m softplus(t) are rounded at their own
+magnitude and then cancel), as the Poisson family's does with large counts."""
 import math
 
 import numpy as np
@@ -61,14 +68,86 @@ def _rows(rows, n):
     return a, b - a
 
 
+def _xlogy(a, b):
+    """a log b with 0 log 0 = 0, float64."""
+    with np.errstate(all="ignore"):
+        return np.where(a > 0, a * np.log(np.where(a > 0, b, 1.0)), 0.0)
+
+
+class Poisson(object):
+    """The Poisson family with the log link: ll = y h - exp(h) - lgamma(y + 1), h = eta + offset; mean exp(h)."""
+    abi = _ffi.GLM_POISSON
+    mean_scale = 1.0                                         # the device's sum of means times this is the sum of E[y]
+
+    def row_constants(self, y, offset, weight=None):
+        return row_constants(y, offset)
+
+    def host_ll(self, eta, y, offset, weight=None):
+        """(ll, mean) float64 of eta (S, m) = x_i . w_s."""
+        h = eta + offset
+        mu = np.exp(h)
+        return y * h - mu - lgamma1p(y), mu
+
+
+class Binomial(object):
+    """y successes out of `weight` = m trials, the logit link: t = eta + offset, ll = y t - m softplus(t) + log C(m, y); mean
+    m sigmoid(t)."""
+    abi = _ffi.GLM_BINOMIAL
+    mean_scale = 1.0
+
+    def terms(self, y, offset, weight):
+        """(o, m, c) float64 of the shared log-likelihood y t - m softplus(t) + c, t = eta + o."""
+        y, m = np.asarray(y, dtype=np.float64), np.asarray(weight, dtype=np.float64)
+        return np.asarray(offset, dtype=np.float64), m, lgamma1p(m) - lgamma1p(y) - lgamma1p(m - y)
+
+    def saturated(self, y, offset, weight=None):
+        """sat = y log(y / m) + (m - y) log(1 - y / m) + c (0 log 0 = 0), float64: the supremum of ll over eta."""
+        y = np.asarray(y, dtype=np.float64)
+        _, m, c = self.terms(y, offset, weight)
+        return _xlogy(y, y / m) + _xlogy(m - y, (m - y) / m) + c
+
+    def row_constants(self, y, offset, weight=None):
+        """(4, n) float32: o, m, sat and c, each formed in float64 and rounded once."""
+        o, m, c = self.terms(y, offset, weight)
+        return np.ascontiguousarray(np.stack([o, m, self.saturated(y, offset, weight), c]), dtype=np.float32)
+
+    def mean(self, t, m):
+        return m / (1.0 + np.exp(-t))
+
+    def host_ll(self, eta, y, offset, weight=None):
+        o, m, c = self.terms(y, offset, weight)
+        t = eta + o
+        return y * t - m * np.logaddexp(0.0, t) + c, self.mean(t, m)
+
+
+class NegBinomial(Binomial):
+    """NB2 counts with mean mu = exp(eta + offset) and variance mu + mu^2 / phi, phi fixed: the binomial's log-likelihood with
+    m = y + phi, o = offset - log phi and c = lgamma(y + phi) - lgamma(phi) - lgamma(y + 1) (`weight` is not used).  The device
+    sums exp(t) = mu / phi: `mean_scale` = phi."""
+    abi = _ffi.GLM_NEGBINOMIAL
+
+    def __init__(self, dispersion):
+        self.phi = self.mean_scale = float(dispersion)
+
+    def terms(self, y, offset, weight=None):
+        y = np.asarray(y, dtype=np.float64)
+        c = _lgamma(y + self.phi).astype(np.float64) - math.lgamma(self.phi) - lgamma1p(y)
+        return np.asarray(offset, dtype=np.float64) - math.log(self.phi), y + self.phi, c
+
+    def mean(self, t, m):
+        return self.phi * np.exp(t)
+
+
 class Glm(object):
-    """The data of one model (X (n, d), y (n,), offset (n,), float32) and its statistics over draws."""
+    """The data of one model (X (n, d), y (n,), offset (n,), float32; `weight` (n,) where the family has one: the binomial's
+    trials) and its statistics over draws under the likelihood `family` (an object: `Poisson()`, `Binomial()`,
+    `NegBinomial(phi)`); `self.family` is its ABI number."""
 
-    family = _ffi.GLM_POISSON
-
-    def __init__(self, X, y, offset):
-        self.X, self.y, self.offset = X, y, offset
-        self.consts = row_constants(y, offset)
+    def __init__(self, X, y, offset, family=None, weight=None):
+        self.X, self.y, self.offset, self.weight = X, y, offset, weight
+        self.lik = Poisson() if family is None else family
+        self.family = self.lik.abi
+        self.consts = self.lik.row_constants(y, offset, weight)
         self.n, self.d = X.shape
         self._dev = {}                                       # device -> ((X, y, consts) there, {(a, m): packed rows})
 
@@ -82,10 +161,9 @@ class Glm(object):
         m = self.n - a if m is None else m
         W = as_numpy(draws, np.float64).reshape(S, self.d)
         X, y, o = (np.asarray(v[a:a + m], dtype=np.float64) for v in (self.X, self.y, self.offset))
+        wt = None if self.weight is None else np.asarray(self.weight[a:a + m], dtype=np.float64)
         with np.errstate(all="ignore"):
-            h = W @ X.T + o
-            mu = np.exp(h)
-            return y * h - mu - lgamma1p(y), mu
+            return self.lik.host_ll(W @ X.T, y, o, wt)
 
     # ---- the device route ----------------------------------------------------------------------------------------------------
     def _device_data(self, dev, X=None, y=None, consts=None):
@@ -134,10 +212,11 @@ class Glm(object):
         W = in_place(draws)
         return self._device_ll(W, S, self._device_data(W.device), a, m)
 
-    def pointwise_sums(self, draws, X=None, offset=None):
+    def pointwise_sums(self, draws, X=None, offset=None, weight=None):
         """{'sum_mu', 'sum_lik', 'sum_ll', 'sum_ll2' (n,) float64 numpy, 'sat', 'n_draws'} over the draws, sum_lik = the sum of
-        exp(ll - sat).  With `X` (and `offset`, default 0) the rows are new ones without responses: only 'sum_mu' means
-        anything (y = 0 is packed)."""
+        exp(ll - sat).  With `X` (and `offset`, default 0; `weight`, default 1, where the family has one) the rows are new ones
+        without responses: only 'sum_mu' means anything (y = 0 is packed)."""
+        w_ = None
         if X is None:
             X_, y_, c_ = self.X, self.y, self.consts
         else:
@@ -148,7 +227,12 @@ class Glm(object):
             if o_.shape != (X_.shape[0],) or not np.all(np.isfinite(o_)):
                 raise ValueError("offset must be finite (n_rows,) = (%d,)" % X_.shape[0])
             y_ = np.zeros(X_.shape[0], dtype=np.float32)
-            c_ = row_constants(y_, o_)
+            if self.weight is not None:
+                w_ = np.ones(X_.shape[0]) if weight is None else np.broadcast_to(as_numpy(weight, np.float64), (X_.shape[0],))
+                if not np.all(np.isfinite(w_)) or not np.all((w_ >= 1.0) & (w_ == np.floor(w_)) & (w_ <= MAX_COUNT)):
+                    raise ValueError("trials must be integers with 1 <= trials <= 2^24")
+                w_ = np.ascontiguousarray(w_, dtype=np.float32)
+            c_ = self.lik.row_constants(y_, o_, w_)
         S, d, n = self._check(draws, X_)
         sat = c_[2].astype(np.float64)
         if is_device_tensor(draws):
@@ -163,8 +247,9 @@ class Glm(object):
             launch(dev, L.l2hmc_glm_predict, W.data_ptr(), S, d, packed.data_ptr(), consts.data_ptr(), n, self.family,
                    sums.data_ptr(), ws.data_ptr())
             s = sums.cpu().numpy()
-            return {"sum_mu": s[0], "sum_lik": s[1], "sum_ll": s[2], "sum_ll2": s[3], "sat": sat, "n_draws": S}
-        model = self if X is None else Glm(X_, y_, c_[0])
+            sum_mu = s[0] if self.lik.mean_scale == 1.0 else s[0] * self.lik.mean_scale
+            return {"sum_mu": sum_mu, "sum_lik": s[1], "sum_ll": s[2], "sum_ll2": s[3], "sat": sat, "n_draws": S}
+        model = self if X is None else Glm(X_, y_, np.ascontiguousarray(o_, dtype=np.float32), self.lik, w_)
         out = {k: np.zeros(n) for k in ("sum_mu", "sum_lik", "sum_ll", "sum_ll2", "m2_ll")}
         step = max(1, predictive._HOST_CHUNK_ELEMS // S)
         with np.errstate(all="ignore"):
@@ -178,10 +263,11 @@ class Glm(object):
         out.update(sat=sat, n_draws=S)
         return out
 
-    def predict_mean(self, draws, X=None, offset=None):
-        """The posterior predictive mean E[y | x] = mean over the draws of exp(x . w + offset) of every row of X (default: the
-        model's own rows and offsets; new rows take `offset`, default 0): (n,) float64."""
-        s = self.pointwise_sums(draws, X, offset)
+    def predict_mean(self, draws, X=None, offset=None, weight=None):
+        """The posterior predictive mean E[y | x] = mean over the draws of the family's mean (Poisson: exp(x . w + offset)) of
+        every row of X (default: the model's own rows and offsets; new rows take `offset`, default 0, and `weight`, default
+        1): (n,) float64."""
+        s = self.pointwise_sums(draws, X, offset, weight)
         return s["sum_mu"] / s["n_draws"]
 
     def waic(self, draws):
