@@ -246,6 +246,11 @@ int32_t l2hmc_last_kernel(char* buf, int32_t n);
  * launch of "traj_fast_kernel<1, 1, 4, 3, 1>" whose grid has at most one workgroup per CU (L2HMC_FAST_ONE_WAVE=0 / 1 in the
  * environment forces the choice for such a launch). */
 int32_t l2hmc_last_kernel_body(char* buf, int32_t n);
+/* The LDS plan of the diagonal Gaussian's one-tile four-wave f16x2 sampler kernel (d <= 64, a schedule of T steps), from the
+ * planner's own function; no GPU needed.  one_wave = 0: "traj_fast_kernel<1, 1, 4, ., 1>", 1: its one-workgroup-per-CU body.
+ * what = 0: the dynamic LDS in bytes, 1: the K-split exchange buffers (4 KB each), 2: the bytes of the schedule records.
+ * L2HMC_ERR_ARG on bad arguments. */
+int64_t l2hmc_sampler_lds_plan(int32_t d, int32_t T, int32_t one_wave, int32_t what);
 
 /* Number of floats of the fragment-ordered weight buffer for both nets, or a negative
  * L2HMC_ERR_* if (d, H) is outside the fused kernels' range. */

@@ -139,6 +139,7 @@ SYMBOLS = {
     "l2hmc_packed_nets_floats": (C.c_int64, [C.c_int32, C.c_int32]),
     "l2hmc_pack_nets": (C.c_int, [C.POINTER(L2hmcNet), C.POINTER(L2hmcNet), C.c_int32, C.c_int32,
                                   _fp, _fp]),
+    "l2hmc_sampler_lds_plan": (C.c_int64, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "l2hmc_packed_gaussian_floats": (C.c_int64, [C.c_int32]),
     "l2hmc_pack_gaussian": (C.c_int, [_fp, C.c_int32, _fp, _fp]),
     "l2hmc_packed_logistic_floats": (C.c_int64, [C.c_int32, C.c_int32]),

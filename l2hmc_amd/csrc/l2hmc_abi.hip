@@ -377,17 +377,18 @@ long long plan_lds(KArgs& k, bool with_nets, bool with_schedule, int NW, int DT)
 
 // LDS plan of traj_fast_kernel (DT <= 2): scaled tail fragments, constant tables, schedule records, then
 // the exchange / reduction / energy areas as in plan_lds.
-long long plan_lds_fast(KArgs& k, int NW, int DT, bool f16) {
+long long plan_lds_fast(KArgs& k, int NW, int DT, bool f16, int ow_items) {
   const int NT = k.NT, DP = 16 * NT, NTp = NW * DT;
+  const bool rec1 = (ow_items & 4) != 0;      // the one-workgroup-per-CU body's per-wave records (fast_rec, traj_fast.hpp)
   long long o = 0;
   k.o_fw = (int)o;
   o += 2LL * fast_fw_net(NTp, f16);
   k.o_fc = (int)o;
   o += 2LL * fast_fc_net(NTp);
   k.o_rec = (int)o;
-  o += 2LL * fast_rec_dir(NTp, k.T);
+  o += 2LL * fast_rec_dir(NTp, k.T, rec1);
   k.o_P = (int)o;
-  if (NW > 1) o += 2LL * NW * 256;
+  if (NW > 1) o += (long long)fast_xchg_bufs(ow_items) * NW * 256;      // (that body: a static buffer per exchange of the step)
   k.xb_stride = DP + 4;
   k.o_XB = (int)o;
   if (NW > 1 && (k.ekind == L2HMC_ENERGY_GAUSS_DENSE || k.ekind == L2HMC_ENERGY_GMM)) o += 16LL * k.xb_stride;
@@ -733,6 +734,18 @@ static int plan_trajectory(const L2hmcTrajectoryArgs& a, KArgs& k, int KH, int c
                             k.logjac_out == nullptr && k.x_out == nullptr && k.v_out == nullptr;
         if (k.ekind == L2HMC_ENERGY_GAUSS_DIAG && p.DT == 1 && p.NW == 4 && common)
           p.one_wave = env.one_wave >= 0 ? env.one_wave != 0 : (a.n_chains + 15) / 16 <= cus;
+        if (p.one_wave) {
+          // that body's own LDS plan (a third exchange buffer, per-wave schedule records: 4 KB + 1.5 KB per row of the schedule
+          // more); a schedule too long for it stays on the two-wave kernel and its plan
+          KArgs k1 = k;
+          const long long lds1 = plan_lds_fast(k1, p.NW, p.DT, true, L2HMC_ONE_WAVE_ITEMS);
+          if (lds1 <= kMaxLdsBytes) {
+            k = k1;
+            p.lds = lds1;
+          } else {
+            p.one_wave = false;
+          }
+        }
         return L2HMC_OK;
       }
     }
@@ -812,6 +825,20 @@ int32_t l2hmc_last_kernel_body(char* buf, int32_t n) {
   if (!buf || n < 1) return fail(L2HMC_ERR_ARG, "l2hmc_last_kernel_body: bad argument%s");
   snprintf(buf, (size_t)n, "%s", g_kernel_body);
   return (int32_t)strlen(g_kernel_body);
+}
+
+int64_t l2hmc_sampler_lds_plan(int32_t d, int32_t T, int32_t one_wave, int32_t what) {
+  if (d < 1 || d > 64 || T < 1 || what < 0 || what > 2) return fail(L2HMC_ERR_ARG, "l2hmc_sampler_lds_plan: bad argument%s");
+  KArgs k{};
+  k.ekind = L2HMC_ENERGY_GAUSS_DIAG;
+  k.d = d;
+  k.NT = (d + 15) / 16;
+  k.T = T;
+  const int items = one_wave ? L2HMC_ONE_WAVE_ITEMS : 0;
+  const long long lds = plan_lds_fast(k, 4, 1, true, items);
+  if (what == 1) return (k.o_XB - k.o_P) / (4 * 256);
+  if (what == 2) return 4LL * (k.o_P - k.o_rec);
+  return lds;
 }
 
 const char* l2hmc_last_error(void) { return g_err; }

@@ -142,11 +142,24 @@ __host__ __device__ constexpr int fast_fw_net_f32(int NTp) { return (3 * NTp + 1
 __host__ __device__ constexpr int fast_fw_net(int NTp, bool f16 = false) { return (3 * NTp + 1) * (f16 ? 512 : 256); }   // staged tail fragments per net (f16x2: 2 x 16 bytes per lane)
 __host__ __device__ inline int fast_dpp(int NTp) { return 16 * NTp + 16; }            // padded row of a constant table
 __host__ __device__ inline int fast_fc_net(int NTp) { return 4 * fast_dpp(NTp); }     // cS(fwd) cS(bwd) cQ bQ
-__host__ __device__ inline int fast_rec(int NTp) { return 32 + 16 * NTp; }            // tbx(16) tbv(16) k1 mask
+// What the one-workgroup-per-CU kernel (traj_fast_cc_kernel below) builds into its body, a bit per item (the OW argument of
+// traj_fast_body; the host's LDS plan reads the same bits).  Bit 0: tails once per launch.  Bit 1: a static exchange buffer per
+// site of the step (a third buffer).  Bit 2: the schedule record in per-wave rows, every field at a constant offset from one
+// per-lane pointer.  Bit 3: the next step's XNet input split one step ahead, under the VNet exchange's reads.  (Bit 4: not
+// built.)  Bit 5: every tail's log-det term added under the reads of the exchange that follows it.
+// profiles/sampler_one_wave.txt, profiles/sampler_step_pipeline.txt.
+#ifndef L2HMC_ONE_WAVE_ITEMS
+#define L2HMC_ONE_WAVE_ITEMS 47
+#endif
+// ow = false: tbx(16) tbv(16) k1 mask(16 NTp).  ow = true (OW bit 2): one block of 64 floats per wave tile,
+// [tbx 16 | tbv 16 | k1 of the tile 16 | 1 - k1 of the tile 16] -- tbx and tbv repeated in every block
+__host__ __device__ inline int fast_rec(int NTp, bool ow = false) { return ow ? 64 * NTp : 32 + 16 * NTp; }
 // T rows plus one never-used row on either side (the next-row prefetch of the last step lands there)
-__host__ __device__ inline int fast_rec_dir(int NTp, int T) { return (T + 2) * fast_rec(NTp) + 16; }
+__host__ __device__ inline int fast_rec_dir(int NTp, int T, bool ow = false) { return (T + 2) * fast_rec(NTp, ow) + 16; }
+__host__ __device__ constexpr int fast_xchg_bufs(int ow_items) { return (ow_items & 2) != 0 ? 3 : 2; }
 
-long long plan_lds_fast(KArgs& k, int NW, int DT, bool f16 = false);
+// ow_items: the items of the one-workgroup-per-CU body when the plan picks it, 0 for every other kernel
+long long plan_lds_fast(KArgs& k, int NW, int DT, bool f16 = false, int ow_items = 0);
 
 // which activation split the four-wave kernel's contractions take (split16 above): measured per place, profiles/r06_f16x2.txt section 3
 // and profiles/r06_paired_tails.txt section 4
@@ -327,6 +340,43 @@ __device__ __forceinline__ void tail_fast2(const TailK<DT, true>& tk, f4 hsa, f4
   }
 }
 
+// xchg (l2hmc_kernels.hpp) for ONE partial vector with the buffer as a template argument: the address of every ds_write / ds_read
+// is the lane's base plus an immediate, and no parity is carried.  Safe whenever two exchanges in a row take different buffers:
+// a wave writes buffer B of exchange n + 2 (or later) only behind the barrier of exchange n + 1, and every wave reaches that
+// barrier behind the s_waitcnt lgkmcnt(0) that completes its own reads of exchange n.
+// In parts, so that work which does not depend on the sum can be issued while the reads are in flight: put = the write,
+// get_issue = wait, barrier and the NW reads, get_sum = the sum in xchg's order.
+template <int NW>
+__device__ __forceinline__ void xchg_put(float* P, f4 p, int w, int lane) {
+  *reinterpret_cast<f4*>(P + (w * 64 + lane) * 4) = p;
+}
+template <int NW>
+__device__ __forceinline__ void xchg_get_issue(const float* P, int lane, f4 (&part)[NW]) {
+  __syncthreads();
+#pragma unroll
+  for (int ww = 0; ww < NW; ++ww) part[ww] = lds4(P + (ww * 64 + lane) * 4);
+  __builtin_amdgcn_sched_barrier(0);
+}
+template <int NW>
+__device__ __forceinline__ f4 xchg_get_sum(const f4 (&part)[NW]) {
+  f4 sum = part[0];
+#pragma unroll
+  for (int ww = 1; ww < NW; ++ww) sum += part[ww];
+  return sum;
+}
+template <int NW>
+__device__ __forceinline__ f4 xchg_get(const float* P, int lane) {
+  f4 part[NW];
+  xchg_get_issue<NW>(P, lane, part);
+  return xchg_get_sum<NW>(part);
+}
+template <int NW, int B>
+__device__ __forceinline__ void xchg_at(f4 (&p)[1], const KArgs& A, float* smem, int w, int lane) {
+  float* P = smem + A.o_P + B * (NW * 256);
+  xchg_put<NW>(P, p[0], w, lane);
+  p[0] = xchg_get<NW>(P, lane);
+}
+
 // layer-1 fragments of the f16x2 form (register-resident, split once per launch)
 template <int DT>
 struct L1W16 {
@@ -346,6 +396,11 @@ __device__ __forceinline__ f4 l1_part16(const f4 (&z)[DT], f4 acc, const WF16* W
 // way: the same bits.
 // OW: what the one-workgroup-per-CU kernel (traj_fast_cc_kernel below) spends its register headroom on, a bit per item; 0 in every
 // other kernel.  Bit 0: both nets' tail fragments and constant rows are loaded once per launch, in front of the proposal loop.
+// Bit 1: the three exchanges of a step take the static buffers 0, 1, 2 (xchg_at).  Bit 2: per-wave schedule records (fast_rec).
+// Bit 3: the next step's XNet input k1 * x and its split are formed one step ahead, under the reads of the VNet exchange (the
+// same expression on the same values; the first step's at the proposal's start, the peeled last step forms none).
+// Bit 5: the log-det accumulation ldv += aS of a tail waits for the exchange that follows the tail and is issued while that
+// exchange's reads are in flight (the same additions in the same order).
 template <int EK, int DT, int NW, int KH, int PK, bool CC, int OW = 0>
 __device__ __forceinline__ void traj_fast_body(const KArgs& A);
 
@@ -385,9 +440,6 @@ __global__ __launch_bounds__(64 * NW, (DT >= 2 && PK == 1) ? L2HMC_FAST_WAVES_DT
 // two-wave bound of traj_fast_kernel keeps half of every SIMD's register file for never arrives there.  Its translation unit
 // (traj_f16_one_wave.hip) is compiled with -mllvm -amdgpu-mfma-vgpr-form: see the note at L2HMC_FAST_WAVES above.  The planner
 // (plan_trajectory) sends it common launches only, so the body is picked without the entry test.
-#ifndef L2HMC_ONE_WAVE_ITEMS
-#define L2HMC_ONE_WAVE_ITEMS 1
-#endif
 template <int EK, int DT, int NW, int KH, int WB, int PK>
 __global__ __launch_bounds__(64 * NW, WB) void traj_fast_cc_kernel(const KArgs A) {
   traj_fast_body<EK, DT, NW, KH, PK, true, L2HMC_ONE_WAVE_ITEMS>(A);
@@ -409,8 +461,15 @@ __device__ __forceinline__ void traj_fast_body(const KArgs& A) {
   const float heps = 0.5f * eps;
   constexpr int NTp = NW * DT;
   constexpr bool F16 = PK == 1;
-  const int FWN = fast_fw_net(NTp, F16), DPp = fast_dpp(NTp), FCN = fast_fc_net(NTp), R = fast_rec(NTp),
-            RECD = fast_rec_dir(NTp, A.T);
+  constexpr bool XS = (OW & 2) != 0, REC1 = (OW & 4) != 0, PIPE = (OW & 8) != 0, LDW = (OW & 32) != 0;
+  static_assert(!(XS || REC1 || PIPE || LDW) || (DT == 1 && PK == 1 && NW > 1), "the step-loop items: the one-tile f16x2 body only");
+  // XS and the exchanges outside the step loop: they keep xchg and its parity, which alternates between buffers 0 and 1.  The
+  // precision fold takes 0 (and ends in a barrier of its own), the first VNet layer-1 sum takes 1, the steps take 0, 1, 2,
+  // 0, 1, 2, ...; a proposal's last exchange (2) is followed by chain_allreduce (its own area, two barriers) and the next
+  // proposal's first (0).  No two exchanges in a row share a buffer, which is all xchg_at needs.
+  static_assert(!LDW || PIPE, "the log-det terms under the reads: with the exchange in its parts");
+  const int FWN = fast_fw_net(NTp, F16), DPp = fast_dpp(NTp), FCN = fast_fc_net(NTp), R = fast_rec(NTp, REC1),
+            RECD = fast_rec_dir(NTp, A.T, REC1);
 
   // ---- prologue: stage the tail fragments (scaled), the constant tables and the schedule records ----
   // (the state and the register-resident layer-1 fragments are asked for first: global loads that nothing below depends on, in flight
@@ -482,8 +541,16 @@ __device__ __forceinline__ void traj_fast_body(const KArgs& A) {
         const int i = i0 + s * nthr, r = i >> 5, j = i & 31;
         if (i < nA) {
           const float tbr = fmaf(a0[s], c0[s], fmaf(a1[s], c1[s], a2[s]));
-          smem[A.o_rec + (r + 1) * R + j] = tbr;
-          smem[A.o_rec + RECD + (r + 1) * R + j] = tbr;
+          if constexpr (REC1) {
+#pragma unroll
+            for (int tg = 0; tg < NTp; ++tg) {
+              smem[A.o_rec + (A.T - r) * R + 64 * tg + j] = tbr;      // (the backward table in the order it is walked)
+              smem[A.o_rec + RECD + (r + 1) * R + 64 * tg + j] = tbr;
+            }
+          } else {
+            smem[A.o_rec + (r + 1) * R + j] = tbr;
+            smem[A.o_rec + RECD + (r + 1) * R + j] = tbr;
+          }
         }
       }
     }
@@ -503,8 +570,18 @@ __device__ __forceinline__ void traj_fast_body(const KArgs& A) {
         const int i = i0 + s * nthr, r = i / W16, dim = i % W16;
         if (i < nB) {
           const float m = dim < A.d ? mk[s] : 0.f;
-          smem[A.o_rec + (r + 1) * R + 32 + dim] = 1.f - m;
-          smem[A.o_rec + RECD + (r + 1) * R + 32 + dim] = m;
+          if constexpr (REC1) {
+            // (k1 and up = 1 - k1 side by side: the expression the step would evaluate, evaluated here)
+            const int o = 64 * (dim >> 4) + 32 + (dim & 15);
+            const float mb = 1.f - m;
+            smem[A.o_rec + (A.T - r) * R + o] = mb;
+            smem[A.o_rec + (A.T - r) * R + o + 16] = 1.f - mb;
+            smem[A.o_rec + RECD + (r + 1) * R + o] = m;
+            smem[A.o_rec + RECD + (r + 1) * R + o + 16] = mb;
+          } else {
+            smem[A.o_rec + (r + 1) * R + 32 + dim] = 1.f - m;
+            smem[A.o_rec + RECD + (r + 1) * R + 32 + dim] = m;
+          }
         }
       }
     }
@@ -573,7 +650,12 @@ __device__ __forceinline__ void traj_fast_body(const KArgs& A) {
     xchg<NW, 1>(cv, A, smem, w, lane, pb);
     // (every column of the tile holds the same cv: lane (c, q) of wave 0 folds it into rows c, c + 16, ... -- one addition per
     //  row as before, two trips instead of 2 T)
-    if (w == 0) {
+    if constexpr (REC1) {      // (every wave folds it into its own block's copy of the row)
+      for (int i = c; i < 2 * A.T; i += 16) {
+        float* tb = smem + A.o_rec + (i / A.T) * RECD + (i % A.T + 1) * R + 64 * w + 16 + 4 * q;
+        *reinterpret_cast<f4*>(tb) = lds4(tb) + cv[0];
+      }
+    } else if (w == 0) {
       for (int i = c; i < 2 * A.T; i += 16) {
         float* tb = smem + A.o_rec + (i / A.T) * RECD + (i % A.T + 1) * R + 16 + 4 * q;
         *reinterpret_cast<f4*>(tb) = lds4(tb) + cv[0];
@@ -668,10 +750,24 @@ __device__ __forceinline__ void traj_fast_body(const KArgs& A) {
     // per-lane direction constants and table addresses
     const float ff = fwd ? 1.f : 0.f, nf = ff - 1.f;
     const int dofs = fwd ? 0 : DPp;
-    const int row0 = fwd ? A.step_begin : (A.T - 1 - A.step_begin);
-    const float* rec = smem + A.o_rec + (fwd ? RECD : 0) + (row0 + 1) * R + 4 * q;   // this lane's record, + 4 q
-    const int drec = fwd ? R : -R;
+    // (REC1: the backward table is stored in the order it is walked -- step s at row s, as the forward one -- so every lane
+    //  advances by the same constant and the read-ahead is an immediate)
+    const int row0 = (REC1 || fwd) ? A.step_begin : (A.T - 1 - A.step_begin);
+    // this lane's record, + 4 q (REC1: + this wave's block -- tbx, tbv, k1 and up at the constant offsets 0, 16, 32, 48)
+    const float* rec = smem + A.o_rec + (fwd ? RECD : 0) + (row0 + 1) * R + (REC1 ? 64 * w : 0) + 4 * q;
+    const int drec = (REC1 || fwd) ? R : -R;
     f4 tbv = lds4(rec + 16);
+    // (the mask row of wave tile t in this lane's record)
+    auto k1_of = [&](const float* rc, int t) { return REC1 ? lds4(rc + 32 + 64 * t) : lds4(rc + 32 + 16 * (w * DT + t)); };
+    f4 k1_c[PIPE ? DT : 1];
+    h8v xb_c[PIPE ? DT : 1];
+    if constexpr (PIPE) {
+#pragma unroll
+      for (int t = 0; t < DT; ++t) {
+        k1_c[t] = k1_of(rec, t);
+        xb_c[t] = split16<L2HMC_FAST_SPLIT_LAT_L1>(k1_c[t] * x[t]);
+      }
+    }
 
     // Resident tails (round 6, profiles/r06_resident_tails.txt): XNet's tail fragments and constants stay in registers for the whole
     // proposal beside VNet's (44 VGPRs per net as f16x2) instead of being re-read from LDS twice per step -- 22 of a step's 37
@@ -716,17 +812,28 @@ __device__ __forceinline__ void traj_fast_body(const KArgs& A) {
     auto step = [&](auto LASTC, bool wantU) {
       constexpr bool LAST = decltype(LASTC)::value;
       f4 k1[DT], vh[DT], y[DT], xin[DT];
+      f4 upr[REC1 ? DT : 1];
       const f4 tbx = lds4(rec);
 #pragma unroll
-      for (int t = 0; t < DT; ++t) k1[t] = lds4(rec + 32 + 16 * (w * DT + t));
+      for (int t = 0; t < DT; ++t) {
+        if constexpr (PIPE) k1[t] = k1_c[t];
+        else k1[t] = k1_of(rec, t);
+        if constexpr (REC1) upr[t] = lds4(rec + 48 + 64 * t);
+      }
       rec += drec;
       const f4 tbv_n = lds4(rec + 16);      // (the last step reads the unused pad row)
+      if constexpr (PIPE && !LAST) {
+#pragma unroll
+        for (int t = 0; t < DT; ++t) k1_c[t] = k1_of(rec, t);      // (k1 holds this step's; read ahead as tbv_n)
+      }
 
       PT_MARK(1);  // step head
       // ---- momentum half-update #1: VNet([x, grad U(x), t])  (dynamics.py:118-125 / :162-170)
+      f4 ldp[LDW ? DT : 1];      // (LDW: a tail's log-det term, added under the reads of the exchange that follows it -- the same order)
       auto vhalf1 = [&](int t, f4 aS, f4 T, f4 EQ) {
         const f4 ES = ex2_4(aS);
-        ldv += aS;
+        if constexpr (LDW) ldp[t] = aS;
+        else ldv += aS;
         const f4 tr = T - EQ * g[t];
         vh[t] = ES * (nf * tr + v[t]) + ff * tr;
       };
@@ -740,10 +847,17 @@ __device__ __forceinline__ void traj_fast_body(const KArgs& A) {
 
       // ---- two masked position updates: XNet([v_h, kept * x, t])  (:127-145 / :172-190)
       if constexpr (!RT) load_tailk<DT>(tk, fwx, fcx, dofs, NTp, w, lane);
+      if constexpr (!PIPE) {
 #pragma unroll
-      for (int t = 0; t < DT; ++t) xin[t] = k1[t] * x[t];
+        for (int t = 0; t < DT; ++t) xin[t] = k1[t] * x[t];
+      }
       f4 pa, px[1];
-      if constexpr (F16) {
+      if constexpr (PIPE) {
+        pa = l1_part16<DT>(vh, Z, l1h.xa);
+        px[0] = pa;
+#pragma unroll
+        for (int t = 0; t < DT; ++t) px[0] = mfma16x2(l1h.xb[t], xb_c[t], px[0]);      // (l1_part16 on the split formed a step ago)
+      } else if constexpr (F16) {
         pa = l1_part16<DT>(vh, Z, l1h.xa);
         px[0] = l1_part16<DT>(xin, pa, l1h.xb);
       } else {
@@ -751,13 +865,30 @@ __device__ __forceinline__ void traj_fast_body(const KArgs& A) {
         px[0] = pa + l1_part<DT, NW>(nullptr, NT, A, w, lane, xin, Z, l1w.xb);
       }
       PT_MARK(3);  // XNet layer-1 partials (a, b)
-      xchg<NW, 1>(px, A, smem, w, lane, pb);
+      // (LDW: the exchange in its parts, the held log-det term added while the reads are in flight)
+      auto xchg_ldw = [&](auto BC, f4 (&p)[1]) {
+        float* P = smem + A.o_P + (XS ? decltype(BC)::value : pb) * (NW * 256);
+        xchg_put<NW>(P, p[0], w, lane);
+        f4 part[NW];
+        xchg_get_issue<NW>(P, lane, part);
+#pragma unroll
+        for (int t = 0; t < DT; ++t) ldv += ldp[t];
+        __builtin_amdgcn_sched_barrier(0);
+        p[0] = xchg_get_sum<NW>(part);
+        if constexpr (!XS) pb ^= 1;
+      };
+      if constexpr (LDW) xchg_ldw(std::integral_constant<int, 0>{}, px);
+      else if constexpr (XS) xchg_at<NW, 0>(px, A, smem, w, lane);
+      else xchg<NW, 1>(px, A, smem, w, lane, pb);
       PT_MARK(4);  // exchange
       tail_fast<DT, KH>(TKX, px[0] + tbx, [&](int t, f4 aS, f4 T, f4 EQ) {
-        const f4 up = 1.f - k1[t];
+        f4 up;
+        if constexpr (REC1) up = upr[t];
+        else up = 1.f - k1[t];
         const f4 aSm = up * aS;
         const f4 ES = ex2_4(aSm);
-        ldv += aSm;
+        if constexpr (LDW) ldp[t] = aSm;
+        else ldv += aSm;
         const f4 tr = up * (EQ * vh[t] + T);
         y[t] = ES * (nf * tr + x[t]) + ff * tr;
         xin[t] = up * y[t];
@@ -767,12 +898,15 @@ __device__ __forceinline__ void traj_fast_body(const KArgs& A) {
       if constexpr (F16) py[0] = l1_part16<DT>(xin, pa, l1h.xb);
       else py[0] = pa + l1_part<DT, NW>(nullptr, NT, A, w, lane, xin, Z, l1w.xb);
       PT_MARK(6);  // XNet layer-1 partial (b only)
-      xchg<NW, 1>(py, A, smem, w, lane, pb);
+      if constexpr (LDW) xchg_ldw(std::integral_constant<int, 1>{}, py);
+      else if constexpr (XS) xchg_at<NW, 1>(py, A, smem, w, lane);
+      else xchg<NW, 1>(py, A, smem, w, lane, pb);
       PT_MARK(7);  // exchange
       tail_fast<DT, KH>(TKX, py[0] + tbx, [&](int t, f4 aS, f4 T, f4 EQ) {
         const f4 aSm = k1[t] * aS;
         const f4 ES = ex2_4(aSm);
-        ldv += aSm;
+        if constexpr (LDW) ldp[t] = aSm;
+        else ldv += aSm;
         const f4 tr = k1[t] * (EQ * vh[t] + T);
         x[t] = ES * (nf * tr + y[t]) + ff * tr;
       });
@@ -783,7 +917,31 @@ __device__ __forceinline__ void traj_fast_body(const KArgs& A) {
       grad(x, g, red[2], wantU);
       pv[0] = vnet_l1(x, g);
       PT_MARK(9);  // grad U + VNet layer-1 partials
-      xchg<NW, 1>(pv, A, smem, w, lane, pb);
+      if constexpr (PIPE) {
+        float* P = smem + A.o_P + (XS ? 2 : pb) * (NW * 256);
+        xchg_put<NW>(P, pv[0], w, lane);
+        f4 part[NW];
+        xchg_get_issue<NW>(P, lane, part);
+        if constexpr (LDW) {
+#pragma unroll
+          for (int t = 0; t < DT; ++t) ldv += ldp[t];
+          if constexpr (LAST) __builtin_amdgcn_sched_barrier(0);
+        }
+        if constexpr (!LAST) {
+          // (pinned between the reads' issue and the first use of what they return -- the one place of the step where the wave
+          //  has nothing else to issue.  In front of the barrier it delays every wave's arrival there: measured slower than not
+          //  doing it at all, profiles/sampler_step_pipeline.txt)
+#pragma unroll
+          for (int t = 0; t < DT; ++t) xb_c[t] = split16<L2HMC_FAST_SPLIT_LAT_L1>(k1_c[t] * x[t]);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        pv[0] = xchg_get_sum<NW>(part);
+        if constexpr (!XS) pb ^= 1;
+      } else if constexpr (XS) {
+        xchg_at<NW, 2>(pv, A, smem, w, lane);
+      } else {
+        xchg<NW, 1>(pv, A, smem, w, lane, pb);
+      }
       PT_MARK(10); // exchange
       auto vhalf2 = [&](int t, f4 aS, f4 T, f4 EQ) {
         const f4 ES = ex2_4(aS);
