@@ -1,5 +1,5 @@
-"""Shared by tests/test_binomial_cpu.py, tests/test_gpu_binomial_target.py, tests/test_gpu_binomial_glm.py and
-tools/binomial_accuracy.py: seeded inputs of the binomial and negative-binomial regressions (`l2hmc_amd.BinomialRegression`,
+"""Shared by tests/test_binomial_cpu.py, tests/test_gpu_binomial_target.py, tests/test_gpu_binomial_glm.py,
+tests/test_gpu_binomial_geometries.py and tools/binomial_accuracy.py: seeded inputs of the binomial and negative-binomial regressions (`l2hmc_amd.BinomialRegression`,
 `NegativeBinomialRegression`; L2HMC_ENERGY_BINOMIAL, L2HMC_GLM_BINOMIAL / L2HMC_GLM_NEGBINOMIAL), a float64 restatement of the
 likelihood and the energy written from the definition with scipy's gammaln (independent of l2hmc_amd), the same statement in
 float32 numpy, and the bounds of the device path, derived from the inputs.
@@ -282,6 +282,62 @@ def far_case():
     m = np.asarray((1, 5, 50, 50)[:4] * 4, dtype=np.float32)
     y = np.asarray([0, 5, 50, 0, 1, 0, 25, 50, 0, 2, 0, 49, 1, 5, 1, 7], dtype=np.float32)
     return {"kind": "binomial", "W": W, "X": X, "y": np.minimum(y, m), "offset": np.zeros(n, dtype=np.float32), "trials": m}
+
+
+# ---- every tile count, long histories and the edges of the likelihood (tests/test_gpu_binomial_geometries.py) --------------------
+# (70, 35, d) with NT / NTM = 3 / 4 (d = 33, 40), 5 / 8 (65), 6 / 8 (96), 7 / 8 (100, 112): `glm_case.SHAPES` says why.  They are
+# no part of STAT_CASES: the K_* above stay "4 x the worst over STAT_CASES"
+GEOM_SHAPES = gc.SHAPES[7:]
+# S > 131072 with three rows: the gather's segments are no multiple of a tile (tests/test_gpu_glm_geometries.py; the
+# segmentation is a function of the number of draws alone)
+LONG = [(131073, 3, 40), (140001, 3, 40), (140001, 3, 100), (140003, 3, 100)]
+EDGE_ROWS = {"certain": 0, "saturated": 5, "underflow": 17, "many_trials": 33, "constant": 34}      # glm_case.EDGE_ROWS' positions
+EDGE_N = gc.EDGE_N
+# name -> (tau, y, trials): the row is x = tau wbar / |wbar|^2, so t = tau at the mean draw, offset 0
+EDGE_SPEC = {"certain": (-120.0, 0.0, 1.0), "saturated": (120.0, 50.0, 50.0), "underflow": (2.0, 0.0, 100000.0),
+             "many_trials": (0.1, float(1 << 23), float(1 << 24)), "constant": (0.0, 7.0, 50.0)}
+NB_EDGE_PHIS = (1e-3, 1e4)
+
+
+def edge_case(S):
+    """(case, ordinary): the binomial case of 37 rows under the draws of `case(S, 32, 3)`, whose 32 rows stand in their order
+    at the indices `ordinary` (37,) bool; at `EDGE_ROWS` stand five rows on the edges of the float32 likelihood, each
+    x = tau wbar / |wbar|^2 with wbar the float64 mean of the draws (t = tau there) and offset 0:
+        certain      tau = -120, y = 0 of 1: ll = -softplus(t) is 0 or below the float32 normal range in every draw
+        saturated    tau = +120, y = 50 of 50: m softplus(t) and y t cancel; the truth is between 0 and -1e-40
+        underflow    tau = 2, y = 0 of 100000: ll about -2e5 and sat = 0, exp(ll - sat) = 0 in every draw
+        many_trials  tau = 0.1, y = 2^23 of 2^24 (the documented limit): every term about 1e7, ll - sat about -2e4
+        constant     tau = 0 (x = 0), y = 7 of 50: the same ll in every draw
+    Edge rows share 16-row blocks and MFMA operands with ordinary ones; rows 32 .. 36 are a ragged third block in a second
+    row group whose last row is ordinary."""
+    base = case(S, 32, 3)
+    wbar = base["W"].astype(np.float64).mean(axis=0)
+    ordinary = np.ones(EDGE_N, dtype=bool)
+    ordinary[list(EDGE_ROWS.values())] = False
+    X, y = np.zeros((EDGE_N, 3), dtype=np.float32), np.zeros(EDGE_N, dtype=np.float32)
+    o, m = np.zeros(EDGE_N, dtype=np.float32), np.ones(EDGE_N, dtype=np.float32)
+    X[ordinary], y[ordinary], o[ordinary], m[ordinary] = base["X"], base["y"], base["offset"], base["trials"]
+    for name, i in EDGE_ROWS.items():
+        tau, yi, mi = EDGE_SPEC[name]
+        X[i], y[i], m[i] = (tau * wbar / (wbar @ wbar)).astype(np.float32), yi, mi
+    return {"kind": "binomial", "W": base["W"], "X": X, "y": y, "offset": o, "trials": m}, ordinary
+
+
+def select_rows(c, mask):
+    """The case restricted to the data rows `mask` (a bool or index array)."""
+    out = dict(c)
+    for k in ("X", "y", "offset", "trials"):
+        if k in out:
+            out[k] = out[k][mask]
+    return out
+
+
+def nb_edge_case(phi):
+    """`case(70, 33, 17, "negbinomial", phi)` at a dispersion far from NB_PHIS, with a count of 100000 in row 5."""
+    c = case(70, 33, 17, "negbinomial", phi)
+    c["y"] = c["y"].copy()
+    c["y"][5] = 100000.0
+    return c
 
 
 # ---- sensitivities of the finished numbers (CPU) -------------------------------------------------------------------------------

@@ -14,6 +14,7 @@ import pytest
 from l2hmc_amd import BinomialRegression, LogisticRegression, NegativeBinomialRegression, PoissonRegression, _ffi, glm
 from l2hmc_amd import distributions as D
 from tests import binomial_case as bc
+from tests import glm_case as gc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FAKE = 4096              # a non-NULL "device pointer" for calls that are refused before anything reads it
@@ -329,6 +330,87 @@ def test_far_rows_are_finite_and_bound():
     assert np.all(np.isfinite(U32)) and np.all(np.isfinite(G32))
     sU, sg = bc.used(U32, G32, U, G, bc.bounds(c))
     assert sU <= 1.0 and sg <= 1.0, (sU, sg)
+
+
+# ---- 3b. the cases of tests/test_gpu_binomial_geometries.py sit where they say ---------------------------------------------------
+def _share(c):
+    """(worst |log_lik32 - log_lik| / B, ll64, t, B) of a case."""
+    ll, t = bc.log_lik(c)
+    B = bc.ll_bounds(c)["B"]
+    with np.errstate(all="ignore"):
+        return float(np.max(np.abs(bc.log_lik32(c).astype(np.float64) - ll) / B)), ll, t, B
+
+
+@pytest.mark.parametrize("kind,phi", BOUND_CASES)
+@pytest.mark.parametrize("S,n,d", bc.GEOM_SHAPES + bc.LONG)
+def test_geometry_and_long_cases_are_bound_and_no_row_underflows(S, n, d, kind, phi):
+    """Every shape of GEOM_SHAPES and LONG under each likelihood: the float32 numpy restatement uses at most half of B
+    (measured 0.003 .. 0.061), and exp(ll - sat) sums to more than 0 in every row."""
+    from tests import glm_case as gc
+    assert bc.GEOM_SHAPES == gc.SHAPES[7:] and [-(-s[2] // 16) for s in bc.GEOM_SHAPES] == [3, 3, 5, 6, 7, 7]
+    assert bc.SHAPES == gc.SHAPES[:7] and len(bc.STAT_CASES) == 11                   # (the K_* stay what they were measured on)
+    c = bc.case(S, n, d, kind, phi)
+    share, ll, _, _ = _share(c)
+    print("%s phi=%s (%d, %d, %d): float32 numpy uses %.3g of the ll bound" % (kind, phi, S, n, d, share))
+    assert share <= 0.5
+    assert np.all(np.exp(ll - bc.saturated(c)).sum(axis=0) > 0.0)
+
+
+@pytest.mark.parametrize("S", gc.EDGE_S)
+def test_edge_case_sits_on_the_edges_it_names(S):
+    """`binomial_case.edge_case`: the ordinary rows are those of `case(S, 32, 3)` in their order, the edge rows stand at
+    `glm_case.EDGE_ROWS`' positions with offset 0; the float32 restatement is within half of B everywhere (B is absolute: it
+    carries 8 u m, so it covers the `certain` row's flush to zero); the `certain` row has |t| where float32 e^-|t| is denormal
+    (S = 4099 only) and where it is 0; `saturated` is 0 to 1e-40 and `certain` below the float32 normal range; `constant` is
+    one value; exp(ll - sat) sums to 0 for `underflow` and `many_trials` alone, which the host `waic` counts; the host `loo`
+    gives khat = inf for the five edge rows and a finite khat for every ordinary row."""
+    from tests import glm_case as gc
+    from tests import loglik_case as lk
+    c, ordinary = bc.edge_case(S)
+    at, n = bc.EDGE_ROWS, bc.EDGE_N
+    assert sorted(at.values()) == sorted(gc.EDGE_ROWS.values()) == [0, 5, 17, 33, 34] and n == 37 and ordinary.sum() == 32
+    assert ordinary[-1] and n % 16 != 0 and c["kind"] == "binomial"
+    base = bc.case(S, 32, 3)
+    assert np.array_equal(c["W"], base["W"])
+    for k in ("X", "y", "offset", "trials"):
+        assert c[k].dtype == np.float32 and c[k].shape[0] == n and np.array_equal(c[k][ordinary], base[k]), k
+    for name, i in at.items():
+        tau, y, m = bc.EDGE_SPEC[name]
+        assert (c["y"][i], c["trials"][i], c["offset"][i]) == (y, m, 0.0), name
+    assert c["trials"][at["many_trials"]] == glm.MAX_COUNT == 1 << 24 and not c["X"][at["constant"]].any()
+    bc.model(c)                                                            # (the library takes every row: y <= trials <= 2^24)
+    share, ll, t, B = _share(c)
+    print("S = %d: float32 numpy uses %.3g of the ll bound" % (S, share))
+    assert share <= 0.5
+    tc = np.abs(t[:, at["certain"]])
+    denormal, zero = (tc > 87.4) & (tc < 103.9), tc > 104.0
+    assert np.all(denormal | zero) and zero.any() and denormal.any() == (S == 4099), (tc.min(), tc.max())
+    assert np.all(np.abs(ll[:, at["certain"]]) < 2.0 ** -126) and np.all(np.abs(ll[:, at["saturated"]]) <= 1e-40)
+    assert np.all(B[:, at["certain"]] > 2.0 ** -126)
+    assert np.all(ll[:, at["constant"]] == ll[0, at["constant"]])
+    sat = bc.saturated(c)
+    assert sat[at["underflow"]] == 0.0 and np.all(ll[:, at["underflow"]] < -1.5e5)
+    assert np.all((ll - sat)[:, [at["underflow"], at["many_trials"]]] < -745.0)
+    dead = np.exp(ll - sat).sum(axis=0) == 0.0
+    assert np.nonzero(dead)[0].tolist() == [at["underflow"], at["many_trials"]]
+    m = bc.model(c)
+    f = m.waic(c["W"])
+    assert f.n_underflow == 2 and np.all(np.isneginf(f.lppd_i[dead])) and np.all(np.isfinite(f.lppd_i[~dead]))
+    for r in (None, lk.r_eff_for(n)):
+        s = m.loo(c["W"], r_eff=r)
+        assert np.all(np.isposinf(s.khat[~ordinary])) and np.all(np.isfinite(s.khat[ordinary])), s.khat
+
+
+@pytest.mark.parametrize("phi,n_finite", list(zip(bc.NB_EDGE_PHIS, (33, 32))))
+def test_dispersion_edge_case(phi, n_finite):
+    """`binomial_case.nb_edge_case` at phi = 1e-3 and 1e4: the float32 restatement within half of B (measured 0.28 and 0.09);
+    the host khat is finite for 33 of 33 and for 32 of 33 rows."""
+    c = bc.nb_edge_case(phi)
+    assert c["y"][5] == 100000 and c["phi"] == phi and c["X"].shape == (33, 17) and phi not in bc.NB_PHIS
+    share = _share(c)[0]
+    print("phi = %g: float32 numpy uses %.3g of the ll bound" % (phi, share))
+    assert share <= 0.5
+    assert int(np.isfinite(bc.model(c).loo(c["W"]).khat).sum()) == n_finite
 
 
 def test_trajectory_step_sizes_come_from_the_oracle():

@@ -65,8 +65,16 @@ def test_binomial_energy_and_gradient_within_the_bounds(n, d, monkeypatch):
     _both_paths(bc.case(40, n, d), monkeypatch, "binomial n=%d d=%d" % (n, d))
 
 
+# d = 40, 65, 96: 3, 5 and 6 live feature tiles -- 3 of the 4 compiled ones of one state tile per wave, 5 and 6 of the 8 of two
+# (the plan goes from one to two state tiles per wave between 4 and 5); above, d = 2 .. 128 has 1, 2, 4 and 8
+@pytest.mark.parametrize("n", [17, 1000])
+@pytest.mark.parametrize("d", [40, 65, 96])
+def test_binomial_energy_and_gradient_within_the_bounds_at_partly_live_tile_counts(n, d, monkeypatch):
+    _both_paths(bc.case(40, n, d), monkeypatch, "binomial n=%d d=%d" % (n, d))
+
+
 @pytest.mark.parametrize("phi", bc.NB_PHIS)
-@pytest.mark.parametrize("n,d", [(1000, 25), (17, 128)])
+@pytest.mark.parametrize("n,d", [(1000, 25), (17, 128), (17, 65)])
 def test_negative_binomial_energy_and_gradient_within_the_bounds(n, d, phi, monkeypatch):
     _both_paths(bc.case(40, n, d, "negbinomial", phi), monkeypatch, "negbinomial phi=%g n=%d d=%d" % (phi, n, d))
 

@@ -50,6 +50,18 @@ def hmc_eps(X, y, o, x, T, seed=3):
 @pytest.mark.parametrize("n", [1, 16, 17, 1000, 8192])
 @pytest.mark.parametrize("d", [2, 5, 25, 50, 128])
 def test_energy_and_gradient_within_the_bounds(n, d, monkeypatch):
+    _energy_and_gradient_within_the_bounds(n, d, monkeypatch)
+
+
+# d = 40, 65, 96: 3, 5 and 6 live feature tiles -- 3 of the 4 compiled ones of one state tile per wave, 5 and 6 of the 8 of two
+# (the plan goes from one to two state tiles per wave between 4 and 5); above, d = 2 .. 128 has 1, 2, 4 and 8
+@pytest.mark.parametrize("n", [17, 1000])
+@pytest.mark.parametrize("d", [40, 65, 96])
+def test_energy_and_gradient_within_the_bounds_at_partly_live_tile_counts(n, d, monkeypatch):
+    _energy_and_gradient_within_the_bounds(n, d, monkeypatch)
+
+
+def _energy_and_gradient_within_the_bounds(n, d, monkeypatch):
     W, X, y, o = pc.case(40, n, d)                                # 40 chains: the last tile is partial
     zero = np.zeros_like(o)
     runs = {}
