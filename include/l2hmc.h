@@ -45,8 +45,10 @@ enum {
   /* (6 is the Python binding's tag of the VAE decoder posterior, which runs on the GEMM engine) */
   L2HMC_ENERGY_LOGISTIC = 7,    /* Bayesian logistic regression   (l2hmc_pack_logistic)        */
   L2HMC_ENERGY_POISSON = 8,     /* Bayesian Poisson regression, log link and offsets (l2hmc_pack_logistic) */
-  L2HMC_ENERGY_BINOMIAL = 9     /* Bayesian binomial (trials) / negative-binomial (fixed dispersion) regression: logit link, per-row
+  L2HMC_ENERGY_BINOMIAL = 9,    /* Bayesian binomial (trials) / negative-binomial (fixed dispersion) regression: logit link, per-row
                                    offsets and weights (l2hmc_pack_logistic, l2hmc_binomial_aux_floats) */
+  L2HMC_ENERGY_PROBIT = 10      /* Bayesian binomial (trials) regression with the probit link: per-row offsets and trials in
+                                   BINOMIAL's layout (l2hmc_pack_logistic, l2hmc_binomial_aux_floats) */
 };
 
 /* One S/T/Q network in the reference's own parameter layout: `Linear` keeps W as
@@ -104,6 +106,19 @@ typedef struct L2hmcNet {
  *                the residual is bounded by max(m, y) and softplus(t) = max(t, 0) + log(1 + exp(-|t|)).  Every training entry
  *                point returns L2HMC_ERR_UNSUPPORTED for it: train on the same likelihood as a caller-supplied energy
  *                (energy_cb), then sample with the trained nets on this kind
+ *   PROBIT     : binomial regression with the probit link on n data rows x_i (d features) with a N(0, sigma^2 I) prior: y_i
+ *                successes out of m_i trials (binary probit: m_i = 1), t_i = x_i . w + o_i, Phi the standard normal distribution
+ *                function and lam(t) = phi(t) / Phi(t),
+ *                        U(w) = -sum_i [y_i log Phi(t_i) + (m_i - y_i) log Phi(-t_i)] + |w|^2 / (2 sigma^2),
+ *                        grad U = X^T ((m - y) lam(-t) - y lam(t)) + w / sigma^2
+ *                (the row constant log C(m, y) is dropped).  The buffers are BINOMIAL's: n_comp = n (>= 1), mu = the buffer
+ *                written by l2hmc_pack_logistic with y in the label slot, prec = l2hmc_binomial_aux_floats(n) floats, per 16-row
+ *                block [16 offsets | 16 trials], zero beyond n (required), eta = sigma^2 (> 0), logc = NULL, easy = 0.  d <= 128.
+ *                Runs where BINOMIAL runs.  log Phi and lam are formed from one float32 erfcx(|t| / sqrt 2) and are accurate to
+ *                a few ulps in both tails (ProbitLink, csrc/l2hmc_kernels.hpp); nothing overflows for |t| up to about 1e19,
+ *                beyond 2.6e19 t^2 / 2 is inf and U is non-finite, which the accept rule rejects.  Every training entry point
+ *                returns L2HMC_ERR_UNSUPPORTED for it: train on the same likelihood as a caller-supplied energy (energy_cb),
+ *                then sample with the trained nets on this kind
  * temperature divides U and grad U (dynamics.py:204-212); 1.0 when unused.
  * anneal_beta in (0, 1): the AIS bridge of utils/ais.py:46-47 with the standard-normal initial
  * energy its caller uses (eval_vae.py:55-56):  U := (1 - beta) |x|^2 / 2 + beta U(x);  0 (or 1) = off. */
@@ -276,7 +291,7 @@ int64_t l2hmc_packed_logistic_floats(int32_t n_data, int32_t d);
 int l2hmc_pack_logistic(const float* X, const float* y, int32_t n_data, int32_t d, float* packed, void* stream);
 /* Floats of the offset buffer of L2HMC_ENERGY_POISSON (L2hmcEnergy.prec): 16 ceil(n_data / 16), the tail zero-padded. */
 int64_t l2hmc_poisson_offset_floats(int32_t n_data);
-/* Floats of the row-constant buffer of L2HMC_ENERGY_BINOMIAL (L2hmcEnergy.prec): 32 ceil(n_data / 16) -- per 16-row data block
+/* Floats of the row-constant buffer of L2HMC_ENERGY_BINOMIAL and L2HMC_ENERGY_PROBIT (L2hmcEnergy.prec): 32 ceil(n_data / 16) -- per 16-row data block
  * [16 offsets | 16 weights], rows beyond n_data zero.  L2HMC_ERR_ARG for n_data outside 1 ... 1048576. */
 int64_t l2hmc_binomial_aux_floats(int32_t n_data);
 
@@ -911,7 +926,11 @@ int l2hmc_logistic_lik_stats(const float* draws, int64_t steps, int64_t n_chains
  *               NEGBINOMIAL (NB2, dispersion phi): m_i = y_i + phi, o_i = offset_i - log phi, c_i = lgamma(y_i + phi) -
  *               lgamma(phi) - lgamma(y_i + 1); sums[0] adds exp(t) = mu / phi (the caller multiplies by phi; +inf as IEEE
  *               gives it).  The absolute error of a float32 ll grows with m |t| (as the Poisson family's with y |h|).
- *               Any other value (0, 2, 5, ...) is L2HMC_ERR_ARG "unknown family".
+ *               L2HMC_GLM_PROBIT: binomial regression with the probit link.  row_consts is the binomial's (4, n_data) [o_i, m_i,
+ *               sat_i, c_i] (the supremum of ll is at Phi(t) = y / m: the same sat).  With t = eta + o_i,
+ *               ll = y_i log Phi(t) + (m_i - y_i) log Phi(-t) + c_i by the float32 operations of L2HMC_ENERGY_PROBIT
+ *               (ProbitLink), whose U term is c_i - ll bit for bit; the predictive mean is m_i Phi(t).
+ *               Any other value (0, 2, 5, 7, ...) is L2HMC_ERR_ARG "unknown family".
  * Every kernel forms ll by the one device function of the family: the bits of ll[s, i] depend on (draws, X, y, row_consts)
  * alone -- not on the entry, the pass, the chunk or the rows that share a call.
  *
@@ -941,7 +960,7 @@ int l2hmc_logistic_lik_stats(const float* draws, int64_t steps, int64_t n_chains
  * n_draws > 2^40 / d, tail_stride outside 0 .. n_draws - 1, tail_stride n_data > 2^31, a NULL required pointer (tail may be
  * NULL when tail_stride = 0), draws / row_consts / cutoff / top / tail / out not 4-byte, packed not 16-byte, n_tail /
  * tail_len_row / sums / workspace not 8-byte aligned. */
-enum { L2HMC_GLM_POISSON = 1, L2HMC_GLM_BINOMIAL = 3, L2HMC_GLM_NEGBINOMIAL = 4 };
+enum { L2HMC_GLM_POISSON = 1, L2HMC_GLM_BINOMIAL = 3, L2HMC_GLM_NEGBINOMIAL = 4, L2HMC_GLM_PROBIT = 6 };
 int l2hmc_glm_log_lik(const float* draws, int64_t n_draws, int32_t d, const float* packed, const float* row_consts /* (3 or 4, n_data) */,
                       int32_t n_data, int32_t family, float* out /* (n_draws, n_data) */, void* stream);
 int64_t l2hmc_glm_predict_workspace_doubles(int64_t n_draws, int32_t n_data, int32_t d);

@@ -10,7 +10,7 @@ from .dynamics import Dynamics  # noqa: F401
 from .sampler import chain_operator, propose, sample_chain, tf_accept  # noqa: F401
 from . import tempering  # noqa: F401
 from .tempering import ParallelTempering, geometric_ladder  # noqa: F401
-from .distributions import LogisticRegression, PoissonRegression, BinomialRegression, NegativeBinomialRegression  # noqa: F401
+from .distributions import LogisticRegression, PoissonRegression, BinomialRegression, NegativeBinomialRegression, ProbitRegression  # noqa: F401
 from . import glm  # noqa: F401
 from .training import LogisticTrainer  # noqa: F401
 from .diagnostics import summarize  # noqa: F401
@@ -22,6 +22,6 @@ from .multivariate import covariance, multi_ess  # noqa: F401
 from .warmup import warmup  # noqa: F401  (the function; its module stays importable as `from l2hmc_amd.warmup import ...`)
 
 __all__ = ["Dynamics", "propose", "tf_accept", "chain_operator", "sample_chain", "ParallelTempering", "geometric_ladder",
-           "LogisticRegression", "PoissonRegression", "BinomialRegression", "NegativeBinomialRegression", "glm", "LogisticTrainer", "summarize", "diagnostics", "warmup", "predictive", "waic", "loo", "relative_eff", "psis", "loo_from_log_lik", "relative_eff_from_log_lik", "quantiles", "describe",
+           "LogisticRegression", "PoissonRegression", "BinomialRegression", "NegativeBinomialRegression", "ProbitRegression", "glm", "LogisticTrainer", "summarize", "diagnostics", "warmup", "predictive", "waic", "loo", "relative_eff", "psis", "loo_from_log_lik", "relative_eff_from_log_lik", "quantiles", "describe",
            "multivariate", "covariance", "multi_ess",
            "layers", "distributions", "func_utils", "losses", "tempering"]

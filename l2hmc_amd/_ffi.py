@@ -15,9 +15,11 @@ LIB_PATH = os.path.abspath(os.environ["L2HMC_LIB"]) if os.environ.get("L2HMC_LIB
 ENERGY_GAUSS_DIAG, ENERGY_GAUSS_DENSE, ENERGY_GMM, ENERGY_ROUGHWELL, ENERGY_FUNNEL = 1, 2, 3, 4, 5
 GLM_POISSON = 1           # include/l2hmc.h L2HMC_GLM_POISSON: the family of the l2hmc_glm_* entries
 GLM_BINOMIAL, GLM_NEGBINOMIAL = 3, 4      # L2HMC_GLM_BINOMIAL, L2HMC_GLM_NEGBINOMIAL (2 is not a family)
+GLM_PROBIT = 6            # L2HMC_GLM_PROBIT: binomial regression with the probit link (5 is not a family)
 ENERGY_LOGISTIC = 7       # Bayesian logistic regression (6 is vae.ENERGY_VAE, the Python-side tag of the decoder posterior)
 ENERGY_POISSON = 8        # Bayesian Poisson regression, log link with offsets (sampling only: no training kernel)
 ENERGY_BINOMIAL = 9       # binomial (trials) / negative-binomial (fixed dispersion) regression (sampling only)
+ENERGY_PROBIT = 10        # binomial (trials) regression with the probit link (sampling only)
 
 _fp = C.c_void_p  # device pointers travel as integers
 

@@ -1,5 +1,5 @@
 // l2hmc_glm_log_lik, l2hmc_glm_loo_tails, l2hmc_glm_predict -- model criticism of a generalised linear model (Poisson regression
-// with the log link, binomial regression with trials and NB2 negative-binomial regression; glm_family.hpp) over every recorded draw, from a history that stays where the sampler wrote it: the
+// with the log link, binomial regression with trials under the logit or the probit link and NB2 negative-binomial regression; glm_family.hpp) over every recorded draw, from a history that stays where the sampler wrote it: the
 // pointwise log-likelihood matrix when it is wanted, the per-row raw material of PSIS-LOO (Vehtari, Gelman, Gabry 2017; Vehtari,
 // Simpson, Gelman, Yao, Gabry 2024) and the sums behind the posterior predictive mean and WAIC without it.  For draws W (S, d),
 // the data packed by l2hmc_pack_logistic (rows x_i, the responses y_i in the label slot) and the row constants (3, n) float32
@@ -43,7 +43,8 @@
 //            (formed and added in float64, one fma).  A draw at or past S and a row at or past n never count; partials are
 //            added in chunk order.
 // The kernels and their launches are templates over the family in glm_kernels.hpp; this unit holds the entries, the plans, the
-// workspace and the Poisson instantiations, glm_binomial.hip those of the binomial and the negative-binomial family.
+// workspace and the Poisson instantiations, glm_binomial.hip those of the binomial and the negative-binomial family, glm_probit.hip
+// those of the probit family.
 // No floating-point atomics anywhere: integer counts and maxima do not depend on arrival order, the tail is a set, the sums have
 // a fixed tree.  Every outward write is an ordinary vector store or an integer atomic from plain C++.  A row's bits do not
 // depend on the other rows of the call.
@@ -62,10 +63,13 @@ namespace l2hmc {
 L2HMC_GLM_LAUNCHES(extern, BinomialLogit)
 L2HMC_GLM_PREDICT(extern, BinomialLogit)
 L2HMC_GLM_PREDICT(extern, NegBinomialLog)
+L2HMC_GLM_LAUNCHES(extern, ProbitBinomial)
+L2HMC_GLM_PREDICT(extern, ProbitBinomial)
 
 static bool glm_family_ok(const char* who, int32_t family) {
-  if (family != PoissonLog::kAbi && family != BinomialLogit::kAbi && family != NegBinomialLog::kAbi) {
-    fail(L2HMC_ERR_ARG, "%s: unknown family %lld (L2HMC_GLM_POISSON = 1, L2HMC_GLM_BINOMIAL = 3, L2HMC_GLM_NEGBINOMIAL = 4)", who, family);
+  if (family != PoissonLog::kAbi && family != BinomialLogit::kAbi && family != NegBinomialLog::kAbi && family != ProbitBinomial::kAbi) {
+    fail(L2HMC_ERR_ARG, "%s: unknown family %lld (L2HMC_GLM_POISSON = 1, L2HMC_GLM_BINOMIAL = 3, L2HMC_GLM_NEGBINOMIAL = 4, "
+                        "L2HMC_GLM_PROBIT = 6)", who, family);
     return false;
   }
   return true;
@@ -80,6 +84,7 @@ static void on_family(int32_t family, Fn&& fn) {
     case PoissonLog::kAbi: fn(family_tag<PoissonLog>{}); break;
     case BinomialLogit::kAbi: fn(family_tag<BinomialLogit>{}); break;
     case NegBinomialLog::kAbi: fn(family_tag<std::conditional_t<LL_ONLY, BinomialLogit, NegBinomialLog>>{}); break;
+    case ProbitBinomial::kAbi: fn(family_tag<ProbitBinomial>{}); break;
   }
 }
 

@@ -1,12 +1,13 @@
-// The likelihoods of the draw-tile statistics kernels, each stated once: PoissonLog, BinomialLogit and NegBinomialLog for every
-// kernel of glm.hip, and BernoulliLogit (at the end) for the logistic kernels of predictive.hip, loo.hip and lik_stats.hip.  For
+// The likelihoods of the draw-tile statistics kernels, each stated once: PoissonLog, BinomialLogit, NegBinomialLog and
+// ProbitBinomial for every kernel of glm.hip, and BernoulliLogit (at the end) for the logistic kernels of predictive.hip, loo.hip and lik_stats.hip.  For
 // glm.hip a family is a struct with
 //     kConsts            the number of per-row constants ll takes: 2 (row_consts[0], row_consts[1]) or 3 (and row_consts[3];
 //                        row_consts[2] is sat for every family, which only the predictive sums read)
 //     ll(eta, y, a, b[, c])   the pointwise log-likelihood of a row with response y under the linear predictor eta = x_i . w_s
 //     mean(eta, a[, b])  the predictive mean
-// and an ABI number (include/l2hmc.h L2HMC_GLM_*).  The kernels call them through family_ll / family_mean below.  The next
-// family (probit) is one more struct here and one more case in glm.hip's dispatch, not another copy of three kernels.
+// and an ABI number (include/l2hmc.h L2HMC_GLM_*).  The kernels call them through family_ll / family_mean below.  A further
+// family (another link) is one more struct here, one more case in glm.hip's dispatch and a unit that instantiates its launches
+// (as glm_probit.hip does for ProbitBinomial), not another copy of three kernels.
 //
 // THE INVARIANT THE SELECT AND THE GATHER OF glm.hip RELY ON: every kernel -- the matrix writer, the four count passes, the
 // gather, the predictive sums -- computes ll by ONE device function, Family::ll, from the eta that tile_logits of draw_tiles.hpp
@@ -61,6 +62,20 @@ struct NegBinomialLog {
   static constexpr int kConsts = 3;
   static __device__ __forceinline__ float ll(float eta, float y, float o, float m, float c) { return BinomialLogit::ll(eta, y, o, m, c); }
   static __device__ __forceinline__ float mean(float eta, float o, float m) { return fexp(BinomialLink(eta, 0.f, o, m).t); }
+};
+
+// Binomial regression with m_i trials and the PROBIT link: with t = eta + o_i,
+//     ll = y_i log Phi(t) + (m_i - y_i) log Phi(-t) + c_i,   c_i = log C(m_i, y_i),   mean m_i Phi(t)
+// formed by ProbitLink of l2hmc_kernels.hpp -- the struct the fused sampling target (L2HMC_ENERGY_PROBIT) moves on: one statement
+// of the operations (log Phi exact in both tails).  The row constants are the binomial's (4, n): [o, m, sat, c].
+struct ProbitBinomial {
+  static constexpr int kAbi = 6;          // L2HMC_GLM_PROBIT
+  static constexpr int kConsts = 3;       // ll reads the offset, the trials and c
+  static __device__ __forceinline__ float ll(float eta, float y, float o, float m, float c) { return ProbitLink(eta, y, o, m).ll(c); }
+  static __device__ __forceinline__ float mean(float eta, float o, float m) {
+#pragma clang fp contract(off)
+    return __fmul_rn(m, ProbitLink(eta, 0.f, o, m).Phi());
+  }
 };
 
 // what the kernels of glm.hip call: the family's ll and mean with as many constants as it declares (k2 is row_consts[3])

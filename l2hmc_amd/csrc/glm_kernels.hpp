@@ -434,7 +434,7 @@ void glm_launch_tails(const GlmPlan& p, hipStream_t s, const float* draws, long 
 }
 
 // the launches of the binomial and the negative-binomial family live in glm_binomial.hip (the two share ll: the matrix and the
-// tails of either are BinomialLogit's)
+// tails of either are BinomialLogit's), those of the probit family in glm_probit.hip
 #define L2HMC_GLM_LAUNCHES(KEYWORD, F)                                                                                            \
   KEYWORD template void glm_launch_matrix<F>(const GlmPlan&, hipStream_t, const float*, long long, int, const float*, const float*, \
                                              int, float*);                                                                         \

@@ -471,6 +471,18 @@ int check_energy(const L2hmcEnergy* e, int d) {
       if (!(e->eta > 0.f) || !(e->eta <= 3.402823466e38f))
         return fail(L2HMC_ERR_ARG, "binomial regression needs eta = prior variance sigma^2 > 0 and finite%s");
       break;
+    case L2HMC_ENERGY_PROBIT:
+      if (!e->mu)
+        return fail(L2HMC_ERR_ARG, "probit regression needs the packed data (mu, l2hmc_pack_logistic with the successes as labels)%s");
+      if (!e->prec)
+        return fail(L2HMC_ERR_ARG, "probit regression needs the offsets and trials (prec: l2hmc_binomial_aux_floats(n_data) floats, "
+                                   "per 16 rows [16 offsets | 16 trials])%s");
+      if (e->n_comp < 1 || e->n_comp > kLogisticMaxRows)
+        return fail(L2HMC_ERR_ARG, "probit regression needs 1 <= n_comp = n_data <= 1048576 (got %s%lld)", "", e->n_comp);
+      if (d > kLogisticMaxDim) return fail(L2HMC_ERR_ARG, "probit regression supports d <= 128 (got %s%lld)", "", d);
+      if (!(e->eta > 0.f) || !(e->eta <= 3.402823466e38f))
+        return fail(L2HMC_ERR_ARG, "probit regression needs eta = prior variance sigma^2 > 0 and finite%s");
+      break;
     default:
       return fail(L2HMC_ERR_ARG, "unknown energy kind %s%lld", "", e->kind);
   }
@@ -608,7 +620,9 @@ static int plan_trajectory(const L2hmcTrajectoryArgs& a, KArgs& k, int KH, int c
   // logistic / Poisson regression: the general kernel only (the data contractions live in its grad U)
   const bool lr = is_data_regression(k.ekind);
   if (lr && (v.forced == FAM_LANE || v.forced == FAM_WIDE || v.forced == FAM_TILE))
-    return fail(L2HMC_ERR_UNSUPPORTED, k.ekind == L2HMC_ENERGY_BINOMIAL
+    return fail(L2HMC_ERR_UNSUPPORTED, k.ekind == L2HMC_ENERGY_PROBIT
+                    ? "variant %s%lld: the probit-regression target runs on the general kernel only (variant 0 or 100 + v)"
+                    : k.ekind == L2HMC_ENERGY_BINOMIAL
                     ? "variant %s%lld: the binomial-regression target runs on the general kernel only (variant 0 or 100 + v)"
                     : k.ekind == L2HMC_ENERGY_POISSON
                     ? "variant %s%lld: the Poisson-regression target runs on the general kernel only (variant 0 or 100 + v)"

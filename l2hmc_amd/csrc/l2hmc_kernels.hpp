@@ -87,6 +87,10 @@ constexpr const char* kPoissonTrainRefusal =
 constexpr const char* kBinomialTrainRefusal =
     "no training kernel for the binomial / negative-binomial regression target: train on the same likelihood as a caller-supplied "
     "energy (energy_cb / hvp_cb of l2hmc_train_split_grad), then sample with the trained nets on the fused kind%s";
+// ... and for L2HMC_ENERGY_PROBIT (its Hessian-vector product is X^T [(y lam(t) (t + lam(t)) + (m - y) lam(-t) (lam(-t) - t)) (X u)])
+constexpr const char* kProbitTrainRefusal =
+    "no training kernel for the probit-regression target: train on the slow path, the same likelihood as a caller-supplied "
+    "energy (energy_cb / hvp_cb of l2hmc_train_split_grad), then load_state_dict the trained nets and sample on the fused kind%s";
 int device_cus();      // l2hmc_abi.hip: compute units of the current device (256 when the query fails)
 struct KArgs;
 // traj_wide.hip: the LDS plan of the LDS-resident-state kernel for d > 256 (elementwise energies) and its waves per workgroup
@@ -126,14 +130,16 @@ __host__ __device__ inline int poisson_offset_floats(int n) { return 16 * ((n + 
 // The data-regression kinds: grad U is two contractions over the packed data (regression_grad) -- the general kernel only, four
 // waves splitting the data blocks, the data staged in LDS or streamed.  Every host rule and kernel branch for them asks this.
 __host__ __device__ constexpr bool is_data_regression(int ek) {
-  return ek == L2HMC_ENERGY_LOGISTIC || ek == L2HMC_ENERGY_POISSON || ek == L2HMC_ENERGY_BINOMIAL;
+  return ek == L2HMC_ENERGY_LOGISTIC || ek == L2HMC_ENERGY_POISSON || ek == L2HMC_ENERGY_BINOMIAL || ek == L2HMC_ENERGY_PROBIT;
 }
 // Binomial / negative-binomial regression (L2HMC_ENERGY_BINOMIAL): the same packed buffer, and two per-row constants beside it
 // (L2hmcEnergy.prec): per 16-row data block 32 floats, [16 offsets | 16 weights], zero beyond n_data.
 __host__ __device__ inline int binomial_aux_floats(int n) { return 32 * ((n + 15) >> 4); }
 // the floats of L2hmcEnergy.prec that travel with the packed data of a data-regression kind (staged behind the data blocks)
 __host__ __device__ inline int regression_aux_floats(int ek, int n) {
-  return ek == L2HMC_ENERGY_POISSON ? poisson_offset_floats(n) : ek == L2HMC_ENERGY_BINOMIAL ? binomial_aux_floats(n) : 0;
+  // (probit regression, L2HMC_ENERGY_PROBIT, has the binomial's [offsets | weights])
+  return ek == L2HMC_ENERGY_POISSON ? poisson_offset_floats(n)
+         : ek == L2HMC_ENERGY_BINOMIAL || ek == L2HMC_ENERGY_PROBIT ? binomial_aux_floats(n) : 0;
 }
 inline int khid_of(int H) { return (H + 1 + 3) / 4; }
 
@@ -588,6 +594,94 @@ struct BinomialLink {
     return __fadd_rn(-u_term(), c);
   }
 };
+// L2HMC_ENERGY_PROBIT: binomial regression with m trials and the PROBIT link, an offset o and a weight m per row (binary probit
+// is m = 1).  With t = L + o, Phi the standard normal distribution function, phi its density and lam(t) = phi(t) / Phi(t):
+//     ll = y log Phi(t) + (m - y) log Phi(-t) + c        U term = -(ll - c)        r = dU/dt = (m - y) lam(-t) - y lam(t)
+// Both tails are exact to a few ulps: nothing forms 1 - Phi or the log of an underflowing erfc.  With a = |t| and x = a / sqrt 2:
+//     E = erfcx(x)     u = rcp(x + 2); s = (x - 2) u refined by one Newton step (e = fma(s + 1, -2, x); e = fma(s, -x, e);
+//                      s = fma(u, e, s)), so that s does not depend on the reciprocal's last bit; E = P(s) u, P of degree 10 by
+//                      Horner (fitted and measured by tools/fit_erfcx.py, worst relative error 5.42 x 2^-24 for
+//                      every x >= 0 with the reciprocal anywhere within one ulp)
+//     h = E / 2        a2 = (a / 2) a        G = exp(-a2) (hardware exp2)        Q = h G = Phi(-a) <= 1/2
+//     log Phi(-a) = ln 2 log2(h) - a2                        (h <= 1/2: no cancellation, no underflow: h >= 4e-20 while a2 is finite)
+//     log Phi(a) = log(1 - Q) = ln 2 log2(w) - rho / w       w = fl(1 - Q), rho = Q - (1 - w) exactly: the rounding of 1 - Q is
+//                                                            put back to first order, so Q < 2^-24 (w = 1) gives -Q, not 0
+//     lam(-a) = sqrt(2 / pi) / E                             lam(a) = G / (sqrt(2 pi) w)
+// and the sign of t selects which of each pair belongs to t and which to -t: branch-free, as the rows of a wave have both signs.
+// One exp2, two log2, three reciprocals (x + 2, E, w).  THE ONE STATEMENT of the family: ProbitBinomial of glm_family.hpp (the
+// history statistics) builds this struct and calls ll() and Phi(), so a trajectory moves on the values `loo` of its history
+// evaluates.  A fixed sequence of individually rounded float32 operations under `fp contract(off)`.
+// Range: nothing overflows for finite |t| up to about 1e19 (E >= 4e-20, |log Phi(-a)| <= 1e38, lam(-a) <= 1.3e19).  Beyond
+// |t| = 2.6e19 a2 = a^2 / 2 is inf: U is non-finite (-inf, or NaN where 0 x inf meets it), which the accept rule rejects.
+struct ProbitLink {
+  static constexpr bool kOffset = true, kWeight = true;
+  static constexpr int kAux = 32;
+  float t, y, m, a2, E, G, Q, w, invw;
+  __device__ __forceinline__ ProbitLink(float L, float y_, float o, float m_) : y(y_), m(m_) {
+#pragma clang fp contract(off)
+    t = __fadd_rn(L, o);
+    const float a = fabsf(t);
+    const float x = __fmul_rn(a, 0.7071067811865476f);
+    const float u = __builtin_amdgcn_rcpf(__fadd_rn(x, 2.f));
+    float s = __fmul_rn(__fadd_rn(x, -2.f), u);
+    float e = fmaf(__fadd_rn(s, 1.f), -2.f, x);
+    e = fmaf(s, -x, e);
+    s = fmaf(u, e, s);
+    float p = fmaf(8.27431722e-05f, s, 7.45708967e-05f);          // the coefficients tools/fit_erfcx.py prints, highest power first
+    p = fmaf(p, s, -0.000595473393f);
+    p = fmaf(p, s, -0.000864148315f);
+    p = fmaf(p, s, 0.00305606565f);
+    p = fmaf(p, s, 0.00648878235f);
+    p = fmaf(p, s, -0.021502696f);
+    p = fmaf(p, s, -0.0364437886f);
+    p = fmaf(p, s, 0.279471427f);
+    p = fmaf(p, s, -0.687160611f);
+    p = fmaf(p, s, 1.02158272f);
+    E = __fmul_rn(p, u);
+    a2 = __fmul_rn(__fmul_rn(0.5f, a), a);
+    G = __builtin_amdgcn_exp2f(__fmul_rn(a2, -1.4426950408889634f));
+    Q = __fmul_rn(__fmul_rn(0.5f, E), G);
+    w = __fsub_rn(1.f, Q);
+    invw = __builtin_amdgcn_rcpf(w);
+  }
+  // log Phi(-|t|) and log Phi(|t|)
+  __device__ __forceinline__ float log_small() const {
+#pragma clang fp contract(off)
+    return __fsub_rn(__fmul_rn(0.6931471805599453f, __builtin_amdgcn_logf(__fmul_rn(0.5f, E))), a2);
+  }
+  __device__ __forceinline__ float log_big() const {
+#pragma clang fp contract(off)
+    const float rho = __fsub_rn(Q, __fsub_rn(1.f, w));
+    return fmaf(-rho, invw, __fmul_rn(0.6931471805599453f, __builtin_amdgcn_logf(w)));
+  }
+  // lam(-|t|) and lam(|t|)
+  __device__ __forceinline__ float lam_small() const {
+#pragma clang fp contract(off)
+    return __fmul_rn(0.7978845608028654f, __builtin_amdgcn_rcpf(E));
+  }
+  __device__ __forceinline__ float lam_big() const {
+#pragma clang fp contract(off)
+    return __fmul_rn(__fmul_rn(G, 0.3989422804014327f), invw);
+  }
+  __device__ __forceinline__ float Phi() const { return t >= 0.f ? w : Q; }
+  __device__ __forceinline__ float residual() const {
+#pragma clang fp contract(off)
+    const float ls = lam_small(), lb = lam_big();
+    const float lam_t = t >= 0.f ? lb : ls, lam_nt = t >= 0.f ? ls : lb;
+    return fmaf(__fsub_rn(m, y), lam_nt, __fmul_rn(-y, lam_t));
+  }
+  __device__ __forceinline__ float u_term() const {
+#pragma clang fp contract(off)
+    const float ls = log_small(), lb = log_big();
+    const float lp = t >= 0.f ? lb : ls, lq = t >= 0.f ? ls : lb;
+    return fmaf(-y, lp, __fmul_rn(__fsub_rn(y, m), lq));
+  }
+  // the log-likelihood of the row with its constant c = log C(m, y): the negation is exact, the sum one rounding
+  __device__ __forceinline__ float ll(float c) const {
+#pragma clang fp contract(off)
+    return __fadd_rn(-u_term(), c);
+  }
+};
 template <class Link, int DT, int NW, bool STAGED>
 __device__ __forceinline__ float regression_grad(const KArgs& A, float* smem, int w, int lane, const f4 (&x)[DT], f4 (&g)[DT],
                                                  bool wantU) {
@@ -817,8 +911,9 @@ __device__ __forceinline__ void grad_energy(const KArgs& A, float* smem, int w, 
   } else if constexpr (is_data_regression(EK)) {
     {
       // data term (the NLL of the labels / counts), then the N(0, sigma^2 I) prior; padded dimensions hold x = 0 and add nothing
-      using Link = std::conditional_t<EK == L2HMC_ENERGY_BINOMIAL, BinomialLink,
-                                      std::conditional_t<EK == L2HMC_ENERGY_POISSON, PoissonLink, LogitLink>>;
+      using Link = std::conditional_t<EK == L2HMC_ENERGY_PROBIT, ProbitLink,
+                                      std::conditional_t<EK == L2HMC_ENERGY_BINOMIAL, BinomialLink,
+                                                         std::conditional_t<EK == L2HMC_ENERGY_POISSON, PoissonLink, LogitLink>>>;
       U = A.easy ? regression_grad<Link, DT, NW, true>(A, smem, w, lane, x, g, wantU)
                  : regression_grad<Link, DT, NW, false>(A, smem, w, lane, x, g, wantU);
       const float iv = 1.f / A.eta;
@@ -1134,7 +1229,7 @@ __device__ __forceinline__ void stage_energy(const KArgs& A, float* smem, int ti
         const f4* so = reinterpret_cast<const f4*>(A.prec);
         for (int i = tid; i < poisson_offset_floats(A.ncomp) / 4; i += nthr) dst[n4 + i] = so[i];
       }
-      if (EK == L2HMC_ENERGY_BINOMIAL) {     // ... and the [offsets | weights] of every block
+      if (EK == L2HMC_ENERGY_BINOMIAL || EK == L2HMC_ENERGY_PROBIT) {     // ... and the [offsets | weights] of every block
         const f4* so = reinterpret_cast<const f4*>(A.prec);
         for (int i = tid; i < binomial_aux_floats(A.ncomp) / 4; i += nthr) dst[n4 + i] = so[i];
       }
@@ -1304,7 +1399,7 @@ template <auto A, auto B, class F>
 int on_either(bool first, F&& f) { return first ? f(ic<A>{}) : f(ic<B>{}); }
 
 // f(ic<EK>) for a built-in energy kind (L2HMC_ENERGY_GAUSS_DIAG = 1 ... L2HMC_ENERGY_FUNNEL = 5, L2HMC_ENERGY_LOGISTIC = 7,
-// L2HMC_ENERGY_POISSON = 8, L2HMC_ENERGY_BINOMIAL = 9)
+// L2HMC_ENERGY_POISSON = 8, L2HMC_ENERGY_BINOMIAL = 9, L2HMC_ENERGY_PROBIT = 10)
 template <class F>
 int on_energy_kind(int ek, F&& f) {
   switch (ek) {
@@ -1316,6 +1411,7 @@ int on_energy_kind(int ek, F&& f) {
     case 7: return f(ic<7>{});
     case 8: return f(ic<8>{});
     case 9: return f(ic<9>{});
+    case 10: return f(ic<10>{});
   }
   return fail(L2HMC_ERR_ARG, "unknown energy kind%s");
 }

@@ -1256,6 +1256,7 @@ int64_t l2hmc_train_fused_lds_bytes(int32_t ek, int32_t n_comp, int32_t d, int32
   if (d < 1 || H < 1 || T < 1) return fail(L2HMC_ERR_ARG, "l2hmc_train_fused_lds_bytes: bad argument%s");
   if (ek == L2HMC_ENERGY_POISSON) return fail(L2HMC_ERR_UNSUPPORTED, kPoissonTrainRefusal);
   if (ek == L2HMC_ENERGY_BINOMIAL) return fail(L2HMC_ERR_UNSUPPORTED, kBinomialTrainRefusal);
+  if (ek == L2HMC_ENERGY_PROBIT) return fail(L2HMC_ERR_UNSUPPORTED, kProbitTrainRefusal);
   if (ek != L2HMC_ENERGY_GAUSS_DIAG && ek != L2HMC_ENERGY_GAUSS_DENSE && ek != L2HMC_ENERGY_GMM &&
       ek != L2HMC_ENERGY_ROUGHWELL && ek != L2HMC_ENERGY_FUNNEL)
     return fail(L2HMC_ERR_UNSUPPORTED, "no fused training kernel for this energy kind%s");
@@ -1309,6 +1310,7 @@ static int train_launch(const L2hmcTrainArgs* a, const L2hmcTrainStep* st, void*
   const int ek = a->energy.kind;
   if (ek == L2HMC_ENERGY_POISSON) return fail(L2HMC_ERR_UNSUPPORTED, kPoissonTrainRefusal);
   if (ek == L2HMC_ENERGY_BINOMIAL) return fail(L2HMC_ERR_UNSUPPORTED, kBinomialTrainRefusal);
+  if (ek == L2HMC_ENERGY_PROBIT) return fail(L2HMC_ERR_UNSUPPORTED, kProbitTrainRefusal);
   if (ek != L2HMC_ENERGY_GAUSS_DIAG && ek != L2HMC_ENERGY_GAUSS_DENSE && ek != L2HMC_ENERGY_GMM &&
       ek != L2HMC_ENERGY_ROUGHWELL && ek != L2HMC_ENERGY_FUNNEL && ek != L2HMC_ENERGY_LOGISTIC)
     return fail(L2HMC_ERR_UNSUPPORTED, "training supports the Gaussian, GMM, Rough-Well, funnel and logistic-regression targets (analytic Hessian-vector products)%s");

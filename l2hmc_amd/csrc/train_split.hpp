@@ -724,6 +724,7 @@ int l2hmc_train_split_grad(const L2hmcTrainSplitArgs* a, void* stream) {
       return fail(L2HMC_ERR_UNSUPPORTED, "a built-in energy excludes decoder / aux_encoder / aux%s");
     if (a->energy->kind == L2HMC_ENERGY_POISSON) return fail(L2HMC_ERR_UNSUPPORTED, kPoissonTrainRefusal);
     if (a->energy->kind == L2HMC_ENERGY_BINOMIAL) return fail(L2HMC_ERR_UNSUPPORTED, kBinomialTrainRefusal);
+    if (a->energy->kind == L2HMC_ENERGY_PROBIT) return fail(L2HMC_ERR_UNSUPPORTED, kProbitTrainRefusal);
     if ((rc = check_energy(a->energy, d))) return rc;
     const int ek = a->energy->kind;
     if (ek == L2HMC_ENERGY_LOGISTIC)

@@ -19,10 +19,11 @@ using GeneralGeomsOf = std::conditional_t<is_data_regression(EK), LogisticGeoms,
 
 template <int EK>
 int launch_ek(const TrajPlan& p, const KArgs& k, hipStream_t s) {
-  // (logistic / Poisson / binomial regression: the general, energy and p_accept kernels only -- no instruction-lean or small-d form)
+  // (logistic / Poisson / binomial / probit regression: the general, energy and p_accept kernels only -- no instruction-lean or small-d form)
   if constexpr (is_data_regression(EK)) {
     if (p.family != FAM_GENERAL && p.family != FAM_ENERGY && p.family != FAM_PACCEPT)
-      return fail(L2HMC_ERR_UNSUPPORTED, EK == L2HMC_ENERGY_BINOMIAL ? "the binomial-regression target runs on the general kernel only%s"
+      return fail(L2HMC_ERR_UNSUPPORTED, EK == L2HMC_ENERGY_PROBIT ? "the probit-regression target runs on the general kernel only%s"
+                                         : EK == L2HMC_ENERGY_BINOMIAL ? "the binomial-regression target runs on the general kernel only%s"
                                          : EK == L2HMC_ENERGY_POISSON ? "the Poisson-regression target runs on the general kernel only%s"
                                                                      : "the logistic-regression target runs on the general kernel only%s");
   }

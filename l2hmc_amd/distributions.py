@@ -220,9 +220,11 @@ class BinomialEnergy(EnergyFunction):
     uses, y in its label slot, and the row constants go beside it: per 16-row block [16 offsets | 16 weights], zero-padded
     (`l2hmc_binomial_aux_floats`; L2hmcEnergy.prec)."""
 
+    KIND = _ffi.ENERGY_BINOMIAL
+
     def __init__(self, X, y, offset, weight, prior_var):
         n, d = X.shape
-        EnergyFunction.__init__(self, _ffi.ENERGY_BINOMIAL, d, n_comp=n, eta=prior_var)
+        EnergyFunction.__init__(self, self.KIND, d, n_comp=n, eta=prior_var)
         self._host = {'X': X, 'y': y, 'offset': offset, 'weight': weight}
 
     def _buffers(self, device):
@@ -242,6 +244,13 @@ class BinomialEnergy(EnergyFunction):
                 aux[:, k, :] = rows.reshape(-1, 16)
             self._dev[key] = {'mu': packed, 'prec': torch.as_tensor(aux.reshape(-1), device=device), 'logc': None, '_X': X, '_y': y}
         return self._dev[key]
+
+
+class ProbitEnergy(BinomialEnergy):
+    """U(w) = -sum_i [y_i log Phi(t_i) + (m_i - y_i) log Phi(-t_i)] + |w|^2 / (2 prior_var), t_i = x_i . w + o_i, on the fused
+    kernels (L2HMC_ENERGY_PROBIT): `BinomialEnergy`'s buffers -- the packed data and the [16 offsets | 16 trials] blocks -- under
+    the probit link's kind."""
+    KIND = _ffi.ENERGY_PROBIT
 
 
 class LogisticRegression(object):
@@ -417,7 +426,8 @@ class PoissonRegression(object):
 
 
 class _WeightedLogitRegression(object):
-    """What `BinomialRegression` and `NegativeBinomialRegression` share: one likelihood (include/l2hmc.h, L2HMC_ENERGY_BINOMIAL)
+    """What `BinomialRegression` and `NegativeBinomialRegression` share (and `ProbitRegression`, which keeps the data handling,
+    the row constants and the statistics and overrides the energy with the probit link's): one likelihood (include/l2hmc.h, L2HMC_ENERGY_BINOMIAL)
 
         ll_i = y_i t_i - m_i softplus(t_i) + c_i,   t_i = x_i . w + o_i,    U(w) = sum_i [m_i softplus(t_i) - y_i t_i] + |w|^2 / (2 prior_var)
 
@@ -432,6 +442,7 @@ class _WeightedLogitRegression(object):
     float32 ll loses absolute accuracy in proportion to m |t|."""
 
     _name = None
+    _fused = BinomialEnergy
 
     def _init(self, X, y, offset, prior_var, family, weight, check_y):
         from . import glm
@@ -485,7 +496,7 @@ class _WeightedLogitRegression(object):
         """The posterior's energy: a `UserEnergy` (torch code, the slow path; what `Trainer` takes), or with `fused=True` a
         `BinomialEnergy` on the fused trajectory kernels (sampling, warm-up, tempering, AIS)."""
         if fused:
-            return BinomialEnergy(self.X, self.y, self._o, self._m, self.prior_var)
+            return self._fused(self.X, self.y, self._o, self._m, self.prior_var)
         return UserEnergy(self.energy, self.grad_energy, x_dim=self.dim)
 
     def log_density(self, W):
@@ -523,6 +534,11 @@ class BinomialRegression(_WeightedLogitRegression):
 
     def __init__(self, X, y, trials, offset=None, prior_var=1.0):
         from . import glm
+        self._check_and_init(X, y, trials, offset, prior_var, glm.Binomial())
+
+    def _check_and_init(self, X, y, trials, offset, prior_var, family):
+        """The checks of y against `trials` and the shared `_init` under `family` (`ProbitRegression` calls it too)."""
+        from . import glm
 
         def check_y(y, n):
             m = np.asarray(trials, dtype=np.float64)
@@ -535,11 +551,71 @@ class BinomialRegression(_WeightedLogitRegression):
             if not np.all(np.isfinite(y)) or not np.all((y >= 0.0) & (y == np.floor(y)) & (y <= m)):
                 raise ValueError("successes y must be integers with 0 <= y <= trials")
             return m
-        self._init(X, y, offset, prior_var, glm.Binomial(), None, check_y)
+        self._init(X, y, offset, prior_var, family, None, check_y)
         self.trials = self._glm.weight
 
     def predict_mean(self, draws, X=None, offset=None, trials=None):
         """The posterior predictive mean E[y | x] = trials x mean over the draws of sigmoid(x . w + offset) of every row of X
+        (default: the model's own rows, offsets and trials; new rows take `offset`, default 0, and `trials`, default 1: the
+        success probability)."""
+        return self._glm.predict_mean(draws, X=X, offset=offset, weight=trials)
+
+
+class ProbitRegression(_WeightedLogitRegression):
+    """Bayesian binomial regression with the PROBIT link: y_i successes out of trials_i ~ Binomial(trials_i, Phi(x_i . w +
+    offset_i)), Phi the standard normal distribution function, and a N(0, prior_var I) prior on the weights w (d <= 128
+    features).  `trials` as `BinomialRegression`'s (default 1: binary probit regression).  With t = x . w + o and
+    lam(t) = phi(t) / Phi(t),
+
+        ll_i = y_i log Phi(t_i) + (m_i - y_i) log Phi(-t_i) + log C(m_i, y_i),    U(w) = -sum_i (ll_i - log C) + |w|^2 / (2 prior_var),
+        grad U = X^T ((m - y) lam(-t) - y lam(t)) + w / prior_var.
+
+    It shares the data handling, the row constants and the history statistics of `BinomialRegression` (the base class keeps
+    its name; only the link between the two data contractions differs): `get_energy_function(fused=True)` is a `ProbitEnergy`
+    (L2HMC_ENERGY_PROBIT) on the general trajectory kernel -- sampling, `warmup`, parallel tempering, AIS -- and `log_lik`,
+    `predict_mean`, `waic`, `loo` and `relative_eff` of a recorded history run on csrc/glm.hip's kernels (L2HMC_GLM_PROBIT),
+    which evaluate log Phi by the very float32 operations the fused energy uses: one erfcx, accurate in both tails, so a row
+    at t = -30 has ll = -454 and not -inf.  `get_energy_function()` -- the default -- is the slow path, a `UserEnergy` in
+    differentiable torch code (`torch.special.log_ndtr`) with the analytic gradient: what a sampler TRAINS on (no training
+    kernel holds this link), then `load_state_dict` into a `Dynamics` on the fused energy."""
+
+    _name = "ProbitRegression"
+    _fused = ProbitEnergy
+    _LOG_SQRT_2PI = 0.9189385332046727
+
+    def __init__(self, X, y, trials=1, offset=None, prior_var=1.0):
+        from . import glm
+        BinomialRegression._check_and_init(self, X, y, trials, offset, prior_var, glm.Probit())
+
+    def _lam(self, t):
+        """phi(t) / Phi(t) = exp(-t^2 / 2 - log sqrt(2 pi) - log Phi(t)): finite in both tails, differentiable."""
+        return torch.exp(-0.5 * t * t - self._LOG_SQRT_2PI - torch.special.log_ndtr(t))
+
+    def energy(self, x):
+        """U(w) of each row of the torch tensor x (N, d), in x's own device and dtype; differentiable."""
+        X, y, o, m = self._data(x)
+        t = x @ X.t() + o
+        nll = -(y * torch.special.log_ndtr(t) + (m - y) * torch.special.log_ndtr(-t))
+        return nll.sum(dim=1) + 0.5 * x.square().sum(dim=1) / self.prior_var
+
+    def grad_energy(self, x):
+        """grad U = X^T ((m - y) lam(-t) - y lam(t)) + w / prior_var, (N, d); differentiable (the trainer's Hessian-vector
+        products)."""
+        X, y, o, m = self._data(x)
+        t = x @ X.t() + o
+        return ((m - y) * self._lam(-t) - y * self._lam(t)) @ X + x / self.prior_var
+
+    def log_density(self, W):
+        """Unnormalised log posterior -U(w) of each row of W (n_w, d), in float64 (the constants c_i are not part of U)."""
+        W = np.asarray(W, dtype=np.float64)
+        lik = self._glm.lik
+        o, m, _ = lik.terms(self.y, self.offset, self._glm.weight)
+        y = self.y.astype(np.float64)
+        t = W @ self.X.astype(np.float64).T + o
+        return (y * lik.log_ndtr(t) + (m - y) * lik.log_ndtr(-t)).sum(axis=1) - 0.5 * np.square(W).sum(axis=1) / self.prior_var
+
+    def predict_mean(self, draws, X=None, offset=None, trials=None):
+        """The posterior predictive mean E[y | x] = trials x mean over the draws of Phi(x . w + offset) of every row of X
         (default: the model's own rows, offsets and trials; new rows take `offset`, default 0, and `trials`, default 1: the
         success probability)."""
         return self._glm.predict_mean(draws, X=X, offset=offset, weight=trials)

@@ -1,6 +1,6 @@
 """Model criticism of a generalised linear model over every recorded draw -- the host side of csrc/glm.hip, behind
-`distributions.PoissonRegression`, `BinomialRegression` and `NegativeBinomialRegression` (the likelihood is a family object:
-`Poisson`, `Binomial`, `NegBinomial` below -- the ABI number, the row constants, the float64 host ll and the mean):
+`distributions.PoissonRegression`, `BinomialRegression`, `NegativeBinomialRegression` and `ProbitRegression` (the likelihood is
+a family object: `Poisson`, `Binomial`, `NegBinomial`, `Probit` below -- the ABI number, the row constants, the float64 host ll and the mean):
 
     m = PoissonRegression(X, y, offset=log_exposure)
     ll = m.log_lik(x_hist[burn_in:], rows=slice(0, 512))      # the (S, 512) matrix, when it is wanted (the slow route)
@@ -23,7 +23,12 @@ The binomial and the negative binomial share one log-likelihood (csrc/glm_family
 o_i, weight m_i and constant c_i, t = eta + o_i and ll = y_i t - m_i softplus(t) + c_i.  Their row constants are (4, n):
 [o, m, sat, c] with sat = y log(y / m) + (m - y) log(1 - y / m) + c (0 log 0 = 0), each formed in float64 and rounded once.
 A float32 ll loses absolute accuracy in proportion to m |t| (the products y t and m softplus(t) are rounded at their own
-magnitude and then cancel), as the Poisson family's does with large counts."""
+magnitude and then cancel), as the Poisson family's does with large counts.
+
+The probit family (`Probit`) is the binomial with the probit link: ll = y log Phi(t) + (m - y) log Phi(-t) + c, mean m Phi(t),
+the same (4, n) row constants (the supremum of ll is at Phi(t) = y / m: the binomial's sat).  The device forms log Phi from one
+float32 erfcx (csrc/l2hmc_kernels.hpp, ProbitLink), accurate in both tails; the host route is `torch.special.log_ndtr` in
+float64."""
 import math
 
 import numpy as np
@@ -138,10 +143,31 @@ class NegBinomial(Binomial):
         return self.phi * np.exp(t)
 
 
+class Probit(Binomial):
+    """y successes out of `weight` = m trials, the probit link: t = eta + offset, ll = y log Phi(t) + (m - y) log Phi(-t) +
+    log C(m, y); mean m Phi(t).  The row constants are the binomial's."""
+    abi = _ffi.GLM_PROBIT
+
+    @staticmethod
+    def log_ndtr(t):
+        """log Phi(t) of a float64 array, by torch.special.log_ndtr (accurate in both tails)."""
+        import torch
+        return torch.special.log_ndtr(torch.as_tensor(np.ascontiguousarray(t, dtype=np.float64))).numpy()
+
+    def mean(self, t, m):
+        import torch
+        return m * torch.special.ndtr(torch.as_tensor(np.ascontiguousarray(t, dtype=np.float64))).numpy()
+
+    def host_ll(self, eta, y, offset, weight=None):
+        o, m, c = self.terms(y, offset, weight)
+        t = eta + o
+        return y * self.log_ndtr(t) + (m - y) * self.log_ndtr(-t) + c, self.mean(t, m)
+
+
 class Glm(object):
     """The data of one model (X (n, d), y (n,), offset (n,), float32; `weight` (n,) where the family has one: the binomial's
     trials) and its statistics over draws under the likelihood `family` (an object: `Poisson()`, `Binomial()`,
-    `NegBinomial(phi)`); `self.family` is its ABI number."""
+    `NegBinomial(phi)`, `Probit()`); `self.family` is its ABI number."""
 
     def __init__(self, X, y, offset, family=None, weight=None):
         self.X, self.y, self.offset, self.weight = X, y, offset, weight

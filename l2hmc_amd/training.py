@@ -70,9 +70,17 @@ _BINOMIAL_ROUTE = ("no training kernel holds the fused binomial / negative-binom
                    "state_dict() into the Dynamics on model.get_energy_function(fused=True) to sample")
 
 
+_PROBIT_ROUTE = ("no training kernel holds the fused probit-regression target: train on the slow path -- "
+                 "Trainer(Dynamics(d, model.get_energy_function(), ...)), the torch form of the same posterior on the GEMM-engine "
+                 "trainer -- then load_state_dict() the trained state_dict() into the Dynamics on "
+                 "model.get_energy_function(fused=True) to sample")
+
+
 class Trainer(object):
     def __new__(cls, dynamics, *args, **kwargs):
         fn = getattr(dynamics, "_fn", None)
+        if fn is not None and getattr(fn, "kind", None) == _ffi.ENERGY_PROBIT:
+            raise NotImplementedError(_PROBIT_ROUTE)
         if fn is not None and getattr(fn, "kind", None) == _ffi.ENERGY_BINOMIAL:
             raise NotImplementedError(_BINOMIAL_ROUTE)
         if fn is not None and getattr(fn, "kind", None) == _ffi.ENERGY_POISSON:
